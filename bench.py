@@ -67,7 +67,15 @@ def parse_args():
                          "auto = whichever of the two puts fewer bytes on the wire for the frames of step 0 (rank 0 decides, every rank follows)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; 'gloo' = single-GPU rehearsal of the N > 1 path "
                     "(all ranks share the visible GPUs, tiles travel through host memory)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last step handed its caller (a seeded sample of the frames' raybuffers, "
+                         "see dump_outputs) as DIR/<name>.npy, to compare two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs covers the single-GPU path only (--gpus 1)")
+    return args
 
 
 def load_world(name: str, rank: int, world_size: int, barrier):
@@ -478,6 +486,9 @@ def main():
             k_ms_total, k_draws = ctx.draw_time_stats(reset=True)
             exchange_verified = verify_exchange(total_steps - 1)
 
+    if args.dump_outputs:
+        dump_outputs(ctx, steps_frames[total_steps - 1], W, H, args.dump_outputs)
+
     breakdown = None
     if sharded and not args.no_exchange:
         # The first multi-GPU line has to explain itself: the last step's render alone, its exchange alone, and what the overlap hid
@@ -873,6 +884,54 @@ def find_counter_summary(args):
 
 def parse_default(name):
     return {"frames": 512, "width": 1920, "height": 1080, "world": "proc2048", "lod_error": 1.0, "pose_range": None, "steps": 10, "warmup": 2}[name]
+
+
+DUMP_FRAMES = 8           # --dump-outputs: frames of the last step, spread over its batch
+DUMP_SAMPLE = 1 << 19     # ... and written pixels per frame (8 x 2^19 x 8 B = 32 MiB)
+
+
+def dump_outputs(ctx, frames, W, H, out_dir):
+    """--dump-outputs: what the last timed step (one cvx_draw_segments_batch, frame b in raybuffer pair b) handed its caller, for comparing two builds.
+    Only the pixels a frame writes count -- its four segments' used rays x [origMin, origMax] (the parity leg's region); the rest of a raybuffer
+    holds stale pixels of earlier draws.  Per dumped frame, those pixels in segment order (rows of a segment in ray order) are one vector:
+      raybuffer_sample.npy        [frames, DUMP_SAMPLE] float64  its ARGB32 words at sorted positions drawn by a generator seeded with the frame's
+                                                                 batch index (with replacement; -1 for a frame that writes nothing)
+      raybuffer_channel_sums.npy  [frames, 4, 4] float64         per segment, the sum of each byte (least significant first) of ALL its written words
+      written_pixels.npy          [frames, 4] float64            per segment, how many pixels it writes
+      frame_index.npy             [frames] float64               the dumped frames' positions in the batch
+    All exact in float64 (words < 2^32, sums < 2^53)."""
+    import numpy as np
+
+    from cpuvox_amd import dist as cdist
+    from cpuvox_amd import gpu
+
+    F = len(frames)
+    picked = sorted({(F * i) // DUMP_FRAMES for i in range(DUMP_FRAMES)})
+    sample = np.full((len(picked), DUMP_SAMPLE), -1.0)
+    sums = np.zeros((len(picked), 4, 4))
+    counts = np.zeros((len(picked), 4))
+    for k, b in enumerate(picked):
+        fr = frames[b]
+        rc = [max(0, sg.RayCount) for sg in fr.segments]
+        bufs = [ctx.read_raybuffer(b, which, 0, n) if n else None
+                for which, n in ((gpu.RAYBUFFER_TOPDOWN, rc[0] + rc[1]), (gpu.RAYBUFFER_LEFTRIGHT, rc[2] + rc[3]))]
+        ranges = cdist.segment_pixel_ranges(fr.vanishingPointScreenSpace, W, H)
+        row0 = [0, rc[0], 0, rc[2]]
+        parts = []
+        for sg in range(4):
+            lo, hi = ranges[sg]
+            part = bufs[sg // 2][row0[sg]: row0[sg] + rc[sg], lo: hi + 1].ravel() if rc[sg] else np.empty(0, dtype=np.uint32)
+            counts[k, sg] = part.size
+            sums[k, sg] = part.view(np.uint8).reshape(-1, 4).sum(axis=0, dtype=np.uint64)
+            parts.append(part)
+        written = np.concatenate(parts)
+        if written.size:
+            pos = np.sort(np.random.default_rng([0x5EED, b]).integers(0, written.size, DUMP_SAMPLE))
+            sample[k] = written[pos]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("raybuffer_sample", sample), ("raybuffer_channel_sums", sums), ("written_pixels", counts),
+                      ("frame_index", np.array(picked, dtype=np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def cpu_baseline(ws, frames, W, H, budget_s: float, parity_frames=()):

@@ -230,6 +230,61 @@ def test_counter_summary_serves_the_drivers_argument_vector(tmp_path, monkeypatc
     assert bench.read_counter_summary(old, 2, 10) is not None and bench.read_counter_summary(old, 5, 20) is None
 
 
+def test_bench_dump_outputs_hold_the_written_pixels_only(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a fixed sample of the pixels the last step's frames WRITE (never a raybuffer's stale rest), as float arrays of at
+    most 64 MB, the same bytes for the same raybuffers.  The raybuffers here are the CPU oracle's, pre-cleared to a marker colour where a frame
+    writes nothing, served through a stand-in for the device context."""
+    import importlib.util
+    import sys
+
+    import numpy as np
+    import oraclelib as O
+    import scenes
+    from cpuvox_amd import dist as cdist
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    args = bench.parse_args()
+    assert (args.steps, args.warmup, args.dump_outputs) == (3, 1, str(tmp_path / "a"))
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", str(tmp_path / "x")]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+
+    marker = 0xDEADBEEF
+    ws, fr, W, H = scenes.scene_frame("proc256_t075_lod8")
+    td, lr, _ = O.draw_segments(ws, fr, W, H, clear=marker)
+
+    class Ctx:
+        def read_raybuffer(self, b, which, first, n):
+            return (td if which == gpu.RAYBUFFER_TOPDOWN else lr)[first:first + n].copy()
+
+    frames = [fr] * 20
+    for d in ("a", "b"):
+        bench.dump_outputs(Ctx(), frames, W, H, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["frame_index.npy", "raybuffer_channel_sums.npy", "raybuffer_sample.npy", "written_pixels.npy"]
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for n in names:
+        assert np.array_equal(out[n[:-4]], np.load(tmp_path / "b" / n)), n
+
+    assert list(out["frame_index"]) == [0, 2, 5, 7, 10, 12, 15, 17]
+    sample = out["raybuffer_sample"]
+    assert sample.shape == (8, bench.DUMP_SAMPLE) and (sample >= 0).all() and not (sample == marker).any()
+    rc = [max(0, sg.RayCount) for sg in fr.segments]
+    row0 = [0, rc[0], 0, rc[2]]
+    for sg, (lo, hi) in enumerate(cdist.segment_pixel_ranges(fr.vanishingPointScreenSpace, W, H)):
+        part = (td if sg < 2 else lr)[row0[sg]: row0[sg] + rc[sg], lo: hi + 1]
+        assert (out["written_pixels"][:, sg] == part.size).all()
+        assert (out["raybuffer_channel_sums"][:, sg] == part.reshape(-1, 1).view(np.uint8).sum(axis=0)).all()
+    assert set(np.unique(sample[0])) <= set(np.unique(np.concatenate([td.ravel(), lr.ravel()])).tolist()) - {marker}
+
+
 def test_gpu_objects_do_not_depend_on_the_build_directory(tmp_path):
     """bench.py attaches the committed counter summary only to the library whose sha-256 it is stamped with, and the GPU box rebuilds stale targets at
     its own scratch path: the product library's objects are compiled with a fixed compilation-unit id (csrc/Makefile), so the same sources give the
