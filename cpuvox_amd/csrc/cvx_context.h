@@ -60,6 +60,18 @@ struct cvx_context {
 	DevWorld hostWorld{};
 	DevWorld *devWorld = nullptr;
 	bool worldDirty = true;
+	// in-place edits (cvx_edit.hip): per level, the tail behind the run list and the colours that replaced columns take their places from.  A level
+	// gets one on its first edit (the arena is laid out again, with headroom); cvx_world_upload of the level drops it.  The host sizes
+	// (HostLevel::runsBytes / elementsBytes) of a level with a tail cover the tail, so that SyncWorld carries it over like any other part.
+	struct EditLevel {
+		bool ready = false;
+		int64_t runsUsed = 0, runsCap = 0;         // run-list entries (uint2) in use / in the region
+		int64_t elementsUsed = 0, elementsCap = 0; // colour slots in use / usable; one line of zeros follows the usable ones
+		int64_t abandonedBytes = 0;                // places of replaced columns and moved blocks nothing refers to any more
+		uint32_t *blockBase = nullptr, *blockDepth = nullptr; // device, colorShift 7: first slot and depth (colours) of every 4 x 8 block
+		size_t blockCap = 0;
+	};
+	EditLevel edit[CVX_LOD_LEVELS];
 
 	// raybuffers
 	int resX = 0, resY = 0;
@@ -136,6 +148,18 @@ int ValidateColumn(cvx_context *ctx, int64_t i, const RefHeader &h, const uint32
 // cvx_lone.hip (its own translation unit: the latency kernel is compiled with its own optimisation level, Makefile): launches lone_kernel<hi> with one
 // workgroup per ray (rays = 64 x tiles), `ldsBytes` of dynamic LDS (merge buffer + the ray's pixel row)
 void LaunchLone(bool hi, unsigned rays, size_t ldsBytes, hipStream_t stream, const DevFrame *frames, const DevTile *tiles, const DevWorld *world);
+
+// cvx_gpu.hip: lays the uploaded levels out in the arena if any is pending (what the next draw would do first)
+int SyncWorld(cvx_context *ctx);
+// cvx_world.hip: exclusive prefix sum of n counts in place on `stream`, *total (device) = their sum; chunkSums: (n + CVX_SCAN_CHUNK - 1) / CVX_SCAN_CHUNK words of 8 bytes
+void ExclusiveScan(hipStream_t stream, uint32_t *values, int n, unsigned long long *chunkSums, unsigned long long *total);
+int ScanChunk();
+// cvx_world.hip: World.DownSample(1 .. levelCount) of a validated LOD-0 blob at dSrc (device) that STAYS on the device: headers[j - 1] / elements[j - 1]
+// = level j (hipFree them), columnsZ as in the blob (dimZ >> j)
+int BuildLodChainOnDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t elementsOfColumns, int dimX, int dimY, int dimZ, int columnCount, int levelCount,
+                          uint32_t **headers, uint32_t **elements);
+// cvx_edit.hip: releases the edit state's device tables (cvx_destroy)
+void FreeEditState(cvx_context *ctx);
 } // namespace cvxi
 
 #define CVX_HIP(ctx, call)                                                                                              \

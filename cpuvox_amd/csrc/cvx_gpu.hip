@@ -464,6 +464,8 @@ int Launch(cvx_context *ctx, int frameCount, int flags)
 
 } // namespace
 
+int cvxi::SyncWorld(cvx_context *ctx) { return ::SyncWorld(ctx); }
+
 extern "C" {
 
 const char *cvx_version(void) { return "cpuvox_gpu 0.2 (gfx950)"; }
@@ -534,6 +536,7 @@ void cvx_destroy(cvx_context *ctx)
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); }
 	FreeRaybuffers(ctx);
+	cvxi::FreeEditState(ctx);
 	if (ctx->arena) { (void)hipFree(ctx->arena); }
 	if (ctx->devWorld) { (void)hipFree(ctx->devWorld); }
 	if (ctx->devFrames) { (void)hipFree(ctx->devFrames); }

@@ -228,6 +228,7 @@ int cvx_world_upload(cvx_context *ctx, int lod, const void *storage, int64_t byt
 	H.elementsBytes = H.elements.size() * sizeof(uint32_t);
 	H.rowShift = rowShift;
 	H.pending = true;
+	ctx->edit[lod].ready = false; // (a new table: no edit tail until the next edit)
 	if (lod == 0) {
 		if (ctx->hostWorld.dimX != dimX || ctx->hostWorld.dimY != dimY || ctx->hostWorld.dimZ != dimZ) {
 			// a LOD 0 of other dimensions starts a new world: the tables of the old LOD 1..5 are indexed with the old
@@ -235,6 +236,7 @@ int cvx_world_upload(cvx_context *ctx, int lod, const void *storage, int64_t byt
 			for (int l = 1; l < CVX_LOD_LEVELS; l++) {
 				ctx->hostLevel[l] = cvx_context::HostLevel();
 				ctx->levelSet[l] = false;
+				ctx->edit[l].ready = false;
 			}
 		}
 		ctx->hostWorld.dimX = dimX;
@@ -291,7 +293,12 @@ int UploadSourceBlob(cvx_context *ctx, const void *storage, int64_t byteLength, 
 	return CVX_OK;
 }
 
-// World.DownSample(extraLods) of the validated blob at dSrc (device); see cvx_world_downsample.
+} // namespace
+
+namespace cvxi {
+
+int ScanChunk() { return CVX_SCAN_CHUNK; }
+
 // Exclusive prefix sum of n counts in place, *total = their sum: chunk sums, their offsets, the chunks again (cvx_downsample.h).
 // chunkSums: (n + CVX_SCAN_CHUNK - 1) / CVX_SCAN_CHUNK words of 8 bytes.
 void ExclusiveScan(hipStream_t stream, uint32_t *values, int n, unsigned long long *chunkSums, unsigned long long *total)
@@ -302,6 +309,13 @@ void ExclusiveScan(hipStream_t stream, uint32_t *values, int n, unsigned long lo
 	hipLaunchKernelGGL(cvxk::scan_apply_kernel, dim3(chunks), dim3(CVX_SCAN_THREADS), 0, stream, values, n, chunkSums);
 }
 
+} // namespace cvxi
+
+namespace {
+
+using cvxi::ExclusiveScan;
+
+// World.DownSample(extraLods) of the validated blob at dSrc (device); see cvx_world_downsample.
 int DownsampleDevice(cvx_context *ctx, const uint8_t *dSrc, int dimX, int dimY, int dimZ, int lod, int columnCount, int extraLods,
                      void **outStorage, int64_t *outByteLength, int32_t *outColumnCount, int64_t *outVoxelCount, float *outDeviceMs)
 {
@@ -441,8 +455,10 @@ int DownsampleDevice(cvx_context *ctx, const uint8_t *dSrc, int dimX, int dimY, 
 // Levels above `kMaxChainLevel` (channel sums of 2^24 voxels x 255 no longer fit 32 bits) are left to DownsampleDevice.
 constexpr int kMaxChainLevel = 7;
 
+// deviceHeaders / deviceElements (cvx_world_edit): the levels stay on the device, handed over instead of copied to the host (outStorage etc. unused).
 int BuildLodChainDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t elementsOfColumns, int dimX, int dimY, int dimZ, int columnCount, int levelCount,
-                        void **outStorage, int64_t *outByteLength, int32_t *outColumnCount, float *outDeviceMs)
+                        void **outStorage, int64_t *outByteLength, int32_t *outColumnCount, float *outDeviceMs,
+                        uint32_t **deviceHeaders = nullptr, uint32_t **deviceElements = nullptr)
 {
 	struct Level {
 		int64_t targetColumns = 0, allocatedColumns = 0;
@@ -557,6 +573,16 @@ int BuildLodChainDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t elementsO
 		if ((int)scalars[(size_t)(j - 1) * 3 + 2] != 0) { return fail(Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "a downsampled column needs more than 65535 runs (World.cs:193-195)")); }
 		if (scalars[(size_t)(j - 1) * 3 + 1] > (unsigned long long)elementBound) { return fail(Fail(ctx, CVX_ERR_CAPACITY, "LOD %d: element total beyond its bound (internal error)", j)); }
 	}
+	if (deviceHeaders) {
+		for (int j = 1; j <= levelCount; j++) {
+			Level &l = L[(size_t)j];
+			deviceHeaders[j - 1] = l.dHeaders;
+			deviceElements[j - 1] = l.dElements;
+			l.dHeaders = l.dElements = nullptr;
+		}
+		release();
+		return CVX_OK;
+	}
 	for (int j = 1; j <= levelCount; j++) {
 		Level &l = L[(size_t)j];
 		const size_t headerBytes = (size_t)l.allocatedColumns * 12, elementTotal = (size_t)scalars[(size_t)(j - 1) * 3 + 1];
@@ -579,6 +605,13 @@ int BuildLodChainDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t elementsO
 }
 
 } // namespace
+
+int cvxi::BuildLodChainOnDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t elementsOfColumns, int dimX, int dimY, int dimZ, int columnCount, int levelCount,
+                                uint32_t **headers, uint32_t **elements)
+{
+	if (levelCount < 1 || levelCount > kMaxChainLevel) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d out of range", levelCount); }
+	return BuildLodChainDevice(ctx, dSrc, elementsOfColumns, dimX, dimY, dimZ, columnCount, levelCount, nullptr, nullptr, nullptr, nullptr, headers, elements);
+}
 
 /* World.DownSample(extraLods), World.cs:45-127, on the device (cvx_downsample.h). */
 int cvx_world_downsample(cvx_context *ctx, const void *storage, int64_t byteLength, int dimX, int dimY, int dimZ, int lod, int columnCount, int extraLods,

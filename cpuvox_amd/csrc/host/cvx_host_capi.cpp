@@ -1,6 +1,8 @@
 // cvx_host_capi.cpp -- extern "C" surface of libcpuvox_host.so (include/cpuvox_host.h).
 #include "cpuvox_host.h"
 
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <dlfcn.h>
@@ -156,6 +158,57 @@ int cvxh_world_downsample_seconds(const cvxh_world_set *worlds, int extraLods, i
 int cvxh_world_lod_count(const cvxh_world_set *worlds) { return worlds ? (int)worlds->worlds.size() : 0; }
 
 int64_t cvxh_world_lod0_voxels(const cvxh_world_set *worlds) { return worlds ? worlds->lod0Voxels : 0; }
+
+int cvxh_world_extract_region(const cvxh_world_set *worlds, int lod, int x0, int z0, int sizeX, int sizeZ, void **out, int64_t *bytes, int32_t *columnCount)
+{
+	if (!worlds || !out || !bytes || !columnCount || lod < 0 || lod >= (int)worlds->worlds.size()) { return Fail("bad argument"); }
+	*out = nullptr;
+	const cvx::World &w = worlds->worlds[(size_t)lod];
+	const int64_t usedX = w.Dimensions().x >> lod, usedZ = w.Dimensions().z >> lod;
+	if (sizeX < 1 || sizeZ < 1 || x0 < 0 || z0 < 0 || x0 + (int64_t)sizeX > usedX || z0 + (int64_t)sizeZ > usedZ || (int64_t)sizeX * sizeZ > 0x7FFFFFFF) {
+		return Fail("rectangle outside the level");
+	}
+	// the reference's layout: headers (World.cs:161-169), then per column [guard][runs][guard][colours] (World.cs:163-165, 205-209)
+	struct Header { int32_t storageOffset; uint16_t runCount, worldMin, worldMax, pad; };
+	static_assert(sizeof(Header) == 12, "RLEColumn is 12 bytes");
+	const Header *src = static_cast<const Header *>(w.StoragePointer());
+	const uint32_t *pool = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(w.StoragePointer()) + (size_t)w.ColumnCount() * 12);
+	const int64_t n = (int64_t)sizeX * sizeZ;
+	std::vector<int64_t> size((size_t)n, 0);
+	int64_t elements = 0;
+	for (int64_t i = 0; i < n; i++) {
+		const Header &h = src[(x0 + i / sizeZ) * usedZ + z0 + i % sizeZ];
+		if (h.runCount == 0) { continue; }
+		int64_t colours = 0;
+		for (int r = 0; r < h.runCount; r++) {
+			const uint32_t raw = pool[(int64_t)h.storageOffset + 1 + r];
+			const int16_t index = (int16_t)(raw & 0xFFFFu), length = (int16_t)(raw >> 16);
+			if (index >= 0) { colours = std::max<int64_t>(colours, (int64_t)index + length); }
+		}
+		size[(size_t)i] = h.runCount + 2 + colours;
+		elements += size[(size_t)i];
+	}
+	const int64_t total = n * 12 + elements * 4;
+	uint8_t *blob = static_cast<uint8_t *>(std::calloc((size_t)total, 1));
+	if (!blob) { return Fail("out of memory"); }
+	Header *dst = reinterpret_cast<Header *>(blob);
+	uint32_t *dstPool = reinterpret_cast<uint32_t *>(blob + n * 12);
+	int64_t cursor = 0;
+	for (int64_t i = 0; i < n; i++) {
+		const Header &h = src[(x0 + i / sizeZ) * usedZ + z0 + i % sizeZ];
+		dst[i] = h;
+		dst[i].storageOffset = (int32_t)cursor;
+		if (h.runCount == 0) { dst[i].storageOffset = 0; continue; }
+		std::memcpy(dstPool + cursor, pool + h.storageOffset, (size_t)size[(size_t)i] * 4);
+		cursor += size[(size_t)i];
+	}
+	*out = blob;
+	*bytes = total;
+	*columnCount = (int32_t)n;
+	return CVX_OK;
+}
+
+void cvxh_free(void *p) { std::free(p); }
 
 int cvxh_world_info_get(const cvxh_world_set *worlds, int lod, cvxh_world_info *out)
 {

@@ -30,7 +30,7 @@ EXPORTS = [
     "cvx_clear_raybuffer", "cvx_read_raybuffer", "cvx_blit_segments", "cvx_blit_segments_batch", "cvx_raybuffer_device_ptr",
     "cvx_screen_device_ptr", "cvx_last_draw_ms", "cvx_enable_counters", "cvx_get_counters",
     "cvx_get_raybuffer_layout", "cvx_version", "cvx_bind_raybuffers", "cvx_draw_time_stats", "cvx_copy_rows", "cvx_draw_segments_placed",
-    "cvx_world_downsample", "cvx_world_build_lods", "cvx_free",
+    "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -144,6 +144,9 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_build_lods.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
         L.cvx_free.argtypes = [C.c_void_p]
+        L.cvx_world_set_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int]
+        L.cvx_world_edit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.cvx_world_edit_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -242,6 +245,27 @@ class Context:
                 lib().cvx_free(outs[k])
         self.last_build_lods_ms = ms.value
         return WorldSet.from_blobs(world_set.dims, blobs)
+
+    # -- editing the uploaded world (World.SetVoxelColumn, World.cs:151) -------
+    def set_columns(self, lod: int, x0: int, z0: int, size_x: int, size_z: int, blob, column_count: int) -> None:
+        """Replaces a size_x x size_z rectangle of level `lod` (its own columns) with the columns of a sub-world blob
+        (WorldSet.extract_region).  Ordered on the context's stream: earlier draws see the old world, later ones the new."""
+        buf = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else np.ascontiguousarray(blob, dtype=np.uint8)
+        self._check(lib().cvx_world_set_columns(self._h, lod, x0, z0, size_x, size_z, buf.ctypes.data, buf.size, column_count))
+
+    def edit(self, x0: int, z0: int, size_x: int, size_z: int, blob, column_count: int, level_count: int = LOD_LEVELS - 1) -> float:
+        """Replaces a LOD-0 rectangle and rebuilds LOD 1..level_count over it on the device (x0, z0, size_x, size_z multiples of
+        2^level_count).  Returns the device milliseconds of the edit."""
+        buf = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else np.ascontiguousarray(blob, dtype=np.uint8)
+        ms = C.c_float()
+        self._check(lib().cvx_world_edit(self._h, x0, z0, size_x, size_z, buf.ctypes.data, buf.size, column_count, level_count, C.byref(ms)))
+        return ms.value
+
+    def edit_stats(self):
+        """(bytes of the arena in use, bytes edits left behind, bytes of headroom left in the edit tails)."""
+        used, abandoned, spare = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(lib().cvx_world_edit_stats(self._h, C.byref(used), C.byref(abandoned), C.byref(spare)))
+        return used.value, abandoned.value, spare.value
 
     def set_resolution(self, width: int, height: int) -> None:
         """RenderManager.SetResolution (RenderManager.cs:94-109)."""

@@ -95,6 +95,9 @@ def lib() -> C.CDLL:
         L.cvxh_last_error.restype = C.c_char_p
         L.cvxh_version.restype = C.c_char_p
         L.cvxh_world_lod0_voxels.restype = C.c_int64
+        L.cvxh_world_extract_region.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int32)]
+        L.cvxh_free.argtypes = [C.c_void_p]
         L.cvxh_world_lod0_voxels.argtypes = [C.c_void_p]
         L.cvxh_world_from_obj.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvxh_world_procedural.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
@@ -225,6 +228,16 @@ class WorldSet:
         i = self.info(lod)
         buf = (C.c_uint8 * i.byteLength).from_address(i.storage)
         return np.frombuffer(buf, dtype=np.uint8)
+
+    def extract_region(self, lod: int, x0: int, z0: int, size_x: int, size_z: int):
+        """A rectangle of one level (in its own columns) as a sub-world blob for Context.set_columns / Context.edit: (blob bytes,
+        column count); column (x, z) is header (x - x0) * size_z + (z - z0)."""
+        out, nbytes, columns = C.c_void_p(), C.c_int64(), C.c_int32()
+        _check(lib().cvxh_world_extract_region(self._h, lod, x0, z0, size_x, size_z, C.byref(out), C.byref(nbytes), C.byref(columns)))
+        try:
+            return C.string_at(out.value, nbytes.value), columns.value
+        finally:
+            lib().cvxh_free(out)
 
     def close(self) -> None:
         if self._h:

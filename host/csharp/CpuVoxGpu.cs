@@ -73,6 +73,11 @@ namespace CpuVox.Gpu
 		[DllImport(Lib)] public static extern int cvx_world_build_lods(IntPtr ctx, void* storage, long byteLength, int dimX, int dimY, int dimZ, int columnCount, int levelCount,
 		                                                               IntPtr* outStorage, long* outByteLength, int* outColumnCount, out float outDeviceMs);
 		[DllImport(Lib)] public static extern void cvx_free(IntPtr p);
+		// World.SetVoxelColumn (World.cs:151) for a rectangle of one level / a LOD-0 rectangle + its LOD refresh, on the device-resident world
+		[DllImport(Lib)] public static extern int cvx_world_set_columns(IntPtr ctx, int lod, int x0, int z0, int sizeX, int sizeZ, void* storage, long byteLength, int columnCount);
+		[DllImport(Lib)] public static extern int cvx_world_edit(IntPtr ctx, int x0, int z0, int sizeX, int sizeZ, void* storage, long byteLength, int columnCount, int levelCount,
+		                                                         out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_world_edit_stats(IntPtr ctx, out long usedBytes, out long abandonedBytes, out long spareBytes);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

@@ -332,6 +332,29 @@ int cvx_world_build_lods(cvx_context *ctx, const void *storage, int64_t byteLeng
                          void **outStorage, int64_t *outByteLength, int32_t *outColumnCount, float *outDeviceMs);
 void cvx_free(void *p);
 
+/* ---- editing the uploaded world in place (World.SetVoxelColumn, World.cs:151-159) -----------------------------------------------------
+ * `storage` is a sub-world blob in the reference's layout: `columnCount` 12-byte RLEColumn headers, then the element pool; column (x, z) of
+ * the rectangle is header (x - x0) * sizeZ + (z - z0) (World.GetIndexKnownInBounds order; cvxh_world_extract_region makes such a blob from a
+ * host world).  Coordinates are in the level's own columns.  Every column is validated on the host like cvx_world_upload's before anything on
+ * the device changes: any failure returns CVX_ERR_INVALID_ARGUMENT (or CVX_ERR_CAPACITY: the 4 GiB arena, 2^30 colour slots per level) and
+ * leaves the world as it was.  The edit is enqueued on the context's stream behind what is already there and the call returns once it is done:
+ * a draw enqueued before it (CVX_DRAW_ASYNC included) renders the old world, every draw after it the new one.  Levels uploaded but not drawn
+ * yet are placed in the arena first (what the next draw would do).  Colours and run-list blocks go to the column's old place when they fit,
+ * else to a tail behind the level's colours / run list (a 4 x 8 colour block that gets too shallow moves there as a whole); the first edit of
+ * a level lays the arena out again with headroom, and the arena grows when the headroom runs out.  Space edits leave behind is not compacted:
+ * cvx_world_edit_stats reports it, and uploading the level again reclaims it.  With several GPUs (one context per rank), every rank applies
+ * the same edit to its own context. */
+/* World.SetVoxelColumn for a sizeX x sizeZ rectangle of one level (the caller supplies that level's columns). */
+int cvx_world_set_columns(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, const void *storage, int64_t byteLength, int columnCount);
+/* Replaces a rectangle of LOD 0 and rebuilds LOD 1 .. levelCount (0 .. 5) over it on the device (World.DownSample of the sub-world, as
+ * cvx_world_build_lods): x0, z0, sizeX, sizeZ must be multiples of 2^levelCount, so that every coarse column is rebuilt from its complete
+ * footprint.  outDeviceMs (may be NULL): device time of the edit, from the sub-blob's upload to the last level's patch. */
+int cvx_world_edit(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const void *storage, int64_t byteLength, int columnCount, int levelCount,
+                   float *outDeviceMs);
+/* Arena occupancy (any pointer may be NULL): bytes in use (abandoned ones included), bytes that edits left behind, bytes of headroom left in
+ * the edit tails.  A context that never edited reports its whole arena as used. */
+int cvx_world_edit_stats(cvx_context *ctx, int64_t *usedBytes, int64_t *abandonedBytes, int64_t *spareBytes);
+
 const char *cvx_version(void);
 
 #ifdef __cplusplus

@@ -57,6 +57,11 @@ void cvxh_world_free(cvxh_world_set *worlds);
 int cvxh_world_lod_count(const cvxh_world_set *worlds);
 int cvxh_world_info_get(const cvxh_world_set *worlds, int lod, cvxh_world_info *out);
 int64_t cvxh_world_lod0_voxels(const cvxh_world_set *worlds);
+/* A sizeX x sizeZ rectangle of level `lod` (in its own columns) as a sub-world blob in the reference's layout: sizeX * sizeZ headers, column
+ * (x, z) at (x - x0) * sizeZ + (z - z0), then each column's guards, runs and colours -- what cvx_world_set_columns / cvx_world_edit take.
+ * *out is released with cvxh_free. */
+int cvxh_world_extract_region(const cvxh_world_set *worlds, int lod, int x0, int z0, int sizeX, int sizeZ, void **out, int64_t *bytes, int32_t *columnCount);
+void cvxh_free(void *p);
 
 /* WorldBuilder (WordBuilder.cs:14-130) for explicit voxel lists: x,y,z,argb arrays of n entries
  * (argb = bytes A,R,G,B in memory order, little-endian packed). */
