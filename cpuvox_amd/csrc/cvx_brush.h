@@ -1,0 +1,320 @@
+// cvx_brush.h -- voxel brushes and ray picking on the device-resident world (cvx_world_brush / cvx_world_pick, cvx_brush.hip).
+//
+// The per-column rules, written once for the device AND the host (tests/test_world_brush_cpu.py compiles them with g++ through
+// tests/brush_rules.cpp and compares them with numpy models):
+//   ArenaColumn  what a LOD-0 record of the arena says about its column: the solid runs top-down (records with 1 .. 3 runs, run-list blocks),
+//                each with its colour index; colours at colorsBase + index << colorShift (blocks of 4 x 8 columns or column after column).
+//   BrushColumn  a column after a list of strokes, emitted as the builder emits it (WordBuilder.cs:181-268): maximal runs from the top, the
+//                top air run first, ColorsIndex = solid voxels above, worldMin / worldMax as the RLEColumn constructor computes them.
+//   PickRay      the first solid voxel along a ray (a 2-D DDA over the columns, one record per step, the solid runs walked in the ray's y order).
+// Everything is read from where the record says it is: tail-moved blocks and run-list blocks of edited columns need nothing special.
+#pragma once
+
+#include <stdint.h>
+
+#include "cpuvox_gpu.h"
+#include "cvx_edit.h" // CVX_HD
+
+namespace cvxb {
+
+// ---- reading a column of the arena (LOD 0: spans in voxels) -----------------------------------------------------------------------------------
+
+struct SolidRun {
+	uint32_t bottom, top; // voxels bottom .. top - 1
+	uint32_t colorsIndex; // colour of voxel y: colorsIndex + (top - 1 - y)
+};
+
+struct ArenaColumn {
+	uint32_t x, y, z, w;   // the record (cvx_device.h)
+	const uint32_t *runs;  // the level's run list, 2 words per entry
+
+	CVX_HD uint32_t Count() const { return x == 0u ? 0u : ((x >> 30) != 0u ? (x >> 30) : w); }
+	CVX_HD uint32_t ColorsBase() const { return x & 0x3FFFFFFFu; }
+	CVX_HD uint32_t WorldMin() const { return y & 0xFFFFu; }
+	CVX_HD uint32_t WorldMax() const { return y >> 16; }
+	// solid run k (0 = the top one) of a column with Count() > k
+	CVX_HD SolidRun Run(uint32_t k) const
+	{
+		const uint32_t code = x >> 30;
+		if (code == 0u) {
+			const uint32_t w0 = runs[2u * (z + k)], w1 = runs[2u * (z + k) + 1u];
+			return SolidRun{ w0 & 0xFFFFu, (w0 >> 16) + 1u, w1 & 0xFFFFu };
+		}
+		// record runs: run 0 = [w.lo, worldMax], run 1 = [z.lo, w.hi + 1], run 2 = [worldMin, z.hi + 1] (cvx_device.h); indices derived
+		const uint32_t b0 = (code == 1u) ? WorldMin() : (w & 0xFFFFu), t0 = WorldMax();
+		if (k == 0u) { return SolidRun{ b0, t0, 0u }; }
+		const uint32_t b1 = (code == 2u) ? WorldMin() : (z & 0xFFFFu), t1 = (w >> 16) + 1u;
+		if (k == 1u) { return SolidRun{ b1, t1, t0 - b0 }; }
+		return SolidRun{ WorldMin(), (z >> 16) + 1u, (t0 - b0) + (t1 - b1) };
+	}
+};
+
+// ---- strokes ----------------------------------------------------------------------------------------------------------------------------------
+
+// Largest h >= 0 with h * h <= v (v >= 0): a float estimate corrected in integers, so that nothing but integers decides what is inside a sphere.
+CVX_HD inline int64_t ISqrt(int64_t v)
+{
+	int64_t h = (int64_t)__builtin_sqrt((double)v);
+	while (h > 0 && h * h > v) { h--; }
+	while ((h + 1) * (h + 1) <= v) { h++; }
+	return h;
+}
+
+// The y interval [lo, hi) a stroke covers in column (cx, cz), clipped to [0, dimY); lo >= hi: none.
+CVX_HD inline void StrokeSpan(const cvx_brush_stroke &s, int64_t cx, int64_t cz, int64_t dimY, int64_t *lo, int64_t *hi)
+{
+	int64_t l = 0, h = 0;
+	if (s.shape == CVX_SHAPE_BOX) {
+		if (cx >= s.a[0] && cx < s.b[0] && cz >= s.a[2] && cz < s.b[2]) { l = s.a[1]; h = s.b[1]; }
+	} else {
+		const int64_t r = s.b[0], dx = cx - s.a[0], dz = cz - s.a[2];
+		const int64_t left = r * r - dx * dx - dz * dz;
+		if (left >= 0) {
+			const int64_t e = ISqrt(left);
+			l = (int64_t)s.a[1] - e;
+			h = (int64_t)s.a[1] + e + 1;
+		}
+	}
+	*lo = l < 0 ? 0 : l;
+	*hi = h > dimY ? dimY : h;
+}
+
+// ---- one column after the strokes -------------------------------------------------------------------------------------------------------------
+
+struct BrushResult {
+	uint32_t runCount;       // runs, air ones included (0: the column is empty)
+	uint32_t colours;        // solid voxels
+	uint32_t worldMin, worldMax;
+	bool overLimit;          // a run count, run length or colour index the format cannot hold
+};
+
+// Walks the column (cx, cz) top-down after `n` strokes.  Every voxel ends as the fold of the strokes that cover it over what the arena holds:
+// FILL -> solid(argb), CARVE -> air, PAINT -> solid ? solid(argb) : air.  So within a y span where the same strokes cover the column and the
+// arena's column does not change between solid and air, every voxel has the same fate: the walk goes span by span, the span ends at the
+// next boundary of a stroke interval or an arena run below it.
+// Out (may be null): runs[r] = colorsIndex | length << 16 (colorsIndex 0xFFFF for air), colours[k] = the k-th solid voxel's colour from the top
+// (colourSlots: the arena's colour array, 4-byte slots, read at the column's colorsBase + index << (colorShift - 2)).
+CVX_HD inline BrushResult BrushColumn(const ArenaColumn &col, const uint32_t *colourSlots, int colorShift, const cvx_brush_stroke *strokes, int n,
+                                      int64_t cx, int64_t cz, int dimY, uint32_t *outRuns, uint32_t *outColours)
+{
+	BrushResult res{ 0u, 0u, 0u, 0u, false };
+	const uint32_t solidRuns = col.Count();
+	uint32_t k = 0;                      // the arena run at or below y
+	bool curSolid = false;
+	int64_t curLength = 0, curIndex = 0; // the run being emitted
+	int64_t lowest = -1, highest = -1;   // solid voxels
+	int64_t y = (int64_t)dimY - 1;
+	while (y >= 0) {
+		// the arena: solid run k or the air above it
+		while (k < solidRuns && (int64_t)col.Run(k).bottom > y) { k++; }
+		SolidRun run{ 0u, 0u, 0u };
+		bool origSolid = false;
+		int64_t bottom = 0;
+		if (k < solidRuns) {
+			run = col.Run(k);
+			origSolid = (int64_t)run.top > y;
+			bottom = origSolid ? (int64_t)run.bottom : (int64_t)run.top;
+		}
+		// the strokes: the last FILL / CARVE and the last FILL / PAINT that cover y, and where the span ends
+		int lastFC = -1, lastFP = -1;
+		for (int s = 0; s < n; s++) {
+			int64_t lo, hi;
+			StrokeSpan(strokes[s], cx, cz, dimY, &lo, &hi);
+			if (lo >= hi) { continue; }
+			if (lo <= y && y < hi) {
+				if (strokes[s].op != CVX_BRUSH_PAINT) { lastFC = s; }
+				if (strokes[s].op != CVX_BRUSH_CARVE) { lastFP = s; }
+				bottom = lo > bottom ? lo : bottom;
+			} else if (hi <= y) {
+				bottom = hi > bottom ? hi : bottom;
+			}
+		}
+		const bool solid = lastFC < 0 ? origSolid : strokes[lastFC].op == CVX_BRUSH_FILL;
+		const bool painted = lastFP >= 0 && lastFP >= lastFC;
+		const int64_t length = y + 1 - bottom;
+		if (solid != curSolid || curLength == 0) {
+			if (curLength > 0) {
+				if (outRuns) { outRuns[res.runCount] = (curSolid ? (uint32_t)curIndex : 0xFFFFu) | ((uint32_t)curLength << 16); }
+				if (curLength > 32767) { res.overLimit = true; }
+				res.runCount++;
+			}
+			curSolid = solid;
+			curLength = 0;
+			curIndex = res.colours;
+			if (solid && curIndex > 32767) { res.overLimit = true; }
+		}
+		curLength += length;
+		if (solid) {
+			if (outColours) {
+				for (int64_t v = y; v >= bottom; v--) {
+					outColours[res.colours + (uint32_t)(y - v)] = painted ? strokes[lastFP].argb
+					                                                        : colourSlots[col.ColorsBase() + ((run.colorsIndex + (run.top - 1u - (uint32_t)v)) << (colorShift - 2))];
+				}
+			}
+			res.colours += (uint32_t)length;
+			if (highest < 0) { highest = y + 1; }
+			lowest = bottom;
+		}
+		y = bottom - 1;
+	}
+	if (curLength > 0) {
+		if (outRuns) { outRuns[res.runCount] = (curSolid ? (uint32_t)curIndex : 0xFFFFu) | ((uint32_t)curLength << 16); }
+		if (curLength > 32767) { res.overLimit = true; }
+		res.runCount++;
+	}
+	if (res.colours == 0u) { // the empty column: RunCount 0, no elements
+		res.runCount = 0u;
+		res.overLimit = false;
+		return res;
+	}
+	if (res.runCount > 65535u) { res.overLimit = true; }
+	res.worldMin = (uint32_t)lowest & 0xFFFFu;
+	res.worldMax = (uint32_t)highest & 0xFFFFu;
+	return res;
+}
+
+// ---- picking ----------------------------------------------------------------------------------------------------------------------------------
+
+struct PickWorld {
+	const uint32_t *records;    // LOD 0's records (uint4 each), row-major with 2^rowShift per row; one row + 4 records either side are readable
+	const uint32_t *runs;       // run list, 2 words per entry
+	const uint8_t *colours;     // colour array (bytes)
+	int rowShift, colorShift;
+	int dimX, dimY, dimZ;
+};
+
+struct PickResult {
+	int32_t voxel[3];
+	int32_t face;
+	uint32_t argb;
+	float t;
+};
+
+// The traversal rule, float64 throughout (one rule, so that a float64 model can say which rays it resolves unambiguously):
+//   1. clip: per axis with d != 0 the slab [0, dim] gives t0 <= t1 (t = (plane - o) * (1 / d)); tEnter = max(0, t0's), tExit = min(maxT, t1's);
+//      the axis whose t0 > 0 set tEnter is the entry face (ties: the lower axis); an axis with d == 0 and o outside [0, dim) misses.
+//   2. start inside the box (tEnter == 0 through no face): the voxel floor(o) solid -> that voxel, face 6, t 0.
+//   3. columns: the column of o + tEnter * d (clamped into the world); per step the ray's t interval in the column is [tc0, tc1], tc1 = the
+//      nearer of the next x / z column planes and tExit.  Its voxels, in ray order: down (d.y < 0) ceil(ya) - 1 .. floor(yb), up floor(ya) ..
+//      ceil(yb) - 1, level floor(o.y) (ya / yb: y at tc0 / tc1; clamped into [0, dimY)).  The first solid one of them is the hit: the first
+//      voxel of the column -> the face the column was entered through, t = tc0; a later one (or any one in the column a ray starts in) -> its +Y
+//      (down) or -Y (up) face, t = the plane's.
+//   4. step to the nearer plane (x on a tie: the diagonal step takes two steps, the second one of length 0); stop at tExit.
+CVX_HD inline PickResult PickMiss(float maxT) { return PickResult{ { -1, -1, -1 }, -1, 0u, maxT }; }
+
+struct alignas(16) Record { uint32_t x, y, z, w; };
+
+CVX_HD inline Record PickRecord(const PickWorld &W, int64_t at) { return *reinterpret_cast<const Record *>(W.records + 4 * at); }
+
+CVX_HD inline int64_t ClampY(double v, int64_t lastY) { return v < 0.0 ? 0 : (v > (double)lastY ? lastY : (int64_t)v); }
+CVX_HD inline bool Finite(double v) { return v > -1e30 && v < 1e30; }
+
+CVX_HD inline uint32_t PickColour(const PickWorld &W, const ArenaColumn &col, const SolidRun &run, uint32_t v)
+{
+	const uint32_t index = run.colorsIndex + (run.top - 1u - v);
+	const uint64_t byte = (uint64_t)col.ColorsBase() * 4u + ((uint64_t)index << W.colorShift);
+	const uint8_t *p = W.colours + byte;
+	return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+CVX_HD inline PickResult PickRay(const PickWorld &W, const float originF[3], const float directionF[3], float maxTF)
+{
+	const double o[3] = { originF[0], originF[1], originF[2] }, d[3] = { directionF[0], directionF[1], directionF[2] };
+	const double dim[3] = { (double)W.dimX, (double)W.dimY, (double)W.dimZ };
+	double inv[3];
+	double tEnter = 0.0, tExit = (double)maxTF;
+	int enterAxis = -1;
+	for (int a = 0; a < 3; a++) {
+		if (!Finite(o[a]) || !Finite(d[a])) { return PickMiss(maxTF); }
+		if (d[a] == 0.0) {
+			inv[a] = 0.0;
+			if (!(o[a] >= 0.0 && o[a] < dim[a])) { return PickMiss(maxTF); }
+			continue;
+		}
+		inv[a] = 1.0 / d[a];
+		double t0 = (0.0 - o[a]) * inv[a], t1 = (dim[a] - o[a]) * inv[a];
+		if (t0 > t1) { const double s = t0; t0 = t1; t1 = s; }
+		if (t0 > tEnter) { tEnter = t0; enterAxis = a; }
+		if (t1 < tExit) { tExit = t1; }
+	}
+	if (!(tEnter <= tExit)) { return PickMiss(maxTF); }
+	const int64_t lastY = W.dimY - 1;
+	const int64_t cx0 = ClampY(__builtin_floor(o[0] + tEnter * d[0]), W.dimX - 1), cz0 = ClampY(__builtin_floor(o[2] + tEnter * d[2]), W.dimZ - 1);
+	int64_t cx = cx0, cz = cz0;
+	const int stepX = d[0] > 0.0 ? 1 : -1, stepZ = d[2] > 0.0 ? 1 : -1;
+	const int64_t recordStepX = (int64_t)stepX << W.rowShift, recordStepZ = stepZ;
+	int face = enterAxis < 0 ? 6 : 2 * enterAxis + (d[enterAxis] > 0.0 ? 0 : 1);
+	int64_t at = (cx << W.rowShift) + cz;
+	Record rec = PickRecord(W, at);
+	if (enterAxis < 0) { // 2. the origin's own voxel
+		const ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, W.runs };
+		const uint32_t v = (uint32_t)ClampY(__builtin_floor(o[1]), lastY);
+		for (uint32_t k = 0; k < col.Count(); k++) {
+			const SolidRun run = col.Run(k);
+			if (v >= run.bottom && v < run.top) {
+				return PickResult{ { (int32_t)cx, (int32_t)v, (int32_t)cz }, 6, PickColour(W, col, run, v), 0.0f };
+			}
+		}
+	}
+	double tc0 = tEnter;
+	const bool down = d[1] < 0.0, level = d[1] == 0.0;
+	for (int64_t guard = (int64_t)W.dimX + W.dimZ + 2; guard > 0; guard--) {
+		const double tx = d[0] != 0.0 ? ((double)(cx + (stepX > 0 ? 1 : 0)) - o[0]) * inv[0] : __builtin_inf();
+		const double tz = d[2] != 0.0 ? ((double)(cz + (stepZ > 0 ? 1 : 0)) - o[2]) * inv[2] : __builtin_inf();
+		const bool stepAlongX = tx <= tz;
+		const double tNext = stepAlongX ? tx : tz;
+		const double tc1 = tNext < tExit ? tNext : tExit;
+		const int64_t nextAt = at + (stepAlongX ? recordStepX : recordStepZ);
+		const Record next = PickRecord(W, nextAt); // one step ahead (the tables have a guard row on both sides)
+		const ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, W.runs };
+		if (col.x != 0u) {
+			const double ya = o[1] + tc0 * d[1], yb = o[1] + tc1 * d[1];
+			int64_t vA, vB;
+			if (level) {
+				vA = vB = ClampY(__builtin_floor(o[1]), lastY);
+			} else if (down) {
+				vA = ClampY(__builtin_ceil(ya) - 1.0, lastY);
+				vB = ClampY(__builtin_floor(yb), lastY);
+			} else {
+				vA = ClampY(__builtin_floor(ya), lastY);
+				vB = ClampY(__builtin_ceil(yb) - 1.0, lastY);
+			}
+			const int64_t lo = vA < vB ? vA : vB, hi = vA < vB ? vB : vA;
+			const bool empty = level ? false : (down ? vA < vB : vA > vB);
+			if (!empty && hi >= (int64_t)col.WorldMin() && lo < (int64_t)col.WorldMax()) {
+				int64_t best = -1;
+				SolidRun bestRun{ 0u, 0u, 0u };
+				for (uint32_t k = 0; k < col.Count(); k++) {
+					const SolidRun run = col.Run(k);
+					if ((int64_t)run.bottom > hi || (int64_t)run.top - 1 < lo) { continue; }
+					const int64_t v = down || level ? ((int64_t)run.top - 1 < vA ? (int64_t)run.top - 1 : vA) : ((int64_t)run.bottom > vA ? (int64_t)run.bottom : vA);
+					if (best < 0 || (down || level ? v > best : v < best)) { best = v; bestRun = run; }
+				}
+				if (best >= 0) {
+					PickResult hit;
+					hit.voxel[0] = (int32_t)cx;
+					hit.voxel[1] = (int32_t)best;
+					hit.voxel[2] = (int32_t)cz;
+					hit.argb = PickColour(W, col, bestRun, (uint32_t)best);
+					if (best == vA && face != 6) { // (face 6: the first column of a ray that starts in it; its own voxel is air)
+						hit.face = face;
+						hit.t = (float)tc0;
+					} else {
+						hit.face = down ? 3 : 2;
+						hit.t = (float)(((double)(down ? best + 1 : best) - o[1]) * inv[1]);
+					}
+					return hit;
+				}
+			}
+		}
+		if (tNext >= tExit) { break; }
+		if (stepAlongX) { cx += stepX; face = stepX > 0 ? 0 : 1; } else { cz += stepZ; face = stepZ > 0 ? 4 : 5; }
+		if (cx < 0 || cx >= W.dimX || cz < 0 || cz >= W.dimZ) { break; }
+		tc0 = tNext;
+		at = nextAt;
+		rec = next;
+	}
+	return PickMiss(maxTF);
+}
+
+} // namespace cvxb

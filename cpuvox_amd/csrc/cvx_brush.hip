@@ -1,0 +1,327 @@
+// cvx_brush.hip -- libcpuvox_gpu.so, voxel brushes (cvx_world_brush) and ray picking (cvx_world_pick, cvx_world_pick_device) on the device-resident
+// world.  See include/cpuvox_gpu.h for the contract, cvx_brush.h for the per-column rules and DESIGN.md sections 3 and 4.
+//
+// A brush is cvx_world_edit with the sub-world built on the device instead of uploaded:
+//   1. count  (a thread per LOD-0 column of the rounded rectangle): the column from the arena, the strokes in order (cvxb::BrushColumn), the
+//             elements its new column needs ([guard][runs][guard][colours]); columns the format cannot hold raise a flag
+//   2. the counts are prefix-scanned into element offsets; ONE copy brings the total and the flag to the host
+//   3. write  (same threads): the sub-world blob in the reference's layout, 12-byte RLEColumn headers then the element pool
+//   4. cvxi::EditFromDevice: the blob goes through cvx_world_edit's machinery (records, tails, growth, LOD 1 .. levelCount) unchanged.
+// Nothing in the arena is written before step 4, so a rejected brush leaves the world as it was.
+// A pick is one thread per ray (a wave per 64 rays) walking LOD 0's records (cvxb::PickRay).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "cvx_brush.h"
+#include "cvx_context.h"
+
+using cvxi::Fail;
+
+namespace cvxbrush {
+
+struct BrushArgs {
+	const uint8_t *arena;
+	uint32_t recordsOff, runsOff, elementsOff;
+	int rowShift, colorShift, dimY;
+	int x0, z0, sizeZ, n;
+	const cvx_brush_stroke *strokes;
+	int strokeCount;
+	uint32_t *counts;              // per column: elements (-> offset after the scan)
+	unsigned int *overLimit;
+	uint32_t *headers;             // write: the sub-world blob, n headers of 3 words
+	uint32_t *elements;
+};
+
+__device__ __forceinline__ cvxb::ArenaColumn Column(const BrushArgs &A, int cx, int cz)
+{
+	const uint4 r = reinterpret_cast<const uint4 *>(A.arena + A.recordsOff)[((size_t)cx << A.rowShift) + (size_t)cz];
+	return cvxb::ArenaColumn{ r.x, r.y, r.z, r.w, reinterpret_cast<const uint32_t *>(A.arena + A.runsOff) };
+}
+
+__global__ __launch_bounds__(256) void brush_count_kernel(BrushArgs A)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= A.n) { return; }
+	const int cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
+	const uint32_t *colours = reinterpret_cast<const uint32_t *>(A.arena + A.elementsOff);
+	const cvxb::BrushResult r = cvxb::BrushColumn(Column(A, cx, cz), colours, A.colorShift, A.strokes, A.strokeCount, cx, cz, A.dimY, nullptr, nullptr);
+	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
+	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+}
+
+__global__ __launch_bounds__(256) void brush_write_kernel(BrushArgs A)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= A.n) { return; }
+	const int cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
+	const uint32_t *colours = reinterpret_cast<const uint32_t *>(A.arena + A.elementsOff);
+	const uint32_t off = A.counts[i];
+	uint32_t *e = A.elements + off;
+	// (the colours go behind the runs' second guard, a place known once the runs are counted: the walk runs twice, the second time writing)
+	const cvxb::ArenaColumn col = Column(A, cx, cz);
+	const cvxb::BrushResult r = cvxb::BrushColumn(col, colours, A.colorShift, A.strokes, A.strokeCount, cx, cz, A.dimY, nullptr, nullptr);
+	uint32_t *h = A.headers + 3 * (size_t)i;
+	if (r.runCount == 0u) {
+		h[0] = 0u;
+		h[1] = 0u;
+		h[2] = 0u;
+		return;
+	}
+	cvxb::BrushColumn(col, colours, A.colorShift, A.strokes, A.strokeCount, cx, cz, A.dimY, e + 1, e + r.runCount + 2u);
+	e[0] = 0u;
+	e[r.runCount + 1u] = 0u;
+	h[0] = off;
+	h[1] = r.runCount | (r.worldMin << 16);
+	h[2] = r.worldMax;
+}
+
+__global__ __launch_bounds__(CVX_WAVE) void pick_kernel(cvxb::PickWorld W, int rayCount, const cvx_pick_ray *rays, cvx_pick_hit *hits)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= rayCount) { return; }
+	const cvx_pick_ray ray = rays[i];
+	const cvxb::PickResult r = cvxb::PickRay(W, ray.origin, ray.direction, ray.maxT);
+	cvx_pick_hit out;
+	out.voxel[0] = r.voxel[0];
+	out.voxel[1] = r.voxel[1];
+	out.voxel[2] = r.voxel[2];
+	out.face = r.face;
+	out.argb = r.argb;
+	out.t = r.t;
+	hits[i] = out;
+}
+
+} // namespace cvxbrush
+
+namespace {
+
+constexpr unsigned kThreads = 256;
+
+unsigned Grid(size_t n, unsigned threads = kThreads) { return (unsigned)((n + threads - 1) / threads); }
+
+int Prepare(cvx_context *ctx)
+{
+	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	CVX_HIP(ctx, hipSetDevice(ctx->device));
+	return cvxi::SyncWorld(ctx);
+}
+
+// The columns [x0, x1) x [z0, z1) a stroke can touch, clipped to the world; false: none (the stroke does nothing)
+bool Footprint(const cvx_brush_stroke &s, int dimX, int dimY, int dimZ, int64_t *x0, int64_t *x1, int64_t *z0, int64_t *z1)
+{
+	int64_t lo[3], hi[3];
+	for (int a = 0; a < 3; a++) {
+		if (s.shape == CVX_SHAPE_BOX) {
+			lo[a] = s.a[a];
+			hi[a] = s.b[a];
+		} else {
+			lo[a] = (int64_t)s.a[a] - s.b[0];
+			hi[a] = (int64_t)s.a[a] + s.b[0] + 1;
+		}
+	}
+	const int64_t dim[3] = { dimX, dimY, dimZ };
+	for (int a = 0; a < 3; a++) {
+		lo[a] = std::max<int64_t>(lo[a], 0);
+		hi[a] = std::min<int64_t>(hi[a], dim[a]);
+		if (lo[a] >= hi[a]) { return false; }
+	}
+	*x0 = lo[0];
+	*x1 = hi[0];
+	*z0 = lo[2];
+	*z1 = hi[2];
+	return true;
+}
+
+cvxb::PickWorld PickWorldOf(const cvx_context *ctx)
+{
+	const DevWorld &W = ctx->hostWorld;
+	const DevWorldLevel &L = W.level[0];
+	cvxb::PickWorld P;
+	P.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
+	P.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
+	P.colours = ctx->arena + L.elementsOff;
+	P.rowShift = L.rowShift;
+	P.colorShift = L.colorShift;
+	P.dimX = W.dimX;
+	P.dimY = W.dimY;
+	P.dimZ = W.dimZ;
+	return P;
+}
+
+} // namespace
+
+namespace cvxi {
+void FreeBrushState(cvx_context *ctx)
+{
+	if (ctx->pickScratch) { (void)hipFree(ctx->pickScratch); }
+	ctx->pickScratch = nullptr;
+	ctx->pickScratchBytes = 0;
+}
+} // namespace cvxi
+
+extern "C" {
+
+int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strokeCount, int levelCount, float *outDeviceMs)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	if (!strokes || strokeCount <= 0 || strokeCount > CVX_BRUSH_MAX_STROKES) {
+		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "strokeCount %d outside 1 .. %d", strokeCount, CVX_BRUSH_MAX_STROKES);
+	}
+	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
+	for (int s = 0; s < strokeCount; s++) {
+		const cvx_brush_stroke &k = strokes[s];
+		if (k.op < CVX_BRUSH_FILL || k.op > CVX_BRUSH_PAINT) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: bad op %d", s, k.op); }
+		if (k.shape != CVX_SHAPE_BOX && k.shape != CVX_SHAPE_SPHERE) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: bad shape %d", s, k.shape); }
+		if (k.shape == CVX_SHAPE_SPHERE && (k.b[0] < 0 || k.b[0] > (1 << 30))) {
+			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: sphere radius %d outside 0 .. 2^30", s, k.b[0]);
+		}
+	}
+	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	const int dimX = ctx->hostWorld.dimX, dimY = ctx->hostWorld.dimY, dimZ = ctx->hostWorld.dimZ;
+	// the strokes that touch the world, and the rectangle: the union of their footprints rounded out to 2^levelCount, clipped to the world
+	std::vector<cvx_brush_stroke> live;
+	int64_t x0 = INT64_MAX, x1 = INT64_MIN, z0 = INT64_MAX, z1 = INT64_MIN;
+	for (int s = 0; s < strokeCount; s++) {
+		int64_t a0, a1, b0, b1;
+		if (!Footprint(strokes[s], dimX, dimY, dimZ, &a0, &a1, &b0, &b1)) { continue; }
+		live.push_back(strokes[s]);
+		x0 = std::min(x0, a0);
+		x1 = std::max(x1, a1);
+		z0 = std::min(z0, b0);
+		z1 = std::max(z1, b1);
+	}
+	if (outDeviceMs) { *outDeviceMs = 0.f; }
+	if (live.empty()) { return CVX_OK; }
+	const int64_t align = ((int64_t)1 << levelCount) - 1;
+	x0 &= ~align;
+	z0 &= ~align;
+	x1 = std::min<int64_t>((x1 + align) & ~align, dimX);
+	z1 = std::min<int64_t>((z1 + align) & ~align, dimZ);
+	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
+		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dimX, dimZ, (long long)align + 1);
+	}
+	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
+	const int n = sizeX * sizeZ;
+	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "a brush over %d x %d columns", sizeX, sizeZ); }
+	int rc = Prepare(ctx);
+	if (rc != CVX_OK) { return rc; }
+
+	hipEvent_t ev[2] = { nullptr, nullptr };
+	uint8_t *scratch = nullptr, *dSrc = nullptr;
+	auto release = [&]() {
+		if (scratch) { (void)hipFree(scratch); }
+		if (dSrc) { (void)hipFree(dSrc); }
+		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
+	};
+	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
+	size_t bytes = 0;
+	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	const size_t oStrokes = carve(live.size() * sizeof(cvx_brush_stroke)), oCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8);
+	struct { unsigned long long total, overLimit; } host = { 0, 0 };
+	cvxbrush::BrushArgs A{};
+	hipError_t e = hipEventCreate(&ev[0]);
+	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
+	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
+	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oStrokes, live.data(), live.size() * sizeof(cvx_brush_stroke), hipMemcpyHostToDevice, ctx->stream); }
+	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, 2 * 8, ctx->stream); }
+	if (e == hipSuccess) {
+		const DevWorldLevel &L = ctx->hostWorld.level[0];
+		A.arena = ctx->arena;
+		A.recordsOff = L.recordsOff;
+		A.runsOff = L.runsOff;
+		A.elementsOff = L.elementsOff;
+		A.rowShift = L.rowShift;
+		A.colorShift = L.colorShift;
+		A.dimY = dimY;
+		A.x0 = (int)x0;
+		A.z0 = (int)z0;
+		A.sizeZ = sizeZ;
+		A.n = n;
+		A.strokes = reinterpret_cast<const cvx_brush_stroke *>(scratch + oStrokes);
+		A.strokeCount = (int)live.size();
+		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
+		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
+		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
+		// 1, 2. count, scan, one copy back
+		hipLaunchKernelGGL(cvxbrush::brush_count_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
+		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
+		e = hipGetLastError();
+		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
+		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
+	}
+	if (e != hipSuccess) {
+		release();
+		return Fail(ctx, CVX_ERR_HIP, "brush failed: %s", hipGetErrorString(e));
+	}
+	if (host.overLimit) {
+		release();
+		return Fail(ctx, CVX_ERR_CAPACITY, "a brushed column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
+	}
+	if (host.total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) {
+		release();
+		return Fail(ctx, CVX_ERR_CAPACITY, "the brushed columns need %llu elements", host.total);
+	}
+	// 3. the sub-world blob
+	const size_t blobBytes = (size_t)n * 12 + (size_t)host.total * 4;
+	e = hipMalloc((void **)&dSrc, std::max<size_t>(blobBytes, 4));
+	if (e == hipSuccess) {
+		A.headers = reinterpret_cast<uint32_t *>(dSrc);
+		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
+		hipLaunchKernelGGL(cvxbrush::brush_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
+		e = hipGetLastError();
+	}
+	if (e != hipSuccess) {
+		release();
+		return Fail(ctx, CVX_ERR_HIP, "brush failed: %s", hipGetErrorString(e));
+	}
+	// 4. cvx_world_edit's machinery
+	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.total, n, levelCount, ev[1]);
+	if (rc == CVX_OK && outDeviceMs) {
+		float ms = 0.f;
+		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+		*outDeviceMs = e == hipSuccess ? ms : 0.f;
+	}
+	release();
+	return rc;
+}
+
+int cvx_world_pick_device(cvx_context *ctx, int rayCount, const cvx_pick_ray *raysDevice, cvx_pick_hit *hitsDevice, void *hipStream)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	if (rayCount < 0 || (rayCount > 0 && (!raysDevice || !hitsDevice))) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad rays / hits (rayCount %d)", rayCount); }
+	const int rc = Prepare(ctx);
+	if (rc != CVX_OK) { return rc; }
+	if (rayCount == 0) { return CVX_OK; }
+	hipStream_t stream = hipStream ? static_cast<hipStream_t>(hipStream) : ctx->stream;
+	hipLaunchKernelGGL(cvxbrush::pick_kernel, dim3(Grid((size_t)rayCount, CVX_WAVE)), dim3(CVX_WAVE), 0, stream, PickWorldOf(ctx), rayCount, raysDevice, hitsDevice);
+	CVX_HIP(ctx, hipGetLastError());
+	return CVX_OK;
+}
+
+int cvx_world_pick(cvx_context *ctx, int rayCount, const cvx_pick_ray *rays, cvx_pick_hit *hits)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	if (rayCount < 0 || (rayCount > 0 && (!rays || !hits))) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad rays / hits (rayCount %d)", rayCount); }
+	int rc = Prepare(ctx);
+	if (rc != CVX_OK) { return rc; }
+	if (rayCount == 0) { return CVX_OK; }
+	const size_t raysBytes = ((size_t)rayCount * sizeof(cvx_pick_ray) + 255) & ~(size_t)255, hitsBytes = (size_t)rayCount * sizeof(cvx_pick_hit);
+	if (ctx->pickScratchBytes < raysBytes + hitsBytes) {
+		cvxi::FreeBrushState(ctx);
+		CVX_HIP(ctx, hipMalloc(&ctx->pickScratch, raysBytes + hitsBytes));
+		ctx->pickScratchBytes = raysBytes + hitsBytes;
+	}
+	cvx_pick_ray *dRays = static_cast<cvx_pick_ray *>(ctx->pickScratch);
+	cvx_pick_hit *dHits = reinterpret_cast<cvx_pick_hit *>(static_cast<uint8_t *>(ctx->pickScratch) + raysBytes);
+	CVX_HIP(ctx, hipMemcpyAsync(dRays, rays, (size_t)rayCount * sizeof(cvx_pick_ray), hipMemcpyHostToDevice, ctx->stream));
+	rc = cvx_world_pick_device(ctx, rayCount, dRays, dHits, nullptr);
+	if (rc != CVX_OK) { return rc; }
+	CVX_HIP(ctx, hipMemcpyAsync(hits, dHits, hitsBytes, hipMemcpyDeviceToHost, ctx->stream));
+	CVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return CVX_OK;
+}
+
+} // extern "C"

@@ -72,6 +72,9 @@ struct cvx_context {
 		size_t blockCap = 0;
 	};
 	EditLevel edit[CVX_LOD_LEVELS];
+	// cvx_world_pick (cvx_brush.hip): device copies of the rays and hits of the last call, grown on demand
+	void *pickScratch = nullptr;
+	size_t pickScratchBytes = 0;
 
 	// raybuffers
 	int resX = 0, resY = 0;
@@ -160,6 +163,13 @@ int BuildLodChainOnDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t element
                           uint32_t **headers, uint32_t **elements);
 // cvx_edit.hip: releases the edit state's device tables (cvx_destroy)
 void FreeEditState(cvx_context *ctx);
+// cvx_edit.hip: cvx_world_edit behind its host validation and upload, for a valid sub-world blob already on the device at dSrc (cvx_world_brush
+// builds one there): World.DownSample of it into LOD 1 .. levelCount and the patch of every level.  `done` (may be null): recorded behind the last
+// patch.  Returns once the stream has run it.
+int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const uint8_t *dSrc, int64_t elementsOfColumns, int columnCount, int levelCount,
+                   hipEvent_t done);
+// cvx_brush.hip: releases the picking scratch (cvx_destroy)
+void FreeBrushState(cvx_context *ctx);
 } // namespace cvxi
 
 #define CVX_HIP(ctx, call)                                                                                              \

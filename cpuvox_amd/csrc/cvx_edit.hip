@@ -488,6 +488,48 @@ int ApplyJobs(cvx_context *ctx, std::vector<Job> &jobs)
 } // namespace
 
 namespace cvxi {
+// The body of cvx_world_edit behind its validation and upload: World.DownSample of the sub-world (sizeX x dimY x sizeZ) on the device -- the
+// coarse columns over the rectangle never go to the host -- and steps 1 .. 4 for LOD 0 .. levelCount.  dSrc is valid and stays the caller's.
+// On success `done` (may be null) is recorded behind the last patch; the call returns once the stream has run it.
+int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const uint8_t *dSrc, int64_t elementsOfColumns, int columnCount, int levelCount,
+                   hipEvent_t done)
+{
+	uint32_t *lodHeaders[CVX_LOD_LEVELS] = {}, *lodElements[CVX_LOD_LEVELS] = {};
+	std::vector<Job> jobs;
+	auto release = [&]() {
+		FreeJobs(jobs);
+		for (int j = 0; j < CVX_LOD_LEVELS; j++) {
+			if (lodHeaders[j]) { (void)hipFree(lodHeaders[j]); }
+			if (lodElements[j]) { (void)hipFree(lodElements[j]); }
+		}
+	};
+	if (levelCount > 0) {
+		const int rc = BuildLodChainOnDevice(ctx, dSrc, elementsOfColumns, sizeX, ctx->hostWorld.dimY, sizeZ, columnCount, levelCount, lodHeaders + 1, lodElements + 1);
+		if (rc != CVX_OK) {
+			release();
+			return rc;
+		}
+	}
+	for (int l = 0; l <= levelCount; l++) {
+		Job j;
+		j.lod = l;
+		j.x0 = x0 >> l;
+		j.z0 = z0 >> l;
+		j.sizeX = sizeX >> l;
+		j.sizeZ = sizeZ >> l;
+		j.headers = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc) : lodHeaders[l];
+		j.elements = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc + (size_t)columnCount * 12) : lodElements[l];
+		jobs.push_back(j);
+	}
+	int rc = ApplyJobs(ctx, jobs);
+	hipError_t e = hipSuccess;
+	if (rc == CVX_OK && done) { e = hipEventRecord(done, ctx->stream); }
+	const hipError_t s = hipStreamSynchronize(ctx->stream);
+	if (rc == CVX_OK && (e != hipSuccess || s != hipSuccess)) { rc = Fail(ctx, CVX_ERR_HIP, "edit failed: %s", hipGetErrorString(e != hipSuccess ? e : s)); }
+	release();
+	return rc;
+}
+
 void FreeEditState(cvx_context *ctx)
 {
 	for (cvx_context::EditLevel &E : ctx->edit) {
@@ -551,14 +593,7 @@ int cvx_world_edit(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 	if (rc != CVX_OK) { return rc; }
 	hipEvent_t ev[2] = { nullptr, nullptr };
 	uint8_t *dSrc = nullptr;
-	uint32_t *lodHeaders[CVX_LOD_LEVELS] = {}, *lodElements[CVX_LOD_LEVELS] = {};
-	std::vector<Job> jobs;
 	auto release = [&]() {
-		FreeJobs(jobs);
-		for (int j = 0; j < CVX_LOD_LEVELS; j++) {
-			if (lodHeaders[j]) { (void)hipFree(lodHeaders[j]); }
-			if (lodElements[j]) { (void)hipFree(lodElements[j]); }
-		}
 		if (dSrc) { (void)hipFree(dSrc); }
 		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
 	};
@@ -571,27 +606,7 @@ int cvx_world_edit(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 		release();
 		return Fail(ctx, CVX_ERR_HIP, "edit upload failed: %s", hipGetErrorString(e));
 	}
-	// World.DownSample of the sub-world (sizeX x dimY x sizeZ): the coarse columns over the rectangle, on the device (they never go to the host)
-	if (levelCount > 0) {
-		rc = cvxi::BuildLodChainOnDevice(ctx, dSrc, elementsOfColumns, sizeX, dimY, sizeZ, columnCount, levelCount, lodHeaders + 1, lodElements + 1);
-		if (rc != CVX_OK) {
-			release();
-			return rc;
-		}
-	}
-	for (int l = 0; l <= levelCount; l++) {
-		Job j;
-		j.lod = l;
-		j.x0 = x0 >> l;
-		j.z0 = z0 >> l;
-		j.sizeX = sizeX >> l;
-		j.sizeZ = sizeZ >> l;
-		j.headers = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc) : lodHeaders[l];
-		j.elements = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc + (size_t)columnCount * 12) : lodElements[l];
-		jobs.push_back(j);
-	}
-	rc = ApplyJobs(ctx, jobs);
-	if (rc == CVX_OK) { e = hipEventRecord(ev[1], ctx->stream); }
+	rc = cvxi::EditFromDevice(ctx, x0, z0, sizeX, sizeZ, dSrc, elementsOfColumns, columnCount, levelCount, ev[1]);
 	const hipError_t s = hipStreamSynchronize(ctx->stream);
 	if (rc == CVX_OK && (e != hipSuccess || s != hipSuccess)) { rc = Fail(ctx, CVX_ERR_HIP, "edit failed: %s", hipGetErrorString(e != hipSuccess ? e : s)); }
 	if (rc == CVX_OK && outDeviceMs) {

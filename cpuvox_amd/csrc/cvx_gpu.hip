@@ -537,6 +537,7 @@ void cvx_destroy(cvx_context *ctx)
 	if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); }
 	FreeRaybuffers(ctx);
 	cvxi::FreeEditState(ctx);
+	cvxi::FreeBrushState(ctx);
 	if (ctx->arena) { (void)hipFree(ctx->arena); }
 	if (ctx->devWorld) { (void)hipFree(ctx->devWorld); }
 	if (ctx->devFrames) { (void)hipFree(ctx->devFrames); }

@@ -31,6 +31,7 @@ EXPORTS = [
     "cvx_screen_device_ptr", "cvx_last_draw_ms", "cvx_enable_counters", "cvx_get_counters",
     "cvx_get_raybuffer_layout", "cvx_version", "cvx_bind_raybuffers", "cvx_draw_time_stats", "cvx_copy_rows", "cvx_draw_segments_placed",
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
+    "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -50,6 +51,64 @@ class Counters(C.Structure):
     def as_dict(self):
         return {"S": self.S, "E": self.E, "C": self.C, "P": self.P, "R": self.R,
                 "lodVisits": list(self.lodVisits), "bytes": self.algorithmic_bytes()}
+
+
+BRUSH_FILL, BRUSH_CARVE, BRUSH_PAINT = 0, 1, 2  # cvx_brush_stroke.op
+SHAPE_BOX, SHAPE_SPHERE = 0, 1                  # cvx_brush_stroke.shape
+BRUSH_MAX_STROKES = 4096
+FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
+
+
+class BrushStroke(C.Structure):
+    _fields_ = [("op", C.c_int32), ("shape", C.c_int32), ("a", C.c_int32 * 3), ("b", C.c_int32 * 3), ("argb", C.c_uint32), ("pad_", C.c_int32)]
+
+
+class PickRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("maxT", C.c_float), ("pad_", C.c_float)]
+
+
+class PickHit(C.Structure):
+    _fields_ = [("voxel", C.c_int32 * 3), ("face", C.c_int32), ("argb", C.c_uint32), ("t", C.c_float)]
+
+
+# numpy views of the same layouts
+STROKE_DTYPE = np.dtype([("op", "<i4"), ("shape", "<i4"), ("a", "<i4", 3), ("b", "<i4", 3), ("argb", "<u4"), ("pad_", "<i4")])
+PICK_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("maxT", "<f4"), ("pad_", "<f4")])
+PICK_HIT_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("argb", "<u4"), ("t", "<f4")])
+
+
+def strokes_array(strokes) -> np.ndarray:
+    """A list of dicts {op, shape, a, b, argb} (b of a sphere may be just the radius) or a STROKE_DTYPE array -> a contiguous STROKE_DTYPE array."""
+    if isinstance(strokes, np.ndarray):
+        return np.ascontiguousarray(strokes.astype(STROKE_DTYPE, copy=False))
+    out = np.zeros(len(strokes), dtype=STROKE_DTYPE)
+    for i, s in enumerate(strokes):
+        b = s["b"] if "b" in s else s["radius"]
+        out[i]["op"], out[i]["shape"] = s["op"], s["shape"]
+        out[i]["a"] = s["a"]
+        out[i]["b"] = [b, 0, 0] if np.isscalar(b) else b
+        out[i]["argb"] = s.get("argb", 0) & 0xFFFFFFFF
+    return out
+
+
+def screen_rays(camera, width: int, height: int, px, py):
+    """(origins [N, 3], directions [N, 3]) of the rays through the centres of pixels (px, py) (row 0 = the bottom row, Unity screen space): the
+    camera position and the inverse of its WorldToScreenMatrix (column-major, world -> 0..width x 0..height after the divide by w)."""
+    m = np.array(camera.WorldToScreenMatrix[:], dtype=np.float64).reshape(4, 4).T  # (column-major storage)
+    pos = np.array([camera.PositionXZ[0], camera.PositionY, camera.PositionXZ[1]], dtype=np.float64)
+    inv = np.linalg.inv(m)
+    # a point in front of the camera fixes the depth row: row 3 of the matrix is the view depth (w) of a point
+    ahead = m @ np.append(pos + m[3, :3], 1.0)
+    depth = ahead[2] / ahead[3]
+    sx = np.asarray(px, dtype=np.float64) + 0.5
+    sy = np.asarray(py, dtype=np.float64) + 0.5
+    if sx.size and (sx.min() < 0 or sx.max() > width or sy.min() < 0 or sy.max() > height):
+        raise ValueError(f"pixels outside the {width} x {height} screen")
+    q = np.stack([sx, sy, np.full_like(sx, depth), np.ones_like(sx)], axis=-1) @ inv.T
+    points = q[..., :3] / q[..., 3:4]
+    directions = points - pos
+    directions /= np.linalg.norm(directions, axis=-1, keepdims=True)
+    return np.broadcast_to(pos, directions.shape).copy(), directions
 
 
 class RaybufferLayout(C.Structure):
@@ -147,6 +206,9 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_set_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int]
         L.cvx_world_edit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_edit_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.cvx_world_brush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.cvx_world_pick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.cvx_world_pick_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -266,6 +328,34 @@ class Context:
         used, abandoned, spare = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(lib().cvx_world_edit_stats(self._h, C.byref(used), C.byref(abandoned), C.byref(spare)))
         return used.value, abandoned.value, spare.value
+
+    # -- voxel brushes and ray picking (cvx_world_brush, cvx_world_pick) ------
+    def brush(self, strokes, level_count: int = LOD_LEVELS - 1) -> float:
+        """Applies the strokes (a list of dicts {op, shape, a, b or radius, argb} or a STROKE_DTYPE array) in order to LOD 0 and rebuilds
+        LOD 1..level_count over their footprint on the device.  Returns the device milliseconds."""
+        arr = strokes_array(strokes)
+        ms = C.c_float()
+        self._check(lib().cvx_world_brush(self._h, arr.ctypes.data if arr.size else None, arr.size, level_count, C.byref(ms)))
+        return ms.value
+
+    def pick(self, origins, directions, max_t):
+        """First solid LOD-0 voxel along each ray -> (voxel int32[N, 3], face int32[N], argb uint32[N], t float32[N]).  max_t: a scalar or
+        one per ray.  Misses: voxel -1, face -1, argb 0, t = max_t."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        rays = np.zeros(n, dtype=PICK_RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["maxT"] = np.broadcast_to(np.asarray(max_t, dtype=np.float32), (n,))
+        hits = np.zeros(n, dtype=PICK_HIT_DTYPE)
+        self._check(lib().cvx_world_pick(self._h, n, rays.ctypes.data, hits.ctypes.data))
+        return hits["voxel"].copy(), hits["face"].copy(), hits["argb"].copy(), hits["t"].copy()
+
+    def pick_screen(self, camera, width: int, height: int, px, py, max_t: float):
+        """pick() through the centres of pixels (px, py) of a width x height screen (row 0 = the bottom row) of `camera` (a cvx_camera_data):
+        the voxel under the cursor."""
+        o, d = screen_rays(camera, width, height, px, py)
+        return self.pick(o, d, max_t)
 
     def set_resolution(self, width: int, height: int) -> None:
         """RenderManager.SetResolution (RenderManager.cs:94-109)."""

@@ -52,6 +52,35 @@ namespace CpuVox.Gpu
 		public int Rows, Kind;
 	}
 
+	// cvx_world_brush: one stroke (include/cpuvox_gpu.h, 40 bytes).  Op: 0 fill, 1 carve, 2 paint; Shape: 0 box [A, B), 1 sphere (centre A, radius B[0])
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct BrushStroke
+	{
+		public int Op, Shape;
+		public fixed int A[3];
+		public fixed int B[3];
+		public uint Argb;
+		public int Pad;
+	}
+
+	// cvx_world_pick: a ray (32 bytes) and its hit (24 bytes; Face -1 = miss, 0..5 = -X, +X, -Y, +Y, -Z, +Z, 6 = started inside)
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct PickRay
+	{
+		public fixed float Origin[3];
+		public fixed float Direction[3];
+		public float MaxT, Pad;
+	}
+
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct PickHit
+	{
+		public fixed int Voxel[3];
+		public int Face;
+		public uint Argb;
+		public float T;
+	}
+
 	public sealed class CvxException : Exception
 	{
 		public readonly int Code;
@@ -78,6 +107,10 @@ namespace CpuVox.Gpu
 		[DllImport(Lib)] public static extern int cvx_world_edit(IntPtr ctx, int x0, int z0, int sizeX, int sizeZ, void* storage, long byteLength, int columnCount, int levelCount,
 		                                                         out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_world_edit_stats(IntPtr ctx, out long usedBytes, out long abandonedBytes, out long spareBytes);
+		// voxel brushes (a LOD-0 edit + its LOD refresh, computed on the device) and first-hit ray picking against LOD 0
+		[DllImport(Lib)] public static extern int cvx_world_brush(IntPtr ctx, BrushStroke* strokes, int strokeCount, int levelCount, out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_world_pick(IntPtr ctx, int rayCount, PickRay* rays, PickHit* hits);
+		[DllImport(Lib)] public static extern int cvx_world_pick_device(IntPtr ctx, int rayCount, IntPtr raysDevice, IntPtr hitsDevice, IntPtr hipStream);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

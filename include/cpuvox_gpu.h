@@ -355,6 +355,56 @@ int cvx_world_edit(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
  * the edit tails.  A context that never edited reports its whole arena as used. */
 int cvx_world_edit_stats(cvx_context *ctx, int64_t *usedBytes, int64_t *abandonedBytes, int64_t *spareBytes);
 
+/* ---- voxel brushes and ray picking on the uploaded world ---------------------------------------------------------------------------------
+ * Everything in LOD-0 voxel coordinates: voxel (x, y, z) is the unit cube [x, x+1) x [y, y+1) x [z, z+1), y = 0 at the bottom.
+ * cvx_world_brush: voxel-level edits, computed on the device and handed to cvx_world_edit's machinery (records, tails, LOD refresh).  A stroke
+ * acts on the voxels inside its shape, all integer: a box holds a <= (x, y, z) < b per axis; a sphere holds (x-a0)^2 + (y-a1)^2 + (z-a2)^2 <= r^2
+ * (r = b[0] >= 0, 64-bit arithmetic).  FILL makes them solid with colour argb (solid ones included), CARVE makes them air, PAINT gives colour argb
+ * to the solid ones and leaves air alone.  Strokes apply in array order (a later one sees what the earlier ones did) and are clipped to the world;
+ * a stroke entirely outside it does nothing.  The call changes LOD 0 and rebuilds LOD 1 .. levelCount (0 .. 5) over the union of the strokes'
+ * XZ footprints, rounded outward to multiples of 2^levelCount and clipped to the world: cvx_world_edit's rectangle.  Columns of that rectangle no
+ * stroke touches are re-encoded with the builder's rule (WordBuilder.cs:181-268), which gives back the same column for every world the builder
+ * made.  Ordering, atomicity and outDeviceMs are cvx_world_edit's.  CVX_ERR_INVALID_ARGUMENT: a bad op / shape, a negative radius, strokeCount
+ * outside 1 .. CVX_BRUSH_MAX_STROKES, a sphere radius above 2^30
+ * or levelCount outside 0 .. 5; CVX_ERR_CAPACITY: a column would need more than 65535 runs, a run longer than
+ * 32767 voxels or a colour index above 32767 (World.cs:161-259 keeps them in ushort / short), or the arena limits of cvx_world_edit.  Either
+ * leaves the world as it was.  With several GPUs every rank applies the same strokes to its own context. */
+enum { CVX_BRUSH_FILL = 0, CVX_BRUSH_CARVE = 1, CVX_BRUSH_PAINT = 2 };
+enum { CVX_SHAPE_BOX = 0, CVX_SHAPE_SPHERE = 1 };
+#define CVX_BRUSH_MAX_STROKES 4096
+typedef struct cvx_brush_stroke { /* 40 bytes */
+	int32_t op;    /* CVX_BRUSH_* */
+	int32_t shape; /* CVX_SHAPE_* */
+	int32_t a[3];  /* box: min corner (inclusive); sphere: centre voxel */
+	int32_t b[3];  /* box: max corner (exclusive); sphere: b[0] = radius, b[1], b[2] ignored */
+	uint32_t argb; /* FILL / PAINT colour (ColorARGB32 byte order, as the blobs hold it) */
+	int32_t pad_;
+} cvx_brush_stroke;
+int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strokeCount, int levelCount, float *outDeviceMs);
+
+/* cvx_world_pick: first-hit ray queries against LOD 0, one per ray.  A ray is origin + t * direction in the space of cvx_camera_data's
+ * PositionXZ / PositionY (direction need not be normalised; t is in its units).  The hit is the first solid voxel whose cube the ray enters for
+ * 0 <= t <= maxT: voxel, the face it came in through (0 .. 5 = -X, +X, -Y, +Y, -Z, +Z: a ray travelling +X enters through -X, face 0), its
+ * colour and t.  A ray that starts inside a solid voxel hits it with face 6 and t = 0.  A miss: voxel {-1, -1, -1}, face -1, argb 0, t = maxT.
+ * Rays that start outside the world are clipped to its box first.  The traversal is float64 (cvx_brush.h, PickRay); rays that graze a voxel
+ * edge within ~1e-9 voxel may resolve either way.  `rays` / `hits` are host arrays of rayCount entries; the call is ordered on the context's
+ * stream behind every edit, brush and draw enqueued before it and returns when the hits are copied back.  cvx_world_pick_device takes device
+ * arrays and enqueues on hipStream (NULL = the context's stream) without waiting; the caller orders that stream after the context's work. */
+typedef struct cvx_pick_ray { /* 32 bytes */
+	float origin[3];
+	float direction[3];
+	float maxT;
+	float pad_;
+} cvx_pick_ray;
+typedef struct cvx_pick_hit { /* 24 bytes */
+	int32_t voxel[3];
+	int32_t face;
+	uint32_t argb;
+	float t;
+} cvx_pick_hit;
+int cvx_world_pick(cvx_context *ctx, int rayCount, const cvx_pick_ray *rays, cvx_pick_hit *hits);
+int cvx_world_pick_device(cvx_context *ctx, int rayCount, const cvx_pick_ray *raysDevice, cvx_pick_hit *hitsDevice, void *hipStream);
+
 const char *cvx_version(void);
 
 #ifdef __cplusplus
