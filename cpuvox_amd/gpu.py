@@ -32,6 +32,7 @@ EXPORTS = [
     "cvx_get_raybuffer_layout", "cvx_version", "cvx_bind_raybuffers", "cvx_draw_time_stats", "cvx_copy_rows", "cvx_draw_segments_placed",
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
+    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -209,6 +210,10 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_brush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_pick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.cvx_world_pick_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvx_world_read_region.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int32)]
+        L.cvx_world_read_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.cvx_world_compact.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -251,6 +256,7 @@ class Context:
         if rc != 0:
             raise CvxError(f"cvx_create({device}) failed ({rc}): {lib().cvx_last_error(None).decode()}")
         self.width = self.height = 0
+        self.dims = None  # (dimX, dimY, dimZ) of the uploaded world
         if buffer_count != 2:
             self._check(lib().cvx_set_buffer_count(self._h, buffer_count))
         self.buffer_count = buffer_count
@@ -279,6 +285,7 @@ class Context:
         for lod in range(world_set.lod_count):
             i = world_set.info(lod)
             self._check(lib().cvx_world_upload(self._h, lod, i.storage, i.byteLength, i.dimX, i.dimY, i.dimZ, i.columnCount))
+            self.dims = (i.dimX, i.dimY, i.dimZ)
 
     def downsample(self, world_set: WorldSet, lod: int, extra_lods: int):
         """World.DownSample(extraLods) (World.cs:45) of level `lod` on the device.  Returns (blob bytes in the reference's
@@ -328,6 +335,37 @@ class Context:
         used, abandoned, spare = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(lib().cvx_world_edit_stats(self._h, C.byref(used), C.byref(abandoned), C.byref(spare)))
         return used.value, abandoned.value, spare.value
+
+    # -- reading the uploaded world back, compacting its arena ----------------
+    def _blob(self, call, *args):
+        out, nbytes, columns = C.c_void_p(), C.c_int64(), C.c_int32()
+        self._check(call(self._h, *args, C.byref(out), C.byref(nbytes), C.byref(columns)))
+        try:
+            return C.string_at(out.value, nbytes.value), columns.value
+        finally:
+            lib().cvx_free(out)
+
+    def read_region(self, lod: int, x0: int, z0: int, size_x: int, size_z: int):
+        """A rectangle of level `lod` (its own columns) as it is on the device now, as a sub-world blob in the builder's encoding: (blob
+        bytes, column count), the shape of WorldSet.extract_region and what set_columns / edit take."""
+        return self._blob(lib().cvx_world_read_region, lod, x0, z0, size_x, size_z)
+
+    def read_level(self, lod: int):
+        """The whole level `lod` as it is on the device now: (blob bytes, World.ColumnCount), the layout cvx_world_upload takes."""
+        return self._blob(lib().cvx_world_read_level, lod)
+
+    def download(self, level_count: int = LOD_LEVELS) -> WorldSet:
+        """The uploaded world with every edit and brush, as a host world set (WorldSet.from_blobs) of its first level_count levels: e.g. to save it."""
+        if self.dims is None:
+            raise CvxError("no world has been uploaded to this context")
+        return WorldSet.from_blobs(self.dims, [self.read_level(lod)[0] for lod in range(level_count)])
+
+    def compact(self):
+        """Lays the edited levels out again without the space edits left behind (on the device).  Returns (bytes reclaimed, device
+        milliseconds)."""
+        reclaimed, ms = C.c_int64(), C.c_float()
+        self._check(lib().cvx_world_compact(self._h, C.byref(reclaimed), C.byref(ms)))
+        return reclaimed.value, ms.value
 
     # -- voxel brushes and ray picking (cvx_world_brush, cvx_world_pick) ------
     def brush(self, strokes, level_count: int = LOD_LEVELS - 1) -> float:

@@ -111,6 +111,10 @@ namespace CpuVox.Gpu
 		[DllImport(Lib)] public static extern int cvx_world_brush(IntPtr ctx, BrushStroke* strokes, int strokeCount, int levelCount, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_world_pick(IntPtr ctx, int rayCount, PickRay* rays, PickHit* hits);
 		[DllImport(Lib)] public static extern int cvx_world_pick_device(IntPtr ctx, int rayCount, IntPtr raysDevice, IntPtr hitsDevice, IntPtr hipStream);
+		// the device-resident world read back (a rectangle / a whole level, blobs in the builder's encoding; release with cvx_free) and its arena compacted
+		[DllImport(Lib)] public static extern int cvx_world_read_region(IntPtr ctx, int lod, int x0, int z0, int sizeX, int sizeZ, out IntPtr outStorage, out long outByteLength, out int outColumnCount);
+		[DllImport(Lib)] public static extern int cvx_world_read_level(IntPtr ctx, int lod, out IntPtr outStorage, out long outByteLength, out int outColumnCount);
+		[DllImport(Lib)] public static extern int cvx_world_compact(IntPtr ctx, out long outReclaimedBytes, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

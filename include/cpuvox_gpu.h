@@ -341,9 +341,9 @@ void cvx_free(void *p);
  * a draw enqueued before it (CVX_DRAW_ASYNC included) renders the old world, every draw after it the new one.  Levels uploaded but not drawn
  * yet are placed in the arena first (what the next draw would do).  Colours and run-list blocks go to the column's old place when they fit,
  * else to a tail behind the level's colours / run list (a 4 x 8 colour block that gets too shallow moves there as a whole); the first edit of
- * a level lays the arena out again with headroom, and the arena grows when the headroom runs out.  Space edits leave behind is not compacted:
- * cvx_world_edit_stats reports it, and uploading the level again reclaims it.  With several GPUs (one context per rank), every rank applies
- * the same edit to its own context. */
+ * a level lays the arena out again with headroom, and the arena grows when the headroom runs out.  Space edits leave behind is not compacted
+ * by the edit: cvx_world_edit_stats reports it, and cvx_world_compact reclaims it on the device (so does uploading the level again).  With several
+ * GPUs (one context per rank), every rank applies the same edit to its own context. */
 /* World.SetVoxelColumn for a sizeX x sizeZ rectangle of one level (the caller supplies that level's columns). */
 int cvx_world_set_columns(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, const void *storage, int64_t byteLength, int columnCount);
 /* Replaces a rectangle of LOD 0 and rebuilds LOD 1 .. levelCount (0 .. 5) over it on the device (World.DownSample of the sub-world, as
@@ -404,6 +404,35 @@ typedef struct cvx_pick_hit { /* 24 bytes */
 } cvx_pick_hit;
 int cvx_world_pick(cvx_context *ctx, int rayCount, const cvx_pick_ray *rays, cvx_pick_hit *hits);
 int cvx_world_pick_device(cvx_context *ctx, int rayCount, const cvx_pick_ray *raysDevice, cvx_pick_hit *hitsDevice, void *hipStream);
+
+/* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
+ * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
+ * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
+ * cvx_world_brush emits): maximal runs from the top, the top air run first, air runs with ColorsIndex -1, both guards 0, ColorsIndex of a solid
+ * run = the solid voxels above it, worldMin / worldMax as the RLEColumn constructor computes them (World.cs:190-234, LOD-0 voxels), header pad 0,
+ * the pool in column order, an all-zero header for an empty column.  The builder and World.DownSample (host and device) produce nothing else, so
+ * for every world the host library builds the blob is byte-identical to what was uploaded.  A column uploaded in another encoding (a foreign blob
+ * with a split run, split air runs, colour indices that share colours, a column with no solid voxel) comes back with the same voxels and colours
+ * in builder form, not byte-identical.
+ * The calls are ordered on the context's stream behind every draw, edit and brush enqueued before them; levels uploaded but not placed yet are
+ * placed first (what the next draw would do); they return once the copy is done, never change the world and free their scratch before they
+ * return.  CVX_ERR_INVALID_ARGUMENT: a NULL out pointer, lod outside 0 .. 5, a rectangle outside the level; CVX_ERR_NOT_READY: the level (or
+ * another one of the world) was never uploaded; CVX_ERR_CAPACITY: out of device or host memory, or a blob beyond 2^31 elements.
+ * *outStorage is malloc'd: release it with cvx_free. */
+/* A rectangle of level `lod` (in that level's own columns) as a sub-world blob: the layout cvx_world_set_columns / cvx_world_edit take and
+ * cvxh_world_extract_region makes (column (x, z) is header (x - x0) * sizeZ + (z - z0), *outColumnCount = sizeX * sizeZ). */
+int cvx_world_read_region(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, void **outStorage, int64_t *outByteLength, int32_t *outColumnCount);
+/* The whole level as cvx_world_upload takes it and cvxh_world_info.storage holds it: *outColumnCount = World.ColumnCount (World.cs:17,
+ * dimX * dimZ / (lod + 1)^2), which for lod >= 2 is more headers than the level has columns; the extra trailing headers are zero. */
+int cvx_world_read_level(cvx_context *ctx, int lod, void **outStorage, int64_t *outByteLength, int32_t *outColumnCount);
+/* Lays every level that has an edit tail out again without the space edits left behind; rendering, picks and read-back are unchanged.  All on the
+ * device: per level the colour blocks get the depth their deepest column needs now (a column-after-column level packs its columns), run-list
+ * blocks and colours are packed in column order, the records are rewritten to the new places; the level keeps its colour layout, and gets the
+ * headroom of a first edit.  Levels never edited are copied as they are; a context that never edited is left alone.  Ordered like the read-back
+ * (a CVX_DRAW_ASYNC draw enqueued before the call renders the old world); the call returns once the new arena is in place.  The peak is the old
+ * arena plus the new one: CVX_ERR_CAPACITY (out of device memory) leaves the world as it was.  outReclaimedBytes (may be NULL): the drop of
+ * cvx_world_edit_stats' used bytes; outDeviceMs (may be NULL): device time of the compaction. */
+int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDeviceMs);
 
 const char *cvx_version(void);
 
