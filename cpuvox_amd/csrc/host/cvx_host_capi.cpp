@@ -2,6 +2,7 @@
 #include "cpuvox_host.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -22,6 +23,13 @@ struct cvxh_world_set {
 	std::vector<cvx::World> worlds;
 	int64_t lod0Voxels = 0;
 };
+
+struct cvxh_mesh {
+	cvx::SimpleMesh mesh;
+};
+static_assert(sizeof(cvx::MeshVertex) == sizeof(cvx_mesh_vertex) && offsetof(cvx::MeshVertex, Color) == offsetof(cvx_mesh_vertex, rgba) &&
+              offsetof(cvx::MeshVertex, UV) == offsetof(cvx_mesh_vertex, uv) && offsetof(cvx::MeshVertex, MaterialIndex) == offsetof(cvx_mesh_vertex, material),
+              "SimpleMesh.Vertex is cvx_mesh_vertex");
 
 struct cvxh_world_builder {
 	std::unique_ptr<cvx::WorldBuilder> builder;
@@ -67,6 +75,96 @@ int cvxh_world_from_obj(const char *path, int maxDimension, int swapYZ, int flip
 	*out = set.release();
 	return CVX_OK;
 }
+
+int cvxh_mesh_load_obj(const char *path, int swapYZ, cvxh_mesh **out)
+{
+	if (!path || !out) { return Fail("bad argument"); }
+	try {
+		auto m = std::make_unique<cvxh_mesh>();
+		std::string error;
+		if (!cvx::ImportObj(path, swapYZ != 0, m->mesh, &error)) { return Fail(error); }
+		*out = m.release();
+	} catch (const std::exception &e) {
+		return Fail(e.what());
+	}
+	return CVX_OK;
+}
+
+int cvxh_mesh_create(const cvx_mesh_vertex *vertices, int vertexCount, const int32_t *indices, int64_t indexCount, const cvx_mesh_texture *materials,
+                     int materialCount, cvxh_mesh **out)
+{
+	if (!out || vertexCount < 0 || (vertexCount > 0 && !vertices) || indexCount < 0 || indexCount % 3 != 0 || (indexCount > 0 && !indices) ||
+	    materialCount < 0 || (materialCount > 0 && !materials)) {
+		return Fail("bad argument");
+	}
+	try {
+		auto m = std::make_unique<cvxh_mesh>();
+		m->mesh.Vertices.resize((size_t)vertexCount);
+		if (vertexCount > 0) { std::memcpy(static_cast<void *>(m->mesh.Vertices.data()), vertices, (size_t)vertexCount * sizeof(cvx_mesh_vertex)); }
+		m->mesh.Indices.assign(indices, indices + indexCount);
+		for (int32_t i : m->mesh.Indices) {
+			if (i < 0 || i >= vertexCount) { return Fail("index " + std::to_string(i) + " outside the vertices"); }
+		}
+		for (int k = 0; k < materialCount; k++) {
+			cvx::MeshMaterial material;
+			material.MaterialIndex = k;
+			material.Name = "material" + std::to_string(k);
+			const cvx_mesh_texture &t = materials[k];
+			if (t.rgba) {
+				if (t.width < 1 || t.height < 1) { return Fail("material " + std::to_string(k) + ": texture without texels"); }
+				material.Diffuse.width = t.width;
+				material.Diffuse.height = t.height;
+				material.Diffuse.rgba.assign(t.rgba, t.rgba + (size_t)t.width * (size_t)t.height * 4);
+			}
+			m->mesh.Materials.push_back(std::move(material));
+		}
+		*out = m.release();
+	} catch (const std::exception &e) {
+		return Fail(e.what());
+	}
+	return CVX_OK;
+}
+
+int cvxh_mesh_rescale(cvxh_mesh *mesh, float maxDimension, int flipX, int flipY, int flipZ, int32_t outDims[3])
+{
+	if (!mesh || !outDims || mesh->mesh.Vertices.empty() || !(maxDimension > 0.f)) { return Fail("bad argument"); }
+	const cvx::int3 d = mesh->mesh.Rescale(maxDimension, cvx::float3(flipX ? -1.f : 1.f, flipY ? -1.f : 1.f, flipZ ? -1.f : 1.f));
+	outDims[0] = d.x;
+	outDims[1] = d.y;
+	outDims[2] = d.z;
+	return CVX_OK;
+}
+
+int cvxh_mesh_vertices(const cvxh_mesh *mesh, const cvx_mesh_vertex **outVertices, int32_t *outCount)
+{
+	if (!mesh || !outVertices || !outCount) { return Fail("bad argument"); }
+	*outVertices = reinterpret_cast<const cvx_mesh_vertex *>(mesh->mesh.Vertices.data());
+	*outCount = (int32_t)mesh->mesh.Vertices.size();
+	return CVX_OK;
+}
+
+int cvxh_mesh_indices(const cvxh_mesh *mesh, const int32_t **outIndices, int64_t *outCount)
+{
+	if (!mesh || !outIndices || !outCount) { return Fail("bad argument"); }
+	*outIndices = mesh->mesh.Indices.data();
+	*outCount = (int64_t)mesh->mesh.Indices.size();
+	return CVX_OK;
+}
+
+int cvxh_mesh_material_count(const cvxh_mesh *mesh) { return mesh ? (int)mesh->mesh.Materials.size() : 0; }
+
+int cvxh_mesh_texture(const cvxh_mesh *mesh, int material, cvx_mesh_texture *out)
+{
+	if (!mesh || !out || material < 0 || material >= (int)mesh->mesh.Materials.size()) { return Fail("bad argument"); }
+	const cvx::Image &img = mesh->mesh.Materials[(size_t)material].Diffuse;
+	const bool has = img.width > 0 && img.height > 0;
+	out->width = has ? img.width : 0;
+	out->height = has ? img.height : 0;
+	out->rgba = has ? img.rgba.data() : nullptr;
+	return CVX_OK;
+}
+
+void cvxh_mesh_free(cvxh_mesh *mesh) { delete mesh; }
 
 int cvxh_world_procedural(int dimX, int dimY, int dimZ, uint32_t seed, int threads, cvxh_world_set **out)
 {

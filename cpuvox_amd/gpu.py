@@ -32,7 +32,7 @@ EXPORTS = [
     "cvx_get_raybuffer_layout", "cvx_version", "cvx_bind_raybuffers", "cvx_draw_time_stats", "cvx_copy_rows", "cvx_draw_segments_placed",
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
-    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact",
+    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -72,10 +72,16 @@ class PickHit(C.Structure):
     _fields_ = [("voxel", C.c_int32 * 3), ("face", C.c_int32), ("argb", C.c_uint32), ("t", C.c_float)]
 
 
+class _TextureStruct(C.Structure):  # cvx_mesh_texture
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
+
+
 # numpy views of the same layouts
 STROKE_DTYPE = np.dtype([("op", "<i4"), ("shape", "<i4"), ("a", "<i4", 3), ("b", "<i4", 3), ("argb", "<u4"), ("pad_", "<i4")])
 PICK_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("maxT", "<f4"), ("pad_", "<f4")])
 PICK_HIT_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("argb", "<u4"), ("t", "<f4")])
+MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex
+STAMP_MAX_MATERIALS = 128
 
 
 def strokes_array(strokes) -> np.ndarray:
@@ -214,6 +220,8 @@ def _bind(path: str) -> C.CDLL:
                                             C.POINTER(C.c_int32)]
         L.cvx_world_read_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.cvx_world_compact.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        L.cvx_world_stamp_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_float)]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -374,6 +382,20 @@ class Context:
         arr = strokes_array(strokes)
         ms = C.c_float()
         self._check(lib().cvx_world_brush(self._h, arr.ctypes.data if arr.size else None, arr.size, level_count, C.byref(ms)))
+        return ms.value
+
+    def stamp_mesh(self, mesh, op: int = BRUSH_FILL, level_count: int = LOD_LEVELS - 1) -> float:
+        """Voxelises `mesh` (a cpuvox_amd.host.Mesh, positions in LOD-0 voxels: Mesh.rescale) on the device with the host voxeliser's rule and
+        merges it into LOD 0 with op (BRUSH_FILL / CARVE / PAINT), then rebuilds LOD 1..level_count over its footprint.  Returns the device
+        milliseconds (0 when the mesh stamps no voxel)."""
+        v, idx = mesh.vertices, mesh.indices
+        textures = (_TextureStruct * max(1, mesh.material_count))()
+        for k in range(mesh.material_count):
+            t = mesh.texture_struct(k)
+            textures[k].width, textures[k].height, textures[k].rgba = t.width, t.height, t.rgba
+        ms = C.c_float()
+        self._check(lib().cvx_world_stamp_mesh(self._h, v.ctypes.data if v.size else None, v.size, idx.ctypes.data if idx.size else None, idx.size,
+                                               C.cast(textures, C.c_void_p), mesh.material_count, op, level_count, C.byref(ms)))
         return ms.value
 
     def pick(self, origins, directions, max_t):

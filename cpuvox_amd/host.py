@@ -79,7 +79,23 @@ class Frame(C.Structure):
     ]
 
 
+class MeshVertex(C.Structure):
+    """SimpleMesh.Vertex (SimpleMesh.cs:108-114) == cvx_mesh_vertex."""
+
+    _fields_ = [("position", C.c_float * 3), ("rgba", C.c_uint8 * 4), ("uv", C.c_float * 2), ("material", C.c_int32)]
+
+
+class MeshTexture(C.Structure):
+    """cvx_mesh_texture: width x height RGBA8 texels, row 0 = the bottom row; rgba NULL = no texture."""
+
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
+
+
+# numpy view of cvx_mesh_vertex (also cpuvox_amd.gpu.MESH_VERTEX_DTYPE)
+MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])
+
 assert C.sizeof(SegmentData) == 36 and C.sizeof(CameraData) == 108
+assert C.sizeof(MeshVertex) == 28 and MESH_VERTEX_DTYPE.itemsize == 28 and C.sizeof(MeshTexture) == 16
 
 _lib = None
 
@@ -119,6 +135,15 @@ def lib() -> C.CDLL:
         L.cvxh_sample_benchmark_path.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.cvxh_sample_benchmark_path.restype = None
         L.cvxh_image_load.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int64]
+        L.cvxh_mesh_load_obj.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.cvxh_mesh_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.cvxh_mesh_rescale.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.cvxh_mesh_vertices.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+        L.cvxh_mesh_indices.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L.cvxh_mesh_material_count.argtypes = [C.c_void_p]
+        L.cvxh_mesh_texture.argtypes = [C.c_void_p, C.c_int, C.POINTER(MeshTexture)]
+        L.cvxh_mesh_free.argtypes = [C.c_void_p]
+        L.cvxh_mesh_free.restype = None
         _lib = L
     return _lib
 
@@ -242,6 +267,97 @@ class WorldSet:
     def close(self) -> None:
         if self._h:
             lib().cvxh_world_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Mesh:
+    """A triangle mesh (SimpleMesh, SimpleMesh.cs:11-106) with its materials' diffuse textures, for cpuvox_amd.gpu.Context.stamp_mesh."""
+
+    def __init__(self, handle: int):
+        self._h = C.c_void_p(handle)
+
+    @staticmethod
+    def from_obj(path: str, swap_yz: bool = False) -> "Mesh":
+        """ObjModel.Import (ObjModel.cs:10-171), the file WorldSet.from_obj reads; positions in the model's units until rescale()."""
+        h = C.c_void_p()
+        _check(lib().cvxh_mesh_load_obj(path.encode(), int(swap_yz), C.byref(h)))
+        return Mesh(h.value)
+
+    @staticmethod
+    def from_arrays(vertices, indices=None, textures=()) -> "Mesh":
+        """A mesh built in code.  vertices: a MESH_VERTEX_DTYPE array, or a dict of arrays {position [N, 3], rgba [N, 4] (default white),
+        uv [N, 2] (default 0), material [N] (default -1)}; indices: int32 [3 * T] (default 0 .. N-1); textures: one entry per material,
+        None (no texture) or uint8 [H, W, 4] RGBA with row 0 = the bottom row."""
+        if isinstance(vertices, dict):
+            pos = np.asarray(vertices["position"], dtype=np.float32).reshape(-1, 3)
+            v = np.zeros(pos.shape[0], dtype=MESH_VERTEX_DTYPE)
+            v["position"] = pos
+            v["rgba"] = np.broadcast_to(np.asarray(vertices.get("rgba", 255), dtype=np.uint8), (pos.shape[0], 4))
+            v["uv"] = np.broadcast_to(np.asarray(vertices.get("uv", 0.0), dtype=np.float32), (pos.shape[0], 2))
+            v["material"] = np.broadcast_to(np.asarray(vertices.get("material", -1), dtype=np.int32), (pos.shape[0],))
+        else:
+            v = np.ascontiguousarray(np.asarray(vertices).astype(MESH_VERTEX_DTYPE, copy=False))
+        idx = np.arange(v.size, dtype=np.int32) if indices is None else np.ascontiguousarray(indices, dtype=np.int32).ravel()
+        texels = [None if t is None else np.ascontiguousarray(t, dtype=np.uint8) for t in textures]
+        table = (MeshTexture * max(1, len(texels)))()
+        for k, t in enumerate(texels):
+            if t is not None:
+                assert t.ndim == 3 and t.shape[2] == 4, "a texture is uint8 [H, W, 4]"
+                table[k].width, table[k].height, table[k].rgba = t.shape[1], t.shape[0], t.ctypes.data
+        h = C.c_void_p()
+        _check(lib().cvxh_mesh_create(v.ctypes.data if v.size else None, v.size, idx.ctypes.data if idx.size else None, idx.size,
+                                      C.cast(table, C.c_void_p), len(texels), C.byref(h)))
+        return Mesh(h.value)
+
+    def rescale(self, max_dimension: float, flip=(True, False, False)):
+        """SimpleMesh.Rescale (SimpleMesh.cs:49-106) as WorldSet.from_obj applies it (X flipped by default, UnityManager.cs:27): positions in
+        LOD-0 voxels of a world of the returned dims (x, y, z)."""
+        dims = (C.c_int32 * 3)()
+        _check(lib().cvxh_mesh_rescale(self._h, float(max_dimension), int(flip[0]), int(flip[1]), int(flip[2]), dims))
+        return tuple(dims)
+
+    @property
+    def vertices(self) -> np.ndarray:
+        """MESH_VERTEX_DTYPE view of the vertex array (valid until the next rescale / close; rescale changes the positions in place)."""
+        p, n = C.c_void_p(), C.c_int32()
+        _check(lib().cvxh_mesh_vertices(self._h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=MESH_VERTEX_DTYPE)
+        return np.frombuffer((C.c_uint8 * (n.value * 28)).from_address(p.value), dtype=MESH_VERTEX_DTYPE)
+
+    @property
+    def indices(self) -> np.ndarray:
+        p, n = C.c_void_p(), C.c_int64()
+        _check(lib().cvxh_mesh_indices(self._h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.int32)
+        return np.frombuffer((C.c_int32 * n.value).from_address(p.value), dtype=np.int32)
+
+    @property
+    def material_count(self) -> int:
+        return lib().cvxh_mesh_material_count(self._h)
+
+    def texture_struct(self, material: int) -> MeshTexture:
+        out = MeshTexture()
+        _check(lib().cvxh_mesh_texture(self._h, material, C.byref(out)))
+        return out
+
+    def texture(self, material: int):
+        """uint8 [H, W, 4] view of material's diffuse texture (row 0 = the bottom row), or None."""
+        t = self.texture_struct(material)
+        if not t.rgba:
+            return None
+        return np.frombuffer((C.c_uint8 * (t.width * t.height * 4)).from_address(t.rgba), dtype=np.uint8).reshape(t.height, t.width, 4)
+
+    def close(self) -> None:
+        if self._h:
+            lib().cvxh_mesh_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -81,10 +81,45 @@ namespace CpuVox.Gpu
 		public float T;
 	}
 
+	// cvx_world_stamp_mesh: a mesh vertex (28 bytes, SimpleMesh.Vertex: position in LOD-0 voxels, colour, uv, material used as (sbyte)) and a
+	// material's diffuse texture (16 bytes: Width x Height RGBA8 texels, row 0 = the bottom row; Rgba null = no texture)
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct MeshVertex
+	{
+		public fixed float Position[3];
+		public fixed byte Rgba[4];
+		public fixed float Uv[2];
+		public int Material;
+	}
+
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public unsafe struct MeshTexture
+	{
+		public int Width, Height;
+		public byte* Rgba;
+	}
+
 	public sealed class CvxException : Exception
 	{
 		public readonly int Code;
 		public CvxException(int code, string message) : base(message) { Code = code; }
+	}
+
+	/// <summary>The mesh entry points of libcpuvox_host.so (include/cpuvox_host.h): OBJ import, SimpleMesh.Rescale and the arrays
+	/// cvx_world_stamp_mesh takes.</summary>
+	public static unsafe class MeshHost
+	{
+		const string HostLib = "cpuvox_host"; // libcpuvox_host.so
+
+		[DllImport(HostLib)] public static extern int cvxh_mesh_load_obj(string path, int swapYZ, out IntPtr mesh);
+		[DllImport(HostLib)] public static extern int cvxh_mesh_create(MeshVertex* vertices, int vertexCount, int* indices, long indexCount, MeshTexture* materials,
+		                                                               int materialCount, out IntPtr mesh);
+		[DllImport(HostLib)] public static extern int cvxh_mesh_rescale(IntPtr mesh, float maxDimension, int flipX, int flipY, int flipZ, int* outDims);
+		[DllImport(HostLib)] public static extern int cvxh_mesh_vertices(IntPtr mesh, out MeshVertex* outVertices, out int outCount);
+		[DllImport(HostLib)] public static extern int cvxh_mesh_indices(IntPtr mesh, out int* outIndices, out long outCount);
+		[DllImport(HostLib)] public static extern int cvxh_mesh_material_count(IntPtr mesh);
+		[DllImport(HostLib)] public static extern int cvxh_mesh_texture(IntPtr mesh, int material, out MeshTexture texture);
+		[DllImport(HostLib)] public static extern void cvxh_mesh_free(IntPtr mesh);
 	}
 
 	/// <summary>Raw entry points, one per declaration of include/cpuvox_gpu.h.</summary>
@@ -115,6 +150,9 @@ namespace CpuVox.Gpu
 		[DllImport(Lib)] public static extern int cvx_world_read_region(IntPtr ctx, int lod, int x0, int z0, int sizeX, int sizeZ, out IntPtr outStorage, out long outByteLength, out int outColumnCount);
 		[DllImport(Lib)] public static extern int cvx_world_read_level(IntPtr ctx, int lod, out IntPtr outStorage, out long outByteLength, out int outColumnCount);
 		[DllImport(Lib)] public static extern int cvx_world_compact(IntPtr ctx, out long outReclaimedBytes, out float outDeviceMs);
+		// a triangle mesh voxelised on the device (the host voxeliser's rule) and merged into LOD 0 (op 0 fill, 1 carve, 2 paint) + its LOD refresh
+		[DllImport(Lib)] public static extern int cvx_world_stamp_mesh(IntPtr ctx, MeshVertex* vertices, int vertexCount, int* indices, long indexCount,
+		                                                               MeshTexture* materials, int materialCount, int op, int levelCount, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

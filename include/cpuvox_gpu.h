@@ -405,6 +405,38 @@ typedef struct cvx_pick_hit { /* 24 bytes */
 int cvx_world_pick(cvx_context *ctx, int rayCount, const cvx_pick_ray *rays, cvx_pick_hit *hits);
 int cvx_world_pick_device(cvx_context *ctx, int rayCount, const cvx_pick_ray *raysDevice, cvx_pick_hit *hitsDevice, void *hipStream);
 
+/* ---- stamping triangle meshes into the uploaded world ------------------------------------------------------------------------------------
+ * cvx_world_stamp_mesh: voxelises a triangle mesh on the device with the host voxeliser's rule (VoxelizerHelper.GetVoxelsInternal,
+ * VoxelizerHelper.cs:28-132, and the material step of WordBuilder.cs:76-88: what cvxh_world_from_obj runs) and merges the voxels into LOD 0, then
+ * rebuilds LOD 1 .. levelCount (0 .. 5).  Vertices are in LOD-0 voxel coordinates (the space cvxh_mesh_rescale produces; the caller applies any
+ * placement or rotation); triangle k is vertices[indices[3k .. 3k+2]].  Per triangle: the corners pushed out by half a voxel, every voxel of the
+ * clamped box within half a voxel of the plane and inside the triangle, at most 262144 such hits (x, then z, then y order); the colour is the
+ * interpolated vertex colour, times the texel of material (int8_t)vertex0.material when that index is in 0 .. materialCount - 1 and the material
+ * has a texture (no texture: white); a texel with alpha < 1 emits no voxel (it still counts towards the 262144).  Parts outside the world are
+ * clipped.  Several hits of one voxel merge into the average of their colours (per channel sum / count, alpha 255: ToFinalColumn).
+ * op: CVX_BRUSH_FILL makes the stamped voxels solid with their colour (solid ones included), CVX_BRUSH_CARVE makes them air, CVX_BRUSH_PAINT
+ * recolours the solid ones and leaves air alone.  The rectangle is the XZ box of the stamped voxels rounded outward to multiples of
+ * 2^levelCount and clipped to the world; no stamped voxel: CVX_OK, nothing changes, *outDeviceMs = 0.  Ordering, atomicity, outDeviceMs and
+ * CVX_ERR_CAPACITY / CVX_ERR_NOT_READY are cvx_world_brush's; a voxel list that does not fit in device memory is CVX_ERR_CAPACITY and leaves the
+ * world as it was.  CVX_ERR_INVALID_ARGUMENT: a bad op, levelCount outside 0 .. 5, indexCount not a multiple of 3, an index outside
+ * 0 .. vertexCount - 1, materialCount outside 0 .. 128, a texture with rgba but a width or height below 1 (or above 2^15), a vertex coordinate
+ * that is not finite or whose magnitude is above 2^24.  Device memory while it runs, besides the mesh and its textures: ~72 bytes per triangle,
+ * 12 bytes per (triangle, column) pair of the triangles' boxes, ~40 bytes per hit (the voxel list and its sort), and cvx_world_brush's scratch
+ * for the rectangle.  With several GPUs every rank stamps its own context. */
+typedef struct cvx_mesh_vertex { /* 28 bytes */
+	float position[3];  /* LOD-0 voxel coordinates */
+	uint8_t rgba[4];    /* vertex colour (alpha unused) */
+	float uv[2];
+	int32_t material;   /* index into `materials`; used as (int8_t)material, like the reference's (sbyte) */
+} cvx_mesh_vertex;
+typedef struct cvx_mesh_texture { /* 16 bytes */
+	int32_t width, height;
+	const uint8_t *rgba; /* width * height RGBA8 texels, row 0 = the BOTTOM row (cvxh_image_load); NULL: no texture */
+} cvx_mesh_texture;
+#define CVX_STAMP_MAX_MATERIALS 128
+int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int vertexCount, const int32_t *indices, int64_t indexCount,
+                         const cvx_mesh_texture *materials, int materialCount, int op, int levelCount, float *outDeviceMs);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what

@@ -63,6 +63,26 @@ int64_t cvxh_world_lod0_voxels(const cvxh_world_set *worlds);
 int cvxh_world_extract_region(const cvxh_world_set *worlds, int lod, int x0, int z0, int sizeX, int sizeZ, void **out, int64_t *bytes, int32_t *columnCount);
 void cvxh_free(void *p);
 
+/* Triangle meshes for cvx_world_stamp_mesh: SimpleMesh (SimpleMesh.cs:11-106) with its materials' diffuse textures.  The vertex array is
+ * cvx_mesh_vertex (include/cpuvox_gpu.h), the layout of SimpleMesh.Vertex.  Release a mesh with cvxh_mesh_free. */
+typedef struct cvxh_mesh cvxh_mesh;
+/* ObjModel.Import (ObjModel.cs:10-171), as cvxh_world_from_obj reads the file: positions in the model's own units until cvxh_mesh_rescale. */
+int cvxh_mesh_load_obj(const char *path, int swapYZ, cvxh_mesh **out);
+/* A mesh built in code: copies the vertices, indices (a multiple of 3, each in 0 .. vertexCount - 1) and textures (rgba NULL: no texture). */
+int cvxh_mesh_create(const cvx_mesh_vertex *vertices, int vertexCount, const int32_t *indices, int64_t indexCount, const cvx_mesh_texture *materials,
+                     int materialCount, cvxh_mesh **out);
+/* SimpleMesh.Rescale (SimpleMesh.cs:49-106; what cvxh_world_from_obj applies, X flipped by default there): moves the mesh's minimum corner to
+ * the origin, scales its largest extent to maxDimension and mirrors the flipped axes inside the world; outDims = the world dimensions it
+ * asks for (NextPowerOfTwo of each scaled extent, 0 for an axis without extent). */
+int cvxh_mesh_rescale(cvxh_mesh *mesh, float maxDimension, int flipX, int flipY, int flipZ, int32_t outDims[3]);
+/* The mesh's arrays, owned by the mesh (valid until the next cvxh_mesh_rescale / cvxh_mesh_free; positions change with a rescale). */
+int cvxh_mesh_vertices(const cvxh_mesh *mesh, const cvx_mesh_vertex **outVertices, int32_t *outCount);
+int cvxh_mesh_indices(const cvxh_mesh *mesh, const int32_t **outIndices, int64_t *outCount);
+int cvxh_mesh_material_count(const cvxh_mesh *mesh);
+/* Material `material`'s diffuse texture (rgba NULL, width = height = 0: none), ready for cvx_world_stamp_mesh's materials array. */
+int cvxh_mesh_texture(const cvxh_mesh *mesh, int material, cvx_mesh_texture *out);
+void cvxh_mesh_free(cvxh_mesh *mesh);
+
 /* WorldBuilder (WordBuilder.cs:14-130) for explicit voxel lists: x,y,z,argb arrays of n entries
  * (argb = bytes A,R,G,B in memory order, little-endian packed). */
 typedef struct cvxh_world_builder cvxh_world_builder;

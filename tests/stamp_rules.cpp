@@ -1,0 +1,200 @@
+// Host build of the stamp rules (cpuvox_amd/csrc/cvx_stamp.h) for tests/test_world_stamp_cpu.py and tests/test_gpu_world_stamp.py.
+//   stamp_rules voxelise <mesh in> <voxels out>
+//     mesh: int32 dimX dimY dimZ vertexCount indexCount materialCount, the cvx_mesh_vertex array, the int32 indices, then per material int32 width
+//     height (width 0: no texture) and width * height * 4 texel bytes.  Every triangle through cvxs::VoxelizeTriangle in order; out: int32
+//     (x, y, z, argb) per emitted voxel, in emission order.
+//   stamp_rules stamp <cases in> <results out>
+//     Each case is one column in the reference's layout plus stamped voxels (int32 words): dimY stride colorsBase runCount (colorsIndex length)*
+//     colourCount colour* op voxelCount (y argb)*.  The column gets its record as in brush_rules; the voxels (any order, duplicates allowed) are
+//     sorted top-down and merged with cvxs::MergeStamped, then cvxs::StampColumn.  Out per case: overLimit runCount colours worldMin worldMax,
+//     then (unless over the limits) the runs and the colours.
+//   stamp_rules args
+//     The argument checks of cvx_world_stamp_mesh on a context that never touched a device (no world): one return code per call.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "cvx_context.h"
+#include "cvx_stamp.h"
+
+static std::vector<uint8_t> ReadFile(const char *path)
+{
+	std::vector<uint8_t> out;
+	FILE *f = std::fopen(path, "rb");
+	if (!f) { std::exit(2); }
+	for (int c; (c = std::fgetc(f)) != EOF;) { out.push_back((uint8_t)c); }
+	std::fclose(f);
+	return out;
+}
+
+static int WriteFile(const char *path, const std::vector<uint32_t> &words)
+{
+	FILE *f = std::fopen(path, "wb");
+	if (!f) { return 2; }
+	std::fwrite(words.data(), 4, words.size(), f);
+	std::fclose(f);
+	return 0;
+}
+
+static int Voxelise(const char *in, const char *outPath)
+{
+	const std::vector<uint8_t> bytes = ReadFile(in);
+	const uint8_t *p = bytes.data();
+	int32_t head[6];
+	std::memcpy(head, p, sizeof head);
+	p += sizeof head;
+	const int dimX = head[0], dimY = head[1], dimZ = head[2], vertexCount = head[3], indexCount = head[4], materialCount = head[5];
+	std::vector<cvx_mesh_vertex> vertices((size_t)vertexCount);
+	std::memcpy(vertices.data(), p, vertices.size() * sizeof(cvx_mesh_vertex));
+	p += vertices.size() * sizeof(cvx_mesh_vertex);
+	std::vector<int32_t> indices((size_t)indexCount);
+	std::memcpy(indices.data(), p, indices.size() * 4);
+	p += indices.size() * 4;
+	std::vector<cvxs::Texture> textures;
+	std::vector<uint8_t> texels;
+	for (int m = 0; m < materialCount; m++) {
+		int32_t wh[2];
+		std::memcpy(wh, p, sizeof wh);
+		p += sizeof wh;
+		if (wh[0] == 0) {
+			textures.push_back(cvxs::Texture{ 0, 0, -1 });
+			continue;
+		}
+		textures.push_back(cvxs::Texture{ wh[0], wh[1], (int64_t)texels.size() });
+		texels.insert(texels.end(), p, p + (size_t)wh[0] * wh[1] * 4);
+		p += (size_t)wh[0] * wh[1] * 4;
+	}
+	std::vector<uint32_t> out;
+	for (int t = 0; t + 2 < indexCount; t += 3) {
+		cvxs::VoxelizeTriangle(vertices[(size_t)indices[(size_t)t]], vertices[(size_t)indices[(size_t)t + 1]], vertices[(size_t)indices[(size_t)t + 2]], dimX, dimY, dimZ,
+		                       textures.data(), materialCount, texels.data(), [&](int x, int y, int z, uint32_t argb) {
+			                       out.push_back((uint32_t)x);
+			                       out.push_back((uint32_t)y);
+			                       out.push_back((uint32_t)z);
+			                       out.push_back(argb);
+		                       });
+	}
+	return WriteFile(outPath, out);
+}
+
+static int Stamp(const char *in, const char *outPath)
+{
+	const std::vector<uint8_t> bytes = ReadFile(in);
+	const int32_t *p = reinterpret_cast<const int32_t *>(bytes.data());
+	const int32_t *end = p + bytes.size() / 4;
+	std::vector<uint32_t> out;
+	while (p < end) {
+		const int dimY = *p++, stride = *p++, colorsBase = *p++, runCount = *p++;
+		std::vector<uint32_t> elements(1, 0u);
+		uint32_t start = 0;
+		int64_t lowest = -1, highest = -1;
+		for (int r = 0; r < runCount; r++) {
+			const int32_t ci = *p++, length = *p++;
+			elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
+			if (ci >= 0) {
+				const int64_t top = (int64_t)dimY - start;
+				if (highest < 0) { highest = top; }
+				lowest = top - length;
+			}
+			start += (uint32_t)length;
+		}
+		elements.push_back(0u);
+		const int colourCount = *p++;
+		std::vector<uint32_t> slots((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u);
+		for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
+		const int op = *p++, voxelCount = *p++;
+		std::vector<std::pair<uint32_t, uint32_t>> voxels((size_t)voxelCount);
+		for (int v = 0; v < voxelCount; v++) {
+			voxels[(size_t)v].first = (uint32_t)*p++;
+			voxels[(size_t)v].second = (uint32_t)*p++;
+		}
+		// the device's order: by y descending (the sort is stable; the merge does not depend on the order anyway)
+		std::stable_sort(voxels.begin(), voxels.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
+		std::vector<uint32_t> ys, argbs;
+		for (size_t i = 0; i < voxels.size();) {
+			size_t e = i + 1;
+			while (e < voxels.size() && voxels[e].first == voxels[i].first) { e++; }
+			std::vector<uint32_t> group;
+			for (size_t k = i; k < e; k++) { group.push_back(voxels[k].second); }
+			ys.push_back(voxels[i].first);
+			argbs.push_back(cvxs::MergeStamped(group.data(), (int)group.size()));
+			i = e;
+		}
+		const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
+		uint32_t x = 0, y = 0, z = 0, w = 0;
+		std::vector<uint32_t> runs(8, 0u);
+		if (runCount > 0) {
+			const cvxe::ColumnWords c = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
+			x = c.x | (uint32_t)colorsBase;
+			y = c.y;
+			z = c.z;
+			w = c.w;
+			if (c.code == 0u) {
+				z = 2u;
+				runs.resize(2u * (2u + c.solid) + 8u, 0u);
+				cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 4);
+			}
+		}
+		const cvxb::ArenaColumn col{ x, y, z, w, runs.data() };
+		const int colorShift = stride == 1 ? 2 : 7;
+		const int m = (int)ys.size();
+		const cvxb::BrushResult r = cvxs::StampColumn(col, slots.data(), colorShift, ys.data(), argbs.data(), m, op, dimY, nullptr, nullptr);
+		out.push_back(r.overLimit ? 1u : 0u);
+		out.push_back(r.runCount);
+		out.push_back(r.colours);
+		out.push_back(r.worldMin);
+		out.push_back(r.worldMax);
+		if (!r.overLimit) {
+			std::vector<uint32_t> newRuns(r.runCount + 1u), newColours(r.colours + 1u);
+			const cvxb::BrushResult again = cvxs::StampColumn(col, slots.data(), colorShift, ys.data(), argbs.data(), m, op, dimY, newRuns.data(), newColours.data());
+			if (again.runCount != r.runCount || again.colours != r.colours) { return 3; }
+			out.insert(out.end(), newRuns.begin(), newRuns.begin() + r.runCount);
+			out.insert(out.end(), newColours.begin(), newColours.begin() + r.colours);
+		}
+	}
+	return WriteFile(outPath, out);
+}
+
+static int Args()
+{
+	cvx_context *ctx = new cvx_context();
+	cvx_mesh_vertex v[3] = {};
+	for (int k = 0; k < 3; k++) { v[k].material = -1; }
+	v[1].position[0] = 4.f;
+	v[2].position[2] = 4.f;
+	const int32_t tri[3] = { 0, 1, 2 }, bad[3] = { 0, 1, 3 };
+	cvx_mesh_vertex nanV[3] = { v[0], v[1], v[2] }, farV[3] = { v[0], v[1], v[2] };
+	nanV[1].position[1] = __builtin_nanf("");
+	farV[2].position[0] = 3.0e7f;
+	cvx_mesh_texture emptyTex{ 0, 4, reinterpret_cast<const uint8_t *>(tri) };
+	cvx_mesh_texture noTex{ 0, 0, nullptr };
+	std::vector<cvx_mesh_texture> many(CVX_STAMP_MAX_MATERIALS + 1, noTex);
+	const int codes[] = {
+		cvx_world_stamp_mesh(nullptr, v, 3, tri, 3, nullptr, 0, CVX_BRUSH_FILL, 0, nullptr),
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 3, nullptr, 0, 3, 0, nullptr),           // op
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 3, nullptr, 0, CVX_BRUSH_FILL, 6, nullptr), // levelCount
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 3, nullptr, 0, CVX_BRUSH_FILL, -1, nullptr),
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 2, nullptr, 0, CVX_BRUSH_FILL, 0, nullptr), // indexCount
+		cvx_world_stamp_mesh(ctx, v, 3, bad, 3, nullptr, 0, CVX_BRUSH_FILL, 0, nullptr), // index
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 3, many.data(), (int)many.size(), CVX_BRUSH_FILL, 0, nullptr), // materialCount
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 3, nullptr, -1, CVX_BRUSH_FILL, 0, nullptr),
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 3, &emptyTex, 1, CVX_BRUSH_FILL, 0, nullptr), // texture size
+		cvx_world_stamp_mesh(ctx, nanV, 3, tri, 3, nullptr, 0, CVX_BRUSH_FILL, 0, nullptr), // coordinates
+		cvx_world_stamp_mesh(ctx, farV, 3, tri, 3, nullptr, 0, CVX_BRUSH_FILL, 0, nullptr),
+		cvx_world_stamp_mesh(ctx, v, 3, tri, 3, &noTex, 1, CVX_BRUSH_PAINT, 5, nullptr), // valid: no world yet
+	};
+	for (int c : codes) { std::printf("%d ", c); }
+	std::printf("\n");
+	return 0;
+}
+
+int main(int argc, char **argv)
+{
+	if (argc == 2 && std::strcmp(argv[1], "args") == 0) { return Args(); }
+	if (argc == 4 && std::strcmp(argv[1], "voxelise") == 0) { return Voxelise(argv[2], argv[3]); }
+	if (argc == 4 && std::strcmp(argv[1], "stamp") == 0) { return Stamp(argv[2], argv[3]); }
+	std::fprintf(stderr, "usage: stamp_rules voxelise <mesh> <voxels> | stamp <cases> <results> | args\n");
+	return 2;
+}
