@@ -134,6 +134,9 @@ struct cvx_context {
 	float tileCostPixelWeight = 0.f;           // launch-order estimate += weight * pixels of the tile's window (CVX_TILE_COST_PIXELS, diagnostics)
 	bool tileCostMiddleRay = false;            // CVX_TILE_COST_MIDDLE_RAY=1 (diagnostics): estimate from the tile's middle ray instead of its longer edge ray
 	int minMaskWords = 0;                      // CVX_MIN_MASK_WORDS (diagnostics): lower bound of the LDS mask words per lane, i.e. an occupancy cap
+#ifdef CVX_EXPERIMENTS
+	int64_t lastLaunch[8] = { -1, 0, 0, 0, 0, 0, 0, 0 }; // cvx_debug_last_launch (include/cpuvox_gpu_diag.h): the shape of the last draw's launch
+#endif
 };
 
 namespace cvxi {

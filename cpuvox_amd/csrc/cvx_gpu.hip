@@ -655,6 +655,15 @@ int cvx_set_shard(cvx_context *ctx, int shardIndex, int shardCount)
 } // extern "C"
 
 namespace {
+#ifdef CVX_EXPERIMENTS
+// cvx_debug_last_launch: what DrawBatch chose for the launch it is about to make (instance: 0 render_kernel<true>, 1 render_kernel<false>, 2 lone_kernel<false>,
+// 3 lone_kernel<true>; distinct rays per wave = lanes of a wave that hold rays of their own, the others duplicate them, 2^dupShift lanes per ray)
+void RecordLaunch(cvx_context *ctx, int instance, size_t tiles, size_t waves, int minRays, int maxRays, int maxDupShift, int split, int ldsWords)
+{
+	const int64_t v[8] = { instance, (int64_t)tiles, (int64_t)waves, minRays, maxRays, maxDupShift, split, ldsWords };
+	std::memcpy(ctx->lastLaunch, v, sizeof v);
+}
+#endif
 // Shared body of cvx_draw_segments_batch (library-owned tile layout) and cvx_draw_segments_placed (caller-chosen
 // output address per tile).
 int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments, const cvx_camera_data *cameras,
@@ -786,6 +795,9 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 				}
 			}
 			ctx->ldsWordsNeeded = 0;
+#ifdef CVX_EXPERIMENTS
+			RecordLaunch(ctx, ctx->launchLone == 2 ? 3 : 2, n, n * (size_t)CVX_WAVE, 1, 1, 0, 0, CVX_WAVE + ctx->lonePixels);
+#endif
 			return Launch(ctx, frameCount, flags);
 		}
 		int split = 1;
@@ -830,6 +842,9 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 		g_sourceTiles = n;
 #endif
 		int ldsWords = 1; // words * lanes of the largest wave
+#ifdef CVX_EXPERIMENTS
+		int minRays = n ? CVX_WAVE : 0, maxRays = 0, maxDup = 0;
+#endif
 		for (size_t i = 0; i < n; i++) {
 			DevTile t = ctx->hostTiles[order[i]];
 			const int words = ctx->hostTileWords[order[i]];
@@ -837,6 +852,10 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 			while (tileSplit < CVX_WAVE && words * (CVX_WAVE / tileSplit) > budget) { tileSplit *= 2; }
 			const int lanesPerWave = CVX_WAVE / tileSplit;
 			ldsWords = std::max(ldsWords, words * lanesPerWave);
+#ifdef CVX_EXPERIMENTS
+			minRays = std::min(minRays, lanesPerWave);
+			maxRays = std::max(maxRays, lanesPerWave);
+#endif
 			if (tileSplit == 1) {
 				sorted.push_back(t);
 #ifdef CVX_TILE_TIMES
@@ -851,6 +870,9 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 				int dupShift = 0;
 				while (!ctx->countersEnabled && (lanesPerWave << dupShift) < CVX_WAVE) { dupShift++; }
 				t.lanes = (k * lanesPerWave) | (lanesPerWave << 8) | (dupShift << 16);
+#ifdef CVX_EXPERIMENTS
+				maxDup = std::max(maxDup, dupShift);
+#endif
 				sorted.push_back(t);
 #ifdef CVX_TILE_TIMES
 				g_waveSource.push_back(order[i]);
@@ -858,6 +880,9 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 			}
 		}
 		ctx->ldsWordsNeeded = ldsWords;
+#ifdef CVX_EXPERIMENTS
+		RecordLaunch(ctx, ctx->countersEnabled ? 0 : 1, n, sorted.size(), minRays, maxRays, maxDup, split, std::max(ldsWords, ctx->minMaskWords * CVX_WAVE));
+#endif
 		ctx->hostTiles.swap(sorted);
 	}
 	return Launch(ctx, frameCount, flags);
@@ -1323,6 +1348,23 @@ int cvx_debug_occupancy(cvx_context *ctx, int64_t ldsBytes, int *blocksPerCU)
 	CVX_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, cvxk::render_kernel<false>, waveThreads, (size_t)ldsBytes));
 	return CVX_OK;
 }
+
+#ifdef CVX_EXPERIMENTS
+int cvx_debug_last_launch(cvx_context *ctx, int64_t out[8])
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	if (!out) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "out is NULL"); }
+	if (ctx->lastLaunch[0] < 0) { return Fail(ctx, CVX_ERR_NOT_READY, "no draw has been made"); }
+	std::memcpy(out, ctx->lastLaunch, sizeof ctx->lastLaunch);
+	return CVX_OK;
+}
+#else
+int cvx_debug_last_launch(cvx_context *ctx, int64_t out[8])
+{
+	(void)out;
+	return ctx ? Fail(ctx, CVX_ERR_NOT_READY, "cvx_debug_last_launch: experiment build only (make gpu-exp)") : CVX_ERR_INVALID_ARGUMENT;
+}
+#endif
 
 int cvx_debug_section_cycles(cvx_context *ctx, uint64_t out[32], int reset)
 {

@@ -39,7 +39,11 @@ EXPORTS = [
     "cvx_image_plan_tile_out", "cvx_image_pack", "cvx_image_exchange", "cvx_image_unpack",
 ]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
-DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram"]
+DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
+                "cvx_debug_last_launch"]
+# cvx_debug_last_launch: out[0], the kernel instance a draw went to
+INSTANCE_COUNTING, INSTANCE_BATCH, INSTANCE_LONE, INSTANCE_LONE_WIDE = 0, 1, 2, 3
+LAUNCH_FIELDS = ("instance", "tiles", "waves", "min_rays", "max_rays", "max_dup_shift", "split", "lds_words")
 
 
 class Counters(C.Structure):
@@ -202,6 +206,7 @@ def _bind(path: str) -> C.CDLL:
             L.cvx_debug_section_cycles.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
             L.cvx_debug_section_histogram.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
             L.cvx_debug_occupancy.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int)]
+            L.cvx_debug_last_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
             L.cvx_selftest_math.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             L.cvx_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
             L.cvx_selftest_lone.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -559,6 +564,17 @@ class Context:
         self._diag("cvx_debug_occupancy")
         self._check(lib().cvx_debug_occupancy(self._h, lds_bytes, C.byref(n)))
         return n.value
+
+    def debug_last_launch(self) -> dict:
+        """Experiment build only: the shape of the last draw's launch, LAUNCH_FIELDS -> value (include/cpuvox_gpu_diag.h)."""
+        out = (C.c_int64 * 8)()
+        self._check(self._diag("cvx_debug_last_launch")(self._h, out))
+        return dict(zip(LAUNCH_FIELDS, list(out)))
+
+    def set_buffer_count(self, buffer_count: int) -> None:
+        """cvx_set_buffer_count: raybuffer pairs of the context (the pools are allocated anew; the world stays)."""
+        self._check(lib().cvx_set_buffer_count(self._h, buffer_count))
+        self.buffer_count = buffer_count
 
     def debug_section_cycles(self, reset: bool = False):
         """Diagnostic build only: wave cycles per render-kernel section (include/cpuvox_gpu_diag.h)."""

@@ -14,6 +14,13 @@ extern "C" {
 /* Resident render-kernel workgroups (= waves) per CU the runtime predicts for a given dynamic LDS size. */
 int cvx_debug_occupancy(cvx_context *ctx, int64_t ldsBytes, int *blocksPerCU);
 
+/* Experiment build only (make gpu-exp): the shape of the last draw's launch as DrawBatch chose it.  out[0] the kernel instance (0 the counting
+ * render_kernel<true>, 1 the batch kernel render_kernel<false>, 2 lone_kernel<false>, 3 lone_kernel<true>), [1] tiles of the draw, [2] waves
+ * (workgroups) launched, [3] / [4] the least / most distinct rays a wave holds (lanes beyond them duplicate its rays; the latency kernel: 1),
+ * [5] the largest dupShift (2^dupShift lanes per ray), [6] the split factor of the launch (0: latency kernel), [7] LDS words (x 4 bytes) per
+ * wave.  CVX_ERR_NOT_READY before the first draw and in the other builds. */
+int cvx_debug_last_launch(cvx_context *ctx, int64_t out[8]);
+
 /* Diagnostic build only (make gpu-prof, -DCVX_PROFILE_SECTIONS): wave cycles spent per code section of the
  * render kernel (s_memtime stamps), accumulated over all launches.  Sections: 0 prologue/epilogue, 1 phase A
  * (DDA step + header + cull), 2 frustum clip, 3 element walk, 4 side-face setup, 5 side-face pixels,

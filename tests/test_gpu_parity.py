@@ -8,6 +8,7 @@ import pytest
 
 import oraclelib as O
 import scenes
+import waves
 from cpuvox_amd import gpu, host
 
 pytestmark = pytest.mark.gpu
@@ -157,6 +158,32 @@ def test_random_poses_fuzz_mill_and_odd_resolutions(contexts):
                 _compare(f"millfuzz {W}x{H} #{i} [{label}] pos={pos} eul={eul}", fr, g_td, g_lr, o_td, o_lr)
 
 
+def test_mill_fuzz_poses_in_full_waves(contexts):
+    """The first poses of test_random_poses_fuzz_mill_and_odd_resolutions (same seed, same draws) at every resolution, rendered again in full
+    64-ray waves (tests/waves.py): one launch per resolution, every frame against the oracle."""
+    rng = np.random.default_rng(7731)
+    ws = scenes.load_world("mill256")
+    for W, H in ((333, 217), (640, 360), (97, 401)):
+        ctx = contexts("mill256", W, H)
+        frames = []
+        for i in range(12):
+            frac = rng.uniform(-0.5, 1.5, size=3)
+            pos = [frac[k] * ws.dims[k] for k in range(3)]
+            eul = [rng.uniform(-89, 89), rng.uniform(0, 360), rng.choice([0.0, rng.uniform(0, 360)])]
+            if i < 6:
+                frames.append(scenes.make_frame(ws, W, H, pos, eul))
+        waves.check_full_waves(ctx, frames, W, H, f"millfuzz {W}x{H} poses 0-5", ws=ws)
+
+
+def test_mill512_1080p_in_full_waves(contexts):
+    """BASELINE config 2 (mill.obj 512^3 at 1920 x 1080, vanishing point on the screen) in full waves: the model world's listed columns and the
+    1080p windows, some of them wide enough for the LDS budget to cut, in one launch."""
+    name = "mill512_t075_1080p"
+    ws, fr, W, H = scenes.scene_frame(name)
+    ctx = contexts(scenes.SCENES[name][0], W, H)
+    waves.check_full_waves(ctx, [fr], W, H, name, ws=ws)
+
+
 def test_latency_kernel_wide_windows_fuzz(contexts):
     """The latency kernel keeps a ray's seen mask in ONE vector register (windows of up to 2048 pixels) or TWO (up to 4096: lone_kernel<true>).  Random poses at
     resolutions whose pixel windows end just below / above 2048 pixels and at odd offsets inside a mask word, both kernels against the oracle."""
@@ -198,33 +225,39 @@ def test_sharded_render_covers_every_tile_once(contexts):
     name = "proc256_t075_lod8"
     ws, fr, W, H = scenes.scene_frame(name)
     ctx = contexts(scenes.SCENES[name][0], W, H)
-    full = _render_gpu(ctx, fr)
-    acc = [np.full_like(full[0], CLEAR), np.full_like(full[1], CLEAR)]
-    for shard in range(3):
-        ctx.set_shard(shard, 3)
-        part = _render_gpu(ctx, fr)
-        for k in range(2):
-            written = part[k] != CLEAR
-            assert (acc[k][written] == CLEAR).all(), "tile rendered by two shards"
-            acc[k][written] = part[k][written]
-    ctx.set_shard(0, 1)
-    assert (acc[0] == full[0]).all() and (acc[1] == full[1]).all()
+    o_td, o_lr, _ = O.draw_segments(ws, fr, W, H, clear=CLEAR, counters=False)
+    for label, mode in BOTH_KERNELS:
+        full = _render_gpu(ctx, fr, latency=mode)
+        _compare(f"{name} unsharded [{label}]", fr, full[0], full[1], o_td, o_lr)
+        acc = [np.full_like(full[0], CLEAR), np.full_like(full[1], CLEAR)]
+        try:
+            for shard in range(3):
+                ctx.set_shard(shard, 3)
+                part = _render_gpu(ctx, fr, latency=mode)
+                for k in range(2):
+                    written = part[k] != CLEAR
+                    assert (acc[k][written] == CLEAR).all(), f"tile rendered by two shards [{label}]"
+                    acc[k][written] = part[k][written]
+        finally:
+            ctx.set_shard(0, 1)
+        assert (acc[0] == full[0]).all() and (acc[1] == full[1]).all(), f"the shards' union differs from the unsharded draw [{label}]"
 
 
 def test_blit_matches_pixel_centre_rule(contexts):
     for name in ("mill256_t075", "mill256_t09_roll", "proc256_t0_lod8"):
         ws, fr, W, H = scenes.scene_frame(name)
         ctx = contexts(scenes.SCENES[name][0], W, H)
-        g_td, g_lr = _render_gpu(ctx, fr)
-        img = ctx.blit_segments(0)
-        ref = O.blit_reference(fr, g_td, g_lr, W, H, clear=0)
-        assert (img == ref).all(), f"{name}: {(img != ref).sum()} screen pixels differ"
-        # ... and an independent check (float64 barycentrics, none of the kernel's edge-function arithmetic): the images may differ only where a
-        # weight or a ray coordinate lies within rounding distance of a boundary, and those pixels are a sliver of the screen
-        ref64, margin = O.blit_reference_f64(fr, g_td, g_lr, W, H, clear=0)
-        differ = img != ref64
-        assert not (differ & (margin > 1e-4)).any(), f"{name}: {(differ & (margin > 1e-4)).sum()} pixels away from every boundary differ from the float64 rule"
-        assert differ.mean() < 2e-3, f"{name}: {differ.sum()} pixels differ from the float64 rule"
+        for label, mode in BOTH_KERNELS:
+            g_td, g_lr = _render_gpu(ctx, fr, latency=mode)
+            img = ctx.blit_segments(0)
+            ref = O.blit_reference(fr, g_td, g_lr, W, H, clear=0)
+            assert (img == ref).all(), f"{name} [{label}]: {(img != ref).sum()} screen pixels differ"
+            # ... and an independent check (float64 barycentrics, none of the kernel's edge-function arithmetic): the images may differ only where a
+            # weight or a ray coordinate lies within rounding distance of a boundary, and those pixels are a sliver of the screen
+            ref64, margin = O.blit_reference_f64(fr, g_td, g_lr, W, H, clear=0)
+            differ = img != ref64
+            assert not (differ & (margin > 1e-4)).any(), f"{name} [{label}]: {(differ & (margin > 1e-4)).sum()} pixels away from every boundary differ from the float64 rule"
+            assert differ.mean() < 2e-3, f"{name} [{label}]: {differ.sum()} pixels differ from the float64 rule"
 
 
 def test_batch_blit_equals_single_blits():
@@ -297,9 +330,11 @@ def test_world_with_device_built_lods_renders_identically(contexts):
         assert np.array_equal(rebuilt.storage(lod), ws.storage(lod)), f"LOD {lod} blob differs"
     ctx.upload_world(rebuilt)
     try:
-        g_td, g_lr = _render_gpu(ctx, fr)
         o_td, o_lr, _ = O.draw_segments(ws, fr, W, H, clear=CLEAR, counters=False)
-        _compare(name, fr, g_td, g_lr, o_td, o_lr)
+        for label, mode in BOTH_KERNELS:
+            g_td, g_lr = _render_gpu(ctx, fr, latency=mode)
+            _compare(f"{name} [{label}]", fr, g_td, g_lr, o_td, o_lr)
+        waves.check_full_waves(ctx, [fr], W, H, name, oracles=[(o_td, o_lr)])
     finally:
         ctx.upload_world(ws)
 
@@ -414,7 +449,9 @@ def test_lod_chain_deeper_than_its_sums_reach_and_its_fallback(exp_library):
 @pytest.mark.parametrize("split", [1, 2, 16, 64])
 def test_sub_tile_split_is_invisible(split, exp_library):
     """Small batches are rendered with tiles cut into sub-tiles of 64 / split rays per wave (DrawBatch); the raybuffers and the
-    counters must not depend on the cut (CVX_TILE_SPLIT pins the factor; the other tests run with the automatic choice)."""
+    counters must not depend on the cut (CVX_TILE_SPLIT pins the factor; the other tests run with the automatic choice).  Counting build,
+    then the rendering build pinned to the batch kernel: there a sub-tile of 64 / split rays gives every ray 2^dupShift = split lanes
+    (cvx_debug_last_launch confirms the shape the launch had)."""
     exp_library.setenv("CVX_TILE_SPLIT", str(split))
     ctx = gpu.Context(0)
     try:
@@ -427,6 +464,43 @@ def test_sub_tile_split_is_invisible(split, exp_library):
             o_td, o_lr, oc = O.draw_segments(ws, fr, W, H, clear=CLEAR)
             _compare(f"{name} split {split}", fr, g_td, g_lr, o_td, o_lr)
             assert (c.S, c.E, c.C, c.P, c.R) == (oc.S, oc.E, oc.C, oc.P, oc.R)
+            shape = ctx.debug_last_launch()
+            assert shape["instance"] == gpu.INSTANCE_COUNTING and shape["split"] == split and shape["max_dup_shift"] == 0, shape
+            g_td, g_lr = _render_gpu(ctx, fr, latency=gpu.LATENCY_NEVER)
+            shape = ctx.debug_last_launch()
+            _compare(f"{name} split {split} [batch kernel, launch {shape}]", fr, g_td, g_lr, o_td, o_lr)
+            assert shape["instance"] == gpu.INSTANCE_BATCH and shape["split"] == split, shape
+            assert shape["min_rays"] == shape["max_rays"] == 64 // split and 1 << shape["max_dup_shift"] == split, shape
+    finally:
+        ctx.close()
+
+
+def test_lds_budget_cuts_only_the_widest_tiles(exp_library):
+    """CVX_MAX_WAVE_MASK_WORDS pins the LDS budget per wave (words x lanes).  Chosen from the frame's tile widths so that the widest tiles need
+    two waves of 32 rays while the narrower ones stay whole: ONE launch at split 1 then mixes 64- and 32-ray waves (the narrow ones with
+    dupShift 1 in the rendering build), which must not change a pixel.  Counting build and batch kernel against the oracle."""
+    name = "mill256_t075"  # vanishing point on the screen: four segments, top / bottom windows narrower than left / right
+    ws, fr, W, H = scenes.scene_frame(name)
+    words = sorted(set(waves.frame_mask_words(fr, W, H)))
+    assert len(words) >= 2, words
+    budget = (words[-1] - 1) * 64  # the widest tiles (words[-1] words per lane) no longer fit 64 lanes, all others do
+    assert words[-1] * 32 <= budget and words[-2] * 64 <= budget
+    exp_library.setenv("CVX_TILE_SPLIT", "1")
+    exp_library.setenv("CVX_MAX_WAVE_MASK_WORDS", str(budget))
+    ctx = gpu.Context(0)
+    try:
+        ctx.upload_world(ws)
+        ctx.set_resolution(W, H)
+        o_td, o_lr, oc = O.draw_segments(ws, fr, W, H, clear=CLEAR)
+        for counting, label, mode in ((True, "counting build", gpu.LATENCY_NEVER), (False, "batch kernel", gpu.LATENCY_NEVER)):
+            g_td, g_lr = _render_gpu(ctx, fr, counters=counting, latency=mode)
+            shape = ctx.debug_last_launch()
+            _compare(f"{name} LDS budget {budget} words [{label}, launch {shape}]", fr, g_td, g_lr, o_td, o_lr)
+            assert shape["split"] == 1 and shape["min_rays"] == 32 and shape["max_rays"] == 64 and shape["lds_words"] <= budget, shape
+            assert shape["max_dup_shift"] == (0 if counting else 1) and shape["tiles"] < shape["waves"] < 2 * shape["tiles"], shape
+            if counting:
+                c = ctx.counters()
+                assert (c.S, c.E, c.C, c.P, c.R) == (oc.S, oc.E, oc.C, oc.P, oc.R)
     finally:
         ctx.close()
 
@@ -445,16 +519,19 @@ def test_launch_order_is_invisible(order, exp_library):
     names = ["proc256_t0_lod8", "proc256_t04_lod8", "proc256_t075_lod8", "proc256_t075_lod1"]  # one world, one resolution
     frames = [scenes.scene_frame(n)[1] for n in names]
     ws, _, W, H = scenes.scene_frame(names[0])
+    oracles = [O.draw_segments(ws, fr, W, H, clear=CLEAR, counters=False)[:2] for fr in frames]
     ctx = gpu.Context(0, buffer_count=len(frames))
     try:
         ctx.upload_world(ws)
         ctx.set_resolution(W, H)
-        for b in range(len(frames)):
-            ctx.clear_raybuffers(b, CLEAR)
-        ctx.draw_segments_batch(frames, 0)
-        for b, (n, fr) in enumerate(zip(names, frames)):
-            o_td, o_lr, _ = O.draw_segments(ws, fr, W, H, clear=CLEAR)
-            _compare(f"{n} order {order}", fr, ctx.read_raybuffer(b, gpu.RAYBUFFER_TOPDOWN), ctx.read_raybuffer(b, gpu.RAYBUFFER_LEFTRIGHT), o_td, o_lr)
+        for label, mode in BOTH_KERNELS:  # the batch kernel (the order is its launch order), then the latency kernel (same sorted tile list)
+            for b in range(len(frames)):
+                ctx.clear_raybuffers(b, CLEAR)
+            ctx.set_latency_kernel(mode)
+            ctx.draw_segments_batch(frames, 0)
+            ctx.set_latency_kernel(gpu.LATENCY_AUTO)
+            for b, (n, fr) in enumerate(zip(names, frames)):
+                _compare(f"{n} order {order} [{label}]", fr, ctx.read_raybuffer(b, gpu.RAYBUFFER_TOPDOWN), ctx.read_raybuffer(b, gpu.RAYBUFFER_LEFTRIGHT), *oracles[b])
     finally:
         ctx.close()
 
@@ -682,7 +759,7 @@ def test_run_rich_world_slow_paths(contexts):
     below it looking up: the world's columns then project INSIDE the pixel window instead of straddling it, so every frustum clip takes the
     reference's own path (`windowUntouched == false`: the four projections, floor / ceil, the window update and the window-closed exit) instead
     of the proven shortcut; cameras inside the world for the straddling case next to it.  Both iteration directions, counting and rendering
-    build, two resolutions, against the oracle."""
+    build, two resolutions, against the oracle -- and every pose again in full 64-ray waves (tests/waves.py), one launch per resolution."""
     name = "stripes128x256x128"
     ws = scenes.load_world(name)
     poses = [((64.3, 128.0, 20.2), (0.0, 10.0, 0.0)), ((64.3, 400.0, 64.2), (60.0, 30.0, 0.0)), ((20.3, 420.0, 30.2), (35.0, 45.0, 0.0)),
@@ -691,17 +768,21 @@ def test_run_rich_world_slow_paths(contexts):
     directions = set()
     for W, H in ((320, 200), (517, 333)):
         ctx = contexts(name, W, H)
+        frames, oracles = [], []
         for pos, eul in poses:
             fr = scenes.make_frame(ws, W, H, pos, eul)
             directions.add(bool(fr.camera.InverseElementIterationDirection))
             o_td, o_lr, cnt = O.draw_segments(ws, fr, W, H, clear=CLEAR)
             assert cnt.E > 15 * cnt.S, "the world is not run-rich for this pose"
-            for counting in (True, False):
-                g_td, g_lr = _render_gpu(ctx, fr, counters=counting)
-                _compare(f"stripes {W}x{H} pos={pos} eul={eul} counting={counting}", fr, g_td, g_lr, o_td, o_lr)
+            for counting, label, mode in [(True, "counting build", gpu.LATENCY_AUTO)] + [(False, l, m) for l, m in BOTH_KERNELS]:
+                g_td, g_lr = _render_gpu(ctx, fr, counters=counting, latency=mode)
+                _compare(f"stripes {W}x{H} pos={pos} eul={eul} [{label}]", fr, g_td, g_lr, o_td, o_lr)
                 if counting:
                     gc = ctx.counters()
                     assert (gc.S, gc.E, gc.C, gc.P, gc.R) == (cnt.S, cnt.E, cnt.C, cnt.P, cnt.R), (gc.as_dict(), cnt.as_dict())
+            frames.append(fr)
+            oracles.append((o_td, o_lr))
+        waves.check_full_waves(ctx, frames, W, H, f"stripes {W}x{H}", oracles=oracles)
     assert directions == {False, True}, "both element iteration directions must be covered"
 
 
@@ -745,6 +826,7 @@ def test_foreign_blob_columns_go_through_the_run_list():
         ctx.upload_world(ws)
         ctx.set_resolution(W, H)
         directions = set()
+        frames, oracles = [], []
         for pos, eul in (((32.3, 70.0, 5.2), (5.0, 10.0, 0.0)), ((32.3, 140.0, 32.2), (70.0, 30.0, 0.0)), ((10.3, -20.0, 50.2), (-40.0, 120.0, 0.0)),
                          ((60.3, 64.0, 60.2), (0.0, 225.0, 0.0)), ((32.3, 100.0, 32.2), (-25.0, 300.0, 0.0))):
             fr = scenes.make_frame(ws, W, H, pos, eul)
@@ -756,7 +838,10 @@ def test_foreign_blob_columns_go_through_the_run_list():
                 if counting:
                     gc = ctx.counters()
                     assert (gc.S, gc.E, gc.C, gc.P, gc.R) == (cnt.S, cnt.E, cnt.C, cnt.P, cnt.R), (gc.as_dict(), cnt.as_dict())
+            frames.append(fr)
+            oracles.append((o_td, o_lr))
         assert directions == {False, True}
+        waves.check_full_waves(ctx, frames, W, H, "foreign blob", oracles=oracles)
     finally:
         ctx.close()
 
@@ -773,16 +858,20 @@ def test_sparse_deep_world_keeps_its_colours_column_after_column():
     try:
         ctx.upload_world(ws)
         ctx.set_resolution(W, H)
+        frames, oracles = [], []
         for pos, eul in (((32.3, 130.0, -20.2), (5.0, 0.0, 0.0)), ((32.3, 300.0, 32.2), (80.0, 30.0, 0.0)), ((-10.3, 100.0, 70.2), (-10.0, 120.0, 0.0)), ((32.3, 128.0, 32.2), (0.0, 45.0, 0.0))):
             fr = scenes.make_frame(ws, W, H, pos, eul)
             o_td, o_lr, cnt = O.draw_segments(ws, fr, W, H, clear=CLEAR)
             assert cnt.P > 0
-            for counting in (True, False):
-                g_td, g_lr = _render_gpu(ctx, fr, counters=counting)
-                _compare(f"sparse world pos={pos} eul={eul} counting={counting}", fr, g_td, g_lr, o_td, o_lr)
+            for counting, label, mode in [(True, "counting build", gpu.LATENCY_AUTO)] + [(False, l, m) for l, m in BOTH_KERNELS]:
+                g_td, g_lr = _render_gpu(ctx, fr, counters=counting, latency=mode)
+                _compare(f"sparse world pos={pos} eul={eul} [{label}]", fr, g_td, g_lr, o_td, o_lr)
                 if counting:
                     gc = ctx.counters()
                     assert (gc.S, gc.E, gc.C, gc.P, gc.R) == (cnt.S, cnt.E, cnt.C, cnt.P, cnt.R), (gc.as_dict(), cnt.as_dict())
+            frames.append(fr)
+            oracles.append((o_td, o_lr))
+        waves.check_full_waves(ctx, frames, W, H, "sparse world", oracles=oracles)
     finally:
         ctx.close()
 
@@ -798,12 +887,13 @@ def test_one_level_uploaded_again_keeps_the_others(contexts):
         for lod in (1, 0, 3):
             i = ws.info(lod)
             ctx._check(gpu.lib().cvx_world_upload(ctx._h, lod, i.storage, i.byteLength, i.dimX, i.dimY, i.dimZ, i.columnCount))
-            for counting in (True, False):
-                g_td, g_lr = _render_gpu(ctx, fr, counters=counting)
-                _compare(f"{name} after level {lod} again, counting={counting}", fr, g_td, g_lr, o_td, o_lr)
+            for counting, label, mode in [(True, "counting build", gpu.LATENCY_AUTO)] + [(False, l, m) for l, m in BOTH_KERNELS]:
+                g_td, g_lr = _render_gpu(ctx, fr, counters=counting, latency=mode)
+                _compare(f"{name} after level {lod} again [{label}]", fr, g_td, g_lr, o_td, o_lr)
                 if counting:
                     gc = ctx.counters()
                     assert (gc.S, gc.E, gc.C, gc.P, gc.R) == (cnt.S, cnt.E, cnt.C, cnt.P, cnt.R), (gc.as_dict(), cnt.as_dict())
+            waves.check_full_waves(ctx, [fr], W, H, f"{name} after level {lod} again", oracles=[(o_td, o_lr)])
     finally:
         ctx.upload_world(ws)
 
@@ -822,17 +912,21 @@ def test_long_world_far_edge_checkpoints(contexts):
     poses = [((3.5, 900.0, 128.5), (0.0, 90.0, 0.0)), ((16380.5, 880.0, 100.2), (0.2, 270.01, 0.0)), ((-3000.0, 870.0, 127.3), (-0.1, 90.0, 0.0)),
              ((8000.0, 860.0, 30.3), (0.1, 89.2, 0.0)), ((100.5, 850.0, 250.0), (0.0, 91.0, 0.0))]
     longest = 0
+    frames, oracles = [], []
     for pos, eul in poses:
         pose = host.camera_pose(pos, eul, W, H)
         fr = host.setup_frame(pose, [200000.0] * 6, 100000.0, W, H, ws.dims[1], True)
         o_td, o_lr, cnt = O.draw_segments(ws, fr, W, H, clear=CLEAR)
-        for counting in (True, False):
-            g_td, g_lr = _render_gpu(ctx, fr, counters=counting)
-            _compare(f"long world pos={pos} eul={eul} counting={counting}", fr, g_td, g_lr, o_td, o_lr)
+        for counting, label, mode in [(True, "counting build", gpu.LATENCY_AUTO)] + [(False, l, m) for l, m in BOTH_KERNELS]:
+            g_td, g_lr = _render_gpu(ctx, fr, counters=counting, latency=mode)
+            _compare(f"long world pos={pos} eul={eul} [{label}]", fr, g_td, g_lr, o_td, o_lr)
             if counting:
                 gc = ctx.counters()
                 assert (gc.S, gc.E, gc.C, gc.P, gc.R) == (cnt.S, cnt.E, cnt.C, cnt.P, cnt.R), (gc.as_dict(), cnt.as_dict())
         longest = max(longest, cnt.S)
+        frames.append(fr)
+        oracles.append((o_td, o_lr))
+    waves.check_full_waves(ctx, frames, W, H, "long world", oracles=oracles)
     assert longest > 10 * 16000, "no frame with ~a dozen rays along the whole world: the scenario no longer exercises the checkpoints"
 
 

@@ -8,6 +8,7 @@ import pytest
 
 import oraclelib as O
 import scenes
+import waves
 from cpuvox_amd import gpu, host
 
 pytestmark = pytest.mark.gpu
@@ -108,12 +109,15 @@ def _assert_same(label, a, b):
 
 
 def _check_world(ctx, ws_expected, frames, label, fresh=True):
-    """ctx renders what the oracle renders on ws_expected (and what a fresh context of ws_expected renders), through both kernels."""
+    """ctx renders what the oracle renders on ws_expected (and what a fresh context of ws_expected renders), through both kernels -- and, as a
+    third mode, the frames repeated into one launch of full 64-ray waves (tests/waves.py), every frame against the oracle."""
     ref = _context(ws_expected) if fresh else None
     visited = np.zeros(6, dtype=np.int64)
+    oracles = []
     try:
         for k, fr in enumerate(frames):
             o_td, o_lr, cnt = O.draw_segments(ws_expected, fr, W, H, clear=CLEAR)
+            oracles.append((o_td, o_lr))
             visited += np.array(cnt.lodVisits[:6])
             n_td, n_lr = scenes.used_rows(fr)
             for name, mode in BOTH_KERNELS:
@@ -121,6 +125,7 @@ def _check_world(ctx, ws_expected, frames, label, fresh=True):
                 _assert_same(f"{label} frame {k} {name} vs oracle", got, (o_td[:n_td], o_lr[:n_lr]))
                 if ref is not None:
                     _assert_same(f"{label} frame {k} {name} vs fresh upload", got, _draw(ref, fr, mode))
+        waves.check_full_waves(ctx, frames, W, H, label, oracles=oracles)
     finally:
         if ref is not None:
             ref.close()
