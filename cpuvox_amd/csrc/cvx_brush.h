@@ -181,6 +181,7 @@ struct PickWorld {
 	const uint8_t *colours;     // colour array (bytes)
 	int rowShift, colorShift;
 	int dimX, dimY, dimZ;
+	int repeat = 0;             // 1: the world repeats in X and Z (cvx_set_world_repeat): PickRayRepeat
 };
 
 struct PickResult {
@@ -200,6 +201,9 @@ struct PickResult {
 //      voxel of the column -> the face the column was entered through, t = tc0; a later one (or any one in the column a ray starts in) -> its +Y
 //      (down) or -Y (up) face, t = the plane's.
 //   4. step to the nearer plane (x on a tie: the diagonal step takes two steps, the second one of length 0); stop at tExit.
+// A repeating world (PickRayRepeat): step 1 clips to the Y slab only, the columns of steps 3 and 4 are looked up wrapped into the tile (floor-mod) and
+// the walk ends at tExit only; maxT must be at most 2^20 (else a miss), and the origin's |x|, |z| below 2^40.  The reported voxel is the wrapped one,
+// t the parameter along the ray itself.
 CVX_HD inline PickResult PickMiss(float maxT) { return PickResult{ { -1, -1, -1 }, -1, 0u, maxT }; }
 
 struct alignas(16) Record { uint32_t x, y, z, w; };
@@ -310,6 +314,121 @@ CVX_HD inline PickResult PickRay(const PickWorld &W, const float originF[3], con
 		if (tNext >= tExit) { break; }
 		if (stepAlongX) { cx += stepX; face = stepX > 0 ? 0 : 1; } else { cz += stepZ; face = stepZ > 0 ? 4 : 5; }
 		if (cx < 0 || cx >= W.dimX || cz < 0 || cz >= W.dimZ) { break; }
+		tc0 = tNext;
+		at = nextAt;
+		rec = next;
+	}
+	return PickMiss(maxTF);
+}
+
+
+// PickRay in a repeating world (W.repeat): the same rule with the changes listed above the miss helper; kept apart from PickRay so that the
+// bounded traversal stays exactly what it was.
+CVX_HD inline PickResult PickRayRepeat(const PickWorld &W, const float originF[3], const float directionF[3], float maxTF)
+{
+	const double o[3] = { originF[0], originF[1], originF[2] }, d[3] = { directionF[0], directionF[1], directionF[2] };
+	const double dim[3] = { (double)W.dimX, (double)W.dimY, (double)W.dimZ };
+	double inv[3];
+	double tEnter = 0.0, tExit = (double)maxTF;
+	int enterAxis = -1;
+	const bool repeat = W.repeat != 0;
+	if (repeat && !(maxTF <= 1048576.0f && __builtin_fabs(o[0]) < 0x1p40 && __builtin_fabs(o[2]) < 0x1p40)) { return PickMiss(maxTF); }
+	for (int a = 0; a < 3; a++) {
+		if (!Finite(o[a]) || !Finite(d[a])) { return PickMiss(maxTF); }
+		if (repeat && a != 1) { // no X / Z slab in a repeating world
+			inv[a] = d[a] == 0.0 ? 0.0 : 1.0 / d[a];
+			continue;
+		}
+		if (d[a] == 0.0) {
+			inv[a] = 0.0;
+			if (!(o[a] >= 0.0 && o[a] < dim[a])) { return PickMiss(maxTF); }
+			continue;
+		}
+		inv[a] = 1.0 / d[a];
+		double t0 = (0.0 - o[a]) * inv[a], t1 = (dim[a] - o[a]) * inv[a];
+		if (t0 > t1) { const double s = t0; t0 = t1; t1 = s; }
+		if (t0 > tEnter) { tEnter = t0; enterAxis = a; }
+		if (t1 < tExit) { tExit = t1; }
+	}
+	if (!(tEnter <= tExit)) { return PickMiss(maxTF); }
+	const int64_t lastY = W.dimY - 1;
+	const int64_t maskX = W.dimX - 1, maskZ = W.dimZ - 1; // (power-of-two dimensions)
+	// (a repeating world: cx / cz are the unwrapped columns along the ray -- the plane distances below use them --, records and voxels their wrapped form)
+	const int64_t cx0 = repeat ? (int64_t)__builtin_floor(o[0] + tEnter * d[0]) : ClampY(__builtin_floor(o[0] + tEnter * d[0]), W.dimX - 1);
+	const int64_t cz0 = repeat ? (int64_t)__builtin_floor(o[2] + tEnter * d[2]) : ClampY(__builtin_floor(o[2] + tEnter * d[2]), W.dimZ - 1);
+	int64_t cx = cx0, cz = cz0;
+	const int stepX = d[0] > 0.0 ? 1 : -1, stepZ = d[2] > 0.0 ? 1 : -1;
+	const int64_t recordStepX = (int64_t)stepX << W.rowShift, recordStepZ = stepZ;
+	int face = enterAxis < 0 ? 6 : 2 * enterAxis + (d[enterAxis] > 0.0 ? 0 : 1);
+	int64_t at = ((cx & maskX) << W.rowShift) + (cz & maskZ);
+	Record rec = PickRecord(W, at);
+	if (enterAxis < 0) { // 2. the origin's own voxel
+		const ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, W.runs };
+		const uint32_t v = (uint32_t)ClampY(__builtin_floor(o[1]), lastY);
+		for (uint32_t k = 0; k < col.Count(); k++) {
+			const SolidRun run = col.Run(k);
+			if (v >= run.bottom && v < run.top) {
+				return PickResult{ { (int32_t)(cx & maskX), (int32_t)v, (int32_t)(cz & maskZ) }, 6, PickColour(W, col, run, v), 0.0f };
+			}
+		}
+	}
+	double tc0 = tEnter;
+	const bool down = d[1] < 0.0, level = d[1] == 0.0;
+	// (a repeating world: the columns up to tExit <= 2^20, at most 2^24 of them)
+	const double repeatSteps = (__builtin_fabs(d[0]) + __builtin_fabs(d[2])) * tExit + 4.0;
+	for (int64_t guard = repeat ? (int64_t)(repeatSteps < 16777216.0 ? repeatSteps : 16777216.0) : (int64_t)W.dimX + W.dimZ + 2; guard > 0; guard--) {
+		const double tx = d[0] != 0.0 ? ((double)(cx + (stepX > 0 ? 1 : 0)) - o[0]) * inv[0] : __builtin_inf();
+		const double tz = d[2] != 0.0 ? ((double)(cz + (stepZ > 0 ? 1 : 0)) - o[2]) * inv[2] : __builtin_inf();
+		const bool stepAlongX = tx <= tz;
+		const double tNext = stepAlongX ? tx : tz;
+		const double tc1 = tNext < tExit ? tNext : tExit;
+		const int64_t nextAt = repeat ? (stepAlongX ? (((cx + stepX) & maskX) << W.rowShift) + (cz & maskZ) : ((cx & maskX) << W.rowShift) + ((cz + stepZ) & maskZ))
+		                              : at + (stepAlongX ? recordStepX : recordStepZ);
+		const Record next = PickRecord(W, nextAt); // one step ahead (the tables have a guard row on both sides)
+		const ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, W.runs };
+		if (col.x != 0u) {
+			const double ya = o[1] + tc0 * d[1], yb = o[1] + tc1 * d[1];
+			int64_t vA, vB;
+			if (level) {
+				vA = vB = ClampY(__builtin_floor(o[1]), lastY);
+			} else if (down) {
+				vA = ClampY(__builtin_ceil(ya) - 1.0, lastY);
+				vB = ClampY(__builtin_floor(yb), lastY);
+			} else {
+				vA = ClampY(__builtin_floor(ya), lastY);
+				vB = ClampY(__builtin_ceil(yb) - 1.0, lastY);
+			}
+			const int64_t lo = vA < vB ? vA : vB, hi = vA < vB ? vB : vA;
+			const bool empty = level ? false : (down ? vA < vB : vA > vB);
+			if (!empty && hi >= (int64_t)col.WorldMin() && lo < (int64_t)col.WorldMax()) {
+				int64_t best = -1;
+				SolidRun bestRun{ 0u, 0u, 0u };
+				for (uint32_t k = 0; k < col.Count(); k++) {
+					const SolidRun run = col.Run(k);
+					if ((int64_t)run.bottom > hi || (int64_t)run.top - 1 < lo) { continue; }
+					const int64_t v = down || level ? ((int64_t)run.top - 1 < vA ? (int64_t)run.top - 1 : vA) : ((int64_t)run.bottom > vA ? (int64_t)run.bottom : vA);
+					if (best < 0 || (down || level ? v > best : v < best)) { best = v; bestRun = run; }
+				}
+				if (best >= 0) {
+					PickResult hit;
+					hit.voxel[0] = (int32_t)(cx & maskX);
+					hit.voxel[1] = (int32_t)best;
+					hit.voxel[2] = (int32_t)(cz & maskZ);
+					hit.argb = PickColour(W, col, bestRun, (uint32_t)best);
+					if (best == vA && face != 6) { // (face 6: the first column of a ray that starts in it; its own voxel is air)
+						hit.face = face;
+						hit.t = (float)tc0;
+					} else {
+						hit.face = down ? 3 : 2;
+						hit.t = (float)(((double)(down ? best + 1 : best) - o[1]) * inv[1]);
+					}
+					return hit;
+				}
+			}
+		}
+		if (tNext >= tExit) { break; }
+		if (stepAlongX) { cx += stepX; face = stepX > 0 ? 0 : 1; } else { cz += stepZ; face = stepZ > 0 ? 4 : 5; }
+		if (!repeat && (cx < 0 || cx >= W.dimX || cz < 0 || cz >= W.dimZ)) { break; }
 		tc0 = tNext;
 		at = nextAt;
 		rec = next;

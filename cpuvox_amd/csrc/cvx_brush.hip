@@ -82,7 +82,7 @@ __global__ __launch_bounds__(CVX_WAVE) void pick_kernel(cvxb::PickWorld W, int r
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= rayCount) { return; }
 	const cvx_pick_ray ray = rays[i];
-	const cvxb::PickResult r = cvxb::PickRay(W, ray.origin, ray.direction, ray.maxT);
+	const cvxb::PickResult r = W.repeat ? cvxb::PickRayRepeat(W, ray.origin, ray.direction, ray.maxT) : cvxb::PickRay(W, ray.origin, ray.direction, ray.maxT);
 	cvx_pick_hit out;
 	out.voxel[0] = r.voxel[0];
 	out.voxel[1] = r.voxel[1];
@@ -147,6 +147,7 @@ cvxb::PickWorld PickWorldOf(const cvx_context *ctx)
 	P.dimX = W.dimX;
 	P.dimY = W.dimY;
 	P.dimZ = W.dimZ;
+	P.repeat = ctx->worldRepeat;
 	return P;
 }
 
@@ -292,7 +293,8 @@ int cvx_world_pick_device(cvx_context *ctx, int rayCount, const cvx_pick_ray *ra
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (rayCount < 0 || (rayCount > 0 && (!raysDevice || !hitsDevice))) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad rays / hits (rayCount %d)", rayCount); }
-	const int rc = Prepare(ctx);
+	int rc = Prepare(ctx);
+	if (rc == CVX_OK && ctx->worldRepeat) { rc = cvxi::ValidateRepeat(ctx); }
 	if (rc != CVX_OK) { return rc; }
 	if (rayCount == 0) { return CVX_OK; }
 	hipStream_t stream = hipStream ? static_cast<hipStream_t>(hipStream) : ctx->stream;
@@ -306,6 +308,12 @@ int cvx_world_pick(cvx_context *ctx, int rayCount, const cvx_pick_ray *rays, cvx
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (rayCount < 0 || (rayCount > 0 && (!rays || !hits))) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad rays / hits (rayCount %d)", rayCount); }
 	int rc = Prepare(ctx);
+	if (rc == CVX_OK && ctx->worldRepeat) {
+		rc = cvxi::ValidateRepeat(ctx);
+		for (int i = 0; i < rayCount && rc == CVX_OK; i++) {
+			if (!(rays[i].maxT <= CVX_REPEAT_MAX_DISTANCE)) { rc = Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "repeating world: ray %d has maxT %g, above 2^20", i, (double)rays[i].maxT); }
+		}
+	}
 	if (rc != CVX_OK) { return rc; }
 	if (rayCount == 0) { return CVX_OK; }
 	const size_t raysBytes = ((size_t)rayCount * sizeof(cvx_pick_ray) + 255) & ~(size_t)255, hitsBytes = (size_t)rayCount * sizeof(cvx_pick_hit);

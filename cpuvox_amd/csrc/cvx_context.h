@@ -123,6 +123,7 @@ struct cvx_context {
 #define CVX_LONE_DEFAULT_MODE 1
 #endif
 	int loneMode = CVX_LONE_DEFAULT_MODE; // 1: lone_kernel for launches of at most loneWaveBudget rays; 0 never, 2 always (experiment build: CVX_LONE=0 / 1; variants: -DCVX_LONE_DEFAULT_MODE)
+	int worldRepeat = 0;             // cvx_set_world_repeat: 1 = the world repeats in X and Z (draws and picks enqueued from then on), 0 = bounded
 	int loneWaveBudget = 12288;      // AUTO: launches of up to this many rays (= waves, tiles x 64) go to lone_kernel: 2 - 3 frames at 1080p; three quarters of it above
 	                                 // 2560 x 1440 (4K: frames of up to ~9 000 rays).  Budget sweep over launches of 2 - 6 frames, per-pose crossover at 4K: profiles/r06_latency.md
 
@@ -151,9 +152,14 @@ inline bool IsPow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // later is covered here.  *solidRuns receives the number of solid runs, *colourCount (optional) the number of colours the runs address.
 int ValidateColumn(cvx_context *ctx, int64_t i, const RefHeader &h, const uint32_t *elements, int64_t elementCount, int maxY, size_t *solidRuns, int64_t *colourCount = nullptr);
 
-// cvx_lone.hip (its own translation unit: the latency kernel is compiled with its own optimisation level, Makefile): launches lone_kernel<hi> with one
-// workgroup per ray (rays = 64 x tiles), `ldsBytes` of dynamic LDS (merge buffer + the ray's pixel row)
-void LaunchLone(bool hi, unsigned rays, size_t ldsBytes, hipStream_t stream, const DevFrame *frames, const DevTile *tiles, const DevWorld *world);
+// cvx_lone.hip (its own translation unit: the latency kernel is compiled with its own optimisation level, Makefile): launches lone_kernel<hi> (repeat:
+// lone_repeat_kernel<hi>) with one workgroup per ray (rays = 64 x tiles), `ldsBytes` of dynamic LDS (merge buffer + the ray's pixel row)
+void LaunchLone(bool hi, bool repeat, unsigned rays, size_t ldsBytes, hipStream_t stream, const DevFrame *frames, const DevTile *tiles, const DevWorld *world);
+
+// Repeating worlds (cvx_set_world_repeat): far clip / pick distance bound, and the check of the world's dimensions every draw and pick makes in that mode
+// (X and Z at least 2^(LOD levels - 1): wrapping by the level-0 mask keeps the bits NextLOD reads, SegmentDDAData.cs:37, and the LOD blocks tile)
+#define CVX_REPEAT_MAX_DISTANCE 1048576.0f
+int ValidateRepeat(cvx_context *ctx);
 
 // cvx_gpu.hip: lays the uploaded levels out in the arena if any is pending (what the next draw would do first)
 int SyncWorld(cvx_context *ctx);

@@ -40,10 +40,21 @@ int Fail(cvx_context *ctx, int code, const char *fmt, ...)
 	return code;
 }
 
+int ValidateRepeat(cvx_context *ctx)
+{
+	const int minDim = 1 << (CVX_LOD_LEVELS - 1);
+	if (ctx->hostWorld.dimX < minDim || ctx->hostWorld.dimZ < minDim) {
+		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "repeating world: X and Z dimensions must be at least %d (the world is %d x %d)", minDim, ctx->hostWorld.dimX,
+		            ctx->hostWorld.dimZ);
+	}
+	return CVX_OK;
+}
+
 } // namespace cvxi
 
 using cvxi::Fail;
 using cvxi::IsPow2;
+using cvxi::ValidateRepeat;
 
 namespace {
 
@@ -135,6 +146,7 @@ float RayColumnVisits(const cvx_context *ctx, const DevFrame &F, const DevSegmen
 	dx /= len;
 	dz /= len;
 	float t0 = 0.f, t1 = F.farClip;
+	if (ctx->worldRepeat) { return t1 > 0.f ? t1 * (std::fabs(dx) + std::fabs(dz)) : 0.f; } // a repeating world: the whole path up to the far clip
 	const float lo[2] = { 0.f, 0.f }, hi[2] = { (float)ctx->hostWorld.dimX, (float)ctx->hostWorld.dimZ };
 	const float o[2] = { F.posX, F.posZ }, d[2] = { dx, dz };
 	for (int a = 0; a < 2; a++) {
@@ -430,12 +442,17 @@ int Launch(cvx_context *ctx, int frameCount, int flags)
 		const size_t ldsBytes = (size_t)std::max(ctx->ldsWordsNeeded, ctx->minMaskWords * CVX_WAVE) * sizeof(uint32_t);
 		dim3 grid((unsigned)(ctx->launchLone ? nTiles * CVX_WAVE : nTiles)), block(CVX_WAVE);
 		const size_t loneLdsBytes = (size_t)(CVX_WAVE + ctx->lonePixels) * sizeof(uint32_t); // lone_kernel: the merge buffer + the ray's pixel row
-		if (ctx->countersEnabled) {
+		const bool repeat = ctx->worldRepeat != 0; // a world that repeats in X and Z (cvx_set_world_repeat): the kernels' repeat instances
+		if (ctx->countersEnabled && repeat) {
+			hipLaunchKernelGGL((cvxk::render_repeat_kernel<true>), grid, block, ldsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld, ctx->devCounters);
+		} else if (ctx->countersEnabled) {
 			hipLaunchKernelGGL((cvxk::render_kernel<true>), grid, block, ldsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld, ctx->devCounters);
 		} else if (ctx->launchLone == 1) { // one wave per ray, lanes = columns (cvx_lone.h): the single interactive frame
-			cvxi::LaunchLone(false, grid.x, loneLdsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld);
+			cvxi::LaunchLone(false, repeat, grid.x, loneLdsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld);
 		} else if (ctx->launchLone == 2) { // ... windows of more than 2048 pixels (4K)
-			cvxi::LaunchLone(true, grid.x, loneLdsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld);
+			cvxi::LaunchLone(true, repeat, grid.x, loneLdsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld);
+		} else if (repeat) {
+			hipLaunchKernelGGL((cvxk::render_repeat_kernel<false>), grid, block, ldsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld, ctx->devCounters);
 		} else {
 			hipLaunchKernelGGL((cvxk::render_kernel<false>), grid, block, ldsBytes, ctx->stream, ctx->devFrames, ctx->devTiles, ctx->devWorld, ctx->devCounters);
 		}
@@ -643,6 +660,14 @@ int cvx_set_latency_kernel(cvx_context *ctx, int mode)
 	return CVX_OK;
 }
 
+int cvx_set_world_repeat(cvx_context *ctx, int repeat)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	if (repeat != 0 && repeat != 1) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad world-repeat mode %d (0 bounded, 1 repeating in X and Z)", repeat); }
+	ctx->worldRepeat = repeat;
+	return CVX_OK;
+}
+
 int cvx_set_shard(cvx_context *ctx, int shardIndex, int shardCount)
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
@@ -657,7 +682,7 @@ int cvx_set_shard(cvx_context *ctx, int shardIndex, int shardCount)
 namespace {
 #ifdef CVX_EXPERIMENTS
 // cvx_debug_last_launch: what DrawBatch chose for the launch it is about to make (instance: 0 render_kernel<true>, 1 render_kernel<false>, 2 lone_kernel<false>,
-// 3 lone_kernel<true>; distinct rays per wave = lanes of a wave that hold rays of their own, the others duplicate them, 2^dupShift lanes per ray)
+// 3 lone_kernel<true>, 4 .. 7 the same four as repeating-world instances: render_repeat_kernel<true> / <false>, lone_repeat_kernel<false> / <true>; distinct rays per wave = lanes of a wave that hold rays of their own, the others duplicate them, 2^dupShift lanes per ray)
 void RecordLaunch(cvx_context *ctx, int instance, size_t tiles, size_t waves, int minRays, int maxRays, int maxDupShift, int split, int ldsWords)
 {
 	const int64_t v[8] = { instance, (int64_t)tiles, (int64_t)waves, minRays, maxRays, maxDupShift, split, ldsWords };
@@ -683,6 +708,15 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 	if (rc != CVX_OK) { return rc; }
 	rc = SyncWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
+	if (ctx->worldRepeat) {
+		rc = ValidateRepeat(ctx);
+		for (int f = 0; f < frameCount && rc == CVX_OK; f++) {
+			if (!(cameras[f].FarClip <= CVX_REPEAT_MAX_DISTANCE)) {
+				rc = Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "repeating world: frame %d has FarClip %g, above 2^20", f, (double)cameras[f].FarClip);
+			}
+		}
+		if (rc != CVX_OK) { return rc; }
+	}
 	int64_t placeCursor = 0;
 	LastDraw placedScratch;
 	ctx->hostFrames.assign((size_t)frameCount, DevFrame());
@@ -796,7 +830,7 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 			}
 			ctx->ldsWordsNeeded = 0;
 #ifdef CVX_EXPERIMENTS
-			RecordLaunch(ctx, ctx->launchLone == 2 ? 3 : 2, n, n * (size_t)CVX_WAVE, 1, 1, 0, 0, CVX_WAVE + ctx->lonePixels);
+			RecordLaunch(ctx, (ctx->launchLone == 2 ? 3 : 2) + (ctx->worldRepeat ? 4 : 0), n, n * (size_t)CVX_WAVE, 1, 1, 0, 0, CVX_WAVE + ctx->lonePixels);
 #endif
 			return Launch(ctx, frameCount, flags);
 		}
@@ -881,7 +915,7 @@ int DrawBatch(cvx_context *ctx, int frameCount, const cvx_segment_data *segments
 		}
 		ctx->ldsWordsNeeded = ldsWords;
 #ifdef CVX_EXPERIMENTS
-		RecordLaunch(ctx, ctx->countersEnabled ? 0 : 1, n, sorted.size(), minRays, maxRays, maxDup, split, std::max(ldsWords, ctx->minMaskWords * CVX_WAVE));
+		RecordLaunch(ctx, (ctx->countersEnabled ? 0 : 1) + (ctx->worldRepeat ? 4 : 0), n, sorted.size(), minRays, maxRays, maxDup, split, std::max(ldsWords, ctx->minMaskWords * CVX_WAVE));
 #endif
 		ctx->hostTiles.swap(sorted);
 	}

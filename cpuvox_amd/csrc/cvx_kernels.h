@@ -248,9 +248,12 @@ struct ColumnCursor {
 	uint32_t rec;                     // arena byte offset of the column's record
 	int recStepX, recStepZ;           // +- (16 << rowShift), +- 16
 };
+// REPEAT (a repeating world, cvx_set_world_repeat): the position is taken modulo the world's dimensions (two's-complement `&`, a floor-mod), so
+// the cursor always stands inside the tile whatever the DDA's own px / pz are.
+template <bool REPEAT = false>
 __device__ __forceinline__ void cursor_set(ColumnCursor &c, const DDA &d, const DevWorldLevel &level, int maskX, int maskZ)
 {
-	c.pos = d.px * 65536 + d.pz;
+	c.pos = REPEAT ? (d.px & maskX) * 65536 + (d.pz & maskZ) : d.px * 65536 + d.pz;
 	c.posStepX = d.sx * 65536;
 	c.posStepZ = d.sz;
 	c.rec = level.recordsOff + record_offset((d.px & maskX) >> level.shift, (d.pz & maskZ) >> level.shift, level.rowShift); // clamped into the table
@@ -509,7 +512,9 @@ struct LaneCounters {
 // out[y*64] and marks them in seen[]; every exit path of the reference ends in
 // WriteSkybox/WriteSkyboxFull, which the caller performs for the whole wave.
 // ---------------------------------------------------------------------------
-template <int DIR, bool COUNT>
+// REPEAT: the world repeats in X and Z (cvx_set_world_repeat; World.REPEAT_WORLD, World.cs:10, :132-133): no entry step, the column lookup wraps, the ray
+// ends only at the far clip (or when its window closes).  REPEAT = false is the bounded world, the reference's default.
+template <int DIR, bool COUNT, bool REPEAT>
 __device__ __forceinline__ void trace_ray(const DevFrame &F, const DevSegment &S, const DevWorld *__restrict__ world, int planeRayIndex,
                                           uint32_t *seen /* &lds[lane] */, int sshift /* log2 of the mask word stride */, gptr_tile tileOut, uint32_t laneByteOff, LaneCounters &cnt, ProfLane &prof)
 {
@@ -534,7 +539,7 @@ __device__ __forceinline__ void trace_ray(const DevFrame &F, const DevSegment &S
 	int lod = 0;
 	float lodMax = F.lod[0];
 	const int dimX = world->dimX, dimZ = world->dimZ;
-	if (ray.px < 0 || ray.pz < 0 || ray.px >= dimX || ray.pz >= dimZ) {
+	if (!REPEAT && (ray.px < 0 || ray.pz < 0 || ray.px >= dimX || ray.pz >= dimZ)) { // (a repeating world has no outside: no entry step)
 		if (!dda_step_to_world_intersection(ray, (float)dimX, (float)dimZ)) {
 			return; // WriteSkyboxFull
 		}
@@ -589,7 +594,8 @@ __device__ __forceinline__ void trace_ray(const DevFrame &F, const DevSegment &S
 	// A DDA walk is monotone in x and z, so it leaves the world after at most
 	// dimX + dimZ column visits; the cap can never bind on valid input and only
 	// keeps a wave from spinning on non-finite camera data.
-	int guardSteps = dimX + dimZ + 16;
+	// In a repeating world the walk ends at the far clip (<= 2^20, checked at draw time): at most sqrt(2) far clip + 2 column visits.
+	int guardSteps = REPEAT ? 2 * (int)m_max(farClip, 0.0f) + 16 : dimX + dimZ + 16;
 
 	// The column being processed ("cur") and the values of the DDA / LOD state that belong to it; `ray` itself
 	// already stands on the NEXT column, whose 16-byte record is in flight while this one is processed.
@@ -1095,11 +1101,11 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 		L = world->level[lod];
 		{ const float next_ = F.lod[min(lod, 5)]; lodMax = lod < 5 ? next_ : __builtin_inff(); }
 	}
-	if ((ray.px & maskX) != ray.px || (ray.pz & maskZ) != ray.pz) {
+	if (!REPEAT && ((ray.px & maskX) != ray.px || (ray.pz & maskZ) != ray.pz)) {
 		return; // out of world bounds -> WriteSkybox
 	}
 	ColumnCursor cur;
-	cursor_set(cur, ray, L, maskX, maskZ);
+	cursor_set<REPEAT>(cur, ray, L, maskX, maskZ);
 	const int outsideBits = ~((maskX << 16) | maskZ); // bits of a cursor position that are set only outside the world
 	rec = ld4(arena, cur.rec);
 
@@ -1211,8 +1217,18 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 		}
 		// NextLOD (:237-243) for the column the ray stands on, if that is why it left the loop: alive, at or beyond this level's LOD distance, not
 		// beyond far clip (the last level's distance is +infinity: lod < 5 here)
-		if (!alive || ray.distLast >= farClip || (cur.pos & outsideBits) != 0) {
+		if (!alive || ray.distLast >= farClip || (!REPEAT && (cur.pos & outsideBits) != 0)) {
 			break; // finished: window closed / frustum left the world / step guard, far clip (:273), left the world (:613)
+		}
+		if (REPEAT && (cur.pos & outsideBits) != 0) {
+			// A repeating world: the ray has just crossed the tile's edge (near the edge the loop comes up after every column, so it stands ONE step
+			// outside: z in [-32, dimZ], x in [-32, dimX]).  Re-base the cursor on the wrapped column (World.cs:132-133, position & dimensionMaskXZ) and
+			// take a fresh edge distance: the next edge is a whole tile away.  (The record fetched for the column outside lies in the table's padding.)
+			const int pz = ((cur.pos + 64) & 0xFFFF) - 64; // the low half as a z in [-64, 65472): undoes the borrow of a z below 0
+			const int px = (cur.pos - pz) >> 16;
+			cur.pos = (px & maskX) * 65536 + (pz & maskZ);
+			cur.rec = L.recordsOff + record_offset((px & maskX) >> L.shift, (pz & maskZ) >> L.shift, L.rowShift);
+			nearEdge = false;
 		}
 		if (!(ray.distLast >= lodMax)) {
 			// neither: a checkpoint, or the ray is within a few columns of the world's edge.  A fresh stop distance beyond where the ray stands means the
@@ -1235,7 +1251,7 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 		voxelScale *= 2;
 		L = world->level[lod];
 		{ const float next_ = F.lod[min(lod, 5)]; lodMax = lod < 5 ? next_ : __builtin_inff(); }
-		cursor_set(cur, ray, L, maskX, maskZ);
+		cursor_set<REPEAT>(cur, ray, L, maskX, maskZ);
 		stopDist = nearEdge ? -__builtin_inff() : stopDistance();
 		rec = ld4(arena, cur.rec);
 		go = true;
@@ -1246,122 +1262,17 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 // ---------------------------------------------------------------------------
 // render kernel: grid = tiles, block = 64 (one wave).  LDS: words*64 uint32.
 // ---------------------------------------------------------------------------
-template <bool COUNT>
 #ifndef CVX_WAVES_PER_SIMD
 #define CVX_WAVES_PER_SIMD 4
 #endif
-__global__ __launch_bounds__(CVX_WAVE, CVX_WAVES_PER_SIMD) void render_kernel(const DevFrame *__restrict__ frames, const DevTile *__restrict__ tiles,
-                                                          const DevWorld *__restrict__ world, DevCounters *__restrict__ counters)
-{
-	extern __shared__ uint32_t lds[];
-	const int lane = threadIdx.x;
-#ifdef CVX_TILE_TIMES
-	const unsigned long long tileStart_ = __builtin_amdgcn_s_memtime();
-#endif
-	const DevTile tile = tiles[blockIdx.x];
-	const DevFrame &F = frames[tile.frame];
-	const DevSegment &S = F.seg[tile.seg];
-
-	// The mask only covers the words that hold pixels [omin, omax]; `seen` is biased so that the
-	// absolute word index w of a pixel addresses seen[w * 64].
-	const int omin = S.omin, omax = S.omax;
-	const int wordBase = omin >> 5;
-	const int words = (omax >> 5) - wordBase + 1;
-	// RaySetupJob (:19-39): tile -> (segment, planeRayIndex)
-	const int firstLane = tile.lanes & 0xFF, laneCount = tile.lanes ? (tile.lanes >> 8) & 0xFF : CVX_WAVE;
-	const int sshift = 31 - __clz(laneCount); // laneCount is a power of two
-	// 2^dupShift physical lanes per ray of a narrow sub-tile (cvx_gpu.hip DrawBatch: a wave with <= 8 active lanes issues ~3.6 x slower); the lanes of a
-	// group hold the same values all the way, read and write the same mask words and store the same pixels
-	const int dupShift = (tile.lanes >> 16) & 7;
-	const int vlane = lane >> dupShift;
-	const bool leader = (lane & ((1 << dupShift) - 1)) == 0; // one lane per ray writes the skybox pixels below (64 stores to one address are not free)
-	const int planeRayIndex = tile.tileInSeg * CVX_WAVE + firstLane + vlane;
-	const bool active = vlane < laneCount && planeRayIndex < S.rayCount;
-	if (vlane < laneCount) {
-		for (int w = 0; w < words; w++) {
-			lds[(w << sshift) + vlane] = 0u; // stackalloc is zero-initialised, :208
-		}
-	}
-	const gptr_tile tileOut = (gptr_tile)tile.out;
-	const uint32_t laneByteOff = (uint32_t)(firstLane + vlane) * 4u;
-	uint32_t *seen = lds + vlane - (wordBase << sshift);
-	ProfLane prof;
-#ifdef CVX_PROFILE_SECTIONS
-	for (int i = 0; i < CVX_NSEC; i++) { prof.acc[i] = 0u; }
-#ifdef CVX_PROFILE_COUNTS
-	for (int i = 0; i < CVX_NSEC; i++) { prof.lanes[i] = 0u; }
-#endif
-	CVX_BEGIN();
-#endif
-
-	LaneCounters cnt;
-	if (COUNT) {
-		cnt.S = cnt.E = cnt.C = cnt.P = 0;
-		for (int i = 0; i < 6; i++) { cnt.lod[i] = 0; }
-	}
-
-	if (active) {
-		// RenderJob.Execute :174-178: the iteration direction is a per-frame (wave-uniform) constant
-		if (F.inverse) {
-			trace_ray<-1, COUNT>(F, S, world, planeRayIndex, seen, sshift, tileOut, laneByteOff, cnt, prof);
-		} else {
-			trace_ray<1, COUNT>(F, S, world, planeRayIndex, seen, sshift, tileOut, laneByteOff, cnt, prof);
-		}
-	}
-
-	// WriteSkybox / WriteSkyboxFull (:699-716) for the whole wave: every pixel
-	// of [omin, omax] not marked seen gets the skybox colour.
-	CVX_BEGIN();
-	unsigned int skyPixels = 0;
-	for (int w = omin >> 5; w <= (omax >> 5); w++) {
-		uint32_t todo = 0u;
-		if (active && leader) { todo = ~seen[w << sshift] & range_mask(w, omin, omax); }
-		const int base = w << 5;
-		if (!COUNT && __ballot(todo != 0u) == 0ull) { continue; } // (a word every ray of the tile has filled -- the ground half of a frame: 3 instructions instead of 32 bit tests; round 5: -0.5 %)
-#pragma unroll 4
-		for (int b = 0; b < 32; b++) {
-			if ((todo >> b) & 1u) {
-				st_pixel_stream(tileOut, laneByteOff, base + b, CVX_SKYBOX_ARGB);
-			}
-		}
-		if (COUNT) { skyPixels += (unsigned int)__popc(todo); }
-	}
-
-#ifdef CVX_PROFILE_SECTIONS
-	CVX_END(8);
-	for (int i = 0; i < CVX_NSEC; i++) {
-#ifdef CVX_PROFILE_COUNTS
-		unsigned long long tot = prof.acc[i], act = prof.lanes[i];
-		for (int o = 32; o > 0; o >>= 1) { tot += (unsigned long long)__shfl_xor((long long)tot, o); act += (unsigned long long)__shfl_xor((long long)act, o); }
-		if (lane == 0) { atomicAdd(&g_sectionCycles[i], tot); atomicAdd(&g_sectionCycles[16 + i], act); }
-#else
-		unsigned int mx = prof.acc[i], sum = prof.acc[i] >> 6;
-		for (int o = 32; o > 0; o >>= 1) {
-			mx = max(mx, (unsigned int)__shfl_xor((int)mx, o));
-			sum += (unsigned int)__shfl_xor((int)sum, o);
-		}
-		if (lane == 0) {
-			atomicAdd(&g_sectionCycles[i], (unsigned long long)mx);
-			atomicAdd(&g_sectionCycles[16 + i], (unsigned long long)sum);
-		}
-#endif
-	}
-#endif
-#ifdef CVX_TILE_TIMES
-	if (!COUNT && lane == 0 && g_tileTimes) { g_tileTimes[blockIdx.x] = __builtin_amdgcn_s_memtime() - tileStart_; }
-#endif
-	if (COUNT) {
-		cnt.P += skyPixels;
-		atomicAdd(&counters->S, (unsigned long long)cnt.S);
-		atomicAdd(&counters->E, (unsigned long long)cnt.E);
-		atomicAdd(&counters->C, (unsigned long long)cnt.C);
-		atomicAdd(&counters->P, (unsigned long long)cnt.P);
-		atomicAdd(&counters->R, active ? 1ull : 0ull);
-		for (int i = 0; i < 6; i++) {
-			atomicAdd(&counters->lodVisits[i], (unsigned long long)cnt.lod[i]);
-		}
-	}
-}
+// the bounded world (the reference's default)
+#define CVX_RENDER_KERNEL render_kernel
+#define CVX_RENDER_REPEAT false
+#include "cvx_render_kernel_body.h"
+// a world that repeats in X and Z (cvx_set_world_repeat)
+#define CVX_RENDER_KERNEL render_repeat_kernel
+#define CVX_RENDER_REPEAT true
+#include "cvx_render_kernel_body.h"
 
 } // namespace cvxk
 namespace cvxk {

@@ -335,8 +335,9 @@ __device__ __forceinline__ RunProj project_run(f3 camSpaceMinLast, f3 camSpaceMa
 
 // ---------------------------------------------------------------------------
 // One ray: TraceToFirstColumnJob + ExecuteRay by one wave.
+// REPEAT: the world repeats in X and Z (cvx_set_world_repeat): no entry step, every lane's column wraps into the tile, the ray ends only at the far clip.
 // ---------------------------------------------------------------------------
-template <int DIR, bool HI>
+template <int DIR, bool HI, bool REPEAT>
 __device__ __forceinline__ void lone_trace_ray(const DevFrame &F, const DevSegment &S, const DevWorld *__restrict__ world, int planeRayIndex,
                                                LoneSeen &seen, uint32_t *merged /* LDS: 64 words, then the ray's pixel row: pixel y at merged[64 + y - omin] */, unsigned int *stat_)
 {
@@ -361,7 +362,7 @@ __device__ __forceinline__ void lone_trace_ray(const DevFrame &F, const DevSegme
 	int lod = 0;
 	float lodMax = F.lod[0];
 	const int dimX = world->dimX, dimZ = world->dimZ;
-	if (ray.px < 0 || ray.pz < 0 || ray.px >= dimX || ray.pz >= dimZ) {
+	if (!REPEAT && (ray.px < 0 || ray.pz < 0 || ray.px >= dimX || ray.pz >= dimZ)) { // (a repeating world has no outside: no entry step)
 		if (!dda_step_to_world_intersection(ray, (float)dimX, (float)dimZ)) {
 			return; // WriteSkyboxFull
 		}
@@ -425,15 +426,17 @@ __device__ __forceinline__ void lone_trace_ray(const DevFrame &F, const DevSegme
 		L = world->level[lod];
 		{ const float next_ = F.lod[min(lod, 5)]; lodMax = lod < 5 ? next_ : __builtin_inff(); }
 	}
-	if ((ray.px & maskX) != ray.px || (ray.pz & maskZ) != ray.pz) {
+	if (!REPEAT && ((ray.px & maskX) != ray.px || (ray.pz & maskZ) != ray.pz)) {
 		return; // out of world bounds -> WriteSkybox
 	}
-	// the column as ONE integer x * 65536 + z and what a step adds to it (ColumnCursor of cvx_kernels.h, without the record address: lanes compute their own)
-	int pos = ray.px * 65536 + ray.pz;
+	// the column as ONE integer x * 65536 + z and what a step adds to it (ColumnCursor of cvx_kernels.h, without the record address: lanes compute their own);
+	// in a repeating world always the wrapped column (World.cs:132-133, position & dimensionMaskXZ: a floor-mod)
+	int pos = REPEAT ? (ray.px & maskX) * 65536 + (ray.pz & maskZ) : ray.px * 65536 + ray.pz;
 	int posStepX = ray.sx * 65536, posStepZ = ray.sz;
 	const int outsideBits = ~((maskX << 16) | maskZ);
-	// A DDA walk is monotone in x and z: it leaves the world after at most dimX + dimZ columns; the cap only keeps a wave from spinning on non-finite camera data
-	int guardSteps = 2 * (dimX + dimZ + 16);
+	// A DDA walk is monotone in x and z: it leaves the world after at most dimX + dimZ columns; the cap only keeps a wave from spinning on non-finite camera data.
+	// In a repeating world the walk ends at the far clip (<= 2^20, checked at draw time): at most sqrt(2) far clip + 2 columns.
+	int guardSteps = REPEAT ? 2 * (2 * (int)m_max(farClip, 0.0f) + 16) : 2 * (dimX + dimZ + 16);
 
 #ifdef CVX_LONE_STATS
 	float lastClipBoundsMin_ = -1.0f, lastClipBoundsMax_ = -1.0f;
@@ -474,18 +477,29 @@ __device__ __forceinline__ void lone_trace_ray(const DevFrame &F, const DevSegme
 			const float C = __uint_as_float(crossing & 0x7FFFFFFFu);
 			const lanemask_t xBits = __ballot(alongX);
 			const int nxBefore = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(xBits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)xBits, 0u)); // x steps among the crossings before this lane's
-			wPos = pos + nxBefore * posStepX + (lane - nxBefore) * posStepZ;
-			const int posAfter = wPos + (alongX ? posStepX : posStepZ);
+			int posAfter;
+			if (REPEAT) {
+				// the lane's column and the one after it, each wrapped into the tile on its own: a window of 64 columns may span several tiles, and the
+				// packed form's z would borrow from x below 0.  (pos itself is wrapped: x in [0, dimX), z in [0, dimZ).)
+				const int sx = posStepX >> 16;
+				const int ax = (pos >> 16) + nxBefore * sx, az = (pos & 0xFFFF) + (lane - nxBefore) * posStepZ;
+				const int bx = alongX ? ax + sx : ax, bz = alongX ? az : az + posStepZ;
+				wPos = (ax & maskX) * 65536 + (az & maskZ);
+				posAfter = (bx & maskX) * 65536 + (bz & maskZ);
+			} else {
+				wPos = pos + nxBefore * posStepX + (lane - nxBefore) * posStepZ;
+				posAfter = wPos + (alongX ? posStepX : posStepZ);
+			}
 			wDistNext = C;
 			wDistLast = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ray.distLast), __float_as_int(C), 0x138, 0xF, 0xF, false)); // wave_shr:1, lane 0 keeps the entry distance
 			// the window ends with the first column whose exit crossing reaches the far clip / this level's LOD distance, or leads out of the world
 			const float stopDistance = m_min(farClip, lodMax);
-			const lanemask_t stops = __ballot(C >= stopDistance || (posAfter & outsideBits) != 0);
+			const lanemask_t stops = __ballot(C >= stopDistance || (!REPEAT && (posAfter & outsideBits) != 0));
 			count = stops != 0ull ? __ffsll((long long)stops) : CVX_WAVE;
 			const int last = count - 1;
 			const float exitDistance = rlf(C, last);
 			const int exitPos = rli(posAfter, last);
-			if (stops != 0ull) { endCode = (exitDistance >= farClip || (exitPos & outsideBits) != 0) ? 1 : 2; }
+			if (stops != 0ull) { endCode = (exitDistance >= farClip || (!REPEAT && (exitPos & outsideBits) != 0)) ? 1 : 2; }
 			// the DDA after `count` steps
 			const int stepsX = __popcll(count < CVX_WAVE ? (xBits & ~lanes_from(count)) : xBits), stepsZ = count - stepsX;
 			const float lastX = rlf(X, min(stepsX, CVX_WAVE - 1)), lastZ = rlf(Z, min(stepsZ, CVX_WAVE - 1));
@@ -1098,70 +1112,16 @@ __device__ __forceinline__ void lone_trace_ray(const DevFrame &F, const DevSegme
 // lone kernel: grid = 64 x tiles (workgroup b renders ray b % 64 of tile b / 64; cvx_gpu.hip DrawBatch), block = 64 (one wave).
 // HI: windows of more than 2048 pixels ([origMin, origMax] spans more than 64 mask words: 4K) carry a second mask register.
 // ---------------------------------------------------------------------------
-template <bool HI>
 #ifndef CVX_LONE_WAVES_PER_SIMD
 #define CVX_LONE_WAVES_PER_SIMD 3
 #endif
-__global__ __launch_bounds__(CVX_WAVE, CVX_LONE_WAVES_PER_SIMD) void lone_kernel(const DevFrame *__restrict__ frames, const DevTile *__restrict__ tiles, const DevWorld *__restrict__ world)
-{
-	extern __shared__ uint32_t lds[]; // [0, 64): the DDA's crossings in merged order (lone_trace_ray); [64, 64 + omax - omin]: the ray's pixel row
-	uint32_t *merged = lds;
-#ifdef CVX_LONE_STATS
-	const unsigned long long waveStart_ = __builtin_amdgcn_s_memtime();
-#endif
-	const DevTile tile = tiles[blockIdx.x >> 6];
-	const DevFrame &F = frames[tile.frame];
-	const DevSegment &S = F.seg[tile.seg];
-	const int firstLane = (int)(blockIdx.x & 63u);
-	const int planeRayIndex = tile.tileInSeg * CVX_WAVE + firstLane; // RaySetupJob (:19-39)
-	if (planeRayIndex >= S.rayCount) { return; }
-#ifdef CVX_LONE_PRIO
-	if ((int)blockIdx.x < CVX_LONE_PRIO) { __builtin_amdgcn_s_setprio(3); } // (experiment: the longest rays of the launch first in their SIMD's issue arbitration)
-#endif
-	const int omin = S.omin, omax = S.omax;
-	LoneSeen seen;
-	seen.w0 = seen.w1 = 0u; // stackalloc is zero-initialised, :208
-	seen.wordBase = omin >> 5;
-	seen.lane = (int)threadIdx.x;
-	const gptr_tile tileOut = (gptr_tile)tile.out;
-	const uint32_t laneByteOff = (uint32_t)firstLane * 4u;
-	// The ray's pixel row [omin, omax] is staged in LDS and written out once, at the end: gfx9 counts loads and stores in ONE counter (vmcnt), so a
-	// pixel store in the column loop would make every later wait for a colour load also wait for the store's acknowledgement from memory.  Staged, the
-	// loop's only vector-memory operations are loads, and the row's stores are issued back to back with nothing waiting for them.  Every pixel starts
-	// as the skybox colour (WriteSkybox / WriteSkyboxFull, :699-716: whatever is not written by a run).
-	uint32_t *pix = lds + CVX_WAVE - omin;
-	for (int y = omin + seen.lane; y <= omax; y += CVX_WAVE) { pix[y] = CVX_SKYBOX_ARGB; }
-#ifdef CVX_LONE_STATS
-	unsigned int stat_[48];
-	for (int i = 0; i < 48; i++) { stat_[i] = 0u; }
-	stat_[30] = (unsigned int)__builtin_amdgcn_s_memtime();
-#else
-	unsigned int *stat_ = nullptr;
-#endif
-	if (F.inverse) { // RenderJob.Execute :174-178
-		lone_trace_ray<-1, HI>(F, S, world, planeRayIndex, seen, merged, stat_);
-	} else {
-		lone_trace_ray<1, HI>(F, S, world, planeRayIndex, seen, merged, stat_);
-	}
-#ifdef CVX_LONE_STATS
-	stat_[16]++;
-	CVX_LSEC(0);
-	if (threadIdx.x == 0) {
-		const unsigned long long life_ = __builtin_amdgcn_s_memtime() - waveStart_;
-		for (int i = 0; i < 48; i++) { if (i != 18 && i != 19 && i != 20) { atomicAdd(&g_loneStats[i], (unsigned long long)stat_[i]); } }
-		atomicAdd(&g_loneStats[18], life_);                 // sum of the waves' lives (clock ticks)
-		atomicMax(&g_loneStats[19], life_);                 // the longest
-		if (life_ == atomicMax(&g_loneStats[19], 0ull)) { // (the counters of the longest wave so far: racy, diagnostic only)
-			g_loneStats[20] = stat_[1];
-			for (int i = 0; i < 48; i++) { g_loneLongest[i] = stat_[i]; }
-		}
-	}
-#endif
-	// the row goes out: pixel y of this ray at tile row y (256 bytes per row, cvx_device.h); first every colour still on its way into the row has to be there
-	__builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0) (gfx9 encoding, see cvx_kernels.h)
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-	CVX_LSEC(11);
-	for (int y = omin + seen.lane; y <= omax; y += CVX_WAVE) { st_pixel(tileOut, laneByteOff, y, pix[y]); }
-}
+// the bounded world (the reference's default)
+#define CVX_LONE_KERNEL lone_kernel
+#define CVX_LONE_REPEAT false
+#include "cvx_lone_kernel_body.h"
+// a world that repeats in X and Z (cvx_set_world_repeat)
+#define CVX_LONE_KERNEL lone_repeat_kernel
+#define CVX_LONE_REPEAT true
+#include "cvx_lone_kernel_body.h"
 
 } // namespace cvxk

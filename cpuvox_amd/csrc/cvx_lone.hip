@@ -1,4 +1,5 @@
-// cvx_lone.hip -- the translation unit of the latency kernel (cvx_lone.h): lone_kernel<false> / lone_kernel<true> and their launcher.
+// cvx_lone.hip -- the translation unit of the latency kernel (cvx_lone.h): lone_kernel<false> / lone_kernel<true>, their
+// repeating-world instances lone_repeat_kernel<false> / <true>, and their launcher.
 //
 // Its own file because it is compiled with its own optimisation level (Makefile: OPT_cvx_lone): the batch kernel is fastest at -Os (one large divergent
 // loop, profiles/r05_experiments.md), the latency kernel -- wave-uniform control flow around short vector sections -- at -O3 (profiles/r06_experiments.md).
@@ -17,9 +18,15 @@
 
 namespace cvxi {
 
-void LaunchLone(bool hi, unsigned rays, size_t ldsBytes, hipStream_t stream, const DevFrame *frames, const DevTile *tiles, const DevWorld *world)
+void LaunchLone(bool hi, bool repeat, unsigned rays, size_t ldsBytes, hipStream_t stream, const DevFrame *frames, const DevTile *tiles, const DevWorld *world)
 {
-	if (hi) { // windows of more than 2048 pixels (4K): a second mask register
+	if (repeat) { // a world that repeats in X and Z (cvx_set_world_repeat)
+		if (hi) {
+			hipLaunchKernelGGL((cvxk::lone_repeat_kernel<true>), dim3(rays), dim3(CVX_WAVE), ldsBytes, stream, frames, tiles, world);
+		} else {
+			hipLaunchKernelGGL((cvxk::lone_repeat_kernel<false>), dim3(rays), dim3(CVX_WAVE), ldsBytes, stream, frames, tiles, world);
+		}
+	} else if (hi) { // windows of more than 2048 pixels (4K): a second mask register
 		hipLaunchKernelGGL((cvxk::lone_kernel<true>), dim3(rays), dim3(CVX_WAVE), ldsBytes, stream, frames, tiles, world);
 	} else {
 		hipLaunchKernelGGL((cvxk::lone_kernel<false>), dim3(rays), dim3(CVX_WAVE), ldsBytes, stream, frames, tiles, world);

@@ -73,9 +73,9 @@ void LimitRotationHorizon(Camera &camera)
 	}
 }
 
-void SetupLods(Camera &cam, int worldMaxDimension, int resolutionX, int resolutionY, float lodError, float out[CVX_LOD_LEVELS])
+void SetupLods(Camera &cam, int worldMaxDimension, int resolutionX, int resolutionY, float lodError, float out[CVX_LOD_LEVELS], bool repeatWorld)
 {
-	const int clipMultiplier = 2; // World.REPEAT_WORLD == false
+	const int clipMultiplier = repeatWorld ? 10 : 2; // World.REPEAT_WORLD, UnityManager.cs:421-423
 	float clipMax = (float)(worldMaxDimension * clipMultiplier);
 	cam.farClipPlane = clipMax;
 

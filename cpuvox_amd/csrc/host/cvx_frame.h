@@ -36,8 +36,8 @@ struct Camera {
 // UnityManager.LimitRotationHorizon, UnityManager.cs:193-201
 void LimitRotationHorizon(Camera &camera);
 
-// UnityManager.SetupLods, UnityManager.cs:417-458.  Also sets camera.farClipPlane.
-void SetupLods(Camera &camera, int worldMaxDimension, int resolutionX, int resolutionY, float lodError, float out[CVX_LOD_LEVELS]);
+// UnityManager.SetupLods, UnityManager.cs:417-458.  Also sets camera.farClipPlane: 2 x worldMaxDimension, 10 x for a repeating world (:421-423).
+void SetupLods(Camera &camera, int worldMaxDimension, int resolutionX, int resolutionY, float lodError, float out[CVX_LOD_LEVELS], bool repeatWorld = false);
 
 // new CameraData(camera, LODDistances, screen), CameraData.cs:18-36
 cvx_camera_data MakeCameraData(const Camera &camera, const float LODDistances[CVX_LOD_LEVELS], float screenX, float screenY);

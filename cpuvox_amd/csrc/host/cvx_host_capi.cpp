@@ -370,9 +370,15 @@ void cvxh_world_builder_free(cvxh_world_builder *b) { delete b; }
 int cvxh_setup_lods(const cvxh_camera_pose *pose, int worldMaxDimension, int resolutionX, int resolutionY, float lodError,
                     float outLODDistances[CVX_LOD_LEVELS], float *outFarClip)
 {
-	if (!pose || !outLODDistances || resolutionX <= 0 || resolutionY <= 0 || lodError <= 0.f) { return Fail("bad argument"); }
+	return cvxh_setup_lods_ex(pose, worldMaxDimension, resolutionX, resolutionY, lodError, 0, outLODDistances, outFarClip);
+}
+
+int cvxh_setup_lods_ex(const cvxh_camera_pose *pose, int worldMaxDimension, int resolutionX, int resolutionY, float lodError, int repeatWorld,
+                       float outLODDistances[CVX_LOD_LEVELS], float *outFarClip)
+{
+	if (!pose || !outLODDistances || resolutionX <= 0 || resolutionY <= 0 || lodError <= 0.f || (repeatWorld != 0 && repeatWorld != 1)) { return Fail("bad argument"); }
 	cvx::Camera cam = CameraFromPose(*pose);
-	cvx::SetupLods(cam, worldMaxDimension, resolutionX, resolutionY, lodError, outLODDistances);
+	cvx::SetupLods(cam, worldMaxDimension, resolutionX, resolutionY, lodError, outLODDistances, repeatWorld != 0);
 	if (outFarClip) { *outFarClip = cam.farClipPlane; }
 	return CVX_OK;
 }
@@ -445,6 +451,17 @@ int cvxh_render_manager_set_resolution(cvxh_render_manager *rm, int resolutionX,
 	try {
 		bool c = rm->rm->SetResolution(resolutionX, resolutionY);
 		if (changed) { *changed = c ? 1 : 0; }
+	} catch (const std::exception &e) {
+		return Fail(e.what());
+	}
+	return CVX_OK;
+}
+
+int cvxh_render_manager_set_world_repeat(cvxh_render_manager *rm, int repeat)
+{
+	if (!rm || (repeat != 0 && repeat != 1)) { return Fail("bad argument"); }
+	try {
+		rm->rm->SetWorldRepeat(repeat != 0);
 	} catch (const std::exception &e) {
 		return Fail(e.what());
 	}

@@ -18,6 +18,7 @@ struct RenderManager::Api {
 	decltype(&cvx_read_raybuffer) read_raybuffer;
 	decltype(&cvx_blit_segments) blit_segments;
 	decltype(&cvx_last_draw_ms) last_draw_ms;
+	decltype(&cvx_set_world_repeat) set_world_repeat;
 };
 
 namespace {
@@ -56,6 +57,7 @@ RenderManager::RenderManager(int device, int screenWidth_, int screenHeight_, co
 		Bind(library, "cvx_read_raybuffer", api->read_raybuffer);
 		Bind(library, "cvx_blit_segments", api->blit_segments);
 		Bind(library, "cvx_last_draw_ms", api->last_draw_ms);
+		Bind(library, "cvx_set_world_repeat", api->set_world_repeat);
 		int rc = api->create(device, &ctx);
 		if (rc != CVX_OK) {
 			throw std::runtime_error(std::string("cvx_create: ") + api->last_error(nullptr));
@@ -86,6 +88,11 @@ void RenderManager::UploadWorld(const std::vector<World> &worldLODs)
 		      "cvx_world_upload");
 	}
 	worldDimensionY = worldLODs.empty() ? 0 : worldLODs[0].Dimensions().y;
+}
+
+void RenderManager::SetWorldRepeat(bool repeat)
+{
+	Check(api->set_world_repeat(ctx, repeat ? 1 : 0), "cvx_set_world_repeat");
 }
 
 void RenderManager::ClearRayBuffer(ERenderMode renderMode)

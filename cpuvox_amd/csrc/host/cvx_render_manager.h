@@ -32,6 +32,7 @@ public:
 	void SwapBuffers() { bufferIndex = (bufferIndex + 1) % BUFFER_COUNT; } // :53-56
 	void ClearRayBuffer(ERenderMode renderMode);                            // :58-92 (pink 255,20,147)
 	bool SetResolution(int resolutionX, int resolutionY);                   // :94-109: true when it changed
+	void SetWorldRepeat(bool repeat);                                       // World.REPEAT_WORLD (World.cs:10): cvx_set_world_repeat
 
 	// RenderManager.DrawWorld, :111-194: vanishing point + segment setup, DrawSegments (GPU), BlitSegments.
 	// `screenArgb32` (W*H uint32, row 0 = bottom) may be null: the image then stays on the device.

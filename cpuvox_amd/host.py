@@ -131,6 +131,7 @@ def lib() -> C.CDLL:
         L.cvxh_world_builder_free.argtypes = [C.c_void_p]
         L.cvxh_world_builder_free.restype = None
         L.cvxh_setup_lods.argtypes = [C.POINTER(CameraPose), C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.cvxh_setup_lods_ex.argtypes = [C.POINTER(CameraPose), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.cvxh_setup_frame.argtypes = [C.POINTER(CameraPose), C.c_int, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(Frame)]
         L.cvxh_sample_benchmark_path.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.cvxh_sample_benchmark_path.restype = None
@@ -379,11 +380,14 @@ def camera_pose(position, euler, width: int, height: int, fov: float = 85.0, nea
     return p
 
 
-def setup_lods(pose: CameraPose, world_max_dimension: int, res_x: int, res_y: int, lod_error: float = 1.0):
-    """UnityManager.SetupLods (UnityManager.cs:417-458) -> (LODDistances[6], farClip)."""
+def setup_lods(pose: CameraPose, world_max_dimension: int, res_x: int, res_y: int, lod_error: float = 1.0, repeat: bool = False):
+    """UnityManager.SetupLods (UnityManager.cs:417-458) -> (LODDistances[6], farClip).  repeat=True: a repeating world (World.REPEAT_WORLD),
+    far clip 10 x world_max_dimension instead of 2 x (UnityManager.cs:421-423)."""
+    if not isinstance(repeat, (bool, int)) or int(repeat) not in (0, 1):
+        raise ValueError(f"setup_lods: repeat must be a bool, got {repeat!r}")
     out = (C.c_float * LOD_LEVELS)()
     far = C.c_float()
-    _check(lib().cvxh_setup_lods(C.byref(pose), world_max_dimension, res_x, res_y, lod_error, out, C.byref(far)))
+    _check(lib().cvxh_setup_lods_ex(C.byref(pose), world_max_dimension, res_x, res_y, lod_error, int(repeat), out, C.byref(far)))
     return list(out), far.value
 
 

@@ -31,6 +31,7 @@ class RenderManager:
         L.cvxh_render_manager_upload_world.argtypes = [C.c_void_p, C.c_void_p]
         L.cvxh_render_manager_set_resolution.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.cvxh_render_manager_swap_buffers.argtypes = [C.c_void_p]
+        L.cvxh_render_manager_set_world_repeat.argtypes = [C.c_void_p, C.c_int]
         L.cvxh_render_manager_clear_raybuffer.argtypes = [C.c_void_p, C.c_int]
         L.cvxh_render_manager_draw_world.argtypes = [C.c_void_p, C.POINTER(host.CameraPose), C.c_int, C.c_float, C.POINTER(C.c_float),
                                                      C.c_void_p, C.POINTER(host.Frame)]
@@ -64,6 +65,10 @@ class RenderManager:
     def swap_buffers(self) -> int:
         """RenderManager.SwapBuffers (RenderManager.cs:53-56)."""
         return host.lib().cvxh_render_manager_swap_buffers(self._h)
+
+    def set_world_repeat(self, repeat: bool) -> None:
+        """World.REPEAT_WORLD (World.cs:10): cvx_set_world_repeat on this manager's context; pair it with host.setup_lods(..., repeat=True)."""
+        host._check(host.lib().cvxh_render_manager_set_world_repeat(self._h, int(bool(repeat))))
 
     def clear_raybuffer(self, render_mode: int) -> None:
         """RenderManager.ClearRayBuffer (RenderManager.cs:58-92): pink (255, 20, 147) debug fill."""

@@ -160,6 +160,7 @@ namespace CpuVox.Gpu
 		[DllImport(Lib)] public static extern int cvx_set_shard(IntPtr ctx, int shardIndex, int shardCount);
 		public const int CVX_LATENCY_AUTO = 0, CVX_LATENCY_NEVER = 1, CVX_LATENCY_ALWAYS = 2;
 		[DllImport(Lib)] public static extern int cvx_set_latency_kernel(IntPtr ctx, int mode);
+		[DllImport(Lib)] public static extern int cvx_set_world_repeat(IntPtr ctx, int repeat);
 		[DllImport(Lib)] public static extern int cvx_synchronize(IntPtr ctx);
 		[DllImport(Lib)] public static extern int cvx_clear_raybuffer(IntPtr ctx, int bufferIndex, int which, uint argb);
 		[DllImport(Lib)] public static extern int cvx_read_raybuffer(IntPtr ctx, int bufferIndex, int which, int firstRay, int rayCount, void* dst);
@@ -241,6 +242,8 @@ namespace CpuVox.Gpu
 
 		/// <summary>Which kernel a draw runs on: Native.CVX_LATENCY_AUTO (default: one blocking frame -> the latency kernel), _NEVER, _ALWAYS.</summary>
 		public void SetLatencyKernel(int mode) { Check(Native.cvx_set_latency_kernel(ctx, mode)); }
+		/// <summary>World.REPEAT_WORLD (World.cs:10): false bounded (default), true the world repeats in X and Z.</summary>
+		public void SetWorldRepeat(bool repeat) { Check(Native.cvx_set_world_repeat(ctx, repeat ? 1 : 0)); }
 
 		/// <summary>RenderManager.DrawSegments (RenderManager.cs:258-372); blocks like render.Complete().</summary>
 		public void DrawSegments(SegmentData* segments4, CameraData* camera, int screenWidth, int screenHeight, float vpX, float vpY, int bufferIndex)

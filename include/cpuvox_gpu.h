@@ -167,6 +167,19 @@ int cvx_set_shard(cvx_context *ctx, int shardIndex, int shardCount);
 enum { CVX_LATENCY_AUTO = 0, CVX_LATENCY_NEVER = 1, CVX_LATENCY_ALWAYS = 2 };
 int cvx_set_latency_kernel(cvx_context *ctx, int mode);
 
+/* Repeating worlds (the reference's World.REPEAT_WORLD, World.cs:10).  0 (default): bounded -- a ray that starts outside the world is stepped to its box
+ * (DrawSegmentRayJob.cs:114-139) and a ray that leaves the box ends with the sky (World.cs:130-142, DrawSegmentRayJob.cs:245-250).  1: the world tiles X and
+ * Z endlessly (Y never repeats): the column at (x, z) is the uploaded one at (x & (dimX - 1), z & (dimZ - 1)) (World.cs:132-133) -- two's-complement
+ * `&`, a floor-mod, so negative coordinates wrap too --, there is no entry step, and a ray ends only at the far clip or when its pixel window closes.
+ * (The reference raises the far clip from 2 x to 10 x the largest dimension in this mode, UnityManager.cs:421-423: cvxh_setup_lods_ex.)
+ * Applies per context to every draw (cvx_draw_segments, _batch, _placed) and pick (cvx_world_pick, _device) enqueued after the call; edits, brushes,
+ * stamps, read-back and compaction address the stored tile and are unchanged.  In mode 1 a draw or pick returns CVX_ERR_INVALID_ARGUMENT if the world's
+ * X or Z dimension is below 32 (2^(LOD levels - 1): wrapping keeps the position bits NextLOD reads, SegmentDDAData.cs:37), a draw if a camera's FarClip is
+ * above 2^20, cvx_world_pick if a ray's maxT is above 2^20 (cvx_world_pick_device reports such a ray as a miss).  A pick in mode 1 clips the ray to the
+ * Y slab only, reports the hit voxel wrapped into [0, dim) (ready for cvx_world_brush / cvx_world_edit) and t along the ray itself.
+ * Any mode other than 0 / 1: CVX_ERR_INVALID_ARGUMENT. */
+int cvx_set_world_repeat(cvx_context *ctx, int repeat);
+
 int cvx_synchronize(cvx_context *ctx);
 
 /*

@@ -104,6 +104,10 @@ typedef struct cvxh_camera_pose {
 /* UnityManager.SetupLods, UnityManager.cs:417-458 (also yields farClip = 2*maxDim). */
 int cvxh_setup_lods(const cvxh_camera_pose *pose, int worldMaxDimension, int resolutionX, int resolutionY,
                     float lodError, float outLODDistances[CVX_LOD_LEVELS], float *outFarClip);
+/* The same for either world mode (World.REPEAT_WORLD, World.cs:10): repeatWorld 0 = cvxh_setup_lods (far clip 2 x worldMaxDimension), 1 = a repeating
+ * world (far clip 10 x, UnityManager.cs:421-423; render it after cvx_set_world_repeat(ctx, 1)).  Any other repeatWorld: an error. */
+int cvxh_setup_lods_ex(const cvxh_camera_pose *pose, int worldMaxDimension, int resolutionX, int resolutionY, float lodError, int repeatWorld,
+                       float outLODDistances[CVX_LOD_LEVELS], float *outFarClip);
 
 typedef struct cvxh_frame {
 	cvx_segment_data segments[4];
@@ -132,6 +136,8 @@ void cvxh_render_manager_destroy(cvxh_render_manager *rm);
 int cvxh_render_manager_upload_world(cvxh_render_manager *rm, const cvxh_world_set *worlds);
 int cvxh_render_manager_set_resolution(cvxh_render_manager *rm, int resolutionX, int resolutionY, int *changed);
 int cvxh_render_manager_swap_buffers(cvxh_render_manager *rm); /* returns the new buffer index */
+/* cvx_set_world_repeat on the twin's context (0 bounded, 1 repeating in X and Z); pair it with cvxh_setup_lods_ex(..., repeatWorld = 1, ...). */
+int cvxh_render_manager_set_world_repeat(cvxh_render_manager *rm, int repeat);
 int cvxh_render_manager_clear_raybuffer(cvxh_render_manager *rm, int renderMode);
 /* UnityManager.LateUpdate body (UnityManager.cs:179-182): LimitRotationHorizon + DrawWorld.  screenArgb32: W*H
  * pixels, row 0 = bottom, may be NULL; outFrame (may be NULL) receives the frame setup that was used. */
