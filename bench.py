@@ -18,6 +18,10 @@ inside the timed region; afterwards frames assembled from N ranks' tiles are com
 whole by their display rank.
 Rank 0 prints ONE JSON line.  World and camera inputs are synthetic and resident in HBM before the timed region; the
 per-step host->device traffic is the frame / tile descriptors (a few hundred KB).
+A plain run does only what that line's headline needs: set up, warm up, time the steps, --dump-outputs, print.  --full adds
+everything else, outside the timed region: the instrumented pass before it (roofline, lod_visits_per_step) and the committed
+counter summary; at N = 1 phase2, the latency legs and cpu_baseline with the parity check of the last step against the CPU
+oracle; at N > 1 the render / exchange breakdown.
 """
 from __future__ import annotations
 
@@ -52,13 +56,16 @@ def parse_args():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--world", default="proc2048", help="proc<dim> | mill512 | mill256")
     ap.add_argument("--lod-error", type=float, default=1.0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="wall time of the cpu_baseline sample at N = 1 (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the instrumented pass (roofline, "
+                    "lod_visits_per_step, counter summary), phase2, the latency legs, cpu_baseline with the parity check against the CPU oracle (N = 1) and "
+                    "the render / exchange breakdown (N > 1).  Without it a run sets up, warms up, times its steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: wall time of the cpu_baseline sample at N = 1 (0 = skip)")
     ap.add_argument("--pose-range", default=None, help="diagnostics: lo:hi -- only benchmark-path samples lo <= i < hi (e.g. 0:450 = one top/bottom segment per frame)")
     ap.add_argument("--no-exchange", action="store_true", help="N > 1: skip the RCCL tile exchange (replica-style throughput)")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: finish each step's exchange before the next render")
     ap.add_argument("--torch-exchange", action="store_true", help="N > 1: exchange with torch.distributed P2P ops instead of cvx_exchange (the C-ABI path)")
-    ap.add_argument("--latency-frames", type=int, default=200, help="N = 1: frames of the single-frame latency legs (0 = skip)")
-    ap.add_argument("--pmc-csv", default=None, help="counter summary of a rocprofv3 --pmc run of THIS command (tools/pmc_passes.sh + "
+    ap.add_argument("--latency-frames", type=int, default=200, help="--full, N = 1: frames of the single-frame latency legs (0 = skip)")
+    ap.add_argument("--pmc-csv", default=None, help="--full: counter summary of a rocprofv3 --pmc run of THIS command (tools/pmc_passes.sh + "
                     "tools/pmc_aggregate.py): fills roofline.traffic from FETCH_SIZE + WRITE_SIZE; without it traffic is null")
     ap.add_argument("--comm-timeout", type=float, default=180.0, help="N > 1: seconds cvx_comm_create may wait for the peers (then exit code 4)")
     ap.add_argument("--gather", choices=("raybuffer", "image", "auto"), default="raybuffer",
@@ -75,6 +82,8 @@ def parse_args():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dump_outputs and args.gpus > 1:
         ap.error("--dump-outputs covers the single-GPU path only (--gpus 1)")
+    if args.pmc_csv and not args.full:
+        ap.error("--pmc-csv fills the roofline of a --full run")
     return args
 
 
@@ -342,17 +351,18 @@ def main():
         else:
             ctx.draw_packed(packed[s], 0, flags)
 
-    # ---- algorithmic bytes per launch: instrumented pass, outside the timed region -------------------
-    ctx.enable_counters(True)
+    # ---- --full: algorithmic bytes per launch, instrumented pass outside the timed region -----------
     alg_bytes, visits, lod_visits, pixels = [], [], [], []
-    for s in range(total_steps):
-        draw(s, gpu.DRAW_SYNC)
-        c = ctx.counters()
-        alg_bytes.append(c.algorithmic_bytes())
-        visits.append(c.S)
-        pixels.append(c.P)
-        lod_visits.append(list(c.lodVisits))
-    ctx.enable_counters(False)
+    if args.full:
+        ctx.enable_counters(True)
+        for s in range(total_steps):
+            draw(s, gpu.DRAW_SYNC)
+            c = ctx.counters()
+            alg_bytes.append(c.algorithmic_bytes())
+            visits.append(c.S)
+            pixels.append(c.P)
+            lod_visits.append(list(c.lodVisits))
+        ctx.enable_counters(False)
 
     def exchange_step(s: int, par: int):
         """The exchange of step s (its tiles lie in the areas of parity `par`), enqueued on the current stream (s_exchange)."""
@@ -490,7 +500,7 @@ def main():
         dump_outputs(ctx, steps_frames[total_steps - 1], W, H, args.dump_outputs)
 
     breakdown = None
-    if sharded and not args.no_exchange:
+    if args.full and sharded and not args.no_exchange:
         # The first multi-GPU line has to explain itself: the last step's render alone, its exchange alone, and what the overlap hid
         last_step = total_steps - 1
         render_alone = alone("render", last_step)
@@ -502,10 +512,6 @@ def main():
     total_rays = sum(rays_per_step[s] for s in steps)  # whole job: every ray of every frame is rendered by exactly one GPU
     total_frames = G * args.steps
     value = total_rays / elapsed / 1e6
-    # roofline of the dominant kernel (render_kernel) on this rank: algorithmic bytes of its launches / their duration
-    k_bytes = sum(alg_bytes[s] for s in steps)
-    k_sec = k_ms_total / 1e3
-    achieved = k_bytes / k_sec / 1e9
     if image_mode and not args.no_exchange:
         parallelism = f"ray-tile sharding x{N}, per-rank Phase 2 + P2P gather of the finished pixels (image gather)" + (" overlapped with the next render" if overlap else "")
     elif sharded and not args.no_exchange:
@@ -550,9 +556,15 @@ def main():
             "exchange_bytes_per_step_per_gpu": (int(np.mean([p.send_pixels for p in img_plans]) * 4) if image_mode else int(np.mean([p.send_total for p in plans]) * 256)) if sharded else 0,
             "world_dims": list(dims),
             "lod_distances": lods,
-            "lod_visits_per_step": [int(np.mean([lod_visits[s][l] for s in steps])) for l in range(6)],
         },
-        "roofline": {
+    }
+    if args.full:
+        # roofline of the dominant kernel (render_kernel) on this rank: algorithmic bytes of its launches (the instrumented pass) / their duration
+        k_bytes = sum(alg_bytes[s] for s in steps)
+        k_sec = k_ms_total / 1e3
+        achieved = k_bytes / k_sec / 1e9
+        result["config"]["lod_visits_per_step"] = [int(np.mean([lod_visits[s][l] for s in steps])) for l in range(6)]
+        result["roofline"] = {
             "bound": "hbm",
             "achieved": round(achieved, 2),
             "peak": HBM_PEAK_GBS,
@@ -564,12 +576,11 @@ def main():
             "algorithmic_bytes_per_launch": int(k_bytes / max(1, k_draws)),
             "bytes_per_ray": round(k_bytes / max(1, total_rays / N), 1),
             "column_visits_per_s": round(sum(visits[s] for s in steps) / k_sec, 1),
-        },
-    }
+        }
 
     if breakdown:
         result.update(breakdown)
-    if not args.pmc_csv and N == 1:
+    if args.full and not args.pmc_csv and N == 1:
         args.pmc_csv = find_counter_summary(args)
     if args.pmc_csv:
         # Counter summary of a rocprofv3 --pmc run of THIS command and build (tools/pmc_passes.sh + tools/pmc_aggregate.py); never a
@@ -622,7 +633,7 @@ def main():
             result["roofline"]["traffic_detail"] = {"error": f"unreadable counter summary {args.pmc_csv}: {e}"}
 
     parity_frames = []
-    if N == 1:
+    if args.full and N == 1:
         # what the GPU rendered for eight frames spread over the LAST timed step (compared with the CPU oracle in the cpu_baseline leg below)
         last = steps_frames[total_steps - 1]
         for b in sorted({(F * i) // 8 for i in range(8)}):
@@ -630,7 +641,7 @@ def main():
             parity_frames.append((b, last[b], ctx.read_raybuffer(b, gpu.RAYBUFFER_TOPDOWN, 0, rc[0] + rc[1]),
                                   ctx.read_raybuffer(b, gpu.RAYBUFFER_LEFTRIGHT, 0, rc[2] + rc[3])))
 
-    if N == 1:
+    if args.full and N == 1:
         # Phase 2 (RenderManager.BlitSegments) over the frames of the last step, image left in HBM: reported beside
         # the Phase-1 metric, never part of `value` (and never allowed to take the Phase-1 line down with it).
         try:
@@ -661,7 +672,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             result["phase2"] = {"error": str(e)}
 
-    if N == 1 and args.latency_frames > 0:
+    if args.full and N == 1 and args.latency_frames > 0:
         # The reference's own call pattern: ONE blocking DrawSegments per frame (RenderManager.cs:155-167,363), and the same with its two
         # raybuffer pairs (BUFFER_COUNT = 2, RenderManager.cs:14,53-56) used as a 2-deep pipeline: frame k is submitted (CVX_DRAW_ASYNC)
         # while the host still holds frame k - 1.  Reported beside the batch metric, never as `value`.
@@ -739,7 +750,7 @@ def main():
             result["latency"] = {"error": str(e)}
 
     parity_failed = False
-    if rank == 0 and N == 1 and args.cpu_seconds > 0:  # the CPU baseline is reported at N = 1 only
+    if args.full and rank == 0 and N == 1 and args.cpu_seconds > 0:  # the CPU baseline is reported at N = 1 only
         try:
             result["cpu_baseline"], parity = cpu_baseline(ws, steps_frames[args.warmup], W, H, args.cpu_seconds, parity_frames)
             result["parity_checked"] = parity["ok"]
@@ -749,7 +760,7 @@ def main():
             result["cpu_baseline"] = {"value": None, "unit": "Mrays/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
             result["parity_checked"] = False
     else:
-        result["parity_checked"] = False  # no oracle leg in this run (N > 1 checks the exchange against single-GPU renders instead)
+        result["parity_checked"] = False  # no oracle leg in this run (only --full has one; N > 1 checks the exchange against single-GPU renders instead)
     if rank == 0:
         print(json.dumps(result), flush=True)
     barrier()

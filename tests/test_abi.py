@@ -285,6 +285,26 @@ def test_bench_dump_outputs_hold_the_written_pixels_only(tmp_path, monkeypatch):
     assert set(np.unique(sample[0])) <= set(np.unique(np.concatenate([td.ravel(), lr.ravel()])).tolist()) - {marker}
 
 
+def test_bench_full_is_off_by_default_and_owns_the_counter_summary(monkeypatch):
+    """A plain bench.py run does only what its headline needs; --full (off by default) adds the instrumented pass, the roofline and the legs beside
+    it.  --pmc-csv only fills the roofline of a --full run, so on its own it is an argument error rather than a flag that is silently dropped."""
+    import importlib.util
+    import sys
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--pmc-csv", "x.csv"])
+    args = bench.parse_args()
+    assert args.full is True and args.pmc_csv == "x.csv"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--pmc-csv", "x.csv"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
 def test_gpu_objects_do_not_depend_on_the_build_directory(tmp_path):
     """bench.py attaches the committed counter summary only to the library whose sha-256 it is stamped with, and the GPU box rebuilds stale targets at
     its own scratch path: the product library's objects are compiled with a fixed compilation-unit id (csrc/Makefile), so the same sources give the

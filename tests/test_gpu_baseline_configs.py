@@ -244,8 +244,8 @@ def test_downsample_refuses_a_non_lod0_source():
 
 def test_two_rank_rehearsal_line_carries_the_scaling_breakdown():
     """The N > 1 path of bench.py as the driver starts it (`python bench.py --gpus 2`), rehearsed on ONE GPU with gloo: the line must verify its exchange
-    and explain itself -- render alone, exchange alone, overlap efficiency, predicted per-link payload time -- and `--gather auto`
-    must name the gather it took and the bytes of both."""
+    and, with --full, explain itself -- render alone, exchange alone, overlap efficiency, predicted per-link payload time -- and
+    `--gather auto` must name the gather it took and the bytes of both."""
     import json
     import os
     import subprocess
@@ -253,7 +253,7 @@ def test_two_rank_rehearsal_line_carries_the_scaling_breakdown():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--frames", "4", "--steps", "2", "--warmup", "1", "--gather", "auto"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--frames", "4", "--steps", "2", "--warmup", "1", "--gather", "auto", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -262,6 +262,35 @@ def test_two_rank_rehearsal_line_carries_the_scaling_breakdown():
         assert isinstance(line[key], float) and line[key] >= 0.0, key
     auto = line["config"]["gather_auto"]
     assert line["config"]["gather"] == auto["gather"] and auto["gather"] == ("image" if auto["image_bytes"] < auto["raybuffer_bytes"] else "raybuffer")
+
+
+def test_plain_bench_line_holds_the_headline_and_full_adds_the_rest():
+    """A plain single-GPU bench.py run prints the headline line and nothing it had to run extra work for; the same run with --full adds the
+    roofline of the instrumented pass, phase2, the latency legs and cpu_baseline with a passing parity check against the CPU oracle."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    small = ["--gpus", "1", "--world", "proc256", "--width", "320", "--height", "200", "--frames", "8", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for label, extra in (("plain", []), ("full", ["--full", "--cpu-seconds", "0.5", "--latency-frames", "8"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + small + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, timeout=600)
+        assert r.returncode == 0, (label, r.stderr[-3000:])
+        lines[label] = json.loads(r.stdout.strip().splitlines()[-1])
+    for line in lines.values():
+        assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and (line["steps"], line["warmup"]) == (2, 1)
+    plain, full = lines["plain"], lines["full"]
+    assert plain["metric"] == full["metric"]
+    assert not {"roofline", "phase2", "latency", "latency_curve", "cpu_baseline", "parity"} & set(plain), sorted(plain)
+    assert "lod_visits_per_step" not in plain["config"] and plain["parity_checked"] is False
+    assert full["roofline"]["achieved"] > 0 and len(full["config"]["lod_visits_per_step"]) == 6
+    assert "blit_ms_per_frame" in full["phase2"] and full["latency"]["frames"] == 1 and full["cpu_baseline"]["value"] > 0
+    assert full["parity_checked"] is True
 
 
 def test_library_owned_rccl_communicator_single_rank():

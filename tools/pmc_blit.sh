@@ -10,7 +10,7 @@ i=0
 while read -r counters; do
   [ -z "$counters" ] && continue
   i=$((i+1))
-  timeout 150 rocprofv3 --pmc $counters --output-format csv -d "$OUT/pass$i" -- python3 "$R/bench.py" --cpu-seconds 0 --latency-frames 0 --steps 1 --warmup 0 > "$OUT/pass$i.log" 2>&1
+  timeout 150 rocprofv3 --pmc $counters --output-format csv -d "$OUT/pass$i" -- python3 "$R/bench.py" --full --cpu-seconds 0 --latency-frames 0 --steps 1 --warmup 0 > "$OUT/pass$i.log" 2>&1
   echo "pass$i ($counters) rc=$?"
 done <<'LIST'
 FETCH_SIZE

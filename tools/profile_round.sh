@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
 # 1. kernel trace + stats of the default command (no CPU leg: the profiler would only see it as idle time)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$R/bench.py" --cpu-seconds 0 --latency-frames 0 > "$OUT/trace_bench.json" 2> "$OUT/trace.log"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$R/bench.py" --full --cpu-seconds 0 --latency-frames 0 > "$OUT/trace_bench.json" 2> "$OUT/trace.log"
 find "$OUT/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
 # 2. counter passes (separate runs, --pmc only) with the DRIVER's step counts (every BENCH_rNN.json: --steps 20 --warmup 5): the summary lists every
 # launch, so bench.py assembles the timed steps of any run these 25 launches cover -- the default 10 / 2 as well (round 4 collected 10 / 2 and the
@@ -16,9 +16,9 @@ DRV="--steps 20 --warmup 5"
 bash "$R/tools/pmc_passes.sh" "$OUT/pmc" --cpu-seconds 0 --latency-frames 0 $DRV > "$OUT/pmc_passes.log" 2>&1
 python3 "$R/tools/pmc_aggregate.py" "$OUT/pmc" "render_kernel<false>" --cpu-seconds 0 --latency-frames 0 $DRV > "$OUT/pmc_render_kernel.csv"
 # 3. the bench line of this build with the measured traffic attached (and the CPU leg, parity check, latency legs)
-timeout 900 python3 "$R/bench.py" --pmc-csv "$OUT/pmc_render_kernel.csv" > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+timeout 900 python3 "$R/bench.py" --full --pmc-csv "$OUT/pmc_render_kernel.csv" > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 # 3b. the driver's own command line, counters looked up as the driver's run will (no --pmc-csv: the file must first be copied to profiles/; here it is only a rehearsal of the timing)
-timeout 900 python3 "$R/bench.py" --gpus 1 $DRV --pmc-csv "$OUT/pmc_render_kernel.csv" > "$OUT/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
+timeout 900 python3 "$R/bench.py" --full --gpus 1 $DRV --pmc-csv "$OUT/pmc_render_kernel.csv" > "$OUT/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
 # 4. SQ counters (128 frames per launch)
 bash "$R/tools/pmc_stalls.sh" libcpuvox_gpu.so > "$OUT/sq_counters.txt" 2>&1
 bash "$R/tools/pmc_insts.sh" libcpuvox_gpu.so >> "$OUT/sq_counters.txt" 2>&1
@@ -29,10 +29,10 @@ C4="--frames 256 --steps 4 --warmup 1 --width 3840 --height 2160"
 C5="--frames 256 --steps 4 --warmup 1 --width 3840 --height 2160 --world proc4096 --lod-error 4"
 PMC_ONLY_TRAFFIC=1 bash "$R/tools/pmc_passes.sh" "$OUT/pmc4" --cpu-seconds 0 --latency-frames 0 $C4 > "$OUT/pmc4_passes.log" 2>&1
 python3 "$R/tools/pmc_aggregate.py" "$OUT/pmc4" "render_kernel<false>" --cpu-seconds 0 --latency-frames 0 $C4 > "$OUT/pmc_render_kernel_config4.csv"
-timeout 900 python3 "$R/bench.py" --cpu-seconds 15 --latency-frames 0 $C4 --pmc-csv "$OUT/pmc_render_kernel_config4.csv" > "$OUT/bench_config4_1gpu.json" 2> "$OUT/bench_config4.err"
+timeout 900 python3 "$R/bench.py" --full --cpu-seconds 15 --latency-frames 0 $C4 --pmc-csv "$OUT/pmc_render_kernel_config4.csv" > "$OUT/bench_config4_1gpu.json" 2> "$OUT/bench_config4.err"
 PMC_ONLY_TRAFFIC=1 PMC_PASS_TIMEOUT=400 bash "$R/tools/pmc_passes.sh" "$OUT/pmc5" --cpu-seconds 0 --latency-frames 0 $C5 > "$OUT/pmc5_passes.log" 2>&1
 python3 "$R/tools/pmc_aggregate.py" "$OUT/pmc5" "render_kernel<false>" --cpu-seconds 0 --latency-frames 0 $C5 > "$OUT/pmc_render_kernel_config5.csv"
-timeout 1100 python3 "$R/bench.py" --cpu-seconds 15 --latency-frames 0 $C5 --pmc-csv "$OUT/pmc_render_kernel_config5.csv" > "$OUT/bench_config5_1gpu.json" 2> "$OUT/bench_config5.err"
+timeout 1100 python3 "$R/bench.py" --full --cpu-seconds 15 --latency-frames 0 $C5 --pmc-csv "$OUT/pmc_render_kernel_config5.csv" > "$OUT/bench_config5_1gpu.json" 2> "$OUT/bench_config5.err"
 rm -rf "$OUT/trace" "$OUT"/pmc*/pass*/runc "$OUT"/pmc*/pass*/*/*agent_info.csv 2>/dev/null
 ls -la "$OUT"
 cat "$OUT/kernel_stats.csv" | head -8

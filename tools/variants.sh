@@ -12,7 +12,7 @@ cd /tmp; export TMPDIR=/tmp
 LOG=/tmp/variants_$$.log; : > $LOG
 for round in $(seq 1 ${ROUNDS:-5}); do
   for L in $LIBS; do
-    CVX_GPU_LIB=$R/cpuvox_amd/$L timeout 600 python3 $R/bench.py --cpu-seconds 0 --latency-frames 0 --frames 256 --steps 8 --warmup 2 "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$L', d['value'], 'Mrays/s kernel_ms', d['roofline']['kernel_ms_avg'])" | tee -a $LOG
+    CVX_GPU_LIB=$R/cpuvox_amd/$L timeout 600 python3 $R/bench.py --full --cpu-seconds 0 --latency-frames 0 --frames 256 --steps 8 --warmup 2 "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$L', d['value'], 'Mrays/s kernel_ms', d['roofline']['kernel_ms_avg'])" | tee -a $LOG
   done
 done
 echo "== kernel ms per build: median / min over the rounds"
