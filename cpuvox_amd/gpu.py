@@ -32,7 +32,7 @@ EXPORTS = [
     "cvx_get_raybuffer_layout", "cvx_version", "cvx_bind_raybuffers", "cvx_draw_time_stats", "cvx_copy_rows", "cvx_draw_segments_placed",
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
-    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh",
+    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -61,6 +61,8 @@ class Counters(C.Structure):
 BRUSH_FILL, BRUSH_CARVE, BRUSH_PAINT = 0, 1, 2  # cvx_brush_stroke.op
 SHAPE_BOX, SHAPE_SPHERE = 0, 1                  # cvx_brush_stroke.shape
 BRUSH_MAX_STROKES = 4096
+COPY_REPLACE = 3                                # cvx_copy_placement.op, besides BRUSH_FILL / CARVE / PAINT
+COPY_MAX_PLACEMENTS = 1024
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
 
@@ -76,6 +78,11 @@ class PickHit(C.Structure):
     _fields_ = [("voxel", C.c_int32 * 3), ("face", C.c_int32), ("argb", C.c_uint32), ("t", C.c_float)]
 
 
+class CopyPlacement(C.Structure):
+    _fields_ = [("srcMin", C.c_int32 * 3), ("srcMax", C.c_int32 * 3), ("dst", C.c_int32 * 3), ("transform", C.c_int32), ("op", C.c_int32),
+                ("move", C.c_int32)]
+
+
 class _TextureStruct(C.Structure):  # cvx_mesh_texture
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
 
@@ -86,6 +93,8 @@ PICK_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("maxT
 PICK_HIT_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("argb", "<u4"), ("t", "<f4")])
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex
 STAMP_MAX_MATERIALS = 128
+COPY_PLACEMENT_DTYPE = np.dtype([("srcMin", "<i4", 3), ("srcMax", "<i4", 3), ("dst", "<i4", 3), ("transform", "<i4"), ("op", "<i4"),
+                                 ("move", "<i4")])  # cvx_copy_placement
 
 
 def strokes_array(strokes) -> np.ndarray:
@@ -99,6 +108,20 @@ def strokes_array(strokes) -> np.ndarray:
         out[i]["a"] = s["a"]
         out[i]["b"] = [b, 0, 0] if np.isscalar(b) else b
         out[i]["argb"] = s.get("argb", 0) & 0xFFFFFFFF
+    return out
+
+
+def copy_placements_array(placements) -> np.ndarray:
+    """A list of dicts {srcMin, srcMax, dst, transform (default 0), op (default COPY_REPLACE), move (default 0)} or a COPY_PLACEMENT_DTYPE array
+    -> a contiguous COPY_PLACEMENT_DTYPE array."""
+    if isinstance(placements, np.ndarray):
+        return np.ascontiguousarray(placements.astype(COPY_PLACEMENT_DTYPE, copy=False))
+    out = np.zeros(len(placements), dtype=COPY_PLACEMENT_DTYPE)
+    for i, p in enumerate(placements):
+        out[i]["srcMin"], out[i]["srcMax"], out[i]["dst"] = p["srcMin"], p["srcMax"], p["dst"]
+        out[i]["transform"] = p.get("transform", 0)
+        out[i]["op"] = p.get("op", COPY_REPLACE)
+        out[i]["move"] = int(p.get("move", 0))
     return out
 
 
@@ -228,6 +251,7 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_compact.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         L.cvx_world_stamp_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_float)]
+        L.cvx_world_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -402,6 +426,15 @@ class Context:
         ms = C.c_float()
         self._check(lib().cvx_world_stamp_mesh(self._h, v.ctypes.data if v.size else None, v.size, idx.ctypes.data if idx.size else None, idx.size,
                                                C.cast(textures, C.c_void_p), mesh.material_count, op, level_count, C.byref(ms)))
+        return ms.value
+
+    def copy(self, placements, level_count: int = LOD_LEVELS - 1) -> float:
+        """Copies, moves, turns or mirrors boxes of LOD-0 voxels inside the world (a list of dicts {srcMin, srcMax, dst, transform, op, move}
+        or a COPY_PLACEMENT_DTYPE array; every source voxel is read from the world as it was before the call), then rebuilds
+        LOD 1..level_count over the footprint.  Returns the device milliseconds (0 when nothing changes)."""
+        arr = copy_placements_array(placements)
+        ms = C.c_float()
+        self._check(lib().cvx_world_copy(self._h, arr.ctypes.data if arr.size else None, arr.size, level_count, C.byref(ms)))
         return ms.value
 
     def pick(self, origins, directions, max_t):

@@ -99,6 +99,17 @@ namespace CpuVox.Gpu
 		public byte* Rgba;
 	}
 
+	// cvx_world_copy: one placement (48 bytes).  Source box [SrcMin, SrcMax) in LOD-0 voxels, destination min corner Dst; Transform bits 0-1 quarter
+	// turns, bit 2 mirror X (before turning), bit 3 flip Y; Op: 0 fill, 1 carve, 2 paint, 3 replace; Move 1: the source box becomes air
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct CopyPlacement
+	{
+		public fixed int SrcMin[3];
+		public fixed int SrcMax[3];
+		public fixed int Dst[3];
+		public int Transform, Op, Move;
+	}
+
 	public sealed class CvxException : Exception
 	{
 		public readonly int Code;
@@ -153,6 +164,8 @@ namespace CpuVox.Gpu
 		// a triangle mesh voxelised on the device (the host voxeliser's rule) and merged into LOD 0 (op 0 fill, 1 carve, 2 paint) + its LOD refresh
 		[DllImport(Lib)] public static extern int cvx_world_stamp_mesh(IntPtr ctx, MeshVertex* vertices, int vertexCount, int* indices, long indexCount,
 		                                                               MeshTexture* materials, int materialCount, int op, int levelCount, out float outDeviceMs);
+		// boxes of voxels copied, moved, turned or mirrored inside LOD 0 (every read from the world before the call) + its LOD refresh
+		[DllImport(Lib)] public static extern int cvx_world_copy(IntPtr ctx, CopyPlacement* placements, int placementCount, int levelCount, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

@@ -450,6 +450,37 @@ typedef struct cvx_mesh_texture { /* 16 bytes */
 int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int vertexCount, const int32_t *indices, int64_t indexCount,
                          const cvx_mesh_texture *materials, int materialCount, int op, int levelCount, float *outDeviceMs);
 
+/* ---- copying, moving and rotating voxel boxes inside the uploaded world ------------------------------------------------------------------
+ * cvx_world_copy: places boxes of voxels the world already holds elsewhere in it (duplicate, move, quarter turns, mirror, scatter), computed on
+ * the device and handed to cvx_world_edit's machinery like a brush.  Let W be LOD 0 before the call; the result R is:
+ *   1. R = W; for every placement with move = 1, every voxel of its source box becomes air in R.
+ *   2. The placements in array order: for every destination voxel d inside the world, s = W(T^-1(d)) -- every read is from W, the snapshot, so
+ *      source and destination may overlap -- and the op decides R(d): CVX_COPY_REPLACE R(d) = s (air included); CVX_BRUSH_FILL: s solid ->
+ *      R(d) = s; CVX_BRUSH_CARVE: s solid -> R(d) = air; CVX_BRUSH_PAINT: s solid and R(d) solid -> R(d) takes s's colour.  Colours are copied
+ *      verbatim (the arena's ARGB words).
+ * The transform T of a placement: (p, q, r) = v - srcMin in the source box of size (sx, sy, sz); mirror X (bit 2): p = sx-1-p; each of the k
+ * quarter turns (bits 0-1): (p, r, sx, sz) = (sz-1-r, p, sz, sx); flip Y (bit 3): q = sy-1-q; the destination voxel is dst + (p, q, r).  After an
+ * odd k the destination box has size (sz, sy, sx).  A source box lies inside the world with srcMin < srcMax per axis; destination voxels outside
+ * the world are dropped; a placement whose destination lies wholly outside writes nothing (its move still carves).  The call edits the bounding
+ * XZ rectangle of every clipped destination footprint and every moving placement's source footprint, rounded outward to multiples of
+ * 2^levelCount and clipped to the world (cvx_world_brush's rectangle); nothing to change: CVX_OK and *outDeviceMs = 0.  Coordinates are LOD-0
+ * voxels of the stored tile: a repeating world does not wrap them.  Ordering, atomicity, outDeviceMs, CVX_ERR_CAPACITY (the brush's format
+ * limits, the arena limits) and CVX_ERR_NOT_READY are cvx_world_brush's; every error leaves the world as it was.  CVX_ERR_INVALID_ARGUMENT: a
+ * bad op, move not 0 / 1, unknown transform bits, placementCount outside 1 .. CVX_COPY_MAX_PLACEMENTS, levelCount outside 0 .. 5, an empty
+ * source box or one outside the world, a |dst| component above 2^30.  With several GPUs every rank applies the same placements to its own
+ * context. */
+enum { CVX_COPY_REPLACE = 3 }; /* op: also CVX_BRUSH_FILL / CVX_BRUSH_CARVE / CVX_BRUSH_PAINT */
+#define CVX_COPY_MAX_PLACEMENTS 1024
+typedef struct cvx_copy_placement { /* 48 bytes */
+	int32_t srcMin[3];  /* source box in LOD-0 voxels, inclusive */
+	int32_t srcMax[3];  /* exclusive */
+	int32_t dst[3];     /* min corner of the destination box */
+	int32_t transform;  /* bits 0-1: quarter turns k; bit 2: mirror X (before turning); bit 3: flip Y; other bits 0 */
+	int32_t op;         /* CVX_COPY_REPLACE, CVX_BRUSH_FILL, CVX_BRUSH_CARVE, CVX_BRUSH_PAINT */
+	int32_t move;       /* 1: the source box becomes air */
+} cvx_copy_placement;
+int cvx_world_copy(cvx_context *ctx, const cvx_copy_placement *placements, int placementCount, int levelCount, float *outDeviceMs);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
