@@ -227,8 +227,14 @@ __device__ __forceinline__ bool dda_step_to_world_intersection(DDA &d, float dim
 		hit = d.dirZ > 0.0f ? floorf(hit) : ceilf(hit);
 		tLastZ = (hit - d.startZ) / d.dirZ;
 	}
-	d.tMaxX = tLastX + d.tDeltaX;
-	d.tMaxZ = tLastZ + d.tDeltaZ;
+	// Deviation from the reference (the oracle's dda_step_to_world_intersection): an axis the ray does not move along gets a
+	// non-finite tLast here (-inf for x, (ceil(s) - s) / +-0 = NaN or +-inf for z) and would keep it; it keeps dda_init's tMax instead and
+	// tLast = tMax - tDelta.  Rays whose entry tMax is finite are untouched.
+	float tMaxX = tLastX + d.tDeltaX, tMaxZ = tLastZ + d.tDeltaZ;
+	if (CVX_RARE(!(fabsf(tMaxX) < inf))) { tLastX = d.tMaxX - d.tDeltaX; tMaxX = d.tMaxX; }
+	if (CVX_RARE(!(fabsf(tMaxZ) < inf))) { tLastZ = d.tMaxZ - d.tDeltaZ; tMaxZ = d.tMaxZ; }
+	d.tMaxX = tMaxX;
+	d.tMaxZ = tMaxZ;
 	d.distLast = m_max(tLastX, tLastZ);
 	d.distNext = m_min(d.tMaxX, d.tMaxZ);
 	float mid = m_lerp(d.distLast, d.distNext, 0.5f);
@@ -272,7 +278,7 @@ __device__ __forceinline__ bool dda_step(DDA &d, float farClip) // :135-150
 	d.px += stepX ? d.sx : 0;
 	d.pz += stepX ? 0 : d.sz;
 	d.distLast = crossed;
-	d.distNext = hw_min(d.tMaxX, d.tMaxZ); // tMax values are sums of positive terms: no negative zero, m_min == v_min_f32
+	d.distNext = hw_min(d.tMaxX, d.tMaxZ); // tMax values are finite and never -0 (see dda_step_cursor): m_min == v_min_f32
 	return crossed >= farClip;
 }
 
@@ -281,7 +287,9 @@ __device__ __forceinline__ bool dda_step_cursor(DDA &d, ColumnCursor &c, float s
 {
 	const bool stepX = d.tMaxX < d.tMaxZ;
 	// the distance crossed is the smaller tMax (:139, :145) -- which is what distNext already holds: every place that sets tMax sets distNext to the
-	// minimum of the two (here, dda_init, dda_next_lod, dda_step_to_world_intersection; tMax values are positive sums, so min and "x < z ? x : z" agree)
+	// minimum of the two (here, dda_init, dda_next_lod, dda_step_to_world_intersection).  min and "x < z ? x : z" agree because no tMax is ever NaN
+	// or -0: dda_init's are (0 .. 1] x tDelta (a +0 at most), the entry step replaces a non-finite one with dda_init's, and the others add tDelta >= 1
+	// to these.  (With a NaN they would not: x < NaN is false, min returns the other operand.)
 	const float crossed = d.distNext;
 	const float nextX = d.tMaxX + d.tDeltaX, nextZ = d.tMaxZ + d.tDeltaZ;
 	d.tMaxX = stepX ? nextX : d.tMaxX;
@@ -592,8 +600,10 @@ __device__ __forceinline__ void trace_ray(const DevFrame &F, const DevSegment &S
 	}
 
 	// A DDA walk is monotone in x and z, so it leaves the world after at most
-	// dimX + dimZ column visits; the cap can never bind on valid input and only
-	// keeps a wave from spinning on non-finite camera data.
+	// dimX + dimZ column visits once both tMax are finite -- which the entry
+	// step guarantees (before its deviation, an axis-parallel ray entering on a
+	// grid plane had tMax.z = NaN, never moved, and this cap bound).  It binds
+	// only on non-finite camera data.
 	// In a repeating world the walk ends at the far clip (<= 2^20, checked at draw time): at most sqrt(2) far clip + 2 column visits.
 	int guardSteps = REPEAT ? 2 * (int)m_max(farClip, 0.0f) + 16 : dimX + dimZ + 16;
 

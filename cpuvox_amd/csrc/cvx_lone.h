@@ -434,7 +434,8 @@ __device__ __forceinline__ void lone_trace_ray(const DevFrame &F, const DevSegme
 	int pos = REPEAT ? (ray.px & maskX) * 65536 + (ray.pz & maskZ) : ray.px * 65536 + ray.pz;
 	int posStepX = ray.sx * 65536, posStepZ = ray.sz;
 	const int outsideBits = ~((maskX << 16) | maskZ);
-	// A DDA walk is monotone in x and z: it leaves the world after at most dimX + dimZ columns; the cap only keeps a wave from spinning on non-finite camera data.
+	// A DDA walk is monotone in x and z: it leaves the world after at most dimX + dimZ columns once both tMax are finite, which the entry step guarantees
+	// (dda_step_to_world_intersection, cvx_kernels.h); the cap binds only on non-finite camera data.
 	// In a repeating world the walk ends at the far clip (<= 2^20, checked at draw time): at most sqrt(2) far clip + 2 columns.
 	int guardSteps = REPEAT ? 2 * (2 * (int)m_max(farClip, 0.0f) + 16) : 2 * (dimX + dimZ + 16);
 

@@ -26,6 +26,11 @@
 #include <omp.h>
 #endif
 
+/* Edge-event counting of orc_draw_segments_events: each worker thread points ev_tls at its own orc_events while it runs the
+ * jobs (NULL under orc_draw_segments).  The hooks only count; no value the walk computes depends on them. */
+static _Thread_local orc_events *ev_tls;
+#define ORC_EVENT(field) do { if (ev_tls) { ev_tls->field++; } } while (0)
+
 /* ------------------------------------------------------------------ */
 /* Unity.Mathematics scalar semantics (math.cs of 1.2.6)               */
 /* ------------------------------------------------------------------ */
@@ -54,6 +59,7 @@ static inline float m_cmin(f2 v) { return m_min(v.x, v.y); }
 static inline int f2i(float x)
 {
 	if (x != x || x >= 2147483648.0f || x < -2147483648.0f) {
+		ORC_EVENT(f2iInvalid);
 		return INT_MIN;
 	}
 	return (int)x;
@@ -125,6 +131,12 @@ static dda_t dda_new(f2 start, f2 dir)
 	d.position.y = f2i(floorf(start.y));
 	d.tDelta.x = 1.0f / m_max(0.0000001f, fabsf(dir.x));
 	d.tDelta.y = 1.0f / m_max(0.0000001f, fabsf(dir.y));
+	if (!(fabsf(dir.x) > 0.0000001f) || !(fabsf(dir.y) > 0.0000001f)) {
+		ORC_EVENT(dirClamped);
+	}
+	if (start.x == floorf(start.x) || start.y == floorf(start.y)) {
+		ORC_EVENT(startOnGrid);
+	}
 	f2 signDir = { m_sign(dir.x), m_sign(dir.y) };
 	d.step.x = f2i(signDir.x);
 	d.step.y = f2i(signDir.y);
@@ -224,8 +236,30 @@ static int dda_step_to_world_intersection(dda_t *d, f2 dimensions)
 		tLast.y = offsetAxisToHit / d->dir.y;
 	}
 
-	d->tMax.x = tLast.x + d->tDelta.x;
-	d->tMax.y = tLast.y + d->tDelta.y;
+	/* DEVIATION from SegmentDDAData.cs:75-120.  An axis the ray does not move along (dir == +-0: tmin stays
+	 * -inf) gets tLast = -inf when it is x, and (ceil(s) - s) / +-0 = NaN or +-inf when it is z; a ray that enters on a grid plane
+	 * (integer z, direction (+-1, 0)) then has tMax.y = NaN, `tMax.x < NaN` is false on every step, the position never moves and
+	 * the reference's walk never ends (a -inf tMax does the same; +inf or a NaN position gives a skybox ray instead).  Such an axis
+	 * keeps the tMax of the SegmentDDAData ctor (:17-28) -- a zero direction never crosses it -- and its tLast = tMax - tDelta, as
+	 * the ctor's intersectionDistances.x has it.  Only rays whose entry tMax is not finite change. */
+	f2 tMaxEntry = { tLast.x + d->tDelta.x, tLast.y + d->tDelta.y };
+	int nonFinite = 0;
+	if (!(fabsf(tMaxEntry.x) < INFINITY)) {
+		tLast.x = d->tMax.x - d->tDelta.x;
+		tMaxEntry.x = d->tMax.x;
+		nonFinite = 1;
+	}
+	if (!(fabsf(tMaxEntry.y) < INFINITY)) {
+		tLast.y = d->tMax.y - d->tDelta.y;
+		tMaxEntry.y = d->tMax.y;
+		nonFinite = 1;
+	}
+	ORC_EVENT(entrySteps);
+	if (nonFinite) {
+		ORC_EVENT(entryNonFinite);
+	}
+
+	d->tMax = tMaxEntry;
 	d->intersectionDistances.x = m_cmax(tLast);
 	d->intersectionDistances.y = m_cmin(d->tMax);
 	float mid = m_lerp(d->intersectionDistances.x, d->intersectionDistances.y, 0.5f);
@@ -238,6 +272,9 @@ static int dda_step_to_world_intersection(dda_t *d, f2 dimensions)
 static inline int dda_step(dda_t *d, float farclip)
 {
 	float crossedBoundaryDistance;
+	if (d->tMax.x == d->tMax.y) {
+		ORC_EVENT(ties);
+	}
 	if (d->tMax.x < d->tMax.y) {
 		crossedBoundaryDistance = d->tMax.x;
 		d->tMax.x += d->tDelta.x;
@@ -249,7 +286,19 @@ static inline int dda_step(dda_t *d, float farclip)
 	}
 	d->intersectionDistances.x = crossedBoundaryDistance;
 	d->intersectionDistances.y = m_cmin(d->tMax);
+	if (crossedBoundaryDistance == farclip) {
+		ORC_EVENT(clipExact);
+	}
 	return crossedBoundaryDistance >= farclip;
+}
+
+/* dda_step of ExecuteRay, counting the ray's steps for orc_events.maxSteps */
+static inline int dda_step_counted(dda_t *d, float farclip, int64_t *steps)
+{
+	if (ev_tls && ++*steps > ev_tls->maxSteps) {
+		ev_tls->maxSteps = *steps;
+	}
+	return dda_step(d, farclip);
 }
 
 /* SegmentDDAData.IsBeyondFarClip, SegmentDDAData.cs:152-155 */
@@ -484,6 +533,16 @@ static void setup_projected_plane_params(const orc_camera_data *camera, const dd
 	}
 }
 
+/* The latency kernel's test for a run projection that needs neither a near-plane clip nor a division outside its short
+ * form (cvx_lone.h project_run: `ordinary`): camera-space depth (y) of the front's two ends and of the face's far end above 0,
+ * and |w| and |x| of the front's ends in [2^-30, 2^30].  Only counted (orc_events.projNonOrdinary). */
+static int div_safe(float x) { return fabsf(x) >= 0x1p-30f && fabsf(x) <= 0x1p30f; }
+static int projection_is_ordinary(f3 frontBottom, f3 frontTop, f3 secA)
+{
+	return !(frontBottom.y <= 0.0f) && !(frontTop.y <= 0.0f) && !(secA.y <= 0.0f) && div_safe(frontBottom.z) && div_safe(frontTop.z) &&
+	       div_safe(frontBottom.x) && div_safe(frontTop.x);
+}
+
 #define FLOAT_EPSILON 1.401298464324817e-45f /* C# float.Epsilon: smallest denormal */
 
 static inline void swapf(float *a, float *b) { float t = *a; *a = *b; *b = t; }
@@ -506,6 +565,7 @@ static void execute_ray(const ray_continuation *rayContext, const draw_context *
 	float lodMax = camera->LODDistances[lod];
 
 	memset(seenPixelCache, 0, (size_t)segmentContext->seenPixelCacheLength); /* stackalloc, zeroed (:208) */
+	int64_t steps = 0; /* dda_step calls of this ray (orc_events.maxSteps) */
 
 	const int omin = segmentContext->originalNextFreePixelMin;
 	const int omax = segmentContext->originalNextFreePixelMax;
@@ -526,6 +586,9 @@ static void execute_ray(const ray_continuation *rayContext, const draw_context *
 	                             &planeStartBottomProjected, &planeStartTopProjected, &planeRayDirectionProjected);
 
 	while (1) {
+		if (ray.intersectionDistances.x == lodMax) {
+			ORC_EVENT(clipExact);
+		}
 		if (ray.intersectionDistances.x >= lodMax && lod < ORC_LOD_LEVELS - 1) { /* :237-243 (+ the same guard) */
 			dda_next_lod(&ray, voxelScale);
 			lod++;
@@ -542,7 +605,7 @@ static void execute_ray(const ray_continuation *rayContext, const draw_context *
 		tc->S++;
 		tc->lod[lod]++;
 		if (columnRuns == 0) {
-			if (dda_step(&ray, farClip)) {
+			if (dda_step_counted(&ray, farClip, &steps)) {
 				break;
 			}
 			continue;
@@ -561,7 +624,7 @@ static void execute_ray(const ray_continuation *rayContext, const draw_context *
 				return;
 			}
 			if ((float)worldColumn.worldMin > newMax || (float)worldColumn.worldMax < newMin) {
-				if (dda_step(&ray, farClip)) {
+				if (dda_step_counted(&ray, farClip, &steps)) {
 					break;
 				}
 				continue;
@@ -741,6 +804,10 @@ static void execute_ray(const ray_continuation *rayContext, const draw_context *
 			float portionTop = m_unlerp(0.0f, worldMaxY, elementBoundsMax);
 			f3 camSpaceFrontBottom = f3_lerp(camSpaceMinLast, camSpaceMaxLast, portionBottom);
 			f3 camSpaceFrontTop = f3_lerp(camSpaceMinLast, camSpaceMaxLast, portionTop);
+			if (ev_tls && !projection_is_ordinary(camSpaceFrontBottom, camSpaceFrontTop,
+			                                      f3_lerp(camSpaceMinNext, camSpaceMaxNext, portionTop < cameraPosYNormalized ? portionTop : portionBottom))) {
+				ev_tls->projNonOrdinary++;
+			}
 
 			/* side of the run, :484-542 */
 			{
@@ -849,7 +916,7 @@ static void execute_ray(const ray_continuation *rayContext, const draw_context *
 			}
 		}
 
-		if (dda_step(&ray, farClip)) {
+		if (dda_step_counted(&ray, farClip, &steps)) {
 			break;
 		}
 	}
@@ -923,6 +990,9 @@ static int trace_to_first_column_job(const ray_dda_context *inRays, const draw_c
 		if (dda_step_to_world_intersection(&cont->ddaRay, dimsf)) {
 			/* "cont->lod < 5": memory-safety guard only (the reference would index LODDistances[6]);
 			 * a ray that far away is beyond far clip and becomes skybox either way. */
+			if (cont->ddaRay.intersectionDistances.x == lodMax) {
+				ORC_EVENT(clipExact);
+			}
 			while (cont->ddaRay.intersectionDistances.x >= lodMax && cont->lod < ORC_LOD_LEVELS - 1) {
 				dda_next_lod(&cont->ddaRay, 1 << cont->lod);
 				cont->lod++;
@@ -968,16 +1038,18 @@ int orc_max_threads(void)
 }
 
 /* RenderManager.DrawSegments, RenderManager.cs:258-372 */
-int orc_draw_segments(const orc_segment_data segments[4],
-                      const orc_world worldLODs[ORC_LOD_LEVELS],
-                      const orc_camera_data *camera,
-                      int screenWidth, int screenHeight,
-                      const float vanishingPointScreenSpace[2],
-                      uint32_t *rayBufferTopDown,
-                      uint32_t *rayBufferLeftRight,
-                      int threads,
-                      orc_counters *counters)
+static int draw_segments(const orc_segment_data segments[4],
+                         const orc_world worldLODs[ORC_LOD_LEVELS],
+                         const orc_camera_data *camera,
+                         int screenWidth, int screenHeight,
+                         const float vanishingPointScreenSpace[2],
+                         uint32_t *rayBufferTopDown,
+                         uint32_t *rayBufferLeftRight,
+                         int threads,
+                         orc_counters *counters,
+                         orc_events *events)
 {
+	if (events) { memset(events, 0, sizeof *events); }
 	if (!segments || !worldLODs || !camera || screenWidth <= 0 || screenHeight <= 0) {
 		return -1;
 	}
@@ -1087,6 +1159,9 @@ int orc_draw_segments(const orc_segment_data segments[4],
 	{
 		tls_counters tc;
 		memset(&tc, 0, sizeof tc);
+		orc_events ev;
+		memset(&ev, 0, sizeof ev);
+		ev_tls = events ? &ev : NULL;
 		uint8_t *seen = (uint8_t *)malloc((size_t)cacheLen);
 
 		/* Schedule(totalRays, 64), RenderManager.cs:358-359 */
@@ -1123,8 +1198,20 @@ int orc_draw_segments(const orc_segment_data segments[4],
 		}
 
 		free(seen);
+		ev_tls = NULL;
 #pragma omp critical
 		{
+			if (events) {
+				events->dirClamped += ev.dirClamped;
+				events->startOnGrid += ev.startOnGrid;
+				events->entrySteps += ev.entrySteps;
+				events->entryNonFinite += ev.entryNonFinite;
+				events->ties += ev.ties;
+				events->f2iInvalid += ev.f2iInvalid;
+				events->projNonOrdinary += ev.projNonOrdinary;
+				events->clipExact += ev.clipExact;
+				if (ev.maxSteps > events->maxSteps) { events->maxSteps = ev.maxSteps; }
+			}
 			total.S += tc.S;
 			total.E += tc.E;
 			total.C += tc.C;
@@ -1153,4 +1240,20 @@ int orc_draw_segments(const orc_segment_data segments[4],
 	free(tdTab);
 	free(lrTab);
 	return totalRays;
+}
+
+int orc_draw_segments(const orc_segment_data segments[4], const orc_world worldLODs[ORC_LOD_LEVELS], const orc_camera_data *camera,
+                      int screenWidth, int screenHeight, const float vanishingPointScreenSpace[2], uint32_t *rayBufferTopDown,
+                      uint32_t *rayBufferLeftRight, int threads, orc_counters *counters)
+{
+	return draw_segments(segments, worldLODs, camera, screenWidth, screenHeight, vanishingPointScreenSpace, rayBufferTopDown, rayBufferLeftRight,
+	                     threads, counters, NULL);
+}
+
+int orc_draw_segments_events(const orc_segment_data segments[4], const orc_world worldLODs[ORC_LOD_LEVELS], const orc_camera_data *camera,
+                             int screenWidth, int screenHeight, const float vanishingPointScreenSpace[2], uint32_t *rayBufferTopDown,
+                             uint32_t *rayBufferLeftRight, int threads, orc_counters *counters, orc_events *events)
+{
+	return draw_segments(segments, worldLODs, camera, screenWidth, screenHeight, vanishingPointScreenSpace, rayBufferTopDown, rayBufferLeftRight,
+	                     threads, counters, events);
 }

@@ -91,6 +91,31 @@ int orc_draw_segments(const orc_segment_data segments[4],
                       int threads,
                       orc_counters *counters /* may be NULL */);
 
+/* Edge events of one frame (tests/edgeposes.py): how often the walk met the exact-value cases the kernels have code for.
+ * Counting only -- orc_draw_segments_events computes the same raybuffers and orc_counters as orc_draw_segments. */
+typedef struct {
+	int64_t dirClamped;      /* rays whose direction hit the 1e-7 clamp of the tDelta (SegmentDDAData.cs:22-23) on either axis */
+	int64_t startOnGrid;     /* rays whose start lies on an integer x or z */
+	int64_t entrySteps;      /* rays that entered the world through StepToWorldIntersection (:75-130) */
+	int64_t entryNonFinite;  /* ... whose tMax the reference computes non-finite (the oracle's deviation, cvx_oracle.c) */
+	int64_t ties;            /* SegmentDDAData.Step (:135-150) with tMax.x == tMax.y exactly (z steps) */
+	int64_t f2iInvalid;      /* (int)float of a NaN or out-of-range value (INT_MIN) */
+	int64_t projNonOrdinary; /* run projections the latency kernel sends down its non-ordinary path (a depth <= 0, a |w| or |x| outside [2^-30, 2^30]) */
+	int64_t maxSteps;        /* the most Step calls of one ray in ExecuteRay: what the kernels' step guard caps */
+	int64_t clipExact;       /* a crossing exactly at the far clip (Step's >=, :149) or a column's distance exactly at its LOD distance (:237, :101) */
+} orc_events;
+
+int orc_draw_segments_events(const orc_segment_data segments[4],
+                             const orc_world worldLODs[ORC_LOD_LEVELS],
+                             const orc_camera_data *camera,
+                             int screenWidth, int screenHeight,
+                             const float vanishingPointScreenSpace[2],
+                             uint32_t *rayBufferTopDown,
+                             uint32_t *rayBufferLeftRight,
+                             int threads,
+                             orc_counters *counters /* may be NULL */,
+                             orc_events *events /* may be NULL */);
+
 int orc_max_threads(void);
 
 #ifdef __cplusplus

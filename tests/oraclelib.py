@@ -49,6 +49,24 @@ class OrcCounters(C.Structure):
                 "bytes": self.algorithmic_bytes()}
 
 
+class OrcEvents(C.Structure):
+    """orc_events (oracle/cvx_oracle.h): edge events of one frame's walk."""
+    _fields_ = [
+        ("dirClamped", C.c_int64),
+        ("startOnGrid", C.c_int64),
+        ("entrySteps", C.c_int64),
+        ("entryNonFinite", C.c_int64),
+        ("ties", C.c_int64),
+        ("f2iInvalid", C.c_int64),
+        ("projNonOrdinary", C.c_int64),
+        ("maxSteps", C.c_int64),
+        ("clipExact", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -69,6 +87,8 @@ def lib() -> C.CDLL:
         L.orc_draw_segments.restype = C.c_int
         L.orc_draw_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.orc_draw_segments_events.restype = C.c_int
+        L.orc_draw_segments_events.argtypes = L.orc_draw_segments.argtypes + [C.c_void_p]
         L.orc_max_threads.restype = C.c_int
         _lib = L
     return _lib
@@ -142,6 +162,22 @@ def draw_segments(world_set, frame, width: int, height: int, threads: int = 0, c
     if rc < 0:
         raise RuntimeError("orc_draw_segments failed")
     return td, lr, cnt
+
+
+def draw_segments_events(world_set, frame, width: int, height: int, threads: int = 0, clear: int = 0):
+    """draw_segments through orc_draw_segments_events: (topDown, leftRight, OrcCounters, OrcEvents).  The raybuffers and counters are
+    orc_draw_segments' own; the events count the exact-value cases the walk met (tests/edgeposes.py)."""
+    (td_rays, td_w), (lr_rays, lr_w) = raybuffer_shapes(width, height)
+    td = np.full((td_rays, td_w), clear, dtype=np.uint32)
+    lr = np.full((lr_rays, lr_w), clear, dtype=np.uint32)
+    worlds = orc_worlds(world_set)
+    cnt, ev = OrcCounters(), OrcEvents()
+    vp = (C.c_float * 2)(*frame.vanishingPointScreenSpace)
+    rc = lib().orc_draw_segments_events(C.addressof(frame.segments), C.addressof(worlds), C.addressof(frame.camera), width, height,
+                                        C.addressof(vp), td.ctypes.data, lr.ctypes.data, threads, C.addressof(cnt), C.addressof(ev))
+    if rc < 0:
+        raise RuntimeError("orc_draw_segments_events failed")
+    return td, lr, cnt, ev
 
 
 def blit_reference(frame, td: np.ndarray, lr: np.ndarray, width: int, height: int, clear: int = 0) -> np.ndarray:

@@ -2,7 +2,7 @@
 (GPU sanitizers are not available on this pool; the HIP side is covered by upload-time validation and the parity tests).
 
   * oracle/libcvx_oracle_asan.so: three scenes (single segment from outside the world, four segments, deep LODs) rendered
-    through the sanitized oracle; the raybuffers must equal the regular build's.
+    through the sanitized oracle; the raybuffers must equal the regular build's.  And the edge-pose catalogue (tests/edgeposes.py).
   * cpuvox_amd/libcpuvox_host_asan.so: world building (procedural, mill.obj voxelisation fixture round trip, LOD chain),
     .world save / load, camera / segment setup and the rejection of malformed files."""
 import os
@@ -61,6 +61,27 @@ def test_oracle_under_asan_and_ubsan():
         ws, fr, W, H = scenes.scene_frame(name)
         td, lr, cnt = O.draw_segments(ws, fr, W, H)
         assert got[name] == [scenes.crc(td), scenes.crc(lr), cnt.S, cnt.P], name
+
+
+def test_edge_pose_catalogue_under_asan_and_ubsan():
+    """The edge-pose catalogue (tests/edgeposes.py: NaN / infinite intermediate values, exact ties, axis-parallel entry steps, 1-pixel screens)
+    through the sanitized oracle, under a time limit; raybuffer CRCs and counters equal the regular build's (tests/golden/edge_poses.json)."""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "libcvx_oracle_asan.so"], stdout=subprocess.DEVNULL)
+    rt = _asan_runtime()
+    if rt is None:
+        pytest.skip("libasan runtime not found")
+    import edgeposes as E
+    from test_edge_poses import render_catalogue_in_child
+
+    got = render_catalogue_in_child({"CVX_ORACLE_LIB": os.path.join(ROOT, "oracle", "libcvx_oracle_asan.so"), "LD_PRELOAD": rt,
+                                     "ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1:halt_on_error=1",
+                                     "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1", "OMP_NUM_THREADS": "4"}, timeout=900)
+    want = E.load_fixture()
+    assert set(got) == set(want)
+    for name, r in got.items():
+        assert r["crcs"] == [want[name]["crcTopDown"], want[name]["crcLeftRight"]], name
+        assert r["counters"]["S"] == want[name]["counters"]["S"] and r["counters"]["P"] == want[name]["counters"]["P"], name
+        assert r["region"] == [], name
 
 
 def test_host_library_under_asan_and_ubsan(tmp_path):
