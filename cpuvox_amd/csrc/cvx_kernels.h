@@ -638,88 +638,98 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 		bool windowClosed = false; // :399-403: the clipped column lies outside the free pixel window -> the ray is finished
 		if (curDistLast > 2.0f && frustumDirMaxWorld == CVX_FLOAT_EPSILON) { // :295-422
 			CVX_COUNT(2);
-			float clipLastMinLerp, clipLastMaxLerp, clipNextMinLerp, clipNextMaxLerp;
 			// CameraData.cs:103,111.  frustumBounds = (integer pixel in [-1, 16385]) -/+ 0.501: magnitude in [0.499, 16386], always "safe"
 			const float invFrustumMin = quot_safe(1.0f, recip_safe(frustumBoundsMin)), invFrustumMax = quot_safe(1.0f, recip_safe(frustumBoundsMax));
-			bool straddlesLast, straddlesNext;
-			bool clippedLast, clippedNext;
+			// What follows the four lerps (:300-421), once per instance of the clip below.  ALL_STRADDLE: every lane of the wave that clips here straddles the
+			// window at both ends (nothing clipped away: the flags are constants); otherwise some lane does not, so the "window untouched" shortcut
+			// cannot hold for the wave and every lane takes the reference's path, which is right for any lane -- no residual tests, no branch.
+			// false = the ray is finished (counting build only).
+			const auto clipTail = [&](auto allStraddleTag, float clipLastMinLerp, float clipLastMaxLerp, float clipNextMinLerp, float clipNextMaxLerp, bool clippedLast_, bool clippedNext_) __attribute__((always_inline)) -> bool {
+				constexpr bool ALL_STRADDLE = decltype(allStraddleTag)::value;
+				const bool clippedLast = !ALL_STRADDLE && clippedLast_, clippedNext = !ALL_STRADDLE && clippedNext_;
+				// (:297-299 leaves here when both ends are outside the window; that exit is taken together with the next one below --
+				// nothing in between has an effect that survives the end of the ray)
+				// :300-390, the three cases (only Next visible / only Last visible / both) folded into selects: each
+				// bound comes from the Last or the Next intersection, chosen exactly as the reference's branches do.
+				const bool minFromLast = !clippedLast && (clippedNext || clipLastMinLerp < clipNextMinLerp);
+				const bool maxFromLast = !clippedLast && (clippedNext || clipLastMaxLerp > clipNextMaxLerp);
+				worldBoundsMin = m_lerp(0.0f, worldMaxY, minFromLast ? clipLastMinLerp : clipNextMinLerp);
+				worldBoundsMax = m_lerp(0.0f, worldMaxY, maxFromLast ? clipLastMaxLerp : clipNextMaxLerp);
+				frustumDirMinWorld = (worldBoundsMin - posY) / (minFromLast ? curDistLast : curDistNext);
+				frustumDirMaxWorld = (worldBoundsMax - posY) / (maxFromLast ? curDistLast : curDistNext);
+				const f3 minClipA = f3_lerp(camSpaceMinLast, camSpaceMaxLast, clipLastMinLerp);
+				const f3 maxClipA = f3_lerp(camSpaceMinLast, camSpaceMaxLast, clipLastMaxLerp);
+				const f3 minClipB = f3_lerp(camSpaceMinNext, camSpaceMaxNext, clipNextMinLerp);
+				const f3 maxClipB = f3_lerp(camSpaceMinNext, camSpaceMaxNext, clipNextMaxLerp);
+				worldBoundsMin = floorf(worldBoundsMin);
+				worldBoundsMax = ceilf(worldBoundsMax);
+
+				// :337-421 project the four clipped points (x / z), order them, and take floor(min) / ceil(max) as the writable pixel range, which
+				// can end the ray (:399-403) or move nextFreePixelMin / Max inwards (:405-416).  Only those two INTEGERS are ever used.  In the
+				// ordinary case -- both ends straddle the window, so the min points were clipped against frustumBoundsMin = k - 0.501 and the max
+				// points against frustumBoundsMax = m + 0.501 (k <= nextFreePixelMin <= nextFreePixelMax <= m, integers: ReducePixelHorizon :682,694) --
+				// a clipped point lies ON its bound up to rounding.  If the residual |x - f * z| (as computed, error < 2^-23 |f z| <= 0.002 |z|) is
+				// below 0.4 |z|, then x / z = f + r / z lies within 0.402 of f, the correctly rounded quotient too (rounding is monotone), hence
+				// floor(min) = k - 1 and ceil(max) = m + 1 whatever the exact quotients are: min < max (no swap, :339-346), the range contains
+				// [nextFreePixelMin, nextFreePixelMax] (no exit, nothing moves), and neither end was clipped away.  So nothing of :337-421 has any
+				// effect and the four divisions are not needed.  Any lane for which this cannot be shown takes the reference's path below.
+				const auto onBound = [](f3 p, float f) { return fabsf(p.x - f * p.z) < 0.4f * fabsf(p.z); };
+				// (`&`, not `&&`: six short tests evaluated straight-line instead of a chain of divergent branches)
+				// (a lane that does not straddle at both ends never qualifies: outside the all-straddle instance the wave holds one, its branch would always be taken)
+				const bool windowUntouched = !COUNT && ALL_STRADDLE && ((int)onBound(minClipA, frustumBoundsMin) & (int)onBound(minClipB, frustumBoundsMin) &
+				                                                        (int)onBound(maxClipA, frustumBoundsMax) & (int)onBound(maxClipB, frustumBoundsMax)) != 0;
+				if (!CVX_USUAL(windowUntouched)) {
+					float minNext = minClipB.x / minClipB.z;
+					float minLast = minClipA.x / minClipA.z;
+					float maxNext = maxClipB.x / maxClipB.z;
+					float maxLast = maxClipA.x / maxClipA.z;
+					if (maxNext < minNext) { float t = maxNext; maxNext = minNext; minNext = t; }
+					if (maxLast < minLast) { float t = maxLast; maxLast = minLast; minLast = t; }
+					// (hw_min / hw_max: the results only go through floor / ceil and (int), which map -0 and +0 to the same 0)
+					const float bothMin = hw_min(minLast, minNext), bothMax = hw_max(maxLast, maxNext); // (computed ahead of the selects: an asm inside a select becomes a branch)
+					const float camSpaceClippedMin = clippedLast ? minNext : (clippedNext ? minLast : bothMin);
+					const float camSpaceClippedMax = clippedLast ? maxNext : (clippedNext ? maxLast : bothMax);
+
+					const int writableMinPixel = f2i_floor(camSpaceClippedMin);
+					const int writableMaxPixel = f2i(ceilf(camSpaceClippedMax));
+
+					if (CVX_RARE((clippedLast && clippedNext) || writableMaxPixel < nextFreePixelMin || writableMinPixel > nextFreePixelMax)) {
+						if (COUNT) { return false; }
+						windowClosed = true; // (rendering build: no early return out of the lambda -- the element loop below gets nothing to do)
+					}
+					if (writableMinPixel > nextFreePixelMin) {
+						nextFreePixelMin = scan_up(seen, sshift, writableMinPixel, omax);
+					}
+					if (writableMaxPixel < nextFreePixelMax) {
+						nextFreePixelMax = scan_down(seen, sshift, writableMaxPixel, omin);
+					}
+					if (COUNT && nextFreePixelMin > nextFreePixelMax) {
+						return false; // :419 (the rendering build notices at the end of the column)
+					}
+				}
+				return true;
+			};
 			{
 				const auto straddle = [&](f3 pMin, f3 pMax) { return ((int)!(pMin.x > pMin.z * frustumBoundsMax) & (int)(pMin.x < pMin.z * frustumBoundsMin) & (int)(pMax.x > pMax.z * frustumBoundsMax)) != 0; };
 				const bool both = ((int)straddle(camSpaceMinLast, camSpaceMaxLast) & (int)straddle(camSpaceMinNext, camSpaceMaxNext)) != 0;
 				// Round 5: when EVERY lane that clips here sees the column's foot below and its top above the window at both ends -- clip_world_bounds' straddle case, the
 				// ordinary view of a world column -- the four lerps are its clip_min against frustumBoundsMin and clip_max against frustumBoundsMax, nothing is
 				// clipped away, and the wave skips the selects and the flag algebra of the general form (same divisions on the same operands: -0.9 %)
+				bool goesOn;
 				if (__ballot(!both) == 0ull) {
-					clipLastMinLerp = clip_min(camSpaceMinLast, camSpaceMaxLast, invFrustumMin);
-					clipLastMaxLerp = clip_max(camSpaceMinLast, camSpaceMaxLast, invFrustumMax);
-					clipNextMinLerp = clip_min(camSpaceMinNext, camSpaceMaxNext, invFrustumMin);
-					clipNextMaxLerp = clip_max(camSpaceMinNext, camSpaceMaxNext, invFrustumMax);
-					clippedLast = clippedNext = false;
-					straddlesLast = straddlesNext = true;
+					CVX_COUNT(13);
+					goesOn = clipTail(std::true_type{}, clip_min(camSpaceMinLast, camSpaceMaxLast, invFrustumMin), clip_max(camSpaceMinLast, camSpaceMaxLast, invFrustumMax),
+					                  clip_min(camSpaceMinNext, camSpaceMaxNext, invFrustumMin), clip_max(camSpaceMinNext, camSpaceMaxNext, invFrustumMax), false, false);
 				} else {
-					clippedLast = clip_world_bounds(camSpaceMinLast, camSpaceMaxLast, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipLastMinLerp, clipLastMaxLerp, straddlesLast);
-					clippedNext = clip_world_bounds(camSpaceMinNext, camSpaceMaxNext, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipNextMinLerp, clipNextMaxLerp, straddlesNext);
+					CVX_COUNT(14);
+					if (both) { CVX_COUNT(15); } // (counting build: the straddling lanes of a wave that holds one that does not -- the lanes that the wave's instance sends down the reference's path)
+					float clipLastMinLerp, clipLastMaxLerp, clipNextMinLerp, clipNextMaxLerp;
+					bool straddlesLast, straddlesNext; // (the tail no longer asks: a wave comes here because some lane does not straddle)
+					const bool clippedLast = clip_world_bounds(camSpaceMinLast, camSpaceMaxLast, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipLastMinLerp, clipLastMaxLerp, straddlesLast);
+					const bool clippedNext = clip_world_bounds(camSpaceMinNext, camSpaceMaxNext, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipNextMinLerp, clipNextMaxLerp, straddlesNext);
+					goesOn = clipTail(std::false_type{}, clipLastMinLerp, clipLastMaxLerp, clipNextMinLerp, clipNextMaxLerp, clippedLast, clippedNext);
 				}
-			}
-
-			// (:297-299 leaves here when both ends are outside the window; that exit is taken together with the next one below --
-			// nothing in between has an effect that survives the end of the ray)
-			// :300-390, the three cases (only Next visible / only Last visible / both) folded into selects: each
-			// bound comes from the Last or the Next intersection, chosen exactly as the reference's branches do.
-			const bool minFromLast = !clippedLast && (clippedNext || clipLastMinLerp < clipNextMinLerp);
-			const bool maxFromLast = !clippedLast && (clippedNext || clipLastMaxLerp > clipNextMaxLerp);
-			worldBoundsMin = m_lerp(0.0f, worldMaxY, minFromLast ? clipLastMinLerp : clipNextMinLerp);
-			worldBoundsMax = m_lerp(0.0f, worldMaxY, maxFromLast ? clipLastMaxLerp : clipNextMaxLerp);
-			frustumDirMinWorld = (worldBoundsMin - posY) / (minFromLast ? curDistLast : curDistNext);
-			frustumDirMaxWorld = (worldBoundsMax - posY) / (maxFromLast ? curDistLast : curDistNext);
-			const f3 minClipA = f3_lerp(camSpaceMinLast, camSpaceMaxLast, clipLastMinLerp);
-			const f3 maxClipA = f3_lerp(camSpaceMinLast, camSpaceMaxLast, clipLastMaxLerp);
-			const f3 minClipB = f3_lerp(camSpaceMinNext, camSpaceMaxNext, clipNextMinLerp);
-			const f3 maxClipB = f3_lerp(camSpaceMinNext, camSpaceMaxNext, clipNextMaxLerp);
-			worldBoundsMin = floorf(worldBoundsMin);
-			worldBoundsMax = ceilf(worldBoundsMax);
-
-			// :337-421 project the four clipped points (x / z), order them, and take floor(min) / ceil(max) as the writable pixel range, which
-			// can end the ray (:399-403) or move nextFreePixelMin / Max inwards (:405-416).  Only those two INTEGERS are ever used.  In the
-			// ordinary case -- both ends straddle the window, so the min points were clipped against frustumBoundsMin = k - 0.501 and the max
-			// points against frustumBoundsMax = m + 0.501 (k <= nextFreePixelMin <= nextFreePixelMax <= m, integers: ReducePixelHorizon :682,694) --
-			// a clipped point lies ON its bound up to rounding.  If the residual |x - f * z| (as computed, error < 2^-23 |f z| <= 0.002 |z|) is
-			// below 0.4 |z|, then x / z = f + r / z lies within 0.402 of f, the correctly rounded quotient too (rounding is monotone), hence
-			// floor(min) = k - 1 and ceil(max) = m + 1 whatever the exact quotients are: min < max (no swap, :339-346), the range contains
-			// [nextFreePixelMin, nextFreePixelMax] (no exit, nothing moves), and neither end was clipped away.  So nothing of :337-421 has any
-			// effect and the four divisions are not needed.  Any lane for which this cannot be shown takes the reference's path below.
-			const auto onBound = [](f3 p, float f) { return fabsf(p.x - f * p.z) < 0.4f * fabsf(p.z); };
-			// (`&`, not `&&`: six short tests evaluated straight-line instead of a chain of divergent branches)
-			const bool windowUntouched = !COUNT && ((int)straddlesLast & (int)straddlesNext & (int)onBound(minClipA, frustumBoundsMin) & (int)onBound(minClipB, frustumBoundsMin) &
-			                                        (int)onBound(maxClipA, frustumBoundsMax) & (int)onBound(maxClipB, frustumBoundsMax)) != 0;
-			if (!CVX_USUAL(windowUntouched)) {
-				float minNext = minClipB.x / minClipB.z;
-				float minLast = minClipA.x / minClipA.z;
-				float maxNext = maxClipB.x / maxClipB.z;
-				float maxLast = maxClipA.x / maxClipA.z;
-				if (maxNext < minNext) { float t = maxNext; maxNext = minNext; minNext = t; }
-				if (maxLast < minLast) { float t = maxLast; maxLast = minLast; minLast = t; }
-				// (hw_min / hw_max: the results only go through floor / ceil and (int), which map -0 and +0 to the same 0)
-				const float bothMin = hw_min(minLast, minNext), bothMax = hw_max(maxLast, maxNext); // (computed ahead of the selects: an asm inside a select becomes a branch)
-				const float camSpaceClippedMin = clippedLast ? minNext : (clippedNext ? minLast : bothMin);
-				const float camSpaceClippedMax = clippedLast ? maxNext : (clippedNext ? maxLast : bothMax);
-
-				const int writableMinPixel = f2i_floor(camSpaceClippedMin);
-				const int writableMaxPixel = f2i(ceilf(camSpaceClippedMax));
-
-				if (CVX_RARE((clippedLast && clippedNext) || writableMaxPixel < nextFreePixelMin || writableMinPixel > nextFreePixelMax)) {
-					if (COUNT) { return false; }
-					windowClosed = true; // (rendering build: no early return out of the lambda -- the element loop below gets nothing to do)
-				}
-				if (writableMinPixel > nextFreePixelMin) {
-					nextFreePixelMin = scan_up(seen, sshift, writableMinPixel, omax);
-				}
-				if (writableMaxPixel < nextFreePixelMax) {
-					nextFreePixelMax = scan_down(seen, sshift, writableMaxPixel, omin);
-				}
-				if (COUNT && nextFreePixelMin > nextFreePixelMax) {
-					return false; // :419 (the rendering build notices at the end of the column)
-				}
+				if (COUNT && !goesOn) { return false; }
 			}
 		}
 
