@@ -1366,8 +1366,20 @@ __global__ void copy_rows_kernel(uint4 *__restrict__ poolTD, uint4 *__restrict__
 //     A1 = (q.y - a.y) * inv, B1 = (a.x - q.x) * inv      (weight of MaxScreen)
 // and a pixel centre c evaluates two edge functions per segment, no division:
 //     wVp = A0 * (c.x - q.x) + B0 * (c.y - q.y),  wMax = A1 * (c.x - q.x) + B1 * (c.y - q.y),  wMin = 1 - wVp - wMax
-// first segment whose weights are all >= 0 wins; x = wMax / (wMax + wMin) (uv.x / (uv.x + uv.y), RayBufferBlit.shader:56);
+// first segment (with rays) whose weights are all >= 0 wins; x = wMax / (wMax + wMin) (uv.x / (uv.x + uv.y), RayBufferBlit.shader:56);
 // ray = clamp(floor(x * RayCount), 0, RayCount - 1).
+// Seam rule: two neighbouring triangles share the edge from the VP to a screen corner, and at a pixel centre ON that edge the exact weight of both is 0.
+// Rounded, it can come out below 0 for both (camera roll 45: the seam is a line y = x + c through one pixel centre per row), and a rasteriser gives
+// such a pixel to exactly one triangle, not to none.  So a pixel that no segment claims goes to the segment with rays whose smallest weight is
+// largest (the first of equals), provided all its weights are >= -eps; otherwise it keeps clearColor (a segment without rays covers it).
+//     eps = CVX_BLIT_SEAM_EPS * ((|A0 dx| + |B0 dy|) + (|A1 dx| + |B1 dy|) + 1),   dx = c.x - q.x, dy = c.y - q.y
+// The bracket bounds the magnitudes that enter the three weights.  Each factor carries a few roundings of 2^-24 (dx, dy: one; a coefficient: a
+// difference, the product with inv, and inv's own chain of differences, products, sum and division, about six), each product and each sum one more,
+// wMin two more: a computed weight lies within about 10 * 2^-24 of the bracket from the exact one.  CVX_BLIT_SEAM_EPS = 2^-20 = 16 * 2^-24 leaves room
+// above that and stays far below what decides anything else: with the products bounded by 1000 as the block-owner shortcut requires
+// (blit_block), eps < 4e-3 at the very worst and ~1e-6 on ordinary frames (brackets of 1 .. 10), against 1e-4 of a weight the tests take as
+// "away from every boundary".  (A den that cancels -- a triangle thinner than float32 resolves -- scales wVp and wMax alike and is not covered;
+// such a triangle holds no pixel centre.)  The rule runs only for pixels the search left unclaimed.
 // ---------------------------------------------------------------------------
 struct BlitParams {
 	float qx[4], qy[4];                 // MinScreen
@@ -1394,6 +1406,7 @@ __device__ __forceinline__ int blit_ray(int rc, float wMax, float wMin)
 	return (rf == rf) ? (int)rf : 0;
 }
 // Which segment owns pixel (px, py) and which ray of it: segment 0..3 (-1: none) and the ray index.
+#define CVX_BLIT_SEAM_EPS 9.5367431640625e-7f // 2^-20, see above
 __device__ __forceinline__ int blit_classify(const BlitParams &p, int px, int py, int &ray)
 {
 	ray = 0;
@@ -1410,7 +1423,27 @@ __device__ __forceinline__ int blit_classify(const BlitParams &p, int px, int py
 			return s;
 		}
 	}
-	return -1;
+	// seam rule (only pixels without a claim get here)
+	int best = -1;
+	float bestLow = -INFINITY;
+#pragma unroll
+	for (int s = 0; s < 4; s++) {
+		const int rc = p.rayCount[s];
+		if (rc <= 0) {
+			continue;
+		}
+		float wVp, wMax, wMin;
+		blit_weights(p, s, px, py, wVp, wMax, wMin);
+		const float dx = ((float)px + 0.5f) - p.qx[s], dy = ((float)py + 0.5f) - p.qy[s];
+		const float eps = ((fabsf(p.a0[s] * dx) + fabsf(p.b0[s] * dy)) + (fabsf(p.a1[s] * dx) + fabsf(p.b1[s] * dy)) + 1.0f) * CVX_BLIT_SEAM_EPS;
+		const float low = fminf(fminf(wVp, wMax), wMin);
+		if (wVp >= -eps && wMax >= -eps && wMin >= -eps && low > bestLow) { // (false for NaN)
+			best = s;
+			bestLow = low;
+			ray = blit_ray(rc, wMax, wMin);
+		}
+	}
+	return best;
 }
 __device__ __forceinline__ uint32_t blit_fetch_td(const uint32_t *__restrict__ poolTD, const BlitParams &p, int s, int ray, int py)
 {
@@ -1432,7 +1465,8 @@ __device__ __forceinline__ uint32_t blit_fetch_lr(const uint32_t *__restrict__ p
 //   weights of s are >= 1e-3 and for every earlier segment one and the same weight is <= -1e-3 (or it has no rays): the weights are
 //   linear in the pixel position up to rounding (|products| < 1000 is checked, so a computed weight is within ~1e-4 of the exact linear
 //   form), hence inside the block all weights of s stay > 0 and that weight of each earlier segment stays < 0 -- the search would pick
-//   s for every pixel.  Any other block searches per pixel.  Same pixels either way.
+//   s for every pixel.  Any other block searches per pixel.  Same pixels either way.  (The seam rule of blit_classify changes nothing here: an owned
+//   block's pixels are claimed by the search itself, weights > 0, so the rule never reaches them.)
 #define CVX_BLIT_TILE 64
 // TH = rows per workgroup: 64 for a batch of frames (a 64 x 64 block: longest contiguous raybuffer spans either way), 16 for a single
 // frame (four times the workgroups: one 1080p frame alone is only 510 blocks of 64 x 64 on a chip with 256 CUs)

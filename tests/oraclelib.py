@@ -180,20 +180,26 @@ def draw_segments_events(world_set, frame, width: int, height: int, threads: int
     return td, lr, cnt, ev
 
 
-def blit_reference(frame, td: np.ndarray, lr: np.ndarray, width: int, height: int, clear: int = 0) -> np.ndarray:
-    """Phase-2 rule (RenderManager.BlitSegments RenderManager.cs:199-256 +
-    RayBufferBlit.shader:48-64) evaluated at pixel centres, numpy.
+BLIT_SEAM_EPS = np.float32(2.0 ** -20)  # eps of the seam rule per unit of weight magnitude (CVX_BLIT_SEAM_EPS, cvx_kernels.h)
+
+
+def blit_classify_reference(frame, width: int, height: int, seam: bool = True):
+    """blit_classify of cvx_kernels.h at every pixel centre, numpy, the same float32 operations in the same order.
 
     For segment s with triangle (VP = a, MaxScreen = b, MinScreen = q): per-frame edge functions
     inv = 1 / den, A0 = (b.y - q.y) inv, B0 = (q.x - b.x) inv, A1 = (q.y - a.y) inv, B1 = (a.x - q.x) inv (float32),
     per pixel centre c: w_vp = A0 (c.x - q.x) + B0 (c.y - q.y), w_max = A1 (c.x - q.x) + B1 (c.y - q.y),
-    w_min = 1 - w_vp - w_max (the same float32 operations, in the same order, as blit_pixel in cvx_kernels.h); inside when all >= 0;
-    x = w_max / (w_max + w_min); ray = min(floor(x * RayCount), RayCount-1);
-    colour = raybuffer[ray + offset][screen y (segments 0,1) or screen x (2,3)].
-    Returns image[H, W] uint32, row 0 = bottom (Unity screen space).
-    """
-    img = np.full((height, width), clear, dtype=np.uint32)
-    done = np.zeros((height, width), dtype=bool)
+    w_min = 1 - w_vp - w_max; the first segment with rays whose weights are all >= 0 claims the pixel.
+    Seam rule (seam=True; False is the rule as it was before it, kept for the tests that show what it repairs): a pixel no segment claims goes
+    to the segment with rays whose smallest weight is largest (the first of equals), provided every weight of it is >= -eps with
+    eps = 2^-20 ((|A0 dx| + |B0 dy|) + (|A1 dx| + |B1 dy|) + 1); otherwise to none.
+    x = w_max / (w_max + w_min); ray = min(max(floor(x * RayCount), 0), RayCount - 1) (0 for NaN).
+    Returns (segment[H, W] int64, -1 = none; ray[H, W] int64)."""
+    owner = np.full((height, width), -1, dtype=np.int64)
+    rays = np.zeros((height, width), dtype=np.int64)
+    best = np.full((height, width), -np.inf, dtype=np.float32)
+    near = np.full((height, width), -1, dtype=np.int64)   # seam rule: candidate segment and its ray
+    near_ray = np.zeros((height, width), dtype=np.int64)
     ys, xs = np.mgrid[0:height, 0:width]
     cx = xs.astype(np.float32) + np.float32(0.5)
     cy = ys.astype(np.float32) + np.float32(0.5)
@@ -206,8 +212,8 @@ def blit_reference(frame, td: np.ndarray, lr: np.ndarray, width: int, height: in
         ax, ay = vpx, vpy
         bx, by = np.float32(seg.MaxScreen[0]), np.float32(seg.MaxScreen[1])
         qx, qy = np.float32(seg.MinScreen[0]), np.float32(seg.MinScreen[1])
-        den = (by - qy) * (ax - qx) + (qx - bx) * (ay - qy)
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            den = (by - qy) * (ax - qx) + (qx - bx) * (ay - qy)
             inv = np.float32(1.0) / den
             a0, b0 = (by - qy) * inv, (qx - bx) * inv
             a1, b1 = (qy - ay) * inv, (ax - qx) * inv
@@ -215,23 +221,47 @@ def blit_reference(frame, td: np.ndarray, lr: np.ndarray, width: int, height: in
             w_vp = a0 * dx + b0 * dy
             w_max = a1 * dx + b1 * dy
             w_min = np.float32(1.0) - w_vp - w_max
-        inside = (w_vp >= 0) & (w_max >= 0) & (w_min >= 0) & ~done
-        with np.errstate(divide="ignore", invalid="ignore"):
             x = w_max / (w_max + w_min)
-        ray = np.clip(np.floor(x * np.float32(rcount)), 0, rcount - 1)
-        ray = np.where(np.isfinite(ray), ray, 0).astype(np.int64)
-        offset = 0
-        if s == 1:
-            offset = frame.segments[0].RayCount
-        if s == 3:
-            offset = frame.segments[2].RayCount
-        if s < 2:
-            vals = td[np.clip(ray + offset, 0, td.shape[0] - 1), ys]
-        else:
-            vals = lr[np.clip(ray + offset, 0, lr.shape[0] - 1), xs]
-        img[inside] = vals[inside]
-        done |= inside
+            ray = np.clip(np.floor(x * np.float32(rcount)), 0, rcount - 1)
+            ray = np.where(np.isfinite(ray), ray, 0).astype(np.int64)
+            inside = (w_vp >= 0) & (w_max >= 0) & (w_min >= 0) & (owner < 0)
+            owner[inside] = s
+            rays[inside] = ray[inside]
+            if seam:
+                eps = ((np.abs(a0 * dx) + np.abs(b0 * dy)) + (np.abs(a1 * dx) + np.abs(b1 * dy)) + np.float32(1.0)) * BLIT_SEAM_EPS
+                low = np.fmin(np.fmin(w_vp, w_max), w_min)
+                cand = (w_vp >= -eps) & (w_max >= -eps) & (w_min >= -eps) & (low > best)
+                best = np.where(cand, low, best)
+                near[cand] = s
+                near_ray[cand] = ray[cand]
+    fill = (owner < 0) & (near >= 0)
+    owner[fill] = near[fill]
+    rays[fill] = near_ray[fill]
+    return owner, rays
+
+
+def blit_gather_reference(frame, owner, rays, td: np.ndarray, lr: np.ndarray, clear: int = 0) -> np.ndarray:
+    """The image of a classification: colour = raybuffer[ray + offset][screen y (segments 0, 1) or screen x (2, 3)], `clear` where no segment owns."""
+    height, width = owner.shape
+    ys, xs = np.mgrid[0:height, 0:width]
+    img = np.full((height, width), clear, dtype=np.uint32)
+    for s in range(4):
+        m = owner == s
+        if not m.any():
+            continue
+        offset = frame.segments[0].RayCount if s == 1 else (frame.segments[2].RayCount if s == 3 else 0)
+        buf, pix = (td, ys) if s < 2 else (lr, xs)
+        img[m] = buf[np.clip(rays[m] + offset, 0, buf.shape[0] - 1), pix[m]]
     return img
+
+
+def blit_reference(frame, td: np.ndarray, lr: np.ndarray, width: int, height: int, clear: int = 0, seam: bool = True) -> np.ndarray:
+    """Phase-2 rule (RenderManager.BlitSegments RenderManager.cs:199-256 +
+    RayBufferBlit.shader:48-64) evaluated at pixel centres, numpy: blit_classify_reference (the kernel's blit_classify, float32 operation by
+    operation, the seam rule included) and the raybuffer pixel it selects.
+    Returns image[H, W] uint32, row 0 = bottom (Unity screen space)."""
+    owner, rays = blit_classify_reference(frame, width, height, seam)
+    return blit_gather_reference(frame, owner, rays, td, lr, clear)
 
 
 def blit_reference_f64(frame, td: np.ndarray, lr: np.ndarray, width: int, height: int, clear: int = 0):

@@ -243,61 +243,7 @@ def test_sharded_render_covers_every_tile_once(contexts):
         assert (acc[0] == full[0]).all() and (acc[1] == full[1]).all(), f"the shards' union differs from the unsharded draw [{label}]"
 
 
-def test_blit_matches_pixel_centre_rule(contexts):
-    for name in ("mill256_t075", "mill256_t09_roll", "proc256_t0_lod8"):
-        ws, fr, W, H = scenes.scene_frame(name)
-        ctx = contexts(scenes.SCENES[name][0], W, H)
-        for label, mode in BOTH_KERNELS:
-            g_td, g_lr = _render_gpu(ctx, fr, latency=mode)
-            img = ctx.blit_segments(0)
-            ref = O.blit_reference(fr, g_td, g_lr, W, H, clear=0)
-            assert (img == ref).all(), f"{name} [{label}]: {(img != ref).sum()} screen pixels differ"
-            # ... and an independent check (float64 barycentrics, none of the kernel's edge-function arithmetic): the images may differ only where a
-            # weight or a ray coordinate lies within rounding distance of a boundary, and those pixels are a sliver of the screen
-            ref64, margin = O.blit_reference_f64(fr, g_td, g_lr, W, H, clear=0)
-            differ = img != ref64
-            assert not (differ & (margin > 1e-4)).any(), f"{name} [{label}]: {(differ & (margin > 1e-4)).sum()} pixels away from every boundary differ from the float64 rule"
-            assert differ.mean() < 2e-3, f"{name} [{label}]: {differ.sum()} pixels differ from the float64 rule"
-
-
-def test_batch_blit_equals_single_blits():
-    """cvx_blit_segments_batch (Phase 2 of a whole batch in one launch, images left on the device) == cvx_blit_segments frame by frame,
-    both into a caller's device buffer (a torch tensor) and into the array the context owns."""
-    import torch
-
-    names = ["proc256_t0_lod8", "proc256_t04_lod8", "proc256_t075_lod8", "proc256_t075_lod1"]  # one world, one resolution
-    frames = []
-    for n in names:
-        ws, fr, W, H = scenes.scene_frame(n)
-        frames.append(fr)
-    ctx = gpu.Context(0, buffer_count=len(frames) + 1)
-    try:
-        ctx.upload_world(ws)
-        ctx.set_resolution(W, H)
-        for b in range(len(frames) + 1):
-            ctx.clear_raybuffers(b, 0)
-        ctx.draw_segments_batch(frames, 1)  # buffers 1 .. n
-        singles = [ctx.blit_segments(1 + i) for i in range(len(frames))]
-        dst = torch.zeros((len(frames), H, W), dtype=torch.int32, device="cuda:0")
-        p = ctx.blit_segments_batch(1, len(frames), dst.data_ptr())
-        assert p == dst.data_ptr()
-        ctx.synchronize()
-        got = dst.cpu().numpy().view(np.uint32)
-        for i, n in enumerate(names):
-            assert (got[i] == singles[i]).all(), f"{n}: batch blit differs from the single blit in {(got[i] != singles[i]).sum()} pixels"
-            td = ctx.read_raybuffer(1 + i, gpu.RAYBUFFER_TOPDOWN)
-            lr = ctx.read_raybuffer(1 + i, gpu.RAYBUFFER_LEFTRIGHT)
-            assert (got[i] == O.blit_reference(frames[i], td, lr, W, H, clear=0)).all(), n
-        # context-owned image array: same pixels (read back through a torch view of the returned address is not possible, so blit a
-        # sub-range twice and compare the two device arrays on the device)
-        own = ctx.blit_segments_batch(2, 2)
-        assert own and own != dst.data_ptr()
-        with pytest.raises(RuntimeError):
-            ctx.blit_segments_batch(1, len(frames) + 1)  # past the last buffer
-        with pytest.raises(RuntimeError):
-            ctx.blit_segments_batch(0, 1)                # buffer 0 was never drawn into
-    finally:
-        ctx.close()
+# (the blit tests -- test_blit_matches_pixel_centre_rule, test_batch_blit_equals_single_blits -- live in tests/test_gpu_blit.py)
 
 
 @pytest.mark.parametrize("name", ["mill256", "proc256", "proc128x512x64", "proc64x4096x32"])  # the last: occupied spans taller than one LDS chunk

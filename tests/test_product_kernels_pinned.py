@@ -46,8 +46,8 @@ def _kernels(lib, work):
             s = line.split("//")[0].strip()
             if name is not None and s and not s.startswith("Disassembly") and not s.endswith("file format elf64-amdgpu"):
                 out[name].append(s)
-    for code in out.values():  # (alignment padding behind a function's last instruction is not code)
-        while code and (code[-1].startswith("s_nop") or code[-1].startswith("s_code_end")):
+    for code in out.values():  # (alignment padding behind a function's last instruction is not code; "..." is llvm-objdump's line for a run of zero bytes in it)
+        while code and (code[-1].startswith("s_nop") or code[-1].startswith("s_code_end") or code[-1] == "..."):
             code.pop()
     return out
 
