@@ -515,7 +515,8 @@ int BuildLodChainDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t elementsO
 		CVX_CH(hipMalloc((void **)&l.dElements, (size_t)elementBound * sizeof(uint32_t)));
 		CVX_CH(hipMemsetAsync(l.dHeaders, 0, (size_t)l.allocatedColumns * 12, ctx->stream));
 	}
-	for (int i = 0; i < 2 && i < levelCount - 1; i++) { CVX_CH(hipMalloc((void **)&dSums[i], (size_t)elementBound * sizeof(cvxk::SumVoxel))); }
+	// (level j < levelCount emits its sums into dSums[j & 1]: a chain of two levels needs dSums[1] alone)
+	for (int j = 1; j <= 2 && j < levelCount; j++) { CVX_CH(hipMalloc((void **)&dSums[j & 1], (size_t)elementBound * sizeof(cvxk::SumVoxel))); }
 	CVX_CH(hipMalloc((void **)&dScalars, (size_t)levelCount * 3 * sizeof(unsigned long long)));
 	CVX_CH(hipMemsetAsync(dScalars, 0, (size_t)levelCount * 3 * sizeof(unsigned long long), ctx->stream));
 	CVX_CH(hipEventCreate(&evBegin));

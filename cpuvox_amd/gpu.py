@@ -32,7 +32,7 @@ EXPORTS = [
     "cvx_get_raybuffer_layout", "cvx_version", "cvx_bind_raybuffers", "cvx_draw_time_stats", "cvx_copy_rows", "cvx_draw_segments_placed",
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
-    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy",
+    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -63,6 +63,8 @@ SHAPE_BOX, SHAPE_SPHERE = 0, 1                  # cvx_brush_stroke.shape
 BRUSH_MAX_STROKES = 4096
 COPY_REPLACE = 3                                # cvx_copy_placement.op, besides BRUSH_FILL / CARVE / PAINT
 COPY_MAX_PLACEMENTS = 1024
+PIECES_REPORT, PIECES_REMOVE = 0, 1              # cvx_world_pieces: op
+ANCHOR_GROUND, ANCHOR_OUTSIDE, ANCHOR_LARGEST = 1, 2, 4  # ... anchors (bits)
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
 
@@ -83,6 +85,14 @@ class CopyPlacement(C.Structure):
                 ("move", C.c_int32)]
 
 
+class Piece(C.Structure):  # cvx_piece
+    _fields_ = [("min", C.c_int32 * 3), ("max", C.c_int32 * 3), ("seed", C.c_int32 * 3), ("pad_", C.c_int32), ("voxels", C.c_int64)]
+
+
+class PiecesSummary(C.Structure):  # cvx_pieces_summary
+    _fields_ = [("floatingPieces", C.c_int64), ("floatingVoxels", C.c_int64), ("anchoredPieces", C.c_int64), ("anchoredVoxels", C.c_int64)]
+
+
 class _TextureStruct(C.Structure):  # cvx_mesh_texture
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
 
@@ -95,6 +105,8 @@ MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", 
 STAMP_MAX_MATERIALS = 128
 COPY_PLACEMENT_DTYPE = np.dtype([("srcMin", "<i4", 3), ("srcMax", "<i4", 3), ("dst", "<i4", 3), ("transform", "<i4"), ("op", "<i4"),
                                  ("move", "<i4")])  # cvx_copy_placement
+PIECE_DTYPE = np.dtype([("min", "<i4", 3), ("max", "<i4", 3), ("seed", "<i4", 3), ("pad_", "<i4"), ("voxels", "<i8")])  # cvx_piece
+PIECES_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("anchoredPieces", "<i8"), ("anchoredVoxels", "<i8")])
 
 
 def strokes_array(strokes) -> np.ndarray:
@@ -252,6 +264,7 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_stamp_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_float)]
         L.cvx_world_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.cvx_world_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -436,6 +449,21 @@ class Context:
         ms = C.c_float()
         self._check(lib().cvx_world_copy(self._h, arr.ctypes.data if arr.size else None, arr.size, level_count, C.byref(ms)))
         return ms.value
+
+    def world_pieces(self, box_min, box_max, anchors: int, op: int = PIECES_REPORT, level_count: int = LOD_LEVELS - 1, capacity: int = 1024):
+        """The connected pieces (face contact) of the solid LOD-0 voxels inside [box_min, box_max) that none of the `anchors` bits (ANCHOR_GROUND /
+        ANCHOR_OUTSIDE / ANCHOR_LARGEST) holds: (the first `capacity` floating pieces as a PIECE_DTYPE array in seed order, the four totals
+        as a dict, device milliseconds).  op = PIECES_REMOVE turns all of them into air and rebuilds LOD 1..level_count over their footprint."""
+        lo, hi = np.ascontiguousarray(box_min, dtype=np.int32), np.ascontiguousarray(box_max, dtype=np.int32)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("world_pieces: box_min and box_max are three integers each")
+        out = np.zeros(max(int(capacity), 0), dtype=PIECE_DTYPE)
+        summary = np.zeros(1, dtype=PIECES_SUMMARY_DTYPE)
+        ms = C.c_float()
+        self._check(lib().cvx_world_pieces(self._h, lo.ctypes.data, hi.ctypes.data, anchors, op, level_count, out.ctypes.data if out.size else None,
+                                           int(capacity), summary.ctypes.data, C.byref(ms)))
+        totals = {name: int(summary[0][name]) for name in PIECES_SUMMARY_DTYPE.names}
+        return out[:min(out.size, totals["floatingPieces"])].copy(), totals, ms.value
 
     def pick(self, origins, directions, max_t):
         """First solid LOD-0 voxel along each ray -> (voxel int32[N, 3], face int32[N], argb uint32[N], t float32[N]).  max_t: a scalar or

@@ -99,6 +99,24 @@ namespace CpuVox.Gpu
 		public byte* Rgba;
 	}
 
+	// cvx_world_pieces: one floating piece (48 bytes): bounding box [Min, Max) in LOD-0 voxels, its first voxel in (x, z, descending y) order, its voxels
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public unsafe struct Piece
+	{
+		public fixed int Min[3];
+		public fixed int Max[3];
+		public fixed int Seed[3];
+		public int Pad;
+		public long Voxels;
+	}
+
+	// cvx_world_pieces: the totals (32 bytes)
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public struct PiecesSummary
+	{
+		public long FloatingPieces, FloatingVoxels, AnchoredPieces, AnchoredVoxels;
+	}
+
 	// cvx_world_copy: one placement (48 bytes).  Source box [SrcMin, SrcMax) in LOD-0 voxels, destination min corner Dst; Transform bits 0-1 quarter
 	// turns, bit 2 mirror X (before turning), bit 3 flip Y; Op: 0 fill, 1 carve, 2 paint, 3 replace; Move 1: the source box becomes air
 	[StructLayout(LayoutKind.Sequential, Pack = 4)]
@@ -166,6 +184,9 @@ namespace CpuVox.Gpu
 		                                                               MeshTexture* materials, int materialCount, int op, int levelCount, out float outDeviceMs);
 		// boxes of voxels copied, moved, turned or mirrored inside LOD 0 (every read from the world before the call) + its LOD refresh
 		[DllImport(Lib)] public static extern int cvx_world_copy(IntPtr ctx, CopyPlacement* placements, int placementCount, int levelCount, out float outDeviceMs);
+		// the pieces of LOD 0 inside a box that nothing anchors (anchors: 1 ground, 2 outside the box, 4 the largest; op 0 report, 1 remove + LOD refresh)
+		[DllImport(Lib)] public static extern int cvx_world_pieces(IntPtr ctx, int* boxMin, int* boxMax, int anchors, int op, int levelCount, Piece* pieces,
+		                                                           int pieceCapacity, PiecesSummary* summary, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

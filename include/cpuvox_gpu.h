@@ -481,6 +481,45 @@ typedef struct cvx_copy_placement { /* 48 bytes */
 } cvx_copy_placement;
 int cvx_world_copy(cvx_context *ctx, const cvx_copy_placement *placements, int placementCount, int levelCount, float *outDeviceMs);
 
+/* ---- finding and removing the floating pieces of the uploaded world ----------------------------------------------------------------------
+ * cvx_world_pieces: what a carve or a move has cut loose.  The voxels considered are the solid voxels of LOD 0 inside [boxMin, boxMax) after
+ * clipping the box to the world (coordinates address the stored tile: a repeating world does not wrap them).  Two of them are connected when
+ * they share a FACE (edge and corner contact does not connect); a piece is a connected component.  A piece is ANCHORED by the bits of `anchors`
+ * (any combination; 0: nothing is anchored): CVX_ANCHOR_GROUND, it holds a voxel with y = 0; CVX_ANCHOR_OUTSIDE, it holds a voxel with a solid
+ * face neighbour inside the world but outside the clipped box (a box cut out of a larger structure does not report the structure);
+ * CVX_ANCHOR_LARGEST, it is the piece with the most voxels (ties: the earlier one in the order below).  Every other piece is FLOATING.
+ * Order: a piece's seed is its voxel in its first column in (x, then z) order and, in that column, the highest y.  The floating pieces are listed
+ * by ascending seed x, then ascending z, then DESCENDING y; the list does not depend on scheduling: the same world gives the same bytes.
+ * `summary` (may be NULL) receives all four totals; `pieces` (may be NULL iff pieceCapacity = 0) the first min(pieceCapacity, floatingPieces)
+ * floating pieces; a smaller capacity is not an error.
+ * CVX_PIECES_REPORT never changes the world.  CVX_PIECES_REMOVE turns every voxel of every floating piece (whatever the capacity) into air
+ * through cvx_world_edit's machinery like a brush: the rectangle is the XZ bounding box of the floating pieces rounded outward to multiples of
+ * 2^levelCount and clipped to the world, LOD 1 .. levelCount (0 .. 5) are rebuilt over it, and columns of it that lose nothing are re-encoded
+ * with the builder's rule (unchanged for every world the builder made).  No floating piece: CVX_OK, nothing changes.  outDeviceMs (may be
+ * NULL): device time of the analysis and, for a REMOVE that removes something, the edit.
+ * Ordering, atomicity and several GPUs as cvx_world_brush: the call is ordered on the context's stream behind everything enqueued before it,
+ * returns when the results are on the host, every error leaves the world as it was, and every rank makes the same call on its own context.
+ * CVX_ERR_INVALID_ARGUMENT: a NULL box, boxMin >= boxMax on an axis, a box wholly outside the world, unknown anchors bits or op, levelCount
+ * outside 0 .. 5, a negative pieceCapacity, pieces NULL with a capacity above 0; CVX_ERR_NOT_READY: LOD 0 has not been uploaded;
+ * CVX_ERR_CAPACITY: the scratch does not fit in device memory, the box holds 2^31 or more columns or solid runs, and on REMOVE the limits of
+ * cvx_world_brush.  Device memory while it runs: 8 bytes per column of the clipped box and 64 bytes per solid run of LOD 0 inside it (its
+ * interval, column and label, and the totals, box and anchor bits of the piece it may be the seed of), plus 48 bytes per listed piece; a REMOVE
+ * adds cvx_world_brush's scratch for its rectangle. */
+enum { CVX_PIECES_REPORT = 0, CVX_PIECES_REMOVE = 1 };
+enum { CVX_ANCHOR_GROUND = 1, CVX_ANCHOR_OUTSIDE = 2, CVX_ANCHOR_LARGEST = 4 };
+typedef struct cvx_piece { /* 48 bytes */
+	int32_t min[3];  /* bounding box in LOD-0 voxels, inclusive */
+	int32_t max[3];  /* exclusive */
+	int32_t seed[3]; /* the piece's first voxel in the order above */
+	int32_t pad_;
+	int64_t voxels;
+} cvx_piece;
+typedef struct cvx_pieces_summary { /* 32 bytes */
+	int64_t floatingPieces, floatingVoxels, anchoredPieces, anchoredVoxels;
+} cvx_pieces_summary;
+int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, int op, int levelCount, cvx_piece *pieces,
+                     int pieceCapacity, cvx_pieces_summary *summary, float *outDeviceMs);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
