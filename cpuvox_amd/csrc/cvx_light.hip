@@ -1,0 +1,343 @@
+// cvx_light.hip -- libcpuvox_gpu.so, sky occlusion and sun shadows baked into the device-resident world (cvx_world_light).  See
+// include/cpuvox_gpu.h for the contract, cvx_light.h for the rules and DESIGN.md sections 3 and 4.
+//
+// The mechanics are cvx_world_brush's: count the elements of every column of the rounded rectangle, scan, write the sub-world blob in the
+// builder's encoding (cvxb::LightColumn: the colours verbatim), then -- new -- shade the blob's colours in place, then cvxi::EditFromDevice.
+// Nothing in the arena is written before that last step, and the blob has one colour per voxel, so runs that share colour slots are shaded once.
+//
+// The shade kernel (light_brick_kernel): a workgroup of 256 threads owns a tile of 16 x 16 columns of the clipped box and walks the y range its
+// columns have solid voxels in, 32 voxels (a slab) at a time:
+//   1. expand   the occupancy of the tile plus a halo of skyRange columns, y = slab .. slab + 63, into LDS: ONE 64-bit word per column (bit b =
+//               voxel slab + b), rows padded to an odd number of words.  The sky term of a voxel of the slab reaches at most skyRange <= 32 voxels
+//               sideways and upwards: all of it is in the brick.
+//   2. compact  every thread counts the solid voxels of its column inside the slab and the box (a popcount), a block-wide exclusive scan (wave
+//               shuffles, then the four wave totals) numbers them, and the voxels are written to a list in LDS, 2048 at a time
+//   3. shade    a LANE PER SOLID VOXEL: the 17 sky directions are word reads and bit tests in LDS; the sun's face neighbours and shadow walk
+//               read LDS while they are inside the brick and the arena's records (cvxb::ArenaOcc) beyond it; the voxel's colour in the blob (the
+//               column's colour base + the solid voxels above it: a popcount of its word + the count above the slab) is read, shaded, written.
+// -DCVX_LIGHT_RECORDS builds the straightforward variant instead (make variant NAME=lightrec DEFS=-DCVX_LIGHT_RECORDS): no brick kernel, the
+// write kernel shades every voxel as it emits it, every occupancy test a record fetch and a run search.  It is the A/B partner of
+// tools/light_bench.py and a second implementation for tests/test_gpu_world_light.py.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+
+#include "cvx_context.h"
+#include "cvx_light.h"
+
+using cvxi::Fail;
+
+namespace cvxlight {
+
+struct LightArgs {
+	cvxb::CopyWorld W;
+	cvxb::PiecesBox B;             // the clipped box
+	cvx_light_params P;
+	int x0, z0, sizeZ, n;          // the rectangle
+	uint32_t *counts;              // per column: elements (-> offset after the scan)
+	unsigned int *overLimit;
+	uint32_t *headers;             // the sub-world blob, n headers of 3 words
+	uint32_t *elements;
+	int tilesZ, brickSide, brickStride; // brick kernel: tiles per row of the box, columns per side of the brick, words per row
+};
+
+template <class Recolour>
+__device__ __forceinline__ void WriteColumn(const LightArgs &A, int i, int cx, int cz, const Recolour &recolour)
+{
+	const uint32_t off = A.counts[i];
+	uint32_t *e = A.elements + off;
+	uint32_t *h = A.headers + 3 * (size_t)i;
+	const cvxb::BrushResult r = cvxb::LightColumn(A.W, cx, cz, nullptr, nullptr, cvxb::LightKeep{});
+	if (r.runCount == 0u) {
+		h[0] = 0u;
+		h[1] = 0u;
+		h[2] = 0u;
+		return;
+	}
+	cvxb::LightColumn(A.W, cx, cz, e + 1, e + r.runCount + 2u, recolour);
+	e[0] = 0u;
+	e[r.runCount + 1u] = 0u;
+	h[0] = off;
+	h[1] = r.runCount | (r.worldMin << 16);
+	h[2] = r.worldMax;
+}
+
+__global__ __launch_bounds__(256) void light_count_kernel(LightArgs A)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= A.n) { return; }
+	const cvxb::BrushResult r = cvxb::LightColumn(A.W, A.x0 + i / A.sizeZ, A.z0 + i % A.sizeZ, nullptr, nullptr, cvxb::LightKeep{});
+	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
+	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+}
+
+__global__ __launch_bounds__(256) void light_write_kernel(LightArgs A)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= A.n) { return; }
+	const int cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
+#ifdef CVX_LIGHT_RECORDS
+	WriteColumn(A, i, cx, cz, cvxb::LightFromRecords{ cvxb::ArenaOcc{ A.W }, A.B, A.P, cx, cz });
+#else
+	WriteColumn(A, i, cx, cz, cvxb::LightKeep{});
+#endif
+}
+
+#ifndef CVX_LIGHT_RECORDS
+
+constexpr int kTile = 16;            // columns per side of a workgroup's tile
+constexpr int kSlab = 32;            // voxels of y shaded per pass; the brick holds kSlab + 32 = 64 of them
+constexpr int kThreads = kTile * kTile;
+constexpr int kList = 2048;          // voxels compacted per round
+
+// occupancy inside the brick, no checks: the sky directions of a voxel of the slab never leave it
+struct BrickNear {
+	const unsigned long long *brick;
+	int stride, ox, oz, oy;
+	__device__ __forceinline__ bool operator()(int x, int y, int z) const { return (brick[(x - ox) * stride + (z - oz)] >> (y - oy)) & 1ull; }
+};
+
+// occupancy anywhere: the brick where it reaches, the records beyond
+struct BrickAny {
+	BrickNear near;
+	int side;
+	cvxb::ArenaOcc far;
+	__device__ __forceinline__ bool operator()(int x, int y, int z) const
+	{
+		if ((unsigned)(x - near.ox) < (unsigned)side && (unsigned)(z - near.oz) < (unsigned)side && (unsigned)(y - near.oy) < 64u) { return near(x, y, z); }
+		return far(x, y, z);
+	}
+};
+
+// bits lo .. hi - 1 (0 <= lo < hi <= 64)
+__device__ __forceinline__ unsigned long long BitSpan(int lo, int hi) { return (~0ull >> (64 - (hi - lo))) << lo; }
+
+__global__ __launch_bounds__(kThreads) void light_brick_kernel(LightArgs A)
+{
+	extern __shared__ unsigned long long brick[];   // brickSide rows of brickStride words
+	__shared__ uint16_t list[kList];                // tile column << 5 | bit
+	__shared__ uint32_t colourAt[kThreads];         // per tile column: the element of its first solid voxel at or below the slab's top
+	__shared__ uint32_t waveSum[kThreads / CVX_WAVE];
+	__shared__ int tileLo, tileHi;
+
+	const int tid = threadIdx.x;
+	const int halo = A.P.skyRange, side = A.brickSide, stride = A.brickStride;
+	const int tx0 = A.B.x0 + (int)(blockIdx.x / A.tilesZ) * kTile, tz0 = A.B.z0 + (int)(blockIdx.x % A.tilesZ) * kTile;
+	const int cx = tx0 + tid / kTile, cz = tz0 + tid % kTile;
+	const bool mine = cx < A.B.x1 && cz < A.B.z1;
+	if (tid == 0) {
+		tileLo = INT_MAX;
+		tileHi = INT_MIN;
+	}
+	__syncthreads();
+	cvxb::ArenaColumn own{ 0u, 0u, 0u, 0u, A.W.runs };
+	uint32_t colourBase = 0u; // the element of the column's first colour in the blob
+	if (mine) {
+		own = cvxb::CopyColumnAt(A.W, cx, cz);
+		if (own.Count() != 0u) {
+			atomicMin(&tileLo, (int)own.WorldMin());
+			atomicMax(&tileHi, (int)own.WorldMax());
+			const uint32_t *h = A.headers + 3 * ((size_t)(cx - A.x0) * A.sizeZ + (size_t)(cz - A.z0));
+			colourBase = h[0] + (h[1] & 0xFFFFu) + 2u;
+		}
+	}
+	__syncthreads();
+	const int yLo = max(A.B.y0, tileLo), yHi = min(A.B.y1, tileHi);
+	const BrickNear near{ brick, stride, tx0 - halo, tz0 - halo, 0 };
+	const cvxb::LightDims dims{ A.W.dimX, A.W.dimY, A.W.dimZ };
+
+	for (int ys = yLo; ys < yHi; ys += kSlab) {
+		// 1. expand
+		for (int c = tid; c < side * side; c += kThreads) {
+			const int bx = c / side, bz = c % side;
+			const int wx = near.ox + bx, wz = near.oz + bz;
+			unsigned long long bits = 0ull;
+			if (wx >= 0 && wx < A.W.dimX && wz >= 0 && wz < A.W.dimZ) {
+				const cvxb::ArenaColumn col = cvxb::CopyColumnAt(A.W, wx, wz);
+				const uint32_t count = col.Count();
+				if (count != 0u && (int)col.WorldMax() > ys && (int)col.WorldMin() < ys + 64) {
+					for (uint32_t k = count > 3u ? cvxb::RunAtOrBelow(col, ys + 63) : 0u; k < count; k++) {
+						const cvxb::SolidRun run = col.Run(k);
+						if ((int)run.top <= ys) { break; }
+						const int lo = max((int)run.bottom, ys) - ys, hi = min((int)run.top, ys + 64) - ys;
+						if (lo < hi) { bits |= BitSpan(lo, hi); }
+					}
+				}
+			}
+			brick[bx * stride + bz] = bits;
+		}
+		__syncthreads();
+		// 2. compact: this column's solid voxels inside the slab and the box
+		const uint32_t word = (uint32_t)brick[(tid / kTile + halo) * stride + (tid % kTile + halo)];
+		const int top = min(yHi - ys, kSlab);
+		const uint32_t m = mine ? word & (uint32_t)BitSpan(0, top) : 0u;
+		uint32_t before = __popc(m);
+		const uint32_t cnt = before;
+		for (int d = 1; d < CVX_WAVE; d <<= 1) {
+			const uint32_t up = __shfl_up(before, d);
+			if ((tid & (CVX_WAVE - 1)) >= d) { before += up; }
+		}
+		if ((tid & (CVX_WAVE - 1)) == CVX_WAVE - 1) { waveSum[tid / CVX_WAVE] = before; }
+		if (m != 0u) { // the solid voxels of the column at or above the slab's last voxel come before the slab's in its colours
+			uint32_t above = 0u;
+			for (uint32_t k = 0; k < own.Count(); k++) {
+				const cvxb::SolidRun run = own.Run(k);
+				if ((int)run.top <= ys + kSlab) { break; }
+				above += run.top - (uint32_t)max((int)run.bottom, ys + kSlab);
+			}
+			colourAt[tid] = colourBase + above;
+		}
+		__syncthreads();
+		uint32_t total = 0u;
+		before -= cnt;
+		for (int w = 0; w < kThreads / CVX_WAVE; w++) {
+			if (w < tid / CVX_WAVE) { before += waveSum[w]; }
+			total += waveSum[w];
+		}
+		// 3. shade, kList voxels per round
+		BrickNear slabNear = near;
+		slabNear.oy = ys;
+		const BrickAny any{ slabNear, side, cvxb::ArenaOcc{ A.W } };
+		for (uint32_t base = 0u; base < total; base += kList) {
+			uint32_t at = before;
+			for (uint32_t rest = m; rest != 0u; rest &= rest - 1u, at++) {
+				if (at - base < (uint32_t)kList) { list[at - base] = (uint16_t)((tid << 5) | (__ffs(rest) - 1)); }
+			}
+			__syncthreads();
+			const uint32_t here = min(total - base, (uint32_t)kList);
+			for (uint32_t j = tid; j < here; j += kThreads) {
+				const int entry = list[j], t = entry >> 5, b = entry & 31;
+				const int x = tx0 + t / kTile, z = tz0 + t % kTile, y = ys + b;
+				const int shade = cvxb::VoxelShade(slabNear, any, dims, A.P, x, y, z);
+				const uint32_t w32 = (uint32_t)brick[(t / kTile + halo) * stride + (t % kTile + halo)];
+				uint32_t *c = A.elements + colourAt[t] + __popc((w32 >> 1) >> b);
+				*c = cvxb::ApplyShade(*c, shade, A.P.target);
+			}
+			__syncthreads();
+		}
+		__syncthreads();
+	}
+}
+
+#endif // !CVX_LIGHT_RECORDS
+
+} // namespace cvxlight
+
+namespace {
+
+unsigned Grid(size_t n, unsigned threads = 256) { return (unsigned)((n + threads - 1) / threads); }
+
+} // namespace
+
+extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params, int levelCount, float *outDeviceMs)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	if (!params) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "params is NULL"); }
+	if (const char *what = cvxb::LightParamsError(*params)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "cvx_light_params: bad %s", what); }
+	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
+	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	const int dimX = ctx->hostWorld.dimX, dimY = ctx->hostWorld.dimY, dimZ = ctx->hostWorld.dimZ;
+	if (outDeviceMs) { *outDeviceMs = 0.f; }
+	cvxb::PiecesBox B;
+	if (!cvxb::PiecesClipBox(params->boxMin, params->boxMax, dimX, dimY, dimZ, &B)) { return CVX_OK; }
+	// the rectangle: the box's footprint rounded out to 2^levelCount, clipped to the world
+	const int64_t align = ((int64_t)1 << levelCount) - 1;
+	const int64_t x0 = B.x0 & ~align, z0 = B.z0 & ~align;
+	const int64_t x1 = std::min<int64_t>((B.x1 + align) & ~align, dimX), z1 = std::min<int64_t>((B.z1 + align) & ~align, dimZ);
+	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
+		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dimX, dimZ, (long long)align + 1);
+	}
+	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
+	const int n = sizeX * sizeZ;
+	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "lighting %d x %d columns", sizeX, sizeZ); }
+	CVX_HIP(ctx, hipSetDevice(ctx->device));
+	int rc = cvxi::SyncWorld(ctx);
+	if (rc != CVX_OK) { return rc; }
+
+	hipEvent_t ev[2] = { nullptr, nullptr };
+	uint8_t *scratch = nullptr, *dSrc = nullptr;
+	auto release = [&]() {
+		if (scratch) { (void)hipFree(scratch); }
+		if (dSrc) { (void)hipFree(dSrc); }
+		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
+	};
+	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
+	size_t bytes = 0;
+	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	const size_t oCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8);
+	struct { unsigned long long total, overLimit; } host = { 0, 0 };
+	cvxlight::LightArgs A{};
+	hipError_t e = hipEventCreate(&ev[0]);
+	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
+	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
+	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, 2 * 8, ctx->stream); }
+	if (e == hipSuccess) {
+		const DevWorldLevel &L = ctx->hostWorld.level[0];
+		A.W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
+		A.W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
+		A.W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
+		A.W.rowShift = L.rowShift;
+		A.W.colorShift = L.colorShift;
+		A.W.dimX = dimX;
+		A.W.dimY = dimY;
+		A.W.dimZ = dimZ;
+		A.B = B;
+		A.P = *params;
+		A.x0 = (int)x0;
+		A.z0 = (int)z0;
+		A.sizeZ = sizeZ;
+		A.n = n;
+		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
+		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
+		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
+		// count, scan, one copy back
+		hipLaunchKernelGGL(cvxlight::light_count_kernel, dim3(Grid((size_t)n)), dim3(256), 0, ctx->stream, A);
+		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
+		e = hipGetLastError();
+		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
+		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
+	}
+	if (e != hipSuccess) {
+		release();
+		return Fail(ctx, CVX_ERR_HIP, "light failed: %s", hipGetErrorString(e));
+	}
+	if (host.overLimit) {
+		release();
+		return Fail(ctx, CVX_ERR_CAPACITY, "a re-emitted column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
+	}
+	if (host.total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) {
+		release();
+		return Fail(ctx, CVX_ERR_CAPACITY, "the lit columns need %llu elements", host.total);
+	}
+	// the sub-world blob, then its colours shaded in place
+	const size_t blobBytes = (size_t)n * 12 + (size_t)host.total * 4;
+	e = hipMalloc((void **)&dSrc, std::max<size_t>(blobBytes, 4));
+	if (e == hipSuccess) {
+		A.headers = reinterpret_cast<uint32_t *>(dSrc);
+		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
+		hipLaunchKernelGGL(cvxlight::light_write_kernel, dim3(Grid((size_t)n)), dim3(256), 0, ctx->stream, A);
+#ifndef CVX_LIGHT_RECORDS
+		const int tilesX = (B.SizeX() + cvxlight::kTile - 1) / cvxlight::kTile;
+		A.tilesZ = (B.SizeZ() + cvxlight::kTile - 1) / cvxlight::kTile;
+		A.brickSide = cvxlight::kTile + 2 * params->skyRange;
+		A.brickStride = A.brickSide | 1;
+		const size_t lds = (size_t)A.brickSide * A.brickStride * 8;
+		hipLaunchKernelGGL(cvxlight::light_brick_kernel, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
+#endif
+		e = hipGetLastError();
+	}
+	if (e != hipSuccess) {
+		release();
+		return Fail(ctx, CVX_ERR_HIP, "light failed: %s", hipGetErrorString(e));
+	}
+	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.total, n, levelCount, ev[1]);
+	if (rc == CVX_OK && outDeviceMs) {
+		float ms = 0.f;
+		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+		*outDeviceMs = e == hipSuccess ? ms : 0.f;
+	}
+	release();
+	return rc;
+}

@@ -33,6 +33,7 @@ EXPORTS = [
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
     "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces",
+    "cvx_world_light",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -65,6 +66,7 @@ COPY_REPLACE = 3                                # cvx_copy_placement.op, besides
 COPY_MAX_PLACEMENTS = 1024
 PIECES_REPORT, PIECES_REMOVE = 0, 1              # cvx_world_pieces: op
 ANCHOR_GROUND, ANCHOR_OUTSIDE, ANCHOR_LARGEST = 1, 2, 4  # ... anchors (bits)
+LIGHT_TO_RGB, LIGHT_TO_ALPHA = 0, 1              # cvx_light_params.target
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
 
@@ -91,6 +93,11 @@ class Piece(C.Structure):  # cvx_piece
 
 class PiecesSummary(C.Structure):  # cvx_pieces_summary
     _fields_ = [("floatingPieces", C.c_int64), ("floatingVoxels", C.c_int64), ("anchoredPieces", C.c_int64), ("anchoredVoxels", C.c_int64)]
+
+
+class LightParams(C.Structure):  # cvx_light_params
+    _fields_ = [("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("sunDir", C.c_int32 * 3), ("sunLevel", C.c_int32), ("sunRange", C.c_int32),
+                ("skyLevel", C.c_int32), ("skyRange", C.c_int32), ("floorLevel", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
 
 
 class _TextureStruct(C.Structure):  # cvx_mesh_texture
@@ -265,6 +272,7 @@ def _bind(path: str) -> C.CDLL:
                                            C.POINTER(C.c_float)]
         L.cvx_world_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_light.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_int, C.POINTER(C.c_float)]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -464,6 +472,20 @@ class Context:
                                            int(capacity), summary.ctypes.data, C.byref(ms)))
         totals = {name: int(summary[0][name]) for name in PIECES_SUMMARY_DTYPE.names}
         return out[:min(out.size, totals["floatingPieces"])].copy(), totals, ms.value
+
+    def world_light(self, box_min, box_max, *, sun_dir=(0, 0, 0), sun_level: int = 0, sun_range: int = 0, sky_level: int = 0, sky_range: int = 0,
+                    floor_level: int = 0, target: int = LIGHT_TO_RGB, level_count: int = LOD_LEVELS - 1) -> float:
+        """Bakes sky occlusion and a sun shadow into the solid LOD-0 voxels inside [box_min, box_max): shade = min(255, floor_level + sky_level *
+        open sky / 26 + (lit ? sun_level * facing / den : 0)), multiplied into R, G, B (LIGHT_TO_RGB, one-shot) or stored in A (LIGHT_TO_ALPHA),
+        then rebuilds LOD 1..level_count over the footprint.  sun_dir points TOWARDS the sun (integers, |.| <= 1024).  Returns the device
+        milliseconds (0 when the box lies outside the world)."""
+        if len(box_min) != 3 or len(box_max) != 3 or len(sun_dir) != 3:
+            raise ValueError("world_light: box_min, box_max and sun_dir are three integers each")
+        p = LightParams((C.c_int32 * 3)(*[int(v) for v in box_min]), (C.c_int32 * 3)(*[int(v) for v in box_max]), (C.c_int32 * 3)(*[int(v) for v in sun_dir]),
+                        sun_level, sun_range, sky_level, sky_range, floor_level, target, 0)
+        ms = C.c_float()
+        self._check(lib().cvx_world_light(self._h, C.byref(p), level_count, C.byref(ms)))
+        return ms.value
 
     def pick(self, origins, directions, max_t):
         """First solid LOD-0 voxel along each ray -> (voxel int32[N, 3], face int32[N], argb uint32[N], t float32[N]).  max_t: a scalar or

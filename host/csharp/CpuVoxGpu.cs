@@ -117,6 +117,18 @@ namespace CpuVox.Gpu
 		public long FloatingPieces, FloatingVoxels, AnchoredPieces, AnchoredVoxels;
 	}
 
+	// cvx_world_light: the call's parameters (64 bytes).  Box [BoxMin, BoxMax) in LOD-0 voxels; SunDir points TOWARDS the sun (integers, |.| <= 1024,
+	// all 0: no sun term); levels 0 .. 255; SunRange 0 .. 4096 voxels of the shadow walk, SkyRange 0 .. 32 voxels per sky direction; Target 0: the
+	// shade is multiplied into R, G, B (one-shot), 1: it is stored in A
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct LightParams
+	{
+		public fixed int BoxMin[3];
+		public fixed int BoxMax[3];
+		public fixed int SunDir[3];
+		public int SunLevel, SunRange, SkyLevel, SkyRange, FloorLevel, Target, Pad;
+	}
+
 	// cvx_world_copy: one placement (48 bytes).  Source box [SrcMin, SrcMax) in LOD-0 voxels, destination min corner Dst; Transform bits 0-1 quarter
 	// turns, bit 2 mirror X (before turning), bit 3 flip Y; Op: 0 fill, 1 carve, 2 paint, 3 replace; Move 1: the source box becomes air
 	[StructLayout(LayoutKind.Sequential, Pack = 4)]
@@ -187,6 +199,8 @@ namespace CpuVox.Gpu
 		// the pieces of LOD 0 inside a box that nothing anchors (anchors: 1 ground, 2 outside the box, 4 the largest; op 0 report, 1 remove + LOD refresh)
 		[DllImport(Lib)] public static extern int cvx_world_pieces(IntPtr ctx, int* boxMin, int* boxMax, int anchors, int op, int levelCount, Piece* pieces,
 		                                                           int pieceCapacity, PiecesSummary* summary, out float outDeviceMs);
+		// sky occlusion and a sun shadow baked into the solid voxels of LOD 0 inside a box (from occupancy alone) + its LOD refresh
+		[DllImport(Lib)] public static extern int cvx_world_light(IntPtr ctx, LightParams* lightParams, int levelCount, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

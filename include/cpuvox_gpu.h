@@ -520,6 +520,46 @@ typedef struct cvx_pieces_summary { /* 32 bytes */
 int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, int op, int levelCount, cvx_piece *pieces,
                      int pieceCapacity, cvx_pieces_summary *summary, float *outDeviceMs);
 
+/* ---- lighting the uploaded world: sky occlusion and sun shadows ----------------------------------------------------------------------------
+ * cvx_world_light: bakes a shade, an integer 0 .. 255, into every solid LOD-0 voxel v inside [boxMin, boxMax) clipped to the world (voxlap's
+ * updatelighting: the call a host makes after an edit).  The shade is computed from occupancy alone -- no colour is read for it, no occupancy
+ * changes --; every voxel outside the world is air, below y = 0 and above dimY too; coordinates address the stored tile: a repeating world does
+ * not wrap them.  No surface normals are used: the worlds are thin shells, and the shell itself is the occluder.
+ *   1. Sky: the 17 directions d = (dx, dy, dz), dx, dz in {-1, 0, 1}, dy in {0, 1}, not (0, 0, 0), weigh 2 (dy = 1) or 1 (dy = 0), 26 in all.
+ *      d is OPEN when every voxel v + s * d, s = 1 .. skyRange, is air; sky = the weights of the open directions; skyTerm = skyLevel * sky / 26.
+ *   2. Sun, for S = sunDir != (0, 0, 0), in exact integers: facing = the sum of |S_i| over the axes with S_i != 0 whose face neighbour
+ *      v + sgn(S_i) * e_i is air, den = the sum of all |S_i|.  The shadow walk follows the ray from the centre of v along S: axis i crosses its
+ *      k-th voxel plane at (2k - 1) / |S_i|; per step ALL axes that attain the smallest pending parameter advance together (an exact edge or
+ *      corner crossing visits no in-between voxel; fractions compared by cross-multiplying in 64 bits); each voxel reached is tested: outside the
+ *      world -> lit, solid -> shadowed; after sunRange voxels -> lit.  sunTerm = lit ? sunLevel * facing / den : 0.
+ *   3. shade = min(255, floorLevel + skyTerm + sunTerm) (every division floors).
+ *   4. target CVX_LIGHT_TO_RGB: each of R, G, B becomes (c * shade + 127) / 255, A stays.  The bake is one-shot: the colours the world holds are
+ *      the albedo, lighting twice shades twice; a caller that relights keeps the unlit rectangle with cvx_world_read_region and puts it back with
+ *      cvx_world_edit first.  CVX_LIGHT_TO_ALPHA: A becomes the shade, R, G, B stay (voxlap's convention, for hosts whose own blit shader
+ *      multiplies); idempotent.  The coarse levels take their alpha by World.DownSample's rule, the alpha of the FIRST voxel of a coarse voxel in
+ *      the reference's insertion order, not an average of the shades.  (A colour word's bytes are a, r, g, b: A is the low byte.)
+ * Mechanics, ordering, atomicity, outDeviceMs and several GPUs are cvx_world_brush's: the rectangle is the clipped box's XZ footprint rounded
+ * outward to multiples of 2^levelCount and clipped to the world; every column of it is re-emitted in the builder's encoding (so a foreign column
+ * with split runs or shared colours gets one colour per voxel), with the new colours inside the box and the old ones elsewhere; LOD 1 ..
+ * levelCount (0 .. 5) are rebuilt over it; every error leaves the world as it was.  A box wholly outside the world: CVX_OK, nothing changes,
+ * *outDeviceMs = 0.  CVX_ERR_INVALID_ARGUMENT: NULL params, boxMin >= boxMax on an axis, a bad target, a level outside 0 .. 255, sunRange outside
+ * 0 .. 4096, skyRange outside 0 .. 32, a |sunDir| component above 1024, levelCount outside 0 .. 5; CVX_ERR_NOT_READY: LOD 0 has not been
+ * uploaded; CVX_ERR_CAPACITY: as cvx_world_brush. */
+enum { CVX_LIGHT_TO_RGB = 0, CVX_LIGHT_TO_ALPHA = 1 };
+typedef struct cvx_light_params { /* 64 bytes */
+	int32_t boxMin[3];   /* LOD-0 voxels, inclusive */
+	int32_t boxMax[3];   /* exclusive */
+	int32_t sunDir[3];   /* TOWARDS the sun, integers, each |.| <= 1024; (0,0,0): no sun term */
+	int32_t sunLevel;    /* 0 .. 255 */
+	int32_t sunRange;    /* 0 .. 4096 voxels visited by the shadow walk; 0: nothing shadows */
+	int32_t skyLevel;    /* 0 .. 255 */
+	int32_t skyRange;    /* 0 .. 32 voxels tested per sky direction; 0: every direction is open */
+	int32_t floorLevel;  /* 0 .. 255: what a fully occluded voxel keeps */
+	int32_t target;      /* CVX_LIGHT_TO_RGB / CVX_LIGHT_TO_ALPHA */
+	int32_t pad_;
+} cvx_light_params;
+int cvx_world_light(cvx_context *ctx, const cvx_light_params *params, int levelCount, float *outDeviceMs);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what

@@ -1,0 +1,93 @@
+"""cvx_world_light on mill512 and on the procedural world of bench.py.
+Usage: python tools/light_bench.py [dim] [repeats] ; prints one JSON line per world and case.
+
+Per world, over the whole world and over a 256^3 box around a surface voxel near the middle: the voxels lit, the device_ms of the product (the LDS
+brick kernel) and, when cpuvox_amd/libcpuvox_gpu_lightrec.so exists (make -C cpuvox_amd/csrc variant NAME=lightrec DEFS=-DCVX_LIGHT_RECORDS), of the
+record-walking variant -- medians of `repeats` calls after one warm-up call, device time from the call's own events, TO_ALPHA so that every repeat
+does the same work --, and beside them the route a host had before this call, timed in the same run: cvx_world_read_level of LOD 0 (the host needs
+the surroundings of the box too), the sequential driver of tests/light_rules.cpp over the blob (its own milliseconds, without loading the blob),
+cvx_world_edit of the rectangle.  Voxels per second for each.  The two libraries' results are compared byte for byte.
+sun (3, 5, 2) level 140 range 256, sky level 90 range 6, floor 25."""
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import scenes  # noqa: E402
+from cpuvox_amd import gpu, host  # noqa: E402
+
+dim = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
+repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+VARIANT = os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_lightrec.so")
+LIGHT = dict(sun_dir=(3, 5, 2), sun_level=140, sun_range=256, sky_level=90, sky_range=6, floor_level=25, target=gpu.LIGHT_TO_ALPHA)
+work = tempfile.mkdtemp(prefix="light_bench")
+rules = os.path.join(work, "light_rules")
+subprocess.check_call(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
+                       os.path.join(ROOT, "tests", "light_rules.cpp"), "-o", rules, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
+
+
+def device(ws, boxes, library):
+    """{case: (median device ms, LOD-0 bytes after the calls)} through one library."""
+    gpu.use_library(library)
+    out = {}
+    ctx = gpu.Context(0)
+    try:
+        ctx.upload_world(ws)
+        for case, (lo, hi) in boxes.items():
+            ctx.world_light(lo, hi, **LIGHT)  # (warm-up; TO_ALPHA: every later call does the same work on the same world)
+            out[case] = (round(float(np.median([ctx.world_light(lo, hi, **LIGHT) for _ in range(repeats)])), 3), ctx.read_level(0)[0])
+    finally:
+        ctx.close()
+        gpu.use_library(None)
+    return out
+
+
+def bench(name, ws):
+    dims = tuple(ws.dims)
+    ctx = gpu.Context(0)
+    ctx.upload_world(ws)
+    o = np.array([[dims[0] * 0.5 + 0.5, dims[1] - 0.5, dims[2] * 0.5 + 0.5]])
+    vox, face, _, _ = ctx.pick(o, np.array([[0.0, -1.0, 0.0]]), float(dims[1]))
+    centre = [int(v) for v in vox[0]] if face[0] >= 0 else [dims[0] // 2, dims[1] // 4, dims[2] // 2]
+    boxes = {"whole": ([0, 0, 0], list(dims)), "box256": ([max(0, c - 128) for c in centre], [c + 128 for c in centre])}
+    product = device(ws, boxes, None)
+    variant = device(ws, boxes, VARIANT) if os.path.exists(VARIANT) else None
+    for case, (lo, hi) in boxes.items():
+        # the route without the call: read LOD 0 back, light it on the host, put the rectangle back
+        t = time.perf_counter()
+        blob, columns = ctx.read_level(0)
+        read_ms = (time.perf_counter() - t) * 1e3
+        path, sub = os.path.join(work, "world.bin"), os.path.join(work, "sub.bin")
+        open(path, "wb").write(blob)
+        words = [*lo, *hi, *LIGHT["sun_dir"], LIGHT["sun_level"], LIGHT["sun_range"], LIGHT["sky_level"], LIGHT["sky_range"], LIGHT["floor_level"], LIGHT["target"], 0]
+        text = subprocess.check_output([rules, "world", path, *[str(d) for d in dims], str(columns), *[str(w) for w in words], "5", sub], text=True).split()
+        rect = [int(v) for v in text[text.index("rect") + 1:text.index("rect") + 5]]
+        voxels, host_ms = int(text[text.index("voxels") + 1]), float(text[text.index("ms") + 1])
+        t = time.perf_counter()
+        ctx.edit(*rect, open(sub, "rb").read(), rect[2] * rect[3], 5)
+        ctx.synchronize()
+        edit_ms = (time.perf_counter() - t) * 1e3
+        row = {"world": name, "case": case, "voxels": voxels, "lds_device_ms": product[case][0], "lds_mvoxels_per_s": round(voxels / product[case][0] / 1e3, 1)}
+        if variant:
+            assert variant[case][1] == product[case][1], "the record-walking variant disagrees with the product"
+            row.update({"records_device_ms": variant[case][0], "records_mvoxels_per_s": round(voxels / variant[case][0] / 1e3, 1),
+                        "records_over_lds": round(variant[case][0] / product[case][0], 2)})
+        host_route = read_ms + host_ms + edit_ms
+        row.update({"read_level_ms": round(read_ms, 1), "host_light_ms": round(host_ms, 1), "edit_call_ms": round(edit_ms, 1), "host_route_ms": round(host_route, 1),
+                    "host_mvoxels_per_s": round(voxels / host_route / 1e3, 2), "host_over_lds": round(host_route / product[case][0], 1), "repeats": repeats})
+        assert ctx.read_level(0)[0] == product[case][1], "the host route disagrees with the device"
+        print(json.dumps(row), flush=True)
+    ctx.close()
+
+
+bench("mill512", scenes.load_world("mill512"))
+t0 = time.perf_counter()
+ws = host.WorldSet.procedural(dim, dim, dim)
+print(json.dumps({"world": f"proc{dim}", "world_build_s": round(time.perf_counter() - t0, 1)}), flush=True)
+bench(f"proc{dim}", ws)
