@@ -33,7 +33,7 @@ EXPORTS = [
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
     "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces",
-    "cvx_world_light",
+    "cvx_world_light", "cvx_world_move", "cvx_world_move_device",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -67,6 +67,9 @@ COPY_MAX_PLACEMENTS = 1024
 PIECES_REPORT, PIECES_REMOVE = 0, 1              # cvx_world_pieces: op
 ANCHOR_GROUND, ANCHOR_OUTSIDE, ANCHOR_LARGEST = 1, 2, 4  # ... anchors (bits)
 LIGHT_TO_RGB, LIGHT_TO_ALPHA = 0, 1              # cvx_light_params.target
+MOVE_UNIT = 256                                  # cvx_move_body: position units per LOD-0 voxel
+MOVE_SOLID_BELOW, MOVE_SOLID_SIDES = 1, 2        # cvx_move_body.flags
+MOVED_BLOCKED_MASK, MOVED_RESTING, MOVED_STARTS_SOLID, MOVED_STEPPED, MOVED_INVALID = 0x3F, 1 << 6, 1 << 7, 1 << 8, -(1 << 31)  # cvx_move_result.flags
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
 
@@ -100,6 +103,14 @@ class LightParams(C.Structure):  # cvx_light_params
                 ("skyLevel", C.c_int32), ("skyRange", C.c_int32), ("floorLevel", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
 
 
+class MoveBody(C.Structure):  # cvx_move_body
+    _fields_ = [("pos", C.c_int32 * 3), ("size", C.c_int32 * 3), ("delta", C.c_int32 * 3), ("stepUp", C.c_int32), ("flags", C.c_int32), ("pad_", C.c_int32)]
+
+
+class MoveResult(C.Structure):  # cvx_move_result
+    _fields_ = [("pos", C.c_int32 * 3), ("flags", C.c_int32)]
+
+
 class _TextureStruct(C.Structure):  # cvx_mesh_texture
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
 
@@ -114,6 +125,8 @@ COPY_PLACEMENT_DTYPE = np.dtype([("srcMin", "<i4", 3), ("srcMax", "<i4", 3), ("d
                                  ("move", "<i4")])  # cvx_copy_placement
 PIECE_DTYPE = np.dtype([("min", "<i4", 3), ("max", "<i4", 3), ("seed", "<i4", 3), ("pad_", "<i4"), ("voxels", "<i8")])  # cvx_piece
 PIECES_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("anchoredPieces", "<i8"), ("anchoredVoxels", "<i8")])
+MOVE_BODY_DTYPE = np.dtype([("pos", "<i4", 3), ("size", "<i4", 3), ("delta", "<i4", 3), ("stepUp", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])  # cvx_move_body
+MOVE_RESULT_DTYPE = np.dtype([("pos", "<i4", 3), ("flags", "<i4")])  # cvx_move_result
 
 
 def strokes_array(strokes) -> np.ndarray:
@@ -127,6 +140,20 @@ def strokes_array(strokes) -> np.ndarray:
         out[i]["a"] = s["a"]
         out[i]["b"] = [b, 0, 0] if np.isscalar(b) else b
         out[i]["argb"] = s.get("argb", 0) & 0xFFFFFFFF
+    return out
+
+
+def bodies_array(bodies) -> np.ndarray:
+    """A list of dicts {pos, size, delta (default 0), stepUp (default 0), flags (default 0)}, all in units of 1 / MOVE_UNIT voxel, or a
+    MOVE_BODY_DTYPE array -> a contiguous MOVE_BODY_DTYPE array."""
+    if isinstance(bodies, np.ndarray):
+        return np.ascontiguousarray(bodies.astype(MOVE_BODY_DTYPE, copy=False))
+    out = np.zeros(len(bodies), dtype=MOVE_BODY_DTYPE)
+    for i, b in enumerate(bodies):
+        out[i]["pos"], out[i]["size"] = b["pos"], b["size"]
+        out[i]["delta"] = b.get("delta", (0, 0, 0))
+        out[i]["stepUp"] = b.get("stepUp", 0)
+        out[i]["flags"] = b.get("flags", 0)
     return out
 
 
@@ -273,6 +300,8 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_light.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_int, C.POINTER(C.c_float)]
+        L.cvx_world_move.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.cvx_world_move_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -486,6 +515,22 @@ class Context:
         ms = C.c_float()
         self._check(lib().cvx_world_light(self._h, C.byref(p), level_count, C.byref(ms)))
         return ms.value
+
+    def world_move(self, bodies) -> np.ndarray:
+        """Moves boxes through LOD 0 with collision, sliding and step-up (include/cpuvox_gpu.h, cvx_world_move): `bodies` is a list of dicts
+        {pos, size, delta, stepUp, flags} or a MOVE_BODY_DTYPE array, in units of 1 / MOVE_UNIT voxel.  Returns a MOVE_RESULT_DTYPE array: the
+        new min corner and the MOVED_* flags of every body.  The world is not changed."""
+        arr = bodies_array(bodies)
+        out = np.zeros(arr.size, dtype=MOVE_RESULT_DTYPE)
+        self._check(lib().cvx_world_move(self._h, arr.size, arr.ctypes.data if arr.size else None, out.ctypes.data if out.size else None))
+        return out
+
+    def world_move_device(self, body_count: int, bodies_ptr: int, results_ptr: int, lanes_per_body: int = 0, stream: int = 0) -> None:
+        """cvx_world_move on device arrays (addresses of body_count cvx_move_body / cvx_move_result, e.g. a torch tensor's data_ptr()): enqueues
+        on `stream` (a hipStream_t as an integer; 0 = the context's stream) and does not wait.  lanes_per_body: 0 (= 16), 1, 4, 16 or 64 lanes
+        of a wave share a body; the results do not depend on it."""
+        self._check(lib().cvx_world_move_device(self._h, int(body_count), C.c_void_p(int(bodies_ptr)), C.c_void_p(int(results_ptr)), int(lanes_per_body),
+                                                C.c_void_p(int(stream)) if stream else None))
 
     def pick(self, origins, directions, max_t):
         """First solid LOD-0 voxel along each ray -> (voxel int32[N, 3], face int32[N], argb uint32[N], t float32[N]).  max_t: a scalar or

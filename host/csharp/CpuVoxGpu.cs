@@ -129,6 +129,25 @@ namespace CpuVox.Gpu
 		public int SunLevel, SunRange, SkyLevel, SkyRange, FloorLevel, Target, Pad;
 	}
 
+	// cvx_world_move: a body (48 bytes) and its result (16 bytes), in units of 1 / 256 LOD-0 voxel.  Pos is the box's min corner; Size 1 .. 64 * 256
+	// per axis; |Delta| <= 256 * 256; StepUp 0 .. 4 * 256; Flags: 1 = solid below y 0, 2 = solid beyond the tile's sides.  Result flags: bits 0 .. 5
+	// stopped going -X, +X, -Y, +Y, -Z, +Z; 64 resting, 128 started inside solid, 256 stepped up, 1 << 31 a body outside the limits (device call)
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct MoveBody
+	{
+		public fixed int Pos[3];
+		public fixed int Size[3];
+		public fixed int Delta[3];
+		public int StepUp, Flags, Pad;
+	}
+
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct MoveResult
+	{
+		public fixed int Pos[3];
+		public int Flags;
+	}
+
 	// cvx_world_copy: one placement (48 bytes).  Source box [SrcMin, SrcMax) in LOD-0 voxels, destination min corner Dst; Transform bits 0-1 quarter
 	// turns, bit 2 mirror X (before turning), bit 3 flip Y; Op: 0 fill, 1 carve, 2 paint, 3 replace; Move 1: the source box becomes air
 	[StructLayout(LayoutKind.Sequential, Pack = 4)]
@@ -201,6 +220,11 @@ namespace CpuVox.Gpu
 		                                                           int pieceCapacity, PiecesSummary* summary, out float outDeviceMs);
 		// sky occlusion and a sun shadow baked into the solid voxels of LOD 0 inside a box (from occupancy alone) + its LOD refresh
 		[DllImport(Lib)] public static extern int cvx_world_light(IntPtr ctx, LightParams* lightParams, int levelCount, out float outDeviceMs);
+		// boxes moved through LOD 0 with collision, sliding and step-up (host arrays; device arrays with lanesPerBody 0 / 1 / 4 / 16 / 64, enqueued only)
+		public const int CVX_MOVE_UNIT = 256, CVX_MOVE_SOLID_BELOW = 1, CVX_MOVE_SOLID_SIDES = 2;
+		public const int CVX_MOVED_BLOCKED_MASK = 0x3F, CVX_MOVED_RESTING = 1 << 6, CVX_MOVED_STARTS_SOLID = 1 << 7, CVX_MOVED_STEPPED = 1 << 8, CVX_MOVED_INVALID = int.MinValue;
+		[DllImport(Lib)] public static extern int cvx_world_move(IntPtr ctx, int bodyCount, MoveBody* bodies, MoveResult* results);
+		[DllImport(Lib)] public static extern int cvx_world_move_device(IntPtr ctx, int bodyCount, IntPtr bodiesDevice, IntPtr resultsDevice, int lanesPerBody, IntPtr hipStream);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

@@ -560,6 +560,58 @@ typedef struct cvx_light_params { /* 64 bytes */
 } cvx_light_params;
 int cvx_world_light(cvx_context *ctx, const cvx_light_params *params, int levelCount, float *outDeviceMs);
 
+/* ---- moving boxes through the uploaded world: collision and sliding ------------------------------------------------------------------------
+ * cvx_world_move: moves axis-aligned boxes (players, NPCs, debris) through LOD 0 without entering solid voxels (voxlap's clipmove: the call a
+ * host makes every frame).  The rule is integer from end to end (cvx_move.h): positions, sizes and displacements are in units of 1 / CVX_MOVE_UNIT
+ * voxel, the same input gives the same bytes on every machine, and neither call changes the world.
+ *   Occupancy.  Voxel (x, y, z) of the stored tile is solid as the arena says.  Outside it, the first rule that applies: y >= dimY is air;
+ *     y < 0 is solid iff CVX_MOVE_SOLID_BELOW; x or z outside the tile is solid iff CVX_MOVE_SOLID_SIDES.  In a repeating world
+ *     (cvx_set_world_repeat) x and z wrap by floor-mod instead and CVX_MOVE_SOLID_SIDES has no effect.
+ *   Overlap.  The box occupies [pos_i, pos_i + size_i) per axis and covers the voxels floor(pos_i / 256) .. floor((pos_i + size_i - 1) / 256)
+ *     (division floors for negatives).
+ *   A leg on axis a by d != 0 from the box's current position; the cross-section is the covered voxel ranges of the other two axes.  Going +:
+ *     with hi the last covered slab, the slabs k = hi + 1 .. floor((pos_a + size_a + d - 1) / 256) are entered in order; the first k with a solid
+ *     voxel in the cross-section stops the box flush, moved = min(d, 256 k - (pos_a + size_a)).  Going -: with lo the first covered slab, k =
+ *     lo - 1 down to floor((pos_a + d) / 256), moved = min(|d|, pos_a - 256 (k + 1)).  Slabs the box already covers are never tested (an embedded
+ *     body can leave).  The leg sets its direction's blocked bit iff moved < |d|.
+ *   Slide A from P0 = pos: legs Y, X, Z with delta's components, zero components skipped (the usual voxel-game move, not a simultaneous sweep).
+ *   Step-up, tried iff stepUp > 0, delta_y <= 0, A set an X or Z blocked bit, and the body is grounded (A's Y leg was blocked going down, or
+ *     delta_y = 0 and P0 is resting).  Attempt B from P0: a +Y leg by stepUp moving r, an X leg by delta_x, a Z leg by delta_z, a -Y leg by
+ *     r - delta_y.  B replaces A iff |x_B - x_0| + |z_B - z_0| is strictly larger than A's; B's flags are the blocked bits of its X and Z legs, -Y
+ *     if its last leg was blocked, and CVX_MOVED_STEPPED (the raise never sets +Y).
+ *   CVX_MOVED_RESTING: at the final position pos_y % 256 = 0 and slab pos_y / 256 - 1 holds a solid voxel under the XZ footprint.
+ *   CVX_MOVED_STARTS_SOLID: the box at P0 overlaps a solid voxel.  A body without it never ends overlapping one.  delta = 0 is a pure overlap
+ *     and ground query.
+ * cvx_world_move takes host arrays; it is ordered on the context's stream behind every draw, edit and brush enqueued before it (levels uploaded
+ * but not placed yet are placed first) and returns when the results are copied back.  cvx_world_move_device takes device arrays and enqueues on
+ * hipStream (NULL = the context's stream) without waiting; the caller orders that stream after the context's work.  lanesPerBody G: G consecutive
+ * lanes of a wave own one body and share the columns of each leg (1: a thread per body, for thousands of small boxes; 64: a wave per body, for a
+ * footprint of hundreds of columns); 0 = 16; the result does not depend on it.  The host-array call picks ONE G for the whole call from the
+ * largest leg region among its bodies: put bodies of very different sizes (debris and a vehicle) into separate calls.
+ * CVX_ERR_NOT_READY: LOD 0 has not been uploaded.  CVX_ERR_INVALID_ARGUMENT: a NULL pointer, bodyCount < 1, lanesPerBody not one of 0, 1, 4, 16,
+ * 64, and in the host-array call any body outside the limits below, with a |pos| component above 2^28 or with unknown flag bits (nothing runs).
+ * The device call cannot read its input on the host: for such a body the kernel writes pos back unchanged with CVX_MOVED_INVALID and walks
+ * nothing; every loop of the kernel is bounded by the limits whatever the input. */
+#define CVX_MOVE_UNIT 256            /* position units per LOD-0 voxel */
+enum { CVX_MOVE_SOLID_BELOW = 1, CVX_MOVE_SOLID_SIDES = 2 };                 /* body.flags */
+enum { CVX_MOVED_BLOCKED_MASK = 0x3F,  /* bits 0..5: stopped going -X,+X,-Y,+Y,-Z,+Z (the pick's face numbers) */
+       CVX_MOVED_RESTING = 1 << 6, CVX_MOVED_STARTS_SOLID = 1 << 7, CVX_MOVED_STEPPED = 1 << 8, CVX_MOVED_INVALID = 1 << 31 };
+typedef struct cvx_move_body {   /* 48 bytes */
+	int32_t pos[3];    /* min corner, units */
+	int32_t size[3];   /* units, 1 .. 64 * 256 per axis */
+	int32_t delta[3];  /* requested displacement, units, |.| <= 256 * 256 */
+	int32_t stepUp;    /* 0 .. 4 * 256 */
+	int32_t flags;     /* CVX_MOVE_SOLID_* */
+	int32_t pad_;
+} cvx_move_body;
+typedef struct cvx_move_result { /* 16 bytes */
+	int32_t pos[3];
+	int32_t flags;     /* CVX_MOVED_* */
+} cvx_move_result;
+int cvx_world_move(cvx_context *ctx, int bodyCount, const cvx_move_body *bodies, cvx_move_result *results);
+int cvx_world_move_device(cvx_context *ctx, int bodyCount, const cvx_move_body *bodiesDevice, cvx_move_result *resultsDevice,
+                          int lanesPerBody, void *hipStream);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
