@@ -15,60 +15,22 @@
 //   5. list   the first pieceCapacity floating pieces, copied to the host behind the totals
 //   6. REMOVE count / scan / write of the sub-world blob of the floating pieces' rectangle (cvxb::PiecesRemoveColumn), then
 //             cvxi::EditFromDevice, exactly as cvx_copy.hip.  Nothing in the arena is written before that.
+// Steps 1 .. 5 are cvxpieces::Analyse (cvx_pieces_nodes.h), which leaves the node tables on the device: cvx_world_settle (cvx_settle.hip) goes on from them too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "cvx_context.h"
 #include "cvx_pieces.h"
+#include "cvx_pieces_nodes.h"
 
 using cvxi::Fail;
 
 namespace cvxpieces {
-
-constexpr uint32_t kFloats = 0x100u; // in a root's bits, besides CVX_ANCHOR_*
-
-struct Totals {
-	unsigned long long nodes;      // the count scan's total
-	unsigned long long floating;   // the rank scan's total
-	unsigned long long elements;   // REMOVE: the blob's element count
-	unsigned long long mostVoxels; // the largest piece
-	unsigned int largest;          // ... its root
-	unsigned int changed;          // a hook pass hooked something
-	unsigned int overLimit;        // REMOVE
-	unsigned int pad;
-	int x0, x1, z0, z1;            // XZ bounding box of the floating pieces
-	cvx_pieces_summary summary;
-};
-
-struct PiecesArgs {
-	cvxb::CopyWorld W;
-	cvxb::PiecesBox B;
-	int n;                         // columns of the box
-	uint32_t nodes;
-	int anchors;
-	uint32_t *offsets;             // n + 1: the first node of every column
-	uint32_t *lohi;                // per node: lo, hi
-	uint32_t *column;              // per node: its column in the box
-	uint32_t *parent;              // per node: the label
-	unsigned long long *voxels;    // per root
-	int32_t *bounds;               // per root: min x, y, z, max x, y, z
-	uint32_t *bits;                // per root: CVX_ANCHOR_* | kFloats
-	uint32_t *rank;                // per node: floating root -> its place in the list; later: the node floats
-	Totals *totals;
-	cvx_piece *list;
-	int capacity;
-	// REMOVE
-	int rx0, rz0, rSizeZ, rn;
-	uint32_t *counts;
-	uint32_t *headers;
-	uint32_t *elements;
-};
-
-__device__ inline uint32_t Load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // The root of i; every node on the way is pointed at its grandparent (labels only ever fall, so a late or lost update is harmless).
 __device__ inline uint32_t Find(uint32_t *parent, uint32_t i)
@@ -165,12 +127,6 @@ __global__ __launch_bounds__(256) void pieces_flatten_kernel(PiecesArgs A)
 	if (i >= A.nodes) { return; }
 	const uint32_t r = Find(A.parent, i);
 	if (r != i) { atomicMin(A.parent + i, r); }
-}
-
-template <typename T, typename F> __device__ inline T WaveReduce(T v, F f)
-{
-	for (int d = 32; d > 0; d >>= 1) { v = f(v, __shfl_xor(v, d, 64)); }
-	return v;
 }
 
 // Totals of the roots.  Neighbouring nodes mostly belong to one piece: a wave whose nodes have one root reduces first and sends one set of atomics.
@@ -297,23 +253,13 @@ __global__ __launch_bounds__(256) void pieces_mark_kernel(PiecesArgs A)
 	A.rank[i] = (A.bits[A.parent[i]] & kFloats) ? 1u : 0u;
 }
 
-// the nodes of column (cx, cz) of the rectangle: none outside the box
-__device__ inline const uint32_t *ColumnNodes(const PiecesArgs &A, int cx, int cz, uint32_t *count)
-{
-	*count = 0u;
-	if (!A.B.Holds(cx, cz)) { return nullptr; }
-	const int64_t c = A.B.Column(cx, cz);
-	*count = A.offsets[c + 1] - A.offsets[c];
-	return A.rank + A.offsets[c];
-}
-
 __global__ __launch_bounds__(256) void pieces_remove_count_kernel(PiecesArgs A)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= A.rn) { return; }
 	const int cx = A.rx0 + i / A.rSizeZ, cz = A.rz0 + i % A.rSizeZ;
 	uint32_t nodes;
-	const uint32_t *floating = ColumnNodes(A, cx, cz, &nodes);
+	const uint32_t *floating = ColumnNodes(A, A.rank, cx, cz, &nodes);
 	const cvxb::BrushResult r = cvxb::PiecesRemoveColumn(A.W, cx, cz, A.B.y0, A.B.y1, floating, nodes, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(&A.totals->overLimit, 1u); }
 	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
@@ -325,7 +271,7 @@ __global__ __launch_bounds__(256) void pieces_remove_write_kernel(PiecesArgs A)
 	if (i >= A.rn) { return; }
 	const int cx = A.rx0 + i / A.rSizeZ, cz = A.rz0 + i % A.rSizeZ;
 	uint32_t nodes;
-	const uint32_t *floating = ColumnNodes(A, cx, cz, &nodes);
+	const uint32_t *floating = ColumnNodes(A, A.rank, cx, cz, &nodes);
 	const uint32_t off = A.counts[i];
 	uint32_t *e = A.elements + off;
 	const cvxb::BrushResult r = cvxb::PiecesRemoveColumn(A.W, cx, cz, A.B.y0, A.B.y1, floating, nodes, nullptr, nullptr);
@@ -344,69 +290,65 @@ __global__ __launch_bounds__(256) void pieces_remove_write_kernel(PiecesArgs A)
 	h[2] = r.worldMax;
 }
 
-} // namespace cvxpieces
-
-namespace {
-
-constexpr unsigned kThreads = 256;
 constexpr size_t kHead = 256; // pieces that come to the host with the totals, in one copy
 
-unsigned Grid(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-int FailHip(cvx_context *ctx, hipError_t e)
+int FailHip(cvx_context *ctx, const char *call, hipError_t e)
 {
 	if (e == hipErrorOutOfMemory) {
 		(void)hipGetLastError();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the scratch of cvx_world_pieces does not fit in device memory");
+		return Fail(ctx, CVX_ERR_CAPACITY, "the scratch of %s does not fit in device memory", call);
 	}
-	return Fail(ctx, CVX_ERR_HIP, "pieces failed: %s", hipGetErrorString(e));
+	return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
 }
 
-} // namespace
-
-extern "C" {
-
-int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, int op, int levelCount, cvx_piece *pieces,
-                     int pieceCapacity, cvx_pieces_summary *summary, float *outDeviceMs)
+void Analysis::Release()
 {
-	using cvxpieces::PiecesArgs;
-	using cvxpieces::Totals;
+	for (uint8_t *p : { columnScratch, nodeScratch }) { if (p) { (void)hipFree(p); } }
+	for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
+	columnScratch = nodeScratch = nullptr;
+	ev[0] = ev[1] = nullptr;
+}
+
+int Analyse(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, const char *extraError, int levelCount,
+            const cvx_piece *pieces, int pieceCapacity, Analysis *R)
+{
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box is NULL"); }
 	for (int a = 0; a < 3; a++) {
 		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box [%d, %d) on axis %d is empty", boxMin[a], boxMax[a], a); }
 	}
 	if (anchors & ~(CVX_ANCHOR_GROUND | CVX_ANCHOR_OUTSIDE | CVX_ANCHOR_LARGEST)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "unknown anchors bits 0x%x", (unsigned)anchors); }
-	if (op != CVX_PIECES_REPORT && op != CVX_PIECES_REMOVE) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad op %d", op); }
+	if (extraError) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", extraError); }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
 	if (pieceCapacity < 0 || (pieceCapacity > 0 && !pieces)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "pieceCapacity %d with %s list", pieceCapacity, pieces ? "a" : "no"); }
 	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	const int dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
-	PiecesArgs A{};
+	int *dim = R->dim;
+	dim[0] = ctx->hostWorld.dimX;
+	dim[1] = ctx->hostWorld.dimY;
+	dim[2] = ctx->hostWorld.dimZ;
+	PiecesArgs &A = R->A;
+	A = PiecesArgs{};
 	if (!cvxb::PiecesClipBox(boxMin, boxMax, dim[0], dim[1], dim[2], &A.B)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box lies outside the world"); }
 	if (A.B.Columns() >= ((int64_t)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "a box of %lld columns", (long long)A.B.Columns()); }
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
 	int rc = cvxi::SyncWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
 	const int n = (int)A.B.Columns();
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	uint8_t *columnScratch = nullptr, *nodeScratch = nullptr, *removeScratch = nullptr, *dSrc = nullptr;
-	auto release = [&]() {
-		for (uint8_t *p : { columnScratch, nodeScratch, removeScratch, dSrc }) { if (p) { (void)hipFree(p); } }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
+	hipEvent_t *ev = R->ev;
+	auto release = [&]() { R->Release(); };
 	size_t bytes = 0;
 	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
 	auto chunksOf = [](size_t count) { return (count + cvxi::ScanChunk() - 1) / cvxi::ScanChunk(); };
 
 	// 1. the nodes of every column, their offsets, the total
 	const size_t oTotals = carve(sizeof(Totals)), oOffsets = carve(((size_t)n + 1) * 4), oChunks = carve(chunksOf((size_t)n + 1) * 8);
-	Totals host{};
+	Totals &host = R->host;
+	host = Totals{};
 	host.largest = 0xFFFFFFFFu;
 	host.x0 = host.z0 = INT_MAX;
 	host.x1 = host.z1 = INT_MIN;
+	uint8_t *&columnScratch = R->columnScratch, *&nodeScratch = R->nodeScratch;
 	hipError_t e = hipEventCreate(&ev[0]);
 	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
 	if (e == hipSuccess) { e = hipMalloc((void **)&columnScratch, bytes); }
@@ -426,7 +368,7 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		A.anchors = anchors;
 		A.totals = reinterpret_cast<Totals *>(columnScratch + oTotals);
 		A.offsets = reinterpret_cast<uint32_t *>(columnScratch + oOffsets);
-		hipLaunchKernelGGL(cvxpieces::pieces_count_kernel, dim3(Grid((size_t)n + 1)), dim3(kThreads), 0, ctx->stream, A);
+		hipLaunchKernelGGL(pieces_count_kernel, dim3(Grid((size_t)n + 1)), dim3(kThreads), 0, ctx->stream, A);
 		cvxi::ExclusiveScan(ctx->stream, A.offsets, n + 1, reinterpret_cast<unsigned long long *>(columnScratch + oChunks), &A.totals->nodes);
 		e = hipGetLastError();
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host.nodes, &A.totals->nodes, sizeof host.nodes, hipMemcpyDeviceToHost, ctx->stream); }
@@ -434,13 +376,14 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 	}
 	if (e != hipSuccess) {
 		release();
-		return FailHip(ctx, e);
+		return FailHip(ctx, call, e);
 	}
 	if (host.nodes >= ((unsigned long long)1 << 31) - 1) {
 		release();
 		return Fail(ctx, CVX_ERR_CAPACITY, "the box holds %llu solid runs", host.nodes);
 	}
 	const size_t nodes = (size_t)host.nodes;
+	R->nodes = nodes;
 	A.nodes = (uint32_t)nodes;
 	A.capacity = pieceCapacity;
 	const size_t listed = std::min<size_t>((size_t)pieceCapacity, nodes);
@@ -455,7 +398,7 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		e = hipMalloc((void **)&nodeScratch, bytes);
 		if (e != hipSuccess) {
 			release();
-			return FailHip(ctx, e);
+			return FailHip(ctx, call, e);
 		}
 		A.list = reinterpret_cast<cvx_piece *>(nodeScratch + oList);
 		A.lohi = reinterpret_cast<uint32_t *>(nodeScratch + oLohi);
@@ -466,26 +409,26 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		A.bits = reinterpret_cast<uint32_t *>(nodeScratch + oBits);
 		A.rank = reinterpret_cast<uint32_t *>(nodeScratch + oRank);
 		const dim3 grid(Grid(nodes)), block(kThreads);
-		hipLaunchKernelGGL(cvxpieces::pieces_nodes_kernel, dim3(Grid((size_t)n)), block, 0, ctx->stream, A);
+		hipLaunchKernelGGL(pieces_nodes_kernel, dim3(Grid((size_t)n)), block, 0, ctx->stream, A);
 		for (;;) { // until a pass hooks nothing
 			e = hipMemsetAsync(&A.totals->changed, 0, sizeof(unsigned int), ctx->stream);
 			if (e != hipSuccess) { break; }
-			hipLaunchKernelGGL(cvxpieces::pieces_hook_kernel, grid, block, 0, ctx->stream, A);
-			hipLaunchKernelGGL(cvxpieces::pieces_flatten_kernel, grid, block, 0, ctx->stream, A);
+			hipLaunchKernelGGL(pieces_hook_kernel, grid, block, 0, ctx->stream, A);
+			hipLaunchKernelGGL(pieces_flatten_kernel, grid, block, 0, ctx->stream, A);
 			e = hipGetLastError();
 			if (e == hipSuccess) { e = hipMemcpyAsync(&host.changed, &A.totals->changed, sizeof host.changed, hipMemcpyDeviceToHost, ctx->stream); }
 			if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 			if (e != hipSuccess || !host.changed) { break; }
 		}
 		if (e == hipSuccess) {
-			hipLaunchKernelGGL(cvxpieces::pieces_stats_kernel, grid, block, 0, ctx->stream, A);
+			hipLaunchKernelGGL(pieces_stats_kernel, grid, block, 0, ctx->stream, A);
 			if (anchors & CVX_ANCHOR_LARGEST) {
-				hipLaunchKernelGGL(cvxpieces::pieces_most_kernel, grid, block, 0, ctx->stream, A);
-				hipLaunchKernelGGL(cvxpieces::pieces_largest_kernel, grid, block, 0, ctx->stream, A);
+				hipLaunchKernelGGL(pieces_most_kernel, grid, block, 0, ctx->stream, A);
+				hipLaunchKernelGGL(pieces_largest_kernel, grid, block, 0, ctx->stream, A);
 			}
-			hipLaunchKernelGGL(cvxpieces::pieces_flag_kernel, grid, block, 0, ctx->stream, A);
+			hipLaunchKernelGGL(pieces_flag_kernel, grid, block, 0, ctx->stream, A);
 			cvxi::ExclusiveScan(ctx->stream, A.rank, (int)nodes, reinterpret_cast<unsigned long long *>(nodeScratch + oRankChunks), &A.totals->floating);
-			if (listed) { hipLaunchKernelGGL(cvxpieces::pieces_list_kernel, grid, block, 0, ctx->stream, A); }
+			if (listed) { hipLaunchKernelGGL(pieces_list_kernel, grid, block, 0, ctx->stream, A); }
 			e = hipGetLastError();
 			// the totals go in front of the list, so that ONE copy brings them and the list's head
 			if (e == hipSuccess) { e = hipMemcpyAsync(nodeScratch + oHead, A.totals, sizeof(Totals), hipMemcpyDeviceToDevice, ctx->stream); }
@@ -495,7 +438,7 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 		if (e != hipSuccess) {
 			release();
-			return FailHip(ctx, e);
+			return FailHip(ctx, call, e);
 		}
 		std::memcpy(&host, back.data(), sizeof host);
 	} else {
@@ -503,24 +446,55 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 		if (e != hipSuccess) {
 			release();
-			return FailHip(ctx, e);
+			return FailHip(ctx, call, e);
 		}
 	}
 	const size_t floating = (size_t)host.summary.floatingPieces, wanted = std::min<size_t>(floating, (size_t)pieceCapacity);
-	std::vector<cvx_piece> list(wanted);
+	R->list.assign(wanted, cvx_piece{});
 	if (wanted) {
 		const size_t head = std::min(wanted, kHead);
-		std::memcpy(list.data(), back.data() + sizeof(Totals), head * sizeof(cvx_piece));
+		std::memcpy(R->list.data(), back.data() + sizeof(Totals), head * sizeof(cvx_piece));
 		if (wanted > head) {
-			e = hipMemcpy(list.data() + head, A.list + head, (wanted - head) * sizeof(cvx_piece), hipMemcpyDeviceToHost);
+			e = hipMemcpy(R->list.data() + head, A.list + head, (wanted - head) * sizeof(cvx_piece), hipMemcpyDeviceToHost);
 			if (e != hipSuccess) {
 				release();
-				return FailHip(ctx, e);
+				return FailHip(ctx, call, e);
 			}
 		}
 	}
-	float ms = 0.f;
-	(void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+	R->ms = 0.f;
+	(void)hipEventElapsedTime(&R->ms, ev[0], ev[1]);
+	return CVX_OK;
+}
+
+} // namespace cvxpieces
+
+extern "C" {
+
+int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, int op, int levelCount, cvx_piece *pieces,
+                     int pieceCapacity, cvx_pieces_summary *summary, float *outDeviceMs)
+{
+	using namespace cvxpieces;
+	static const char *const call = "cvx_world_pieces";
+	char bad[32];
+	std::snprintf(bad, sizeof bad, "bad op %d", op);
+	Analysis R;
+	int rc = Analyse(ctx, call, boxMin, boxMax, anchors, op != CVX_PIECES_REPORT && op != CVX_PIECES_REMOVE ? bad : nullptr, levelCount, pieces, pieceCapacity, &R);
+	if (rc != CVX_OK) { return rc; }
+	PiecesArgs &A = R.A;
+	Totals &host = R.host;
+	const int *dim = R.dim;
+	const size_t nodes = R.nodes, floating = (size_t)host.summary.floatingPieces;
+	const int64_t align = ((int64_t)1 << levelCount) - 1;
+	float ms = R.ms;
+	uint8_t *removeScratch = nullptr, *dSrc = nullptr;
+	auto release = [&]() {
+		for (uint8_t *p : { removeScratch, dSrc }) { if (p) { (void)hipFree(p); } }
+		R.Release();
+	};
+	size_t bytes = 0;
+	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	auto chunksOf = [](size_t count) { return (count + cvxi::ScanChunk() - 1) / cvxi::ScanChunk(); };
 
 	// 6. REMOVE: the floating pieces' rectangle without them, through cvx_world_edit's machinery
 	if (op == CVX_PIECES_REMOVE && floating) {
@@ -536,9 +510,8 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 			release();
 			return Fail(ctx, CVX_ERR_CAPACITY, "a removal over %d x %d columns", sizeX, sizeZ);
 		}
-		bytes = 0;
 		const size_t oCounts = carve((size_t)rn * 4), oCountChunks = carve(chunksOf((size_t)rn) * 8);
-		e = hipMalloc((void **)&removeScratch, bytes);
+		hipError_t e = hipMalloc((void **)&removeScratch, bytes);
 		if (e == hipSuccess) {
 			A.rx0 = (int)x0;
 			A.rz0 = (int)z0;
@@ -546,8 +519,8 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 			A.rn = rn;
 			A.counts = reinterpret_cast<uint32_t *>(removeScratch + oCounts);
 			const dim3 block(kThreads);
-			hipLaunchKernelGGL(cvxpieces::pieces_mark_kernel, dim3(Grid(nodes)), block, 0, ctx->stream, A);
-			hipLaunchKernelGGL(cvxpieces::pieces_remove_count_kernel, dim3(Grid((size_t)rn)), block, 0, ctx->stream, A);
+			hipLaunchKernelGGL(pieces_mark_kernel, dim3(Grid(nodes)), block, 0, ctx->stream, A);
+			hipLaunchKernelGGL(pieces_remove_count_kernel, dim3(Grid((size_t)rn)), block, 0, ctx->stream, A);
 			cvxi::ExclusiveScan(ctx->stream, A.counts, rn, reinterpret_cast<unsigned long long *>(removeScratch + oCountChunks), &A.totals->elements);
 			e = hipGetLastError();
 			if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
@@ -555,7 +528,7 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		}
 		if (e != hipSuccess) {
 			release();
-			return FailHip(ctx, e);
+			return FailHip(ctx, call, e);
 		}
 		if (host.overLimit) {
 			release();
@@ -569,25 +542,25 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		if (e == hipSuccess) {
 			A.headers = reinterpret_cast<uint32_t *>(dSrc);
 			A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)rn * 12);
-			hipLaunchKernelGGL(cvxpieces::pieces_remove_write_kernel, dim3(Grid((size_t)rn)), dim3(kThreads), 0, ctx->stream, A);
+			hipLaunchKernelGGL(pieces_remove_write_kernel, dim3(Grid((size_t)rn)), dim3(kThreads), 0, ctx->stream, A);
 			e = hipGetLastError();
 		}
 		if (e != hipSuccess) {
 			release();
-			return FailHip(ctx, e);
+			return FailHip(ctx, call, e);
 		}
-		rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.elements, rn, levelCount, ev[1]);
+		rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.elements, rn, levelCount, R.ev[1]);
 		if (rc != CVX_OK) {
 			release();
 			return rc;
 		}
-		(void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+		(void)hipEventElapsedTime(&ms, R.ev[0], R.ev[1]);
 	}
-	release();
 	// (nothing is handed out before the call can no longer fail)
-	if (wanted) { std::memcpy(pieces, list.data(), wanted * sizeof(cvx_piece)); }
+	if (!R.list.empty()) { std::memcpy(pieces, R.list.data(), R.list.size() * sizeof(cvx_piece)); }
 	if (summary) { *summary = host.summary; }
 	if (outDeviceMs) { *outDeviceMs = ms; }
+	release();
 	return CVX_OK;
 }
 

@@ -32,7 +32,7 @@ EXPORTS = [
     "cvx_get_raybuffer_layout", "cvx_version", "cvx_bind_raybuffers", "cvx_draw_time_stats", "cvx_copy_rows", "cvx_draw_segments_placed",
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
-    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces",
+    "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces", "cvx_world_settle",
     "cvx_world_light", "cvx_world_move", "cvx_world_move_device",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
@@ -41,7 +41,7 @@ EXPORTS = [
 ]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
-                "cvx_debug_last_launch"]
+                "cvx_debug_last_launch", "cvx_debug_settle"]
 # cvx_debug_last_launch: out[0], the kernel instance a draw went to
 INSTANCE_COUNTING, INSTANCE_BATCH, INSTANCE_LONE, INSTANCE_LONE_WIDE = 0, 1, 2, 3
 LAUNCH_FIELDS = ("instance", "tiles", "waves", "min_rays", "max_rays", "max_dup_shift", "split", "lds_words")
@@ -66,6 +66,7 @@ COPY_REPLACE = 3                                # cvx_copy_placement.op, besides
 COPY_MAX_PLACEMENTS = 1024
 PIECES_REPORT, PIECES_REMOVE = 0, 1              # cvx_world_pieces: op
 ANCHOR_GROUND, ANCHOR_OUTSIDE, ANCHOR_LARGEST = 1, 2, 4  # ... anchors (bits)
+SETTLE_UNLIMITED = 0                             # cvx_world_settle: maxDrop
 LIGHT_TO_RGB, LIGHT_TO_ALPHA = 0, 1              # cvx_light_params.target
 MOVE_UNIT = 256                                  # cvx_move_body: position units per LOD-0 voxel
 MOVE_SOLID_BELOW, MOVE_SOLID_SIDES = 1, 2        # cvx_move_body.flags
@@ -98,6 +99,11 @@ class PiecesSummary(C.Structure):  # cvx_pieces_summary
     _fields_ = [("floatingPieces", C.c_int64), ("floatingVoxels", C.c_int64), ("anchoredPieces", C.c_int64), ("anchoredVoxels", C.c_int64)]
 
 
+class SettleSummary(C.Structure):  # cvx_settle_summary
+    _fields_ = [("floatingPieces", C.c_int64), ("floatingVoxels", C.c_int64), ("fallenPieces", C.c_int64), ("fallenVoxels", C.c_int64),
+                ("largestDrop", C.c_int32), ("pad_", C.c_int32)]
+
+
 class LightParams(C.Structure):  # cvx_light_params
     _fields_ = [("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("sunDir", C.c_int32 * 3), ("sunLevel", C.c_int32), ("sunRange", C.c_int32),
                 ("skyLevel", C.c_int32), ("skyRange", C.c_int32), ("floorLevel", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
@@ -125,6 +131,8 @@ COPY_PLACEMENT_DTYPE = np.dtype([("srcMin", "<i4", 3), ("srcMax", "<i4", 3), ("d
                                  ("move", "<i4")])  # cvx_copy_placement
 PIECE_DTYPE = np.dtype([("min", "<i4", 3), ("max", "<i4", 3), ("seed", "<i4", 3), ("pad_", "<i4"), ("voxels", "<i8")])  # cvx_piece
 PIECES_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("anchoredPieces", "<i8"), ("anchoredVoxels", "<i8")])
+SETTLE_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("fallenPieces", "<i8"), ("fallenVoxels", "<i8"),
+                                 ("largestDrop", "<i4"), ("pad_", "<i4")])  # cvx_settle_summary
 MOVE_BODY_DTYPE = np.dtype([("pos", "<i4", 3), ("size", "<i4", 3), ("delta", "<i4", 3), ("stepUp", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])  # cvx_move_body
 MOVE_RESULT_DTYPE = np.dtype([("pos", "<i4", 3), ("flags", "<i4")])  # cvx_move_result
 
@@ -277,6 +285,7 @@ def _bind(path: str) -> C.CDLL:
             L.cvx_debug_section_histogram.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
             L.cvx_debug_occupancy.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int)]
             L.cvx_debug_last_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+            L.cvx_debug_settle.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
             L.cvx_selftest_math.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             L.cvx_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
             L.cvx_selftest_lone.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -299,6 +308,8 @@ def _bind(path: str) -> C.CDLL:
                                            C.POINTER(C.c_float)]
         L.cvx_world_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_settle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.POINTER(C.c_float)]
         L.cvx_world_light.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_move.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.cvx_world_move_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -501,6 +512,31 @@ class Context:
                                            int(capacity), summary.ctypes.data, C.byref(ms)))
         totals = {name: int(summary[0][name]) for name in PIECES_SUMMARY_DTYPE.names}
         return out[:min(out.size, totals["floatingPieces"])].copy(), totals, ms.value
+
+    def world_settle(self, box_min, box_max, anchors: int, max_drop: int = SETTLE_UNLIMITED, level_count: int = LOD_LEVELS - 1, capacity: int = 8192):
+        """The floating pieces of world_pieces(box_min, box_max, anchors) fall straight down until they rest on something static or on each other,
+        at most `max_drop` voxels (SETTLE_UNLIMITED: all the way), and LOD 1..level_count are rebuilt over the footprint of those that moved:
+        (the first `capacity` floating pieces BEFORE the fall as a PIECE_DTYPE array in seed order, how far each fell as an int32 array, the totals
+        of cvx_settle_summary as a dict, device milliseconds).  A piece that fell only part of the way is still floating for the next call."""
+        lo, hi = np.ascontiguousarray(box_min, dtype=np.int32), np.ascontiguousarray(box_max, dtype=np.int32)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("world_settle: box_min and box_max are three integers each")
+        out = np.zeros(max(int(capacity), 0), dtype=PIECE_DTYPE)
+        drops = np.zeros(max(int(capacity), 0), dtype=np.int32)
+        summary = np.zeros(1, dtype=SETTLE_SUMMARY_DTYPE)
+        ms = C.c_float()
+        self._check(lib().cvx_world_settle(self._h, lo.ctypes.data, hi.ctypes.data, anchors, max_drop, level_count, out.ctypes.data if out.size else None,
+                                           drops.ctypes.data if drops.size else None, int(capacity), summary.ctypes.data, C.byref(ms)))
+        totals = {name: int(summary[0][name]) for name in SETTLE_SUMMARY_DTYPE.names if name != "pad_"}
+        listed = min(out.size, totals["floatingPieces"])
+        return out[:listed].copy(), drops[:listed].copy(), totals, ms.value
+
+    def debug_settle(self, one_sweep_per_launch: int = -1) -> dict:
+        """Diagnostics build only (include/cpuvox_gpu_diag.h): the last world_settle's device ms split (analysis, gap + relax, edit), its solid runs,
+        relax sweeps and launches; one_sweep_per_launch 1 / 0 switches the comparison variant of the relax loop on / off for later calls."""
+        ms, counts = (C.c_float * 3)(), (C.c_int64 * 4)()
+        self._check(self._diag("cvx_debug_settle")(self._h, one_sweep_per_launch, ms, counts))
+        return {"analysis_ms": ms[0], "relax_ms": ms[1], "edit_ms": ms[2], "nodes": counts[0], "sweeps": counts[1], "launches": counts[2], "single_workgroup": bool(counts[3])}
 
     def world_light(self, box_min, box_max, *, sun_dir=(0, 0, 0), sun_level: int = 0, sun_range: int = 0, sky_level: int = 0, sky_range: int = 0,
                     floor_level: int = 0, target: int = LIGHT_TO_RGB, level_count: int = LOD_LEVELS - 1) -> float:

@@ -117,6 +117,14 @@ namespace CpuVox.Gpu
 		public long FloatingPieces, FloatingVoxels, AnchoredPieces, AnchoredVoxels;
 	}
 
+	// cvx_world_settle: the totals (40 bytes): the floating pieces as PiecesSummary counts them, those that fell (drop > 0), the largest drop
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public struct SettleSummary
+	{
+		public long FloatingPieces, FloatingVoxels, FallenPieces, FallenVoxels;
+		public int LargestDrop, Pad;
+	}
+
 	// cvx_world_light: the call's parameters (64 bytes).  Box [BoxMin, BoxMax) in LOD-0 voxels; SunDir points TOWARDS the sun (integers, |.| <= 1024,
 	// all 0: no sun term); levels 0 .. 255; SunRange 0 .. 4096 voxels of the shadow walk, SkyRange 0 .. 32 voxels per sky direction; Target 0: the
 	// shade is multiplied into R, G, B (one-shot), 1: it is stored in A
@@ -218,6 +226,10 @@ namespace CpuVox.Gpu
 		// the pieces of LOD 0 inside a box that nothing anchors (anchors: 1 ground, 2 outside the box, 4 the largest; op 0 report, 1 remove + LOD refresh)
 		[DllImport(Lib)] public static extern int cvx_world_pieces(IntPtr ctx, int* boxMin, int* boxMax, int anchors, int op, int levelCount, Piece* pieces,
 		                                                           int pieceCapacity, PiecesSummary* summary, out float outDeviceMs);
+		// the floating pieces fall straight down until they rest, at most maxDrop voxels (0: all the way); pieces: before the fall, drops: how far each fell
+		public const int CVX_SETTLE_UNLIMITED = 0;
+		[DllImport(Lib)] public static extern int cvx_world_settle(IntPtr ctx, int* boxMin, int* boxMax, int anchors, int maxDrop, int levelCount, Piece* pieces,
+		                                                           int* drops, int pieceCapacity, SettleSummary* summary, out float outDeviceMs);
 		// sky occlusion and a sun shadow baked into the solid voxels of LOD 0 inside a box (from occupancy alone) + its LOD refresh
 		[DllImport(Lib)] public static extern int cvx_world_light(IntPtr ctx, LightParams* lightParams, int levelCount, out float outDeviceMs);
 		// boxes moved through LOD 0 with collision, sliding and step-up (host arrays; device arrays with lanesPerBody 0 / 1 / 4 / 16 / 64, enqueued only)

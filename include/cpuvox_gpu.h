@@ -520,6 +520,47 @@ typedef struct cvx_pieces_summary { /* 32 bytes */
 int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, int op, int levelCount, cvx_piece *pieces,
                      int pieceCapacity, cvx_pieces_summary *summary, float *outDeviceMs);
 
+/* ---- letting the floating pieces of the uploaded world fall ---------------------------------------------------------------------------------
+ * cvx_world_settle: the floating pieces of cvx_world_pieces fall straight down until they rest (voxlap makes its loose pieces fall; the call a
+ * host makes after a carve instead of CVX_PIECES_REMOVE).  Let W be LOD 0 before the call.
+ *   Which pieces.  The floating pieces F_1 .. F_m are exactly the list cvx_world_pieces(..., CVX_PIECES_REPORT, ...) gives for the same box and
+ *     anchors: the same clipping, anchor rules and order.  pieces[i] (may be NULL iff pieceCapacity = 0) describes F_i BEFORE the fall, the same
+ *     bytes as REPORT; drops[i] (drops may be NULL) is how many voxels F_i fell.  Both receive the first min(pieceCapacity, m) entries; a smaller
+ *     capacity is not an error, and all pieces fall whatever the capacity.
+ *   Static.  Every solid voxel of W that belongs to no floating piece is static -- anywhere in its column, inside or outside the box -- and so is
+ *     everything at y < 0.
+ *   The fall, as unit steps.  Repeat: let M be the largest set of floating pieces such that every voxel (x, y, z) of a piece of M, at its current
+ *     place, has y > 0 and (x, y - 1, z) is air or a voxel of a piece of M.  If M is empty, or maxDrop steps have been made
+ *     (CVX_SETTLE_UNLIMITED: no bound), stop; otherwise every piece of M moves down by one.  Pieces are rigid: they never rotate or break, and they
+ *     move in y only.
+ *   Closed form (what the device computes).  For every node of a floating piece p (a solid run clipped to the box's y range) take the next solid
+ *     voxel below it in its column, g >= 0 voxels of air away.  Static (the floor counts, with g = the node's lowest y): d_p <= g.  A voxel of
+ *     another floating piece q: d_p <= d_q + g.  A voxel of p itself: no constraint.  d is the largest solution, i.e. the shortest-path distance
+ *     to "static" in the piece graph (which may hold cycles: interlocked pieces fall and stop together), and drop = min(d, maxDrop).  The unit
+ *     steps never violate a constraint and stop only when every piece has a tight chain down to something static, so both give the same drops.
+ *   Result.  Static voxels stay; voxel (x, y, z) of F_i moves to (x, y - drop_i, z) with its colour word verbatim (a baked shade travels with it:
+ *     relight with cvx_world_light); runs that come to touch merge.
+ *   Animation.  A piece that has fallen only part of the way is still floating: k calls with maxDrop = 1 equal one call with maxDrop = k.
+ *   Torn pieces.  As with CVX_PIECES_REMOVE, without CVX_ANCHOR_OUTSIDE a "piece" may be the clipped part of a larger structure, and it is torn
+ *     from it: the part of a run above the box's top stays while the part inside falls.  A run that crosses the box's BOTTOM leaves its lower part
+ *     static directly beneath the node (g = 0): that piece does not move.
+ * Mechanics as CVX_PIECES_REMOVE: the rectangle is the XZ bounding box of the pieces with drop > 0 rounded outward to multiples of 2^levelCount
+ * and clipped to the world, LOD 1 .. levelCount (0 .. 5) are rebuilt over it, and columns of it that nothing moves in are re-encoded with the
+ * builder's rule.  Nothing falls: CVX_OK, the arena is untouched.  `summary` (may be NULL): floatingPieces / floatingVoxels as cvx_pieces_summary,
+ * fallenPieces / fallenVoxels those with drop > 0, largestDrop.  outDeviceMs (may be NULL): device time of the analysis and, when something
+ * falls, the edit.  Ordering, atomicity and several GPUs as cvx_world_brush; every error leaves the world as it was.  Errors are those of
+ * cvx_world_pieces (its bad op aside), and CVX_ERR_INVALID_ARGUMENT for maxDrop < 0.  Device memory while it runs: cvx_world_pieces' and 16 more
+ * bytes per solid run inside the box. */
+#define CVX_SETTLE_UNLIMITED 0
+typedef struct cvx_settle_summary { /* 40 bytes */
+	int64_t floatingPieces, floatingVoxels; /* as cvx_pieces_summary */
+	int64_t fallenPieces, fallenVoxels;     /* those with drop > 0 */
+	int32_t largestDrop;
+	int32_t pad_;
+} cvx_settle_summary;
+int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, int maxDrop, int levelCount, cvx_piece *pieces,
+                     int32_t *drops, int pieceCapacity, cvx_settle_summary *summary, float *outDeviceMs);
+
 /* ---- lighting the uploaded world: sky occlusion and sun shadows ----------------------------------------------------------------------------
  * cvx_world_light: bakes a shade, an integer 0 .. 255, into every solid LOD-0 voxel v inside [boxMin, boxMax) clipped to the world (voxlap's
  * updatelighting: the call a host makes after an edit).  The shade is computed from occupancy alone -- no colour is read for it, no occupancy

@@ -21,6 +21,11 @@ int cvx_debug_occupancy(cvx_context *ctx, int64_t ldsBytes, int *blocksPerCU);
  * wave.  CVX_ERR_NOT_READY before the first draw and in the other builds. */
 int cvx_debug_last_launch(cvx_context *ctx, int64_t out[8]);
 
+/* cvx_world_settle's last call in this process (tools/settle_bench.py): outMs (may be NULL) = device ms of the analysis, of gap + relax, of the
+ * edit; outCounts (may be NULL) = solid runs in the box (-1: no call yet), relax sweeps, relax launches, 1 if one workgroup relaxed the box.
+ * oneSweepPerLaunch 1 / 0: later calls relax with one sweep per launch and a host round trip between / as the product does; -1: leave it. */
+int cvx_debug_settle(cvx_context *ctx, int oneSweepPerLaunch, float outMs[3], int64_t outCounts[4]);
+
 /* Diagnostic build only (make gpu-prof, -DCVX_PROFILE_SECTIONS): wave cycles spent per code section of the
  * render kernel (s_memtime stamps), accumulated over all launches.  Sections: 0 prologue/epilogue, 1 phase A
  * (DDA step + header + cull), 2 frustum clip, 3 element walk, 4 side-face setup, 5 side-face pixels,
