@@ -24,7 +24,7 @@
 #include <climits>
 
 #include "cvx_context.h"
-#include "cvx_light.h"
+#include "cvx_lamps.h"
 
 using cvxi::Fail;
 
@@ -40,6 +40,8 @@ struct LightArgs {
 	uint32_t *headers;             // the sub-world blob, n headers of 3 words
 	uint32_t *elements;
 	int tilesZ, brickSide, brickStride; // brick kernel: tiles per row of the box, columns per side of the brick, words per row
+	const cvx_lamp *lamps;         // cvx_world_light_lamps: the call's lamps on the device (lampCount 0: none, the kernels of cvx_world_light run)
+	int lampCount;
 };
 
 template <class Recolour>
@@ -78,7 +80,11 @@ __global__ __launch_bounds__(256) void light_write_kernel(LightArgs A)
 	if (i >= A.n) { return; }
 	const int cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
 #ifdef CVX_LIGHT_RECORDS
-	WriteColumn(A, i, cx, cz, cvxb::LightFromRecords{ cvxb::ArenaOcc{ A.W }, A.B, A.P, cx, cz });
+	if (A.lampCount > 0) {
+		WriteColumn(A, i, cx, cz, cvxb::LightLampsFromRecords{ cvxb::ArenaOcc{ A.W }, A.B, A.P, cx, cz, A.lamps, A.lampCount });
+	} else {
+		WriteColumn(A, i, cx, cz, cvxb::LightFromRecords{ cvxb::ArenaOcc{ A.W }, A.B, A.P, cx, cz });
+	}
 #else
 	WriteColumn(A, i, cx, cz, cvxb::LightKeep{});
 #endif
@@ -90,6 +96,7 @@ constexpr int kTile = 16;            // columns per side of a workgroup's tile
 constexpr int kSlab = 32;            // voxels of y shaded per pass; the brick holds kSlab + 32 = 64 of them
 constexpr int kThreads = kTile * kTile;
 constexpr int kList = 2048;          // voxels compacted per round
+constexpr int kLampList = 256;       // lamps a tile-slab's cull keeps in LDS per round (tests/test_gpu_world_lamps.py reads this constant)
 
 // occupancy inside the brick, no checks: the sky directions of a voxel of the slab never leave it
 struct BrickNear {
@@ -113,6 +120,54 @@ struct BrickAny {
 // bits lo .. hi - 1 (0 <= lo < hi <= 64)
 __device__ __forceinline__ unsigned long long BitSpan(int lo, int hi) { return (~0ull >> (64 - (hi - lo))) << lo; }
 
+// The lamps of the call that reach the range lo .. hi (inclusive voxels): a lamp reaches it when its cube [L - (r - 1), L + (r - 1)] meets it (a
+// voxel with d2 < r2 has every |D_i| <= r - 1).  Block-wide: every thread tests a contiguous share of the lamps and counts, an exclusive scan
+// numbers the survivors, and those numbered first .. first + kLampList - 1 are written to `out` (x, y, z, radius << 8 | level).  Returns the
+// number of survivors.  A lamp of level 0 contributes nothing anywhere and is dropped here.
+__device__ __forceinline__ bool LampReaches(const cvx_lamp &l, const int *lo, const int *hi)
+{
+	const int r = l.radius - 1;
+	return l.level > 0 && l.pos[0] + r >= lo[0] && l.pos[0] - r <= hi[0] && l.pos[1] + r >= lo[1] && l.pos[1] - r <= hi[1] && l.pos[2] + r >= lo[2] && l.pos[2] - r <= hi[2];
+}
+
+__device__ __forceinline__ int CullLamps(const LightArgs &A, const int *lo, const int *hi, int first, int4 *out, uint32_t *waveSum)
+{
+	const int tid = threadIdx.x;
+	const int share = (A.lampCount + kThreads - 1) / kThreads;
+	const int from = min(tid * share, A.lampCount), to = min(from + share, A.lampCount);
+	uint32_t before = 0u;
+	for (int l = from; l < to; l++) { before += LampReaches(A.lamps[l], lo, hi) ? 1u : 0u; }
+	const uint32_t cnt = before;
+	for (int d = 1; d < CVX_WAVE; d <<= 1) {
+		const uint32_t up = __shfl_up(before, d);
+		if ((tid & (CVX_WAVE - 1)) >= d) { before += up; }
+	}
+	if ((tid & (CVX_WAVE - 1)) == CVX_WAVE - 1) { waveSum[tid / CVX_WAVE] = before; }
+	__syncthreads(); // (also: every lane has finished with the list of the round before)
+	uint32_t total = 0u;
+	before -= cnt;
+	for (int w = 0; w < kThreads / CVX_WAVE; w++) {
+		if (w < tid / CVX_WAVE) { before += waveSum[w]; }
+		total += waveSum[w];
+	}
+	if (cnt != 0u) {
+		uint32_t at = before - (uint32_t)first; // (wraps below `first`: the unsigned comparison drops those too)
+		for (int l = from; l < to; l++) {
+			const cvx_lamp lamp = A.lamps[l];
+			if (!LampReaches(lamp, lo, hi)) { continue; }
+			if (at < (uint32_t)kLampList) { out[at] = make_int4(lamp.pos[0], lamp.pos[1], lamp.pos[2], (lamp.radius << 8) | lamp.level); }
+			at++;
+		}
+	}
+	__syncthreads();
+	return (int)total;
+}
+
+// kLamps false: cvx_world_light's kernel.  true: after the slab's brick is expanded the workgroup culls the call's lamps against the slab's part of
+// the tile and the box (CullLamps), and every voxel lane adds the terms of the survivors to its shade before the one min.  More than kLampList
+// survivors are taken kLampList at a time, the partial sum carried in the lane's register: the voxels are shaded 256 at a time (one per lane)
+// and the list is rebuilt per round for each 256 -- the rare case pays, the common one (one round) culls once per slab.
+template <bool kLamps>
 __global__ __launch_bounds__(kThreads) void light_brick_kernel(LightArgs A)
 {
 	extern __shared__ unsigned long long brick[];   // brickSide rows of brickStride words
@@ -120,6 +175,8 @@ __global__ __launch_bounds__(kThreads) void light_brick_kernel(LightArgs A)
 	__shared__ uint32_t colourAt[kThreads];         // per tile column: the element of its first solid voxel at or below the slab's top
 	__shared__ uint32_t waveSum[kThreads / CVX_WAVE];
 	__shared__ int tileLo, tileHi;
+	__shared__ int4 lampList[kLamps ? kLampList : 1];
+	__shared__ uint32_t lampWaveSum[kThreads / CVX_WAVE];
 
 	const int tid = threadIdx.x;
 	const int halo = A.P.skyRange, side = A.brickSide, stride = A.brickStride;
@@ -195,6 +252,12 @@ __global__ __launch_bounds__(kThreads) void light_brick_kernel(LightArgs A)
 			if (w < tid / CVX_WAVE) { before += waveSum[w]; }
 			total += waveSum[w];
 		}
+		int lampLo[3] = { 0, 0, 0 }, lampHi[3] = { 0, 0, 0 }, survivors = 0;
+		if constexpr (kLamps) { // the lamps that reach this slab's part of the tile and the box
+			lampLo[0] = tx0, lampLo[1] = ys, lampLo[2] = tz0;
+			lampHi[0] = min(tx0 + kTile, A.B.x1) - 1, lampHi[1] = ys + top - 1, lampHi[2] = min(tz0 + kTile, A.B.z1) - 1;
+			survivors = total != 0u ? CullLamps(A, lampLo, lampHi, 0, lampList, lampWaveSum) : 0;
+		}
 		// 3. shade, kList voxels per round
 		BrickNear slabNear = near;
 		slabNear.oy = ys;
@@ -206,13 +269,36 @@ __global__ __launch_bounds__(kThreads) void light_brick_kernel(LightArgs A)
 			}
 			__syncthreads();
 			const uint32_t here = min(total - base, (uint32_t)kList);
-			for (uint32_t j = tid; j < here; j += kThreads) {
-				const int entry = list[j], t = entry >> 5, b = entry & 31;
-				const int x = tx0 + t / kTile, z = tz0 + t % kTile, y = ys + b;
-				const int shade = cvxb::VoxelShade(slabNear, any, dims, A.P, x, y, z);
-				const uint32_t w32 = (uint32_t)brick[(t / kTile + halo) * stride + (t % kTile + halo)];
-				uint32_t *c = A.elements + colourAt[t] + __popc((w32 >> 1) >> b);
-				*c = cvxb::ApplyShade(*c, shade, A.P.target);
+			if constexpr (!kLamps) {
+				for (uint32_t j = tid; j < here; j += kThreads) {
+					const int entry = list[j], t = entry >> 5, b = entry & 31;
+					const int x = tx0 + t / kTile, z = tz0 + t % kTile, y = ys + b;
+					const int shade = cvxb::VoxelShade(slabNear, any, dims, A.P, x, y, z);
+					const uint32_t w32 = (uint32_t)brick[(t / kTile + halo) * stride + (t % kTile + halo)];
+					uint32_t *c = A.elements + colourAt[t] + __popc((w32 >> 1) >> b);
+					*c = cvxb::ApplyShade(*c, shade, A.P.target);
+				}
+			} else {
+				for (uint32_t j0 = 0u; j0 < here; j0 += kThreads) { // (uniform: CullLamps synchronises the workgroup)
+					const uint32_t j = j0 + tid;
+					const bool live = j < here;
+					const int entry = live ? list[j] : 0, t = entry >> 5, b = entry & 31;
+					const int x = tx0 + t / kTile, z = tz0 + t % kTile, y = ys + b;
+					int shade = live ? cvxb::VoxelShade(slabNear, any, dims, A.P, x, y, z) : 255;
+					for (int first = 0; first < survivors; first += kLampList) {
+						if (survivors > kLampList) { (void)CullLamps(A, lampLo, lampHi, first, lampList, lampWaveSum); }
+						const int n = min(survivors - first, kLampList);
+						for (int l = 0; l < n && shade < 255; l++) {
+							const int4 lamp = lampList[l];
+							shade += cvxb::LampVoxelTerm(any, x, y, z, lamp.x, lamp.y, lamp.z, lamp.w >> 8, lamp.w & 255);
+						}
+					}
+					if (live) {
+						const uint32_t w32 = (uint32_t)brick[(t / kTile + halo) * stride + (t % kTile + halo)];
+						uint32_t *c = A.elements + colourAt[t] + __popc((w32 >> 1) >> b);
+						*c = cvxb::ApplyShade(*c, min(shade, 255), A.P.target);
+					}
+				}
 			}
 			__syncthreads();
 		}
@@ -230,11 +316,13 @@ unsigned Grid(size_t n, unsigned threads = 256) { return (unsigned)((n + threads
 
 } // namespace
 
-extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params, int levelCount, float *outDeviceMs)
+// cvx_world_light (lamps NULL, lampCount 0) and cvx_world_light_lamps
+static int Light(cvx_context *ctx, const cvx_light_params *params, const cvx_lamp *lamps, int lampCount, int levelCount, float *outDeviceMs)
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (!params) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "params is NULL"); }
 	if (const char *what = cvxb::LightParamsError(*params)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "cvx_light_params: bad %s", what); }
+	if (const char *what = cvxb::LampParamsError(lamps, lampCount)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "cvx_lamp: bad %s (lampCount %d)", what, lampCount); }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
 	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
 	const int dimX = ctx->hostWorld.dimX, dimY = ctx->hostWorld.dimY, dimZ = ctx->hostWorld.dimZ;
@@ -265,7 +353,7 @@ extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params,
 	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	size_t bytes = 0;
 	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
-	const size_t oCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8);
+	const size_t oCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8), oLamps = carve((size_t)lampCount * sizeof(cvx_lamp));
 	struct { unsigned long long total, overLimit; } host = { 0, 0 };
 	cvxlight::LightArgs A{};
 	hipError_t e = hipEventCreate(&ev[0]);
@@ -292,10 +380,13 @@ extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params,
 		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
 		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
 		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
+		A.lamps = reinterpret_cast<const cvx_lamp *>(scratch + oLamps);
+		A.lampCount = lampCount;
+		if (lampCount > 0) { e = hipMemcpyAsync(scratch + oLamps, lamps, (size_t)lampCount * sizeof(cvx_lamp), hipMemcpyHostToDevice, ctx->stream); }
 		// count, scan, one copy back
 		hipLaunchKernelGGL(cvxlight::light_count_kernel, dim3(Grid((size_t)n)), dim3(256), 0, ctx->stream, A);
 		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
-		e = hipGetLastError();
+		if (e == hipSuccess) { e = hipGetLastError(); }
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	}
@@ -324,7 +415,11 @@ extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params,
 		A.brickSide = cvxlight::kTile + 2 * params->skyRange;
 		A.brickStride = A.brickSide | 1;
 		const size_t lds = (size_t)A.brickSide * A.brickStride * 8;
-		hipLaunchKernelGGL(cvxlight::light_brick_kernel, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
+		if (lampCount > 0) {
+			hipLaunchKernelGGL(cvxlight::light_brick_kernel<true>, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
+		} else {
+			hipLaunchKernelGGL(cvxlight::light_brick_kernel<false>, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
+		}
 #endif
 		e = hipGetLastError();
 	}
@@ -340,4 +435,14 @@ extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params,
 	}
 	release();
 	return rc;
+}
+
+extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params, int levelCount, float *outDeviceMs)
+{
+	return Light(ctx, params, nullptr, 0, levelCount, outDeviceMs);
+}
+
+extern "C" int cvx_world_light_lamps(cvx_context *ctx, const cvx_light_params *params, const cvx_lamp *lamps, int lampCount, int levelCount, float *outDeviceMs)
+{
+	return Light(ctx, params, lamps, lampCount, levelCount, outDeviceMs);
 }

@@ -33,7 +33,7 @@ EXPORTS = [
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
     "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces", "cvx_world_settle",
-    "cvx_world_light", "cvx_world_move", "cvx_world_move_device",
+    "cvx_world_light", "cvx_world_light_lamps", "cvx_world_move", "cvx_world_move_device",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -68,6 +68,7 @@ PIECES_REPORT, PIECES_REMOVE = 0, 1              # cvx_world_pieces: op
 ANCHOR_GROUND, ANCHOR_OUTSIDE, ANCHOR_LARGEST = 1, 2, 4  # ... anchors (bits)
 SETTLE_UNLIMITED = 0                             # cvx_world_settle: maxDrop
 LIGHT_TO_RGB, LIGHT_TO_ALPHA = 0, 1              # cvx_light_params.target
+LIGHT_MAX_LAMPS, LAMP_MAX_RADIUS = 4096, 64      # cvx_world_light_lamps
 MOVE_UNIT = 256                                  # cvx_move_body: position units per LOD-0 voxel
 MOVE_SOLID_BELOW, MOVE_SOLID_SIDES = 1, 2        # cvx_move_body.flags
 MOVED_BLOCKED_MASK, MOVED_RESTING, MOVED_STARTS_SOLID, MOVED_STEPPED, MOVED_INVALID = 0x3F, 1 << 6, 1 << 7, 1 << 8, -(1 << 31)  # cvx_move_result.flags
@@ -107,6 +108,10 @@ class SettleSummary(C.Structure):  # cvx_settle_summary
 class LightParams(C.Structure):  # cvx_light_params
     _fields_ = [("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("sunDir", C.c_int32 * 3), ("sunLevel", C.c_int32), ("sunRange", C.c_int32),
                 ("skyLevel", C.c_int32), ("skyRange", C.c_int32), ("floorLevel", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
+
+
+class Lamp(C.Structure):  # cvx_lamp
+    _fields_ = [("pos", C.c_int32 * 3), ("radius", C.c_int32), ("level", C.c_int32), ("pad_", C.c_int32 * 3)]
 
 
 class MoveBody(C.Structure):  # cvx_move_body
@@ -162,6 +167,18 @@ def bodies_array(bodies) -> np.ndarray:
         out[i]["delta"] = b.get("delta", (0, 0, 0))
         out[i]["stepUp"] = b.get("stepUp", 0)
         out[i]["flags"] = b.get("flags", 0)
+    return out
+
+
+def lamps_array(lamps):
+    """A list of (pos, radius, level) or of dicts {pos, radius, level} -> a ctypes array of Lamp (cvx_world_light_lamps)."""
+    out = (Lamp * len(lamps))()
+    for i, lamp in enumerate(lamps):
+        pos, radius, level = (lamp["pos"], lamp["radius"], lamp["level"]) if isinstance(lamp, dict) else lamp
+        if len(pos) != 3:
+            raise ValueError("a lamp's pos is three integers")
+        out[i].pos[:] = [int(v) for v in pos]
+        out[i].radius, out[i].level = int(radius), int(level)
     return out
 
 
@@ -311,6 +328,7 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_settle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                        C.POINTER(C.c_float)]
         L.cvx_world_light.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_int, C.POINTER(C.c_float)]
+        L.cvx_world_light_lamps.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_move.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.cvx_world_move_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.cvx_free.restype = None
@@ -550,6 +568,21 @@ class Context:
                         sun_level, sun_range, sky_level, sky_range, floor_level, target, 0)
         ms = C.c_float()
         self._check(lib().cvx_world_light(self._h, C.byref(p), level_count, C.byref(ms)))
+        return ms.value
+
+    def world_light_lamps(self, box_min, box_max, lamps, *, sun_dir=(0, 0, 0), sun_level: int = 0, sun_range: int = 0, sky_level: int = 0,
+                          sky_range: int = 0, floor_level: int = 0, target: int = LIGHT_TO_RGB, level_count: int = LOD_LEVELS - 1) -> float:
+        """world_light with point lights in the same bake: `lamps` is a list of (pos, radius, level) or of dicts {pos, radius, level} -- pos the
+        LOD-0 voxel at whose centre the lamp sits (anywhere, also outside the world), radius 1 .. LAMP_MAX_RADIUS voxels, level 0 .. 255, at most
+        LIGHT_MAX_LAMPS of them.  A lit voxel with an air face towards a lamp it sees gains level * (1 - (d / radius)^2) * facing / den; the terms of
+        all lamps are summed before the one min(255, ...).  No lamps: exactly world_light.  Returns the device milliseconds."""
+        if len(box_min) != 3 or len(box_max) != 3 or len(sun_dir) != 3:
+            raise ValueError("world_light_lamps: box_min, box_max and sun_dir are three integers each")
+        p = LightParams((C.c_int32 * 3)(*[int(v) for v in box_min]), (C.c_int32 * 3)(*[int(v) for v in box_max]), (C.c_int32 * 3)(*[int(v) for v in sun_dir]),
+                        sun_level, sun_range, sky_level, sky_range, floor_level, target, 0)
+        arr = lamps_array(lamps)
+        ms = C.c_float()
+        self._check(lib().cvx_world_light_lamps(self._h, C.byref(p), arr if len(arr) else None, len(arr), level_count, C.byref(ms)))
         return ms.value
 
     def world_move(self, bodies) -> np.ndarray:

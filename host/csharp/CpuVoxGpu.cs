@@ -137,6 +137,16 @@ namespace CpuVox.Gpu
 		public int SunLevel, SunRange, SkyLevel, SkyRange, FloorLevel, Target, Pad;
 	}
 
+	// cvx_world_light_lamps: a point light (32 bytes).  Pos is the LOD-0 voxel at whose centre the lamp sits (anywhere, |.| <= 2^20); Radius 1 .. 64
+	// voxels; Level 0 .. 255.  Lamps are white.
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct Lamp
+	{
+		public fixed int Pos[3];
+		public int Radius, Level;
+		public fixed int Pad[3];
+	}
+
 	// cvx_world_move: a body (48 bytes) and its result (16 bytes), in units of 1 / 256 LOD-0 voxel.  Pos is the box's min corner; Size 1 .. 64 * 256
 	// per axis; |Delta| <= 256 * 256; StepUp 0 .. 4 * 256; Flags: 1 = solid below y 0, 2 = solid beyond the tile's sides.  Result flags: bits 0 .. 5
 	// stopped going -X, +X, -Y, +Y, -Z, +Z; 64 resting, 128 started inside solid, 256 stepped up, 1 << 31 a body outside the limits (device call)
@@ -232,6 +242,10 @@ namespace CpuVox.Gpu
 		                                                           int* drops, int pieceCapacity, SettleSummary* summary, out float outDeviceMs);
 		// sky occlusion and a sun shadow baked into the solid voxels of LOD 0 inside a box (from occupancy alone) + its LOD refresh
 		[DllImport(Lib)] public static extern int cvx_world_light(IntPtr ctx, LightParams* lightParams, int levelCount, out float outDeviceMs);
+		// ... with point lights in the same bake (at most CVX_LIGHT_MAX_LAMPS; lampCount 0: cvx_world_light)
+		public const int CVX_LIGHT_MAX_LAMPS = 4096, CVX_LAMP_MAX_RADIUS = 64;
+		[DllImport(Lib)] public static extern int cvx_world_light_lamps(IntPtr ctx, LightParams* lightParams, Lamp* lamps, int lampCount, int levelCount,
+		                                                                out float outDeviceMs);
 		// boxes moved through LOD 0 with collision, sliding and step-up (host arrays; device arrays with lanesPerBody 0 / 1 / 4 / 16 / 64, enqueued only)
 		public const int CVX_MOVE_UNIT = 256, CVX_MOVE_SOLID_BELOW = 1, CVX_MOVE_SOLID_SIDES = 2;
 		public const int CVX_MOVED_BLOCKED_MASK = 0x3F, CVX_MOVED_RESTING = 1 << 6, CVX_MOVED_STARTS_SOLID = 1 << 7, CVX_MOVED_STEPPED = 1 << 8, CVX_MOVED_INVALID = int.MinValue;

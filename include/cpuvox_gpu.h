@@ -601,6 +601,35 @@ typedef struct cvx_light_params { /* 64 bytes */
 } cvx_light_params;
 int cvx_world_light(cvx_context *ctx, const cvx_light_params *params, int levelCount, float *outDeviceMs);
 
+/* cvx_world_light_lamps: cvx_world_light with point lights (voxlap's vx5.lightsrc: torches, lamps, a flash baked after an explosion).  The bake
+ * is one-shot, so a lamp cannot be added by a second call: its term goes into the same sum before the one min.  Everything cvx_world_light
+ * documents holds (mechanics, ordering, atomicity, rectangle rounding, outDeviceMs, box clipping, errors; a box outside the world: CVX_OK and
+ * 0 ms); with lampCount == 0 (lamps may be NULL then) the call gives the bytes cvx_world_light gives.  Lamps are white.
+ * The rule, exact integers from end to end, for solid voxel v inside the clipped box and lamp l at voxel L (its CENTRE), D = L - v, d2 = |D|^2,
+ * r2 = radius^2:
+ *   1. D = 0 or d2 >= r2: the term is 0.
+ *   2. facing = the sum of |D_i| over the axes with D_i != 0 whose face neighbour v + sgn(D_i) * e_i is air, den = the sum of all |D_i| (the
+ *      sun's rule with S = D).
+ *   3. The shadow walk is the sun's walk from the centre of v along D (plane crossings at (2k - 1) / |D_i|, all axes that tie advance
+ *      together).  It ends when it ARRIVES at voxel L, which it does exactly, after at most |D_x| + |D_y| + |D_z| steps.  Every voxel reached
+ *      before L is tested: outside the world is air and the walk goes on, a solid voxel means shadowed.  L itself is never tested: a lamp set
+ *      into a wall lights the room.
+ *   4. term_l = lit ? level * (r2 - d2) * facing / (r2 * den) : 0, ONE floored division (a falloff of 1 - (d / r)^2).
+ *   5. shade = min(255, floorLevel + skyTerm + sunTerm + the sum of term_l over ALL lamps): an integer sum before one min, so no lamp order and
+ *      no schedule shows in the result.
+ * A lamp may lie in a solid voxel, in air, outside the box or outside the world.  CVX_ERR_INVALID_ARGUMENT besides cvx_world_light's (all
+ * checked on the host before anything is enqueued): lampCount outside 0 .. CVX_LIGHT_MAX_LAMPS, lamps NULL with lampCount > 0, a radius outside
+ * 1 .. CVX_LAMP_MAX_RADIUS, a level outside 0 .. 255, a |pos| component above 2^20. */
+#define CVX_LIGHT_MAX_LAMPS   4096
+#define CVX_LAMP_MAX_RADIUS   64
+typedef struct cvx_lamp {     /* 32 bytes */
+	int32_t pos[3];           /* the LOD-0 voxel whose CENTRE the lamp sits at; may lie outside the world or the box; |.| <= 2^20 */
+	int32_t radius;           /* 1 .. 64 voxels */
+	int32_t level;            /* 0 .. 255 */
+	int32_t pad_[3];
+} cvx_lamp;
+int cvx_world_light_lamps(cvx_context *ctx, const cvx_light_params *params, const cvx_lamp *lamps, int lampCount, int levelCount, float *outDeviceMs);
+
 /* ---- moving boxes through the uploaded world: collision and sliding ------------------------------------------------------------------------
  * cvx_world_move: moves axis-aligned boxes (players, NPCs, debris) through LOD 0 without entering solid voxels (voxlap's clipmove: the call a
  * host makes every frame).  The rule is integer from end to end (cvx_move.h): positions, sizes and displacements are in units of 1 / CVX_MOVE_UNIT

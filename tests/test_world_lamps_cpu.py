@@ -1,0 +1,334 @@
+"""CPU (no GPU needed): the rules behind cvx_world_light_lamps (cpuvox_amd/csrc/cvx_lamps.h), compiled for the host through tests/lamp_rules.cpp
+(every occupancy test answered from the records), against the independent dense model of tests/lampmodel.py.
+
+- Column mode: 2000 random small worlds (the generator of tests/test_world_light_cpu.py, seed 4051) with 0 .. 8 lamps each -- inside solid voxels,
+  in air, outside the world, on the box's faces; radii 1, 2, 64 and random; D exactly axis-parallel, exactly diagonal, near-diagonal; levels 0, 255
+  and random; both targets and random sky / sun parameters, so that the min(255, ...) saturates in some cases and not in others: every emitted
+  column must equal the model's exactly.  The coverage conditions are asserted from the model BEFORE anything is compared.
+- Constructed cases whose terms are derived by hand and asserted as literals.
+- lampCount == 0 gives the bytes of the cvx_world_light rule (tests/light_rules.cpp on the same cases).
+- The struct layout of the header against the ctypes and C# mirrors; every INVALID_ARGUMENT case on a context without a world."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import lampmodel
+import lightmodel
+import pyworld
+from cpuvox_amd import gpu
+from test_world_brush_cpu import _random_column
+from test_world_light_cpu import random_params
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def rules(tmp_path_factory):
+    """{"lamp": tests/lamp_rules.cpp, "light": tests/light_rules.cpp}, built for the host."""
+    out = {}
+    for name in ("lamp", "light"):
+        out[name] = str(tmp_path_factory.mktemp(name) / f"{name}_rules")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
+                               os.path.join(ROOT, "tests", f"{name}_rules.cpp"), "-o", out[name], f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
+                               f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
+    return out
+
+
+DIRECTIONS = {
+    "axis": [(1, 0, 0), (0, 1, 0), (0, 0, 1)],
+    "diagonal": [(1, 1, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1)],
+    "near": [(31, 32, 1), (44, 45, 1), (1, 2, 3), (63, 64, 1)],   # (63, 64, 1): d2 = 8066 >= 64^2, out of every lamp's range
+}
+
+
+def random_lamps(rng, solid, p, most):
+    """0 .. most lamps for a call with parameters p on the world `solid` (the GPU test uses them too): placed in solid voxels, in air, outside the
+    world, on the clipped box's faces, and at chosen D from a solid voxel of the box (axis-parallel, exactly diagonal, near-diagonal)."""
+    dims = solid.shape
+    lo, hi = lightmodel.clip_box(dims, p["box_min"], p["box_max"])
+    sx, sy, sz = np.nonzero(solid)
+    inside = np.nonzero((sx >= lo[0]) & (sx < hi[0]) & (sy >= lo[1]) & (sy < hi[1]) & (sz >= lo[2]) & (sz < hi[2]))[0]
+    lamps = []
+    for _ in range(int(rng.integers(0, most + 1))):
+        radius = int(rng.choice([1, 2, 64, int(rng.integers(1, 65)), int(rng.integers(2, 12))]))
+        level = int(rng.choice([0, 255, 255, int(rng.integers(0, 256)), int(rng.integers(0, 256))]))
+        kind = int(rng.integers(0, 8))
+        if kind == 0 and len(sx):      # inside a solid voxel
+            k = int(rng.integers(0, len(sx)))
+            pos = [int(sx[k]), int(sy[k]), int(sz[k])]
+        elif kind == 1:                # anywhere in the world: mostly air
+            pos = [int(rng.integers(0, dims[a])) for a in range(3)]
+        elif kind == 2:                # outside the world
+            pos = [int(rng.integers(-3, dims[a] + 3)) for a in range(3)]
+            a = int(rng.integers(0, 3))
+            pos[a] = int(rng.choice([-1 - int(rng.integers(0, 5)), dims[a] + int(rng.integers(0, 5))]))
+        elif kind == 3:                # on a face of the clipped box
+            pos = [int(rng.integers(lo[a], hi[a])) for a in range(3)]
+            a = int(rng.integers(0, 3))
+            pos[a] = int(rng.choice([lo[a], hi[a] - 1]))
+        elif len(inside):              # at a chosen D from a solid voxel of the box
+            k = int(inside[int(rng.integers(0, len(inside)))])
+            base = DIRECTIONS[["axis", "diagonal", "near", "near"][kind - 4]]
+            d = [int(c) for c in rng.permutation(base[int(rng.integers(0, len(base)))])]
+            m = 1 if kind >= 6 else int(rng.integers(1, 12))
+            d = [c * m * int(rng.choice([-1, 1])) for c in d]
+            pos = [int(sx[k]) + d[0], int(sy[k]) + d[1], int(sz[k]) + d[2]]
+            if kind >= 6:
+                radius = 64
+            elif rng.random() < 0.7:
+                radius = min(64, max(abs(c) for c in d) * int(rng.integers(1, 3)) + 1)
+        else:
+            pos = [int(rng.integers(0, dims[a])) for a in range(3)]
+        lamps.append(lampmodel.lamp(pos, radius, level))
+    return lamps
+
+
+# ---- column mode -------------------------------------------------------------------------------------------------------------------------------
+
+def _model_case(solid, colour, p, lamps):
+    lit = lampmodel.light(solid, colour, p, lamps)
+    gx, dim_y, gz = solid.shape
+    columns = []
+    for x in range(gx):
+        for z in range(gz):
+            ys = np.nonzero(solid[x, :, z])[0][::-1]
+            col = pyworld.final_column([(int(y), int(lit[x, y, z])) for y in ys], dim_y - 1, 1)
+            if col is None:
+                columns.append((False, [], [], 0, 0))
+                continue
+            runs, colours, wmin, wmax = col
+            columns.append((False, [((ci & 0xFFFF) | (n << 16)) for ci, n in runs], list(colours), wmin, wmax))
+    return columns
+
+
+def _run_columns(binary, tmp_path, cases, with_lamps=True):
+    words = []
+    for dim_y, gx, gz, stride, columns, p, lamps in cases:
+        words += [dim_y, gx, gz, stride]
+        for base, runs, colours in columns:
+            words += [base, len(runs)]
+            for ci, n in runs:
+                words += [ci, n]
+            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
+        words += lightmodel.words(p)
+        if with_lamps:
+            words += lampmodel.words(lamps)
+    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
+    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
+    subprocess.check_call([binary, "columns", str(src), str(dst)])
+    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+    results, at = [], 0
+    for dim_y, gx, gz, *_ in cases:
+        columns = []
+        for _ in range(gx * gz):
+            over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
+            at += 5
+            if over:
+                columns.append((True, None, None, None, None))
+                continue
+            runs = out[at:at + rc].tolist()
+            at += rc
+            colours = out[at:at + nc].tolist()
+            at += nc
+            columns.append((False, runs, colours, wmin, wmax))
+        results.append(columns)
+    assert at == len(out)
+    return results
+
+
+def _random_world(rng):
+    """A world of the generator of test_world_light_cpu: up to 4 x 4 random columns (1 .. 3 runs and listed, split runs, shared colours)."""
+    dim_y = int(rng.choice([8, 16, 64, 256]))
+    gx, gz = int(rng.integers(1, 5)), int(rng.integers(1, 5))
+    stride = int(rng.choice([1, 32]))
+    solid = np.zeros((gx, dim_y, gz), dtype=bool)
+    colour = np.zeros((gx, dim_y, gz), dtype=np.uint32)
+    columns = []
+    for k in range(gx * gz):
+        runs, colours, _, dense = _random_column(rng, dim_y)
+        x, z = k // gz, k % gz
+        colour[x, :, z] = dense
+        top = dim_y
+        for ci, n in runs:
+            if ci >= 0:
+                solid[x, top - n:top, z] = True
+            top -= n
+        columns.append((32 + k * 20000 + int(rng.integers(0, 100)), runs, colours))
+    colour[~solid] = 0
+    return dim_y, gx, gz, stride, solid, colour, columns
+
+
+def test_rules_match_the_dense_model_on_random_small_worlds(rules, tmp_path):
+    rng = np.random.default_rng(4051)
+    cases, models = [], []
+    lit = shadowed = ties = saturated = unsaturated = 0
+    for _ in range(2000):
+        dim_y, gx, gz, stride, solid, colour, columns = _random_world(rng)
+        p = random_params(rng, (gx, dim_y, gz))
+        lamps = random_lamps(rng, solid, p, 8)
+        cases.append((dim_y, gx, gz, stride, columns, p, lamps))
+        models.append(_model_case(solid, colour, p, lamps))
+        total, stats = lampmodel.lamp_sum(solid, p, lamps)
+        lit, shadowed, ties = lit + stats["lit"], shadowed + stats["shadowed"], ties + stats["ties"]
+        mask, without = lightmodel.shades(solid, p)
+        saturated += int((mask & (total > 0) & (without + total > 255)).sum())
+        unsaturated += int((mask & (total > 0) & (without + total < 255)).sum())
+    # the coverage conditions, from the model alone
+    assert lit >= 5000 and shadowed >= 1000 and ties >= 100 and saturated >= 500 and unsaturated >= 500, (lit, shadowed, ties, saturated, unsaturated)
+    results = _run_columns(rules["lamp"], tmp_path, cases)
+    bad = [i for i, (got, want) in enumerate(zip(results, models)) if got != want]
+    if bad:
+        i = bad[0]
+        k = next(k for k in range(len(models[i])) if results[i][k] != models[i][k])
+        raise AssertionError(f"{len(bad)} of {len(cases)} cases differ; first: case {i} {cases[i]}\ncolumn {k}\n got {results[i][k]}\nwant {models[i][k]}")
+
+
+def test_no_lamps_give_the_bytes_of_the_light_rule(rules, tmp_path):
+    rng = np.random.default_rng(4052)
+    cases = []
+    for _ in range(200):
+        dim_y, gx, gz, stride, solid, colour, columns = _random_world(rng)
+        cases.append((dim_y, gx, gz, stride, columns, random_params(rng, (gx, dim_y, gz)), []))
+    assert _run_columns(rules["lamp"], tmp_path, cases) == _run_columns(rules["light"], tmp_path, cases, with_lamps=False)
+
+
+# ---- constructed cases: terms derived by hand ------------------------------------------------------------------------------------------------------
+
+DIMS = (16, 16, 16)
+DARK = lightmodel.params((0, 0, 0), DIMS, sky_range=0, target=lightmodel.TO_ALPHA)   # floor 0, no sky, no sun: the shade is the lamps' sum
+
+
+def _terms(rules, p, voxels, at, lamps):
+    """(the shade without lamps, [every lamp's term], the shade with them) of voxel `at` in a world of the listed solid voxels, from the rules;
+    the model must give the same final shade."""
+    text = subprocess.check_output([rules["lamp"], "shade", *[str(d) for d in DIMS], *[str(v) for v in lightmodel.words(p)], str(len(voxels)),
+                                    *[str(v) for voxel in voxels for v in voxel], "--", *[str(v) for v in at], *[str(v) for v in lampmodel.words(lamps)]], text=True)
+    numbers = [int(v) for v in text.split()]
+    solid = np.zeros(DIMS, dtype=bool)
+    for v in voxels:
+        solid[tuple(v)] = True
+    mask, model = lampmodel.shades(solid, p, lamps)
+    assert mask[tuple(at)] and int(model[tuple(at)]) == numbers[-1], (int(model[tuple(at)]), numbers)
+    return numbers[0], numbers[1:-1], numbers[-1]
+
+
+def _floor():
+    return [(x, 0, z) for x in range(DIMS[0]) for z in range(DIMS[2])]
+
+
+def test_a_lamp_one_voxel_above_a_flat_floor(rules):
+    L = lampmodel.lamp
+    # the voxel below, D = (0, 1, 0): d2 = 1, its +y neighbour (the lamp's voxel) is air: facing 1 of den 1, the walk arrives at once.
+    # radius 2: 255 * (4 - 1) / 4 = 191; radius 4: 255 * 15 / 16 = 239; radius 1: d2 = r2, nothing
+    assert _terms(rules, DARK, _floor(), (8, 0, 8), [L((8, 1, 8), 2, 255), L((8, 1, 8), 4, 255), L((8, 1, 8), 1, 255)]) == (0, [191, 239, 0], 255)
+    # d2 = r2 - 1: (7, 0, 7) with radius 2, D = (1, 1, 1), d2 = 3: only the +y neighbour is air: facing 1 of den 3; the diagonal walk arrives in one
+    # step: 255 * (4 - 3) * 1 / (4 * 3) = 21.  The same voxel with radius 3: 255 * 6 * 1 / (9 * 3) = 56
+    assert _terms(rules, DARK, _floor(), (7, 0, 7), [L((8, 1, 8), 2, 255), L((8, 1, 8), 3, 255)]) == (0, [21, 56], 77)
+    # d2 = r2 - 1 at radius 6: (3, 0, 5), D = (5, 1, 3), d2 = 35: 255 * 1 * 1 / (36 * 9) floors to 0
+    assert _terms(rules, DARK, _floor(), (3, 0, 5), [L((8, 1, 8), 6, 255)]) == (0, [0], 0)
+    # d2 = r2: a lone voxel 3 below a lamp of radius 3 gets nothing, of radius 4: 255 * (16 - 9) * 3 / (16 * 3) = 111
+    assert _terms(rules, DARK, [(8, 5, 8)], (8, 5, 8), [L((8, 8, 8), 3, 255), L((8, 8, 8), 4, 255)]) == (0, [0, 111], 111)
+    # ... and on the floor: (6, 0, 6), D = (2, 1, 2), d2 = 9 = r2 at radius 3
+    assert _terms(rules, DARK, _floor(), (6, 0, 6), [L((8, 1, 8), 3, 255)]) == (0, [0], 0)
+
+
+def test_a_post_shadows_the_voxels_on_the_line_through_an_edge_or_a_corner(rules):
+    """A wall at x = 12, a lamp at (6, 8, 8), radius 16.  Wall voxel (12, 14, 8) has D = (-6, -6, 0): x and y cross their planes together, so the
+    walk visits (12 - k, 14 - k, 8) only -- through voxel EDGES, never (11, 14, 8) or (12, 13, 8)'s neighbours.  A post at (9, 11, 8) shadows it; a
+    post at (9, 12, 8) or (10, 11, 8), which a walk taking one axis before the other would visit, does not."""
+    wall = [(12, y, z) for y in range(16) for z in range(16)]
+    lamp = [lampmodel.lamp((6, 8, 8), 16, 255)]
+    # lit: the -x neighbour is air (6), the -y neighbour is wall: facing 6 of den 12, d2 = 72: 255 * (256 - 72) * 6 / (256 * 12) = 91
+    assert _terms(rules, DARK, wall, (12, 14, 8), lamp) == (0, [91], 91)
+    assert _terms(rules, DARK, wall + [(9, 11, 8)], (12, 14, 8), lamp) == (0, [0], 0)
+    assert _terms(rules, DARK, wall + [(9, 12, 8)], (12, 14, 8), lamp) == (0, [91], 91)
+    assert _terms(rules, DARK, wall + [(10, 11, 8)], (12, 14, 8), lamp) == (0, [91], 91)
+    # its neighbour (12, 13, 8), D = (-6, -5, 0): x crosses at 5, 15, 25 (/ 30), y at 6, 18: (11, 13) (11, 12) (10, 12) (10, 11) (9, 11): the same post
+    # shadows it.  Lit it has facing 6 of den 11, d2 = 61: 255 * 195 * 6 / (256 * 11) = 105
+    assert _terms(rules, DARK, wall, (12, 13, 8), lamp) == (0, [105], 105)
+    assert _terms(rules, DARK, wall + [(9, 11, 8)], (12, 13, 8), lamp) == (0, [0], 0)
+    # through a CORNER: (12, 14, 14), D = (-6, -6, -6) visits (12 - k, 14 - k, 14 - k): a post at (9, 11, 11) shadows it, at (9, 11, 10) not.
+    # facing 6 of den 18, d2 = 108: 255 * 148 * 6 / (256 * 18) = 49
+    assert _terms(rules, DARK, wall + [(9, 11, 11)], (12, 14, 14), lamp) == (0, [0], 0)
+    assert _terms(rules, DARK, wall + [(9, 11, 10)], (12, 14, 14), lamp) == (0, [49], 49)
+
+
+def test_a_lamp_inside_a_solid_voxel(rules):
+    """The lamp's own voxel is never tested by a walk: the voxels two steps away along the six axes see it -- D = (+-2, 0, 0): the neighbour towards
+    the lamp is air, the walk tests it and arrives: 160 * (16 - 4) * 2 / (16 * 2) = 120 --, the lamp's voxel itself (D = 0) gets nothing, and a
+    face neighbour of it has no air face towards the lamp (facing 0)."""
+    six = [(10, 8, 8), (6, 8, 8), (8, 10, 8), (8, 6, 8), (8, 8, 10), (8, 8, 6)]
+    lamp = [lampmodel.lamp((8, 8, 8), 4, 160)]
+    for v in six:
+        assert _terms(rules, DARK, [(8, 8, 8)] + six, v, lamp) == (0, [120], 120)
+    assert _terms(rules, DARK, [(8, 8, 8)] + six, (8, 8, 8), lamp) == (0, [0], 0)
+    assert _terms(rules, DARK, [(8, 8, 8), (9, 8, 8)], (9, 8, 8), lamp) == (0, [0], 0)
+    # the same six around a lamp in AIR: the same terms; something between: shadowed
+    for v in six:
+        assert _terms(rules, DARK, six, v, lamp) == (0, [120], 120)
+    assert _terms(rules, DARK, six + [(9, 8, 8)], (10, 8, 8), lamp) == (0, [0], 0)
+
+
+def test_two_lamps_add_and_then_clamp(rules):
+    L = lampmodel.lamp
+    p = dict(DARK, floor_level=10)
+    # (8, 0, 8): the lamp at (8, 1, 8), radius 2: level * 3 / 4; the lamp at (8, 2, 8), radius 4, D = (0, 2, 0): level * 12 * 2 / (16 * 2) = level * 3 / 4
+    assert _terms(rules, p, _floor(), (8, 0, 8), [L((8, 1, 8), 2, 100), L((8, 2, 8), 4, 80)]) == (10, [75, 60], 145)
+    assert _terms(rules, p, _floor(), (8, 0, 8), [L((8, 1, 8), 2, 255), L((8, 2, 8), 4, 200)]) == (10, [191, 150], 255)
+    # with sky and sun in the same sum: 30 + 130 * 18 / 26 (= 90) = 120 without the sun, + 75 + 60 = 255 exactly; one level less: 254
+    q = lightmodel.params((0, 0, 0), DIMS, sky_level=130, sky_range=2, floor_level=30, target=lightmodel.TO_ALPHA)
+    assert _terms(rules, q, _floor(), (8, 0, 8), [L((8, 1, 8), 2, 100), L((8, 2, 8), 4, 80)]) == (120, [75, 60], 255)
+    assert _terms(rules, dict(q, floor_level=29), _floor(), (8, 0, 8), [L((8, 1, 8), 2, 100), L((8, 2, 8), 4, 80)]) == (119, [75, 60], 254)
+
+
+# ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
+
+def test_struct_layout_matches_the_mirrors():
+    assert C.sizeof(gpu.Lamp) == 32
+    names = [f[0] for f in gpu.Lamp._fields_]
+    assert [getattr(gpu.Lamp, n).offset for n in names] == [0, 12, 16, 20]
+    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
+    body = re.search(r"typedef struct cvx_lamp \{[^\n]*\n(.*?)\} cvx_lamp;", header, flags=re.S).group(1)
+    assert re.findall(r"^\s*int32_t ([a-zA-Z_]+)(\[3\])?;", body, flags=re.M) == [("pos", "[3]"), ("radius", ""), ("level", ""), ("pad_", "[3]")]
+    assert re.search(r"#define CVX_LIGHT_MAX_LAMPS\s+(\d+)", header).group(1) == str(gpu.LIGHT_MAX_LAMPS) == "4096"
+    assert re.search(r"#define CVX_LAMP_MAX_RADIUS\s+(\d+)", header).group(1) == str(gpu.LAMP_MAX_RADIUS) == "64"
+    assert C.sizeof(gpu.LightParams) == 64
+    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
+    body = re.search(r"public unsafe struct Lamp\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
+    fields = []
+    for m in re.finditer(r"public\s+(fixed\s+)?int\s+([^;]+);", body):
+        for n in m.group(2).split(","):
+            k = re.search(r"(\w+)\[(\d+)\]", n)
+            fields.append((k.group(1).lower(), int(k.group(2))) if k else (n.strip().lower(), 1))
+    assert fields == [("pos", 3), ("radius", 1), ("level", 1), ("pad", 3)] and sum(4 * n for _, n in fields) == 32
+    assert "CVX_LIGHT_MAX_LAMPS = 4096" in cs and "CVX_LAMP_MAX_RADIUS = 64" in cs
+    assert "cvx_world_light_lamps" in gpu.EXPORTS and "cvx_world_light_lamps" in open(os.path.join(ROOT, "README.md")).read()
+    arr = gpu.lamps_array([((1, -2, 3), 4, 5), dict(pos=(6, 7, 8), radius=9, level=10)])
+    assert np.frombuffer(bytes(arr), dtype=np.int32).tolist() == [1, -2, 3, 4, 5, 0, 0, 0, 6, 7, 8, 9, 10, 0, 0, 0]
+
+
+def test_lamps_fail_cleanly_without_a_context_or_world(rules):
+    """Every INVALID_ARGUMENT case is decided on the host before the world is looked at: on a context without a device or world
+    (tests/lamp_rules.cpp) the bad calls return -1 with the member named, the good ones -3 (CVX_ERR_NOT_READY)."""
+    L = gpu.lib()
+    p = gpu.LightParams()
+    p.boxMax[0] = p.boxMax[1] = p.boxMax[2] = 8
+    ms = C.c_float()
+    assert L.cvx_world_light_lamps(None, C.byref(p), None, 0, 0, C.byref(ms)) == -1  # CVX_ERR_INVALID_ARGUMENT: no context
+    lines = subprocess.check_output([rules["lamp"], "args"], text=True).split("\n")
+    codes = [int(v) for v in lines[0].split()]
+    assert codes == [-1] * 13 + [-3] * 4, codes
+    named = ["", "params", "lampCount", "lampCount", "lamps", "radius", "radius", "level", "level", "pos", "pos", "skyRange", "levelCount"]
+    for text, name in zip(lines[1:], named):
+        assert name in text, (name, text)
+    h = C.c_void_p()
+    if L.cvx_create(0, C.byref(h)) == 0:  # (a machine with a device: the world is missing)
+        try:
+            assert L.cvx_world_light_lamps(h, C.byref(p), None, 0, 0, C.byref(ms)) == -3
+            assert L.cvx_world_light_lamps(h, C.byref(p), None, 1, 0, C.byref(ms)) == -1
+        finally:
+            L.cvx_destroy(h)
