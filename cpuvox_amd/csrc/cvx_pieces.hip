@@ -32,36 +32,6 @@ using cvxi::Fail;
 
 namespace cvxpieces {
 
-// The root of i; every node on the way is pointed at its grandparent (labels only ever fall, so a late or lost update is harmless).
-__device__ inline uint32_t Find(uint32_t *parent, uint32_t i)
-{
-	for (;;) {
-		const uint32_t p = Load(parent + i);
-		if (p == i) { return i; }
-		const uint32_t g = Load(parent + p);
-		if (g != p) { atomicMin(parent + i, g); }
-		i = g;
-	}
-}
-
-// Joins the pieces of a and b: the larger root goes under the smaller one.  atomicMin returns what the larger one pointed at: itself -> hooked;
-// anything else -> somebody hooked it first, and whichever of the two labels it keeps now, the other one still has to be joined with it.
-__device__ inline bool Unite(uint32_t *parent, uint32_t a, uint32_t b)
-{
-	bool changed = false;
-	for (;;) {
-		a = Find(parent, a);
-		b = Find(parent, b);
-		if (a == b) { return changed; }
-		const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-		const uint32_t old = atomicMin(parent + hi, lo);
-		changed = true;
-		if (old == hi) { return true; }
-		a = old;
-		b = lo;
-	}
-}
-
 __global__ __launch_bounds__(256) void pieces_count_kernel(PiecesArgs A)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,5 +1,5 @@
 // cvx_pieces_nodes.h -- the node tables of cvx_pieces.hip (steps 1 .. 5 of its header comment), left on the device for the calls that go on from
-// them: cvx_world_pieces' REMOVE and cvx_world_settle (cvx_settle.hip).  cvxpieces::Analyse checks the arguments the two calls share, runs the
+// them: cvx_world_pieces' REMOVE and cvx_world_settle (cvx_settle.hip); the lock-free union-find is shared with cvx_world_cavities (cvx_cavity.hip).  cvxpieces::Analyse checks the arguments the two calls share, runs the
 // analysis and brings the totals and the head of the list to the host; the caller frees the tables with Analysis::Release.
 #pragma once
 
@@ -82,6 +82,36 @@ template <typename T, typename F> __device__ inline T WaveReduce(T v, F f)
 {
 	for (int d = 32; d > 0; d >>= 1) { v = f(v, __shfl_xor(v, d, 64)); }
 	return v;
+}
+
+// The root of i; every node on the way is pointed at its grandparent (labels only ever fall, so a late or lost update is harmless).
+__device__ inline uint32_t Find(uint32_t *parent, uint32_t i)
+{
+	for (;;) {
+		const uint32_t p = Load(parent + i);
+		if (p == i) { return i; }
+		const uint32_t g = Load(parent + p);
+		if (g != p) { atomicMin(parent + i, g); }
+		i = g;
+	}
+}
+
+// Joins the pieces of a and b: the larger root goes under the smaller one.  atomicMin returns what the larger one pointed at: itself -> hooked;
+// anything else -> somebody hooked it first, and whichever of the two labels it keeps now, the other one still has to be joined with it.
+__device__ inline bool Unite(uint32_t *parent, uint32_t a, uint32_t b)
+{
+	bool changed = false;
+	for (;;) {
+		a = Find(parent, a);
+		b = Find(parent, b);
+		if (a == b) { return changed; }
+		const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+		const uint32_t old = atomicMin(parent + hi, lo);
+		changed = true;
+		if (old == hi) { return true; }
+		a = old;
+		b = lo;
+	}
 }
 
 // the nodes of column (cx, cz) of the rectangle in a per-node table: none outside the box

@@ -224,7 +224,7 @@ int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, in
 	// 1, 2. count, scan, one copy back
 	unsigned long long total = 0;
 	hipError_t e = hipMalloc((void **)&scratch, bytes);
-	if (e == hipSuccess) {
+	if (e == hipSuccess && n > 0) { // (n = 0: a level without columns, LOD 5 of a world 16 columns wide -- its blob is the zero headers alone)
 		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
 		unsigned long long *dTotal = reinterpret_cast<unsigned long long *>(scratch + oTotal);
 		hipLaunchKernelGGL(cvxread::read_count_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
@@ -247,7 +247,7 @@ int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, in
 	}
 	e = hipMalloc((void **)&dBlob, std::max<size_t>(blobBytes, 4));
 	if (e == hipSuccess && headerBytes > (size_t)n * 12) { e = hipMemsetAsync(dBlob + (size_t)n * 12, 0, headerBytes - (size_t)n * 12, ctx->stream); }
-	if (e == hipSuccess) {
+	if (e == hipSuccess && n > 0) {
 		A.headers = reinterpret_cast<uint32_t *>(dBlob);
 		A.elements = reinterpret_cast<uint32_t *>(dBlob + headerBytes);
 		hipLaunchKernelGGL(cvxread::read_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);

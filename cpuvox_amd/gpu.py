@@ -33,6 +33,7 @@ EXPORTS = [
     "cvx_world_downsample", "cvx_world_build_lods", "cvx_free", "cvx_world_set_columns", "cvx_world_edit", "cvx_world_edit_stats",
     "cvx_world_brush", "cvx_world_pick", "cvx_world_pick_device",
     "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces", "cvx_world_settle",
+    "cvx_world_cavities",
     "cvx_world_light", "cvx_world_light_lamps", "cvx_world_move", "cvx_world_move_device",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
@@ -41,7 +42,7 @@ EXPORTS = [
 ]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
-                "cvx_debug_last_launch", "cvx_debug_settle"]
+                "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
 # cvx_debug_last_launch: out[0], the kernel instance a draw went to
 INSTANCE_COUNTING, INSTANCE_BATCH, INSTANCE_LONE, INSTANCE_LONE_WIDE = 0, 1, 2, 3
 LAUNCH_FIELDS = ("instance", "tiles", "waves", "min_rays", "max_rays", "max_dup_shift", "split", "lds_words")
@@ -67,6 +68,8 @@ COPY_MAX_PLACEMENTS = 1024
 PIECES_REPORT, PIECES_REMOVE = 0, 1              # cvx_world_pieces: op
 ANCHOR_GROUND, ANCHOR_OUTSIDE, ANCHOR_LARGEST = 1, 2, 4  # ... anchors (bits)
 SETTLE_UNLIMITED = 0                             # cvx_world_settle: maxDrop
+CAVITIES_REPORT, CAVITIES_FILL = 0, 1            # cvx_cavity_params.op
+CAVITY_OPEN_DEFAULT = 0x3B                       # ... openFaces: every face but -Y
 LIGHT_TO_RGB, LIGHT_TO_ALPHA = 0, 1              # cvx_light_params.target
 LIGHT_MAX_LAMPS, LAMP_MAX_RADIUS = 4096, 64      # cvx_world_light_lamps
 MOVE_UNIT = 256                                  # cvx_move_body: position units per LOD-0 voxel
@@ -105,6 +108,16 @@ class SettleSummary(C.Structure):  # cvx_settle_summary
                 ("largestDrop", C.c_int32), ("pad_", C.c_int32)]
 
 
+class CavityParams(C.Structure):  # cvx_cavity_params
+    _fields_ = [("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("openFaces", C.c_int32), ("op", C.c_int32), ("argb", C.c_uint32), ("pad_", C.c_int32),
+                ("maxVoxels", C.c_int64)]
+
+
+class CavitiesSummary(C.Structure):  # cvx_cavities_summary
+    _fields_ = [("enclosedCavities", C.c_int64), ("enclosedVoxels", C.c_int64), ("selectedCavities", C.c_int64), ("selectedVoxels", C.c_int64),
+                ("openRegions", C.c_int64), ("openVoxels", C.c_int64)]
+
+
 class LightParams(C.Structure):  # cvx_light_params
     _fields_ = [("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("sunDir", C.c_int32 * 3), ("sunLevel", C.c_int32), ("sunRange", C.c_int32),
                 ("skyLevel", C.c_int32), ("skyRange", C.c_int32), ("floorLevel", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
@@ -138,6 +151,8 @@ PIECE_DTYPE = np.dtype([("min", "<i4", 3), ("max", "<i4", 3), ("seed", "<i4", 3)
 PIECES_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("anchoredPieces", "<i8"), ("anchoredVoxels", "<i8")])
 SETTLE_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("fallenPieces", "<i8"), ("fallenVoxels", "<i8"),
                                  ("largestDrop", "<i4"), ("pad_", "<i4")])  # cvx_settle_summary
+CAVITIES_SUMMARY_DTYPE = np.dtype([("enclosedCavities", "<i8"), ("enclosedVoxels", "<i8"), ("selectedCavities", "<i8"), ("selectedVoxels", "<i8"),
+                                   ("openRegions", "<i8"), ("openVoxels", "<i8")])  # cvx_cavities_summary
 MOVE_BODY_DTYPE = np.dtype([("pos", "<i4", 3), ("size", "<i4", 3), ("delta", "<i4", 3), ("stepUp", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])  # cvx_move_body
 MOVE_RESULT_DTYPE = np.dtype([("pos", "<i4", 3), ("flags", "<i4")])  # cvx_move_result
 
@@ -303,6 +318,7 @@ def _bind(path: str) -> C.CDLL:
             L.cvx_debug_occupancy.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int)]
             L.cvx_debug_last_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
             L.cvx_debug_settle.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
+            L.cvx_debug_cavities.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
             L.cvx_selftest_math.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             L.cvx_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
             L.cvx_selftest_lone.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -327,6 +343,7 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_settle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                        C.POINTER(C.c_float)]
+        L.cvx_world_cavities.argtypes = [C.c_void_p, C.POINTER(CavityParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_light.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_light_lamps.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_move.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -555,6 +572,31 @@ class Context:
         ms, counts = (C.c_float * 3)(), (C.c_int64 * 4)()
         self._check(self._diag("cvx_debug_settle")(self._h, one_sweep_per_launch, ms, counts))
         return {"analysis_ms": ms[0], "relax_ms": ms[1], "edit_ms": ms[2], "nodes": counts[0], "sweeps": counts[1], "launches": counts[2], "single_workgroup": bool(counts[3])}
+
+    def world_cavities(self, box_min, box_max, op: int = CAVITIES_REPORT, open_faces: int = CAVITY_OPEN_DEFAULT, max_voxels: int = 0, argb: int = 0,
+                       level_count: int = LOD_LEVELS - 1, capacity: int = 1024):
+        """The enclosed cavities of the LOD-0 air inside [box_min, box_max): the connected air regions (face contact) that reach no face of the
+        clipped box whose bit is set in `open_faces` (bits 0..5 = -X,+X,-Y,+Y,-Z,+Z) with air across it: (the first `capacity` selected cavities
+        -- the enclosed ones of at most `max_voxels` voxels, 0: all -- as a PIECE_DTYPE array in seed order, the six totals as a dict, device
+        milliseconds).  op = CAVITIES_FILL makes all of them solid with `argb` and rebuilds LOD 1..level_count over their footprint."""
+        if len(box_min) != 3 or len(box_max) != 3:
+            raise ValueError("world_cavities: box_min and box_max are three integers each")
+        p = CavityParams((C.c_int32 * 3)(*[int(v) for v in box_min]), (C.c_int32 * 3)(*[int(v) for v in box_max]), open_faces, op, argb & 0xFFFFFFFF, 0,
+                         max_voxels)
+        out = np.zeros(max(int(capacity), 0), dtype=PIECE_DTYPE)
+        summary = np.zeros(1, dtype=CAVITIES_SUMMARY_DTYPE)
+        ms = C.c_float()
+        self._check(lib().cvx_world_cavities(self._h, C.byref(p), level_count, out.ctypes.data if out.size else None, int(capacity), summary.ctypes.data,
+                                             C.byref(ms)))
+        totals = {name: int(summary[0][name]) for name in CAVITIES_SUMMARY_DTYPE.names}
+        return out[:min(out.size, totals["selectedCavities"])].copy(), totals, ms.value
+
+    def debug_cavities(self) -> dict:
+        """Diagnostics build only (include/cpuvox_gpu_diag.h): the last world_cavities' device ms split (analysis, edit), its air intervals and
+        hook rounds."""
+        ms, counts = (C.c_float * 2)(), (C.c_int64 * 2)()
+        self._check(self._diag("cvx_debug_cavities")(self._h, ms, counts))
+        return {"analysis_ms": ms[0], "edit_ms": ms[1], "nodes": counts[0], "rounds": counts[1]}
 
     def world_light(self, box_min, box_max, *, sun_dir=(0, 0, 0), sun_level: int = 0, sun_range: int = 0, sky_level: int = 0, sky_range: int = 0,
                     floor_level: int = 0, target: int = LIGHT_TO_RGB, level_count: int = LOD_LEVELS - 1) -> float:

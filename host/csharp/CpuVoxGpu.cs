@@ -125,6 +125,26 @@ namespace CpuVox.Gpu
 		public int LargestDrop, Pad;
 	}
 
+	// cvx_world_cavities: the call's parameters (48 bytes).  Box [BoxMin, BoxMax) in LOD-0 voxels; OpenFaces bits 0..5 = -X,+X,-Y,+Y,-Z,+Z: the faces
+	// of the clipped box air may escape through (0x3B: every face but -Y); Op 0 report, 1 fill with Argb; MaxVoxels 0: no limit
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public unsafe struct CavityParams
+	{
+		public fixed int BoxMin[3];
+		public fixed int BoxMax[3];
+		public int OpenFaces, Op;
+		public uint Argb;
+		public int Pad;
+		public long MaxVoxels;
+	}
+
+	// cvx_world_cavities: the totals (48 bytes): every enclosed cavity, those within MaxVoxels (listed, and filled by a FILL), the open regions
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public struct CavitiesSummary
+	{
+		public long EnclosedCavities, EnclosedVoxels, SelectedCavities, SelectedVoxels, OpenRegions, OpenVoxels;
+	}
+
 	// cvx_world_light: the call's parameters (64 bytes).  Box [BoxMin, BoxMax) in LOD-0 voxels; SunDir points TOWARDS the sun (integers, |.| <= 1024,
 	// all 0: no sun term); levels 0 .. 255; SunRange 0 .. 4096 voxels of the shadow walk, SkyRange 0 .. 32 voxels per sky direction; Target 0: the
 	// shade is multiplied into R, G, B (one-shot), 1: it is stored in A
@@ -240,6 +260,10 @@ namespace CpuVox.Gpu
 		public const int CVX_SETTLE_UNLIMITED = 0;
 		[DllImport(Lib)] public static extern int cvx_world_settle(IntPtr ctx, int* boxMin, int* boxMax, int anchors, int maxDrop, int levelCount, Piece* pieces,
 		                                                           int* drops, int pieceCapacity, SettleSummary* summary, out float outDeviceMs);
+		// the enclosed cavities of LOD 0 inside a box (air regions that reach no open face of it), listed as Piece; op 1 fills them + LOD refresh
+		public const int CVX_CAVITY_OPEN_DEFAULT = 0x3B;
+		[DllImport(Lib)] public static extern int cvx_world_cavities(IntPtr ctx, CavityParams* cavityParams, int levelCount, Piece* cavities, int cavityCapacity,
+		                                                             CavitiesSummary* summary, out float outDeviceMs);
 		// sky occlusion and a sun shadow baked into the solid voxels of LOD 0 inside a box (from occupancy alone) + its LOD refresh
 		[DllImport(Lib)] public static extern int cvx_world_light(IntPtr ctx, LightParams* lightParams, int levelCount, out float outDeviceMs);
 		// ... with point lights in the same bake (at most CVX_LIGHT_MAX_LAMPS; lampCount 0: cvx_world_light)

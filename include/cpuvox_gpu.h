@@ -561,6 +561,51 @@ typedef struct cvx_settle_summary { /* 40 bytes */
 int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, int maxDrop, int levelCount, cvx_piece *pieces,
                      int32_t *drops, int pieceCapacity, cvx_settle_summary *summary, float *outDeviceMs);
 
+/* ---- finding and filling the enclosed cavities of the uploaded world -----------------------------------------------------------------------
+ * cvx_world_cavities: what a stamped or built shell encloses (voxlap's sethollowfill: the call a host makes after cvx_world_stamp_mesh, so that a
+ * later carve cuts into rock instead of an empty inside).  The voxels considered are the AIR voxels of LOD 0 inside [boxMin, boxMax) after
+ * clipping the box to the world (coordinates address the stored tile: a repeating world does not wrap them).  Two of them are connected when
+ * they share a FACE; a REGION is a connected component inside the clipped box.  A region is OPEN when for some face f of the clipped box with
+ * bit f set in openFaces (bits 0..5 = -X,+X,-Y,+Y,-Z,+Z, the pick's face numbers) it holds a voxel lying on face f and the voxel across that
+ * face is air: a voxel outside the world counts as air, below y = 0 and above dimY too; inside the world the arena decides.  Every other
+ * region is an ENCLOSED CAVITY.  A box that cuts a cavity in two leaves its inner part open through the cut; with the cut face's bit cleared the
+ * inner part counts as enclosed, and it alone is filled.  The SELECTED cavities are the enclosed ones of at most maxVoxels voxels (0: all).
+ * Order: seed, bounding box, `voxels` and the order are exactly cvx_world_pieces': a cavity's seed is its voxel in its first column in (x, then
+ * z) order and, there, the highest y; the list is by ascending seed x, then ascending z, then DESCENDING y, and does not depend on scheduling:
+ * the same world gives the same bytes.  `summary` (may be NULL) receives the six totals; `cavities` (may be NULL iff cavityCapacity = 0) the
+ * first min(cavityCapacity, selectedCavities) selected cavities; a smaller capacity is not an error.
+ * CVX_CAVITIES_REPORT never changes the world.  CVX_CAVITIES_FILL makes every voxel of every selected cavity (whatever the capacity) solid
+ * with the colour word argb, verbatim, through cvx_world_edit's machinery like CVX_PIECES_REMOVE: the rectangle is the XZ bounding box of the
+ * selected cavities rounded outward to multiples of 2^levelCount and clipped to the world, LOD 1 .. levelCount (0 .. 5) are rebuilt over it,
+ * columns of it that gain nothing are re-encoded with the builder's rule, and runs that come to touch merge.  Nothing selected: CVX_OK, the
+ * arena is untouched.  outDeviceMs (may be NULL): device time of the analysis and, for a FILL that fills something, the edit.
+ * Ordering, atomicity and several GPUs as cvx_world_pieces; every error leaves the world as it was.
+ * CVX_ERR_INVALID_ARGUMENT: NULL params, boxMin >= boxMax on an axis, a box wholly outside the world, openFaces bits above 0x3F, a bad op,
+ * maxVoxels < 0, levelCount outside 0 .. 5, a negative cavityCapacity, cavities NULL with a capacity above 0; CVX_ERR_NOT_READY: LOD 0 has not
+ * been uploaded; CVX_ERR_CAPACITY: the scratch does not fit in device memory, the box holds 2^31 or more columns or air intervals, and on FILL
+ * the format and arena limits of cvx_world_brush (a filled column needs one colour per voxel: at most 32767 solid voxels above a run).
+ * Device memory while it runs: 8 bytes per column of the clipped box and 64 bytes per air interval of LOD 0 inside it (a maximal run of air
+ * voxels of one column: its interval, column and label, and the totals, box and open bits of the region it may be the seed of), plus 48 bytes
+ * per listed cavity; a FILL adds cvx_world_brush's scratch for its rectangle. */
+enum { CVX_CAVITIES_REPORT = 0, CVX_CAVITIES_FILL = 1 };
+#define CVX_CAVITY_OPEN_DEFAULT 0x3B   /* every face but -Y: the ground is watertight */
+typedef struct cvx_cavity_params {     /* 48 bytes */
+	int32_t boxMin[3];   /* LOD-0 voxels, inclusive */
+	int32_t boxMax[3];   /* exclusive */
+	int32_t openFaces;   /* bits 0..5 = -X,+X,-Y,+Y,-Z,+Z (the pick's face numbers): the faces of the clipped box air may escape through */
+	int32_t op;          /* CVX_CAVITIES_* */
+	uint32_t argb;       /* FILL: the colour word every filled voxel gets, verbatim */
+	int32_t pad_;
+	int64_t maxVoxels;   /* 0: no limit; else only cavities of at most this many voxels are selected */
+} cvx_cavity_params;
+typedef struct cvx_cavities_summary {  /* 48 bytes */
+	int64_t enclosedCavities, enclosedVoxels;   /* every enclosed cavity, whatever maxVoxels */
+	int64_t selectedCavities, selectedVoxels;   /* those within maxVoxels: what is listed and what FILL fills */
+	int64_t openRegions, openVoxels;
+} cvx_cavities_summary;
+int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int levelCount, cvx_piece *cavities, int cavityCapacity,
+                       cvx_cavities_summary *summary, float *outDeviceMs);
+
 /* ---- lighting the uploaded world: sky occlusion and sun shadows ----------------------------------------------------------------------------
  * cvx_world_light: bakes a shade, an integer 0 .. 255, into every solid LOD-0 voxel v inside [boxMin, boxMax) clipped to the world (voxlap's
  * updatelighting: the call a host makes after an edit).  The shade is computed from occupancy alone -- no colour is read for it, no occupancy

@@ -26,6 +26,10 @@ int cvx_debug_last_launch(cvx_context *ctx, int64_t out[8]);
  * oneSweepPerLaunch 1 / 0: later calls relax with one sweep per launch and a host round trip between / as the product does; -1: leave it. */
 int cvx_debug_settle(cvx_context *ctx, int oneSweepPerLaunch, float outMs[3], int64_t outCounts[4]);
 
+/* cvx_world_cavities' last call in this process (tools/cavity_bench.py): outMs (may be NULL) = device ms of the analysis and of the edit (0: a
+ * REPORT, or nothing selected); outCounts (may be NULL) = air intervals in the box (-1: no call yet), hook / flatten rounds. */
+int cvx_debug_cavities(cvx_context *ctx, float outMs[2], int64_t outCounts[2]);
+
 /* Diagnostic build only (make gpu-prof, -DCVX_PROFILE_SECTIONS): wave cycles spent per code section of the
  * render kernel (s_memtime stamps), accumulated over all launches.  Sections: 0 prologue/epilogue, 1 phase A
  * (DDA step + header + cull), 2 frustum clip, 3 element walk, 4 side-face setup, 5 side-face pixels,

@@ -1,0 +1,296 @@
+"""CPU (no GPU needed): the rules behind cvx_world_cavities (cpuvox_amd/csrc/cvx_cavity.h), compiled for the host through tests/cavity_rules.cpp
+(which drives them with a sequential union-find), against the independent dense model of tests/cavitymodel.py (scipy.ndimage.label on the air).
+
+- Column mode: 2000 random small worlds (seed 2047) of up to 4 x 4 random columns (records with 1..3 runs and listed columns, both colour
+  layouts, foreign encodings with split runs and shared colours, empty columns) with random boxes (partly outside the world), random openFaces
+  0 .. 63 and maxVoxels from {0, 1, 5}: the summary, the ordered list and every column of the world with the selected cavities filled (runs,
+  colours, worldMin / worldMax in the builder's encoding) must equal the model's exactly.
+- World mode: the three _pick_world worlds and the two noise worlds uploaded into a host-only context; list and summary equal the model's and
+  the sub-world blob of the FILL rectangle equals, byte for byte, the same rectangle of the model's world built on the host.
+- The struct layouts of the header against the ctypes, numpy and C# mirrors; the call without a context / world and every INVALID_ARGUMENT case."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import cavitymodel
+import piecesmodel
+import pyworld
+from cpuvox_amd import gpu, host
+from test_world_brush_cpu import _pick_world, _random_column
+from test_world_pieces_cpu import pieces_rows
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ARGB = 0xFF123456
+NOISE_DIMS = [(32, 32, 32), (16, 64, 32)]
+
+
+@pytest.fixture(scope="module")
+def rules(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("cavity") / "cavity_rules")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
+                           os.path.join(ROOT, "tests", "cavity_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
+                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
+    return out
+
+
+def noise_world(dims):
+    """The noise worlds of the issue: np.random.default_rng(1).random(dims) < 0.7 -> (solid, colour, ws)."""
+    solid = np.random.default_rng(1).random(dims) < 0.7
+    x, y, z = np.nonzero(solid)
+    colour = np.zeros(dims, dtype=np.uint32)
+    colour[x, y, z] = (0xFF000000 | ((x * 2654435761 + y * 40503 + z * 2246822519) >> 7) & 0xFFFFFF).astype(np.uint32)
+    ws = host.WorldSet.from_voxels(dims, x.astype(np.int32), y.astype(np.int32), z.astype(np.int32), colour[x, y, z], threads=2)
+    return solid, colour, ws
+
+
+def random_call(rng, dims):
+    """(box_min, box_max, open_faces, max_voxels): a random box partly outside the world (the whole world when nothing of it is inside); every
+    second mask is the AND of three draws, so that masks with few open faces -- the ones that leave something enclosed -- are common."""
+    box_min = [int(rng.integers(-2, dims[a])) for a in range(3)]
+    box_max = [int(rng.integers(box_min[a] + 1, dims[a] + 3)) for a in range(3)]
+    if piecesmodel.clip_box(dims, box_min, box_max) is None:
+        box_min, box_max = [0, 0, 0], list(dims)
+    open_faces = int(rng.integers(0, 64))
+    if rng.random() < 0.5:
+        open_faces &= int(rng.integers(0, 64)) & int(rng.integers(0, 64))
+    return box_min, box_max, open_faces, int(rng.choice([0, 1, 5]))
+
+
+# ---- column mode -------------------------------------------------------------------------------------------------------------------------------
+
+def _model_case(solid, colour, box_min, box_max, open_faces, max_voxels):
+    cavities, summary, _ = cavitymodel.analyse(solid, box_min, box_max, open_faces, max_voxels)
+    s, c = cavitymodel.fill(solid, colour, box_min, box_max, open_faces, max_voxels, ARGB)
+    gx, dim_y, gz = solid.shape
+    columns = []
+    for x in range(gx):
+        for z in range(gz):
+            ys = np.nonzero(s[x, :, z])[0][::-1]
+            col = pyworld.final_column([(int(y), int(c[x, y, z])) for y in ys], dim_y - 1, 1)
+            if col is None:
+                columns.append((False, [], [], 0, 0))
+                continue
+            runs, colours, wmin, wmax = col
+            columns.append((False, [((ci & 0xFFFF) | (n << 16)) for ci, n in runs], list(colours), wmin, wmax))
+    return summary, pieces_rows(cavities), columns
+
+
+def _run_columns(rules, tmp_path, cases):
+    words = []
+    for dim_y, gx, gz, stride, columns, box_min, box_max, open_faces, max_voxels in cases:
+        words += [dim_y, gx, gz, stride]
+        for base, runs, colours in columns:
+            words += [base, len(runs)]
+            for ci, n in runs:
+                words += [ci, n]
+            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
+        words += list(box_min) + list(box_max) + [open_faces, max_voxels, int(np.int32(np.uint32(ARGB)))]
+    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
+    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
+    subprocess.check_call([rules, "columns", str(src), str(dst)])
+    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+    results, at = [], 0
+    for dim_y, gx, gz, *_ in cases:
+        totals = [int(v) for v in out[at:at + 6]]
+        at += 6
+        rows = []
+        for _ in range(totals[2]):
+            w = out[at:at + 10].astype(np.int32).tolist()
+            at += 10
+            rows.append((w[0:3], w[3:6], w[6:9], w[9]))
+        columns = []
+        for _ in range(gx * gz):
+            over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
+            at += 5
+            if over:
+                columns.append((True, None, None, None, None))
+                continue
+            runs = out[at:at + rc].tolist()
+            at += rc
+            colours = out[at:at + nc].tolist()
+            at += nc
+            columns.append((False, runs, colours, wmin, wmax))
+        results.append((dict(zip(cavitymodel.SUMMARY_NAMES, totals)), rows, columns))
+    assert at == len(out)
+    return results
+
+
+def test_rules_match_the_dense_model_on_random_small_worlds(rules, tmp_path):
+    rng = np.random.default_rng(2047)
+    cases, models = [], []
+    split = listed_like = empty = enclosed = selected = opened = multi = 0
+    for _ in range(2000):
+        dim_y = int(rng.choice([8, 16, 64, 256]))
+        gx, gz = int(rng.integers(1, 5)), int(rng.integers(1, 5))
+        stride = int(rng.choice([1, 32]))
+        solid = np.zeros((gx, dim_y, gz), dtype=bool)
+        colour = np.zeros((gx, dim_y, gz), dtype=np.uint32)
+        columns = []
+        for k in range(gx * gz):
+            runs, colours, _, dense = _random_column(rng, dim_y)
+            x, z = k // gz, k % gz
+            colour[x, :, z] = dense
+            top = dim_y
+            previous_solid = False
+            for ci, n in runs:
+                if ci >= 0:
+                    solid[x, top - n:top, z] = True
+                    split += previous_solid
+                previous_solid = ci >= 0
+                top -= n
+            columns.append((32 + k * 20000 + int(rng.integers(0, 100)), runs, colours))
+            listed_like += sum(1 for ci, _ in runs if ci >= 0) > 3
+            empty += not runs
+        colour[~solid] = 0
+        dims = (gx, dim_y, gz)
+        box_min, box_max, open_faces, max_voxels = random_call(rng, dims)
+        if rng.random() < 0.3:
+            box_min, box_max = [0, 0, 0], list(dims)
+        cases.append((dim_y, gx, gz, stride, columns, box_min, box_max, open_faces, max_voxels))
+        models.append(_model_case(solid, colour, box_min, box_max, open_faces, max_voxels))
+        enclosed += models[-1][0]["enclosedCavities"]
+        selected += models[-1][0]["selectedCavities"]
+        opened += models[-1][0]["openRegions"]
+        multi += models[-1][0]["enclosedCavities"] + models[-1][0]["openRegions"] > 2
+    results = _run_columns(rules, tmp_path, cases)
+    bad = [i for i, (got, want) in enumerate(zip(results, models)) if got != want]
+    if bad:
+        i = bad[0]
+        part = next(k for k in range(3) if results[i][k] != models[i][k])
+        raise AssertionError(f"{len(bad)} of {len(cases)} cases differ; first: case {i} {cases[i]}\n got {results[i][part]}\nwant {models[i][part]}")
+    assert split > 100 and listed_like > 300 and empty > 100 and enclosed > 500 and 200 < selected < enclosed and opened > 1000 and multi > 100, \
+        (split, listed_like, empty, enclosed, selected, opened, multi)
+
+
+# ---- world mode ---------------------------------------------------------------------------------------------------------------------------------
+
+def run_world(rules, tmp_path, ws, box_min, box_max, open_faces, max_voxels, argb, level_count):
+    """tests/cavity_rules.cpp `world` on LOD 0 of ws -> (summary dict, cavities array, rectangle, blob bytes, colorShift, listed, over, nodes, ms)."""
+    info = ws.info(0)
+    blob, lst, out = tmp_path / "world.bin", tmp_path / "list.bin", tmp_path / "sub.bin"
+    blob.write_bytes(ws.storage(0).tobytes())
+    text = subprocess.check_output([rules, "world", str(blob), str(info.dimX), str(info.dimY), str(info.dimZ), str(info.columnCount),
+                                    *[str(int(v)) for v in box_min], *[str(int(v)) for v in box_max], str(open_faces), str(max_voxels), str(argb), str(level_count),
+                                    str(lst), str(out)], text=True)
+    m = re.match(r"colorShift (\d+) listed (\d+) over (\d+) rect (\d+) (\d+) (\d+) (\d+) nodes (\d+) ms ([0-9.]+)", text)
+    assert m, text
+    raw = lst.read_bytes()
+    summary = np.frombuffer(raw[:48], dtype=gpu.CAVITIES_SUMMARY_DTYPE)[0]
+    cavities = np.frombuffer(raw[48:], dtype=gpu.PIECE_DTYPE)
+    return ({n: int(summary[n]) for n in gpu.CAVITIES_SUMMARY_DTYPE.names}, cavities, tuple(int(m.group(k)) for k in range(4, 8)), out.read_bytes(),
+            int(m.group(1)), int(m.group(2)), int(m.group(3)), int(m.group(8)), float(m.group(9)))
+
+
+def world_boxes(dims):
+    """Named (box_min, box_max, open_faces, max_voxels) over a world of `dims` (the GPU test uses them too): world_pieces' boxes with masks in place
+    of anchors."""
+    dx, dy, dz = dims
+    return {
+        "whole world, default faces": ((0, 0, 0), dims, 0x3B, 0),
+        "whole world, every face": ((0, 0, 0), dims, 0x3F, 0),
+        "whole world, no face": ((0, 0, 0), dims, 0, 0),
+        "inner box, every face": ((3, 2, 5), (dx - 4, dy - 3, dz - 2), 0x3F, 0),
+        "inner box, no face, small ones": ((3, 2, 5), (dx - 4, dy - 3, dz - 2), 0, 5),
+        "upper half, top and sides": ((0, dy // 4, 0), (dx, dy, dz), 0x3B, 0),
+        "partly outside the world": ((-5, -3, dz // 2), (dx // 2, dy + 9, dz + 4), 0x3B, 1),
+        "one column": ((3, 0, 1), (4, dy, 2), 0x08, 0),
+    }
+
+
+def _check_calls(rules, tmp_path, solid, colour, ws, dims, calls, level_count):
+    filled = 0
+    for name, (box_min, box_max, open_faces, max_voxels) in calls.items():
+        want_cavities, want_summary, _ = cavitymodel.analyse(solid, box_min, box_max, open_faces, max_voxels)
+        summary, cavities, rect, got, _, _, over, _, _ = run_world(rules, tmp_path, ws, box_min, box_max, open_faces, max_voxels, ARGB, level_count)
+        assert over == 0
+        assert summary == want_summary, name
+        assert pieces_rows(cavities) == pieces_rows(want_cavities), name
+        want_rect = cavitymodel.rectangle(want_cavities, dims, level_count)
+        if want_rect is None:
+            assert got == b"", name
+            continue
+        assert rect == want_rect, name
+        s, c = cavitymodel.fill(solid, colour, box_min, box_max, open_faces, max_voxels, ARGB)
+        x, y, z = np.nonzero(s)
+        want_ws = host.WorldSet.from_voxels(dims, x.astype(np.int32), y.astype(np.int32), z.astype(np.int32), c[x, y, z], threads=2)
+        try:
+            want, _ = want_ws.extract_region(0, *rect)
+        finally:
+            want_ws.close()
+        assert got == want, f"{name}: the sub-world blob of {rect} differs from the model's ({len(got)} vs {len(want)} bytes)"
+        filled += 1
+    return filled
+
+
+@pytest.mark.parametrize("dims,sparse,level_count,seed", [((32, 32, 32), False, 3, 1), ((16, 64, 32), False, 0, 2), ((32, 128, 32), True, 5, 3)])
+def test_filled_rectangle_equals_the_model_world(rules, tmp_path, dims, sparse, level_count, seed):
+    """The terrain worlds hold few cavities: the sky region, the zero-node columns and (sparse) the empty columns are the point; with no open
+    face the whole air is one enclosed cavity and the FILL makes the world solid."""
+    rng = np.random.default_rng(seed)
+    solid, colour, ws = _pick_world(rng, dims, sparse)
+    try:
+        assert _check_calls(rules, tmp_path, solid, colour, ws, dims, world_boxes(dims), level_count) >= 1
+    finally:
+        ws.close()
+
+
+@pytest.mark.parametrize("dims,level_count", [(NOISE_DIMS[0], 3), (NOISE_DIMS[1], 0)])
+def test_noise_worlds_with_random_boxes_masks_and_limits(rules, tmp_path, dims, level_count):
+    solid, colour, ws = noise_world(dims)
+    try:
+        _, summary, _ = cavitymodel.analyse(solid, (0, 0, 0), dims, 0x3B, 0)
+        cavities, _, _ = cavitymodel.analyse(solid, (0, 0, 0), dims, 0x3B, 0)
+        assert summary["enclosedCavities"] >= 100 and int((cavities["voxels"] > 1).sum()) >= 20
+        calls = dict(world_boxes(dims))
+        rng = np.random.default_rng(dims[0])
+        for k in range(12):
+            calls[f"random call {k}"] = random_call(rng, dims)
+        assert _check_calls(rules, tmp_path, solid, colour, ws, dims, calls, level_count) >= 10
+    finally:
+        ws.close()
+
+
+# ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
+
+def test_struct_layouts_match_the_mirrors():
+    assert C.sizeof(gpu.CavityParams) == 48 and C.sizeof(gpu.CavitiesSummary) == gpu.CAVITIES_SUMMARY_DTYPE.itemsize == 48
+    assert [f[0] for f in gpu.CavitiesSummary._fields_] == list(gpu.CAVITIES_SUMMARY_DTYPE.names) == list(cavitymodel.SUMMARY_NAMES)
+    assert [getattr(gpu.CavityParams, n).offset for n in ("boxMin", "boxMax", "openFaces", "op", "argb", "pad_", "maxVoxels")] == [0, 12, 24, 28, 32, 36, 40]
+    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
+    body = re.search(r"typedef struct cvx_cavity_params \{[^\n]*\n(.*?)\} cvx_cavity_params;", header, flags=re.S).group(1)
+    assert re.findall(r"^\s*u?int(?:32|64)_t ([a-zA-Z_]+)", body, flags=re.M) == [f[0] for f in gpu.CavityParams._fields_]
+    body = re.search(r"typedef struct cvx_cavities_summary \{[^\n]*\n(.*?)\} cvx_cavities_summary;", header, flags=re.S).group(1)
+    assert [n for part in re.findall(r"int64_t ([a-zA-Z, ]+);", body) for n in part.split(", ")] == [f[0] for f in gpu.CavitiesSummary._fields_]
+    for name, value in (("CVX_CAVITIES_REPORT", gpu.CAVITIES_REPORT), ("CVX_CAVITIES_FILL", gpu.CAVITIES_FILL)):
+        assert re.search(name + r" = (\d+)", header).group(1) == str(value)
+    assert int(re.search(r"#define CVX_CAVITY_OPEN_DEFAULT (0x[0-9A-Fa-f]+)", header).group(1), 16) == gpu.CAVITY_OPEN_DEFAULT == cavitymodel.OPEN_DEFAULT == 0x3B
+    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
+    sizes = {"int": 4, "uint": 4, "long": 8}
+    for name, want in (("CavityParams", 48), ("CavitiesSummary", 48)):
+        body = re.search(r"public (?:unsafe )?struct " + name + r"\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
+        total = 0
+        for m in re.finditer(r"public\s+(fixed\s+)?(int|uint|long)\s+([^;]+);", body):
+            for n in m.group(3).split(","):
+                k = re.search(r"\[(\d+)\]", n)
+                total += sizes[m.group(2)] * (int(k.group(1)) if k else 1)
+        assert total == want, (name, total)
+
+
+def test_cavities_fails_cleanly_without_a_context_or_world(rules):
+    L = gpu.lib()
+    p = gpu.CavityParams((C.c_int32 * 3)(0, 0, 0), (C.c_int32 * 3)(8, 8, 8), gpu.CAVITY_OPEN_DEFAULT, gpu.CAVITIES_REPORT, 0, 0, 0)
+    ms = C.c_float()
+    assert L.cvx_world_cavities(None, C.byref(p), 0, None, 0, None, C.byref(ms)) == -1  # CVX_ERR_INVALID_ARGUMENT: no context
+    # a context without a device or world (tests/cavity_rules.cpp): bad arguments first, then CVX_ERR_NOT_READY
+    codes = [int(v) for v in subprocess.check_output([rules, "args"], text=True).split()]
+    assert codes == [-1] * 13 + [-3], codes
+    h = C.c_void_p()
+    if L.cvx_create(0, C.byref(h)) == 0:  # (a machine with a device: the world is missing)
+        try:
+            assert L.cvx_world_cavities(h, C.byref(p), 0, None, 0, None, C.byref(ms)) == -3
+        finally:
+            L.cvx_destroy(h)
