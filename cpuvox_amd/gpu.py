@@ -35,6 +35,7 @@ EXPORTS = [
     "cvx_world_read_region", "cvx_world_read_level", "cvx_world_compact", "cvx_world_stamp_mesh", "cvx_world_copy", "cvx_world_pieces", "cvx_world_settle",
     "cvx_world_cavities",
     "cvx_world_light", "cvx_world_light_lamps", "cvx_world_move", "cvx_world_move_device",
+    "cvx_world_nav_build", "cvx_nav_field_goals", "cvx_nav_query", "cvx_nav_query_device", "cvx_nav_field_destroy",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -75,6 +76,7 @@ LIGHT_MAX_LAMPS, LAMP_MAX_RADIUS = 4096, 64      # cvx_world_light_lamps
 MOVE_UNIT = 256                                  # cvx_move_body: position units per LOD-0 voxel
 MOVE_SOLID_BELOW, MOVE_SOLID_SIDES = 1, 2        # cvx_move_body.flags
 MOVED_BLOCKED_MASK, MOVED_RESTING, MOVED_STARTS_SOLID, MOVED_STEPPED, MOVED_INVALID = 0x3F, 1 << 6, 1 << 7, 1 << 8, -(1 << 31)  # cvx_move_result.flags
+NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
 
@@ -135,6 +137,20 @@ class MoveResult(C.Structure):  # cvx_move_result
     _fields_ = [("pos", C.c_int32 * 3), ("flags", C.c_int32)]
 
 
+class NavParams(C.Structure):  # cvx_nav_params
+    _fields_ = [("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("width", C.c_int32), ("height", C.c_int32), ("stepUp", C.c_int32),
+                ("maxDrop", C.c_int32), ("maxSteps", C.c_int32), ("pad_", C.c_int32)]
+
+
+class NavStep(C.Structure):  # cvx_nav_step
+    _fields_ = [("cell", C.c_int32 * 3), ("distance", C.c_int32), ("next", C.c_int32 * 3), ("direction", C.c_int32)]
+
+
+class NavSummary(C.Structure):  # cvx_nav_summary
+    _fields_ = [("nodes", C.c_int64), ("reached", C.c_int64), ("goalsResolved", C.c_int32), ("largestDistance", C.c_int32),
+                ("columnsWithSeveralNodes", C.c_int64), ("launches", C.c_int32), ("pad_", C.c_int32)]
+
+
 class _TextureStruct(C.Structure):  # cvx_mesh_texture
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
 
@@ -155,6 +171,9 @@ CAVITIES_SUMMARY_DTYPE = np.dtype([("enclosedCavities", "<i8"), ("enclosedVoxels
                                    ("openRegions", "<i8"), ("openVoxels", "<i8")])  # cvx_cavities_summary
 MOVE_BODY_DTYPE = np.dtype([("pos", "<i4", 3), ("size", "<i4", 3), ("delta", "<i4", 3), ("stepUp", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])  # cvx_move_body
 MOVE_RESULT_DTYPE = np.dtype([("pos", "<i4", 3), ("flags", "<i4")])  # cvx_move_result
+NAV_STEP_DTYPE = np.dtype([("cell", "<i4", 3), ("distance", "<i4"), ("next", "<i4", 3), ("direction", "<i4")])  # cvx_nav_step
+NAV_SUMMARY_DTYPE = np.dtype([("nodes", "<i8"), ("reached", "<i8"), ("goalsResolved", "<i4"), ("largestDistance", "<i4"),
+                              ("columnsWithSeveralNodes", "<i8"), ("launches", "<i4"), ("pad_", "<i4")])  # cvx_nav_summary
 
 
 def strokes_array(strokes) -> np.ndarray:
@@ -348,6 +367,12 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_light_lamps.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_move.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.cvx_world_move_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.cvx_world_nav_build.argtypes = [C.c_void_p, C.POINTER(NavParams), C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_nav_field_goals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_nav_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.cvx_nav_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvx_nav_field_destroy.argtypes = [C.c_void_p]
+        L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
@@ -394,6 +419,7 @@ class Context:
         if buffer_count != 2:
             self._check(lib().cvx_set_buffer_count(self._h, buffer_count))
         self.buffer_count = buffer_count
+        self._nav_fields = []  # the NavFields still open: closed with the context, which they must not outlive
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -401,6 +427,8 @@ class Context:
 
     def close(self) -> None:
         if self._h:
+            for field in list(getattr(self, "_nav_fields", ())):
+                field.close()
             lib().cvx_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -643,6 +671,22 @@ class Context:
         self._check(lib().cvx_world_move_device(self._h, int(body_count), C.c_void_p(int(bodies_ptr)), C.c_void_p(int(results_ptr)), int(lanes_per_body),
                                                 C.c_void_p(int(stream)) if stream else None))
 
+    def nav_build(self, box_min, box_max, goals, *, width: int = 1, height: int = 2, step_up: int = 1, max_drop: int = 3, max_steps: int = 0) -> "NavField":
+        """A walking-distance field (include/cpuvox_gpu.h, cvx_world_nav_build) over the places a width x height x width box can stand inside
+        [box_min, box_max), towards `goals` (int triples; each resolves to the floor below it): a NavField with .summary (dict), .ms, .goals(),
+        .query(), .query_device() and .close().  The field is a snapshot of the world as it is now; the context closes the fields it still owns."""
+        if len(box_min) != 3 or len(box_max) != 3:
+            raise ValueError("nav_build: box_min and box_max are three integers each")
+        g = np.ascontiguousarray(np.asarray(goals, dtype=np.int32).reshape(-1, 3))
+        p = NavParams((C.c_int32 * 3)(*[int(v) for v in box_min]), (C.c_int32 * 3)(*[int(v) for v in box_max]), width, height, step_up, max_drop, max_steps, 0)
+        handle, ms = C.c_void_p(), C.c_float()
+        summary = np.zeros(1, dtype=NAV_SUMMARY_DTYPE)
+        self._check(lib().cvx_world_nav_build(self._h, C.byref(p), g.ctypes.data if g.size else None, len(g), C.byref(handle), summary.ctypes.data, C.byref(ms)))
+        field = NavField(self, handle)
+        field._took(summary, ms)
+        self._nav_fields.append(field)
+        return field
+
     def pick(self, origins, directions, max_t):
         """First solid LOD-0 voxel along each ray -> (voxel int32[N, 3], face int32[N], argb uint32[N], t float32[N]).  max_t: a scalar or
         one per ray.  Misses: voxel -1, face -1, argb 0, t = max_t."""
@@ -857,6 +901,53 @@ class Context:
         total = C.c_uint64()
         self._check(self._diag("cvx_selftest_scan")(self._h, v.size, v.ctypes.data, C.byref(total)))
         return v, int(total.value)
+
+
+class NavField:
+    """A cvx_nav_field: made by Context.nav_build, closed by .close() or with its context."""
+
+    def __init__(self, ctx: "Context", handle):
+        self._ctx, self._h = ctx, handle
+        self.summary, self.ms = {}, 0.0
+
+    def _took(self, summary, ms) -> None:
+        self.summary = {name: int(summary[0][name]) for name in NAV_SUMMARY_DTYPE.names if name != "pad_"}
+        self.ms = ms.value
+
+    def goals(self, goals, max_steps: int = 0) -> dict:
+        """Solves the same nodes and steps for new goals (cvx_nav_field_goals) -> the new summary."""
+        g = np.ascontiguousarray(np.asarray(goals, dtype=np.int32).reshape(-1, 3))
+        summary, ms = np.zeros(1, dtype=NAV_SUMMARY_DTYPE), C.c_float()
+        self._ctx._check(lib().cvx_nav_field_goals(self._ctx._h, self._h, g.ctypes.data if g.size else None, len(g), int(max_steps), summary.ctypes.data, C.byref(ms)))
+        self._took(summary, ms)
+        return self.summary
+
+    def query(self, cells) -> np.ndarray:
+        """cvx_nav_query: positions (int triples) -> a NAV_STEP_DTYPE array, one cvx_nav_step each."""
+        c = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 3))
+        out = np.zeros(len(c), dtype=NAV_STEP_DTYPE)
+        self._ctx._check(lib().cvx_nav_query(self._ctx._h, self._h, len(c), c.ctypes.data if len(c) else None, out.ctypes.data if len(c) else None))
+        return out
+
+    def query_device(self, count: int, cells_ptr: int, steps_ptr: int, stream: int = 0) -> None:
+        """cvx_nav_query on device arrays (addresses of 3 * count int32 and count cvx_nav_step): enqueues on `stream` (a hipStream_t as an
+        integer; 0 = the context's stream) and does not wait."""
+        self._ctx._check(lib().cvx_nav_query_device(self._ctx._h, self._h, int(count), C.c_void_p(int(cells_ptr)), C.c_void_p(int(steps_ptr)),
+                                                    C.c_void_p(int(stream)) if stream else None))
+
+    def close(self) -> None:
+        if self._h:
+            lib().cvx_nav_field_destroy(self._h)
+            self._h = C.c_void_p()
+            if self in self._ctx._nav_fields:
+                self._ctx._nav_fields.remove(self)
+
+    def __del__(self):
+        try:
+            if self._ctx._h:  # (a context that is gone has closed its fields)
+                self.close()
+        except Exception:
+            pass
 
 
 def pack_frames(frames):

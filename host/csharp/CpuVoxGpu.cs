@@ -186,6 +186,37 @@ namespace CpuVox.Gpu
 		public int Flags;
 	}
 
+	// cvx_world_nav_build: the call's parameters (48 bytes).  Box [BoxMin, BoxMax) in LOD-0 voxels; the body is Width x Height x Width voxels
+	// (1 .. 8, 1 .. 64); StepUp 0 .. Height and MaxDrop 0 .. 4096 voxels per step; MaxSteps 0: no bound
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct NavParams
+	{
+		public fixed int BoxMin[3];
+		public fixed int BoxMax[3];
+		public int Width, Height, StepUp, MaxDrop, MaxSteps, Pad;
+	}
+
+	// cvx_nav_query: what a position resolves to (32 bytes).  Cell: the stand cell ({-1,-1,-1}: none); Distance: steps to the nearest goal (-1: no
+	// cell or unreached); Next: the cell to step to (the own cell at a goal); Direction 0, 1, 4, 5 = -X, +X, -Z, +Z (-1: at a goal or Distance < 0)
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct NavStep
+	{
+		public fixed int Cell[3];
+		public int Distance;
+		public fixed int Next[3];
+		public int Direction;
+	}
+
+	// cvx_world_nav_build / cvx_nav_field_goals: the totals (40 bytes); Launches is informative, not part of the deterministic result
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public struct NavSummary
+	{
+		public long Nodes, Reached;
+		public int GoalsResolved, LargestDistance;
+		public long ColumnsWithSeveralNodes;
+		public int Launches, Pad;
+	}
+
 	// cvx_world_copy: one placement (48 bytes).  Source box [SrcMin, SrcMax) in LOD-0 voxels, destination min corner Dst; Transform bits 0-1 quarter
 	// turns, bit 2 mirror X (before turning), bit 3 flip Y; Op: 0 fill, 1 carve, 2 paint, 3 replace; Move 1: the source box becomes air
 	[StructLayout(LayoutKind.Sequential, Pack = 4)]
@@ -275,6 +306,15 @@ namespace CpuVox.Gpu
 		public const int CVX_MOVED_BLOCKED_MASK = 0x3F, CVX_MOVED_RESTING = 1 << 6, CVX_MOVED_STARTS_SOLID = 1 << 7, CVX_MOVED_STEPPED = 1 << 8, CVX_MOVED_INVALID = int.MinValue;
 		[DllImport(Lib)] public static extern int cvx_world_move(IntPtr ctx, int bodyCount, MoveBody* bodies, MoveResult* results);
 		[DllImport(Lib)] public static extern int cvx_world_move_device(IntPtr ctx, int bodyCount, IntPtr bodiesDevice, IntPtr resultsDevice, int lanesPerBody, IntPtr hipStream);
+		// a walking-distance field over the places a Width x Height x Width box can stand, towards goals (int triples): built and solved on the device,
+		// re-solved for new goals, queried for host or device arrays of positions (int triples -> NavStep); a snapshot, destroyed before its context
+		public const int CVX_NAV_MAX_GOALS = 4096;
+		[DllImport(Lib)] public static extern int cvx_world_nav_build(IntPtr ctx, NavParams* navParams, int* goals, int goalCount, out IntPtr outField, NavSummary* summary,
+		                                                              out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_nav_field_goals(IntPtr ctx, IntPtr field, int* goals, int goalCount, int maxSteps, NavSummary* summary, out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_nav_query(IntPtr ctx, IntPtr field, int count, int* cells, NavStep* steps);
+		[DllImport(Lib)] public static extern int cvx_nav_query_device(IntPtr ctx, IntPtr field, int count, IntPtr cellsDevice, IntPtr stepsDevice, IntPtr hipStream);
+		[DllImport(Lib)] public static extern void cvx_nav_field_destroy(IntPtr field);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

@@ -727,6 +727,79 @@ int cvx_world_move(cvx_context *ctx, int bodyCount, const cvx_move_body *bodies,
 int cvx_world_move_device(cvx_context *ctx, int bodyCount, const cvx_move_body *bodiesDevice, cvx_move_result *resultsDevice,
                           int lanesPerBody, void *hipStream);
 
+/* ---- walking-distance fields over the uploaded world -----------------------------------------------------------------------------------------
+ * cvx_world_nav_build: the question that precedes every cvx_world_move -- which way should this body go?  The call builds a DISTANCE FIELD (a
+ * flow field) over the places a box of width x height x width voxels can stand in LOD 0, walking towards one or more goals with step-up and
+ * drop limits; cvx_nav_query reads it for thousands of agents per frame.  The rule is exact integers in LOD-0 voxels of the stored tile (a
+ * repeating world does not wrap); neither call changes the world.
+ *   Blocked.  A CELL (x, y, z) is the voxel of the body's min corner.  B(x, y, z) is true when any voxel (x + i, y, z + k), 0 <= i, k < width, is
+ *     solid in the arena; everything at y >= dimY is air, y < 0 is the floor (solid).  Cells exist only for x0 <= x <= x1 - width and
+ *     z0 <= z <= z1 - width of the box clipped to the world: the body lies inside the clipped box in X and Z.  A box narrower than the body has
+ *     no cells: CVX_OK and an empty field.
+ *   Stand cell.  y0 <= y < y1 (the clipped box's y range selects floors only; headroom is read above y1 as well), B(x, y + j, z) false for
+ *     j = 0 .. height - 1, and y = 0 or B(x, y - 1, z) true: exactly a body for which cvx_world_move with CVX_MOVE_SOLID_BELOW reports
+ *     CVX_MOVED_RESTING without CVX_MOVED_STARTS_SOLID.
+ *   Step.  From stand cell a = (x, y, z) to stand cell b = (x', y', z') with |x - x'| + |z - z'| = 1, when -maxDrop <= y' - y <= stepUp and, with
+ *     t = max(y, y') + height, B(x, j, z) is false for y <= j < t and B(x', j, z') for y' <= j < t: the body rises in place or falls in the
+ *     destination through clear air.  Steps are directed (a cliff may be descended and not climbed); every step costs 1.
+ *   Distance.  A goal (gx, gy, gz) RESOLVES to the stand cell (gx, y, gz), y <= gy, with B(gx, j, gz) false for y <= j <= gy -- the floor the body
+ *     would fall to -- or to nothing.  distance(c) = the fewest steps from c to any resolved goal; maxSteps > 0 leaves cells farther than that
+ *     unreached.  No resolved goal: CVX_OK, nothing reached.
+ *   Next.  For a reached cell with distance > 0 the target of a step with distance - 1: the first direction in the order -X, +X, -Z, +Z that has
+ *     one, and in it the highest y'.  At a goal the cell itself.
+ * The whole field is a function of the world and the arguments: no schedule and no goal order shows in it.  What the device computes: per cell
+ * column the maximal air intervals [lo, hi) of the union of its width x width arena columns (the topmost open upwards); an interval with
+ * hi - lo >= height and y0 <= lo < y1 is a NODE with stand cell (x, lo, z); a step a -> b exists iff -maxDrop <= lo_b - lo_a <= stepUp and
+ * min(hi_a, hi_b) >= max(lo_a, lo_b) + height; distances by relaxation to the unique fixpoint.
+ * A query position resolves exactly as a goal does: an airborne agent gets the floor below it; a position in solid, outside the cell grid or
+ * over an interval too low for the body gets no cell.  cvx_nav_field_goals keeps the nodes and steps and solves for new goals (the player
+ * moved).  The field is a SNAPSHOT: later edits do not change it, the host rebuilds after an edit.  It owns its device memory and must be
+ * destroyed before its context; destroying NULL is a no-op.  `goals` and `cells` hold three int32 per entry.
+ * `summary` (may be NULL): nodes, reached nodes, the goals that resolved (entries, duplicates included), the largest distance of a reached
+ * node (0: none), the cell columns with two or more nodes, and the relax launches made (informative: not part of the deterministic result).
+ * Ordering as cvx_world_pieces / cvx_world_move: build and _goals are ordered on the context's stream behind everything enqueued before them
+ * (build places unplaced levels first) and return when the summary is on the host; cvx_nav_query returns when the steps are copied back;
+ * cvx_nav_query_device enqueues on hipStream (NULL = the context's) without waiting.  outDeviceMs (may be NULL): device time of the call.
+ * Errors, all checked on the host before anything is enqueued; a failing build leaves *outField NULL and frees everything.
+ * CVX_ERR_INVALID_ARGUMENT: NULL pointers, boxMin >= boxMax on an axis, a box wholly outside the world, width outside 1 .. 8, height outside
+ * 1 .. 64, stepUp outside 0 .. height, maxDrop outside 0 .. 4096, a negative maxSteps, goalCount outside 1 .. CVX_NAV_MAX_GOALS, a negative
+ * count, a field of another context; CVX_ERR_NOT_READY: LOD 0 has not been uploaded; CVX_ERR_CAPACITY: the tables do not fit in device memory,
+ * or 2^31 or more cell columns or nodes.  The device query cannot validate its input: a position that resolves to nothing gets no cell, and every
+ * loop of it is bounded by the column's node count whatever the input.
+ * Device memory of a field: 4 bytes per cell column and 16 bytes per node (its interval, distance and next); a build adds the count scan's
+ * scratch while it runs (8 bytes per chunk of columns), _goals 12 bytes per goal, and cvx_nav_query 44 bytes per position. */
+#define CVX_NAV_MAX_GOALS 4096
+typedef struct cvx_nav_params {   /* 48 bytes */
+	int32_t boxMin[3], boxMax[3]; /* LOD-0 voxels, inclusive / exclusive */
+	int32_t width;                /* 1 .. 8   footprint, voxels, square */
+	int32_t height;               /* 1 .. 64 */
+	int32_t stepUp;               /* 0 .. height */
+	int32_t maxDrop;              /* 0 .. 4096 */
+	int32_t maxSteps;             /* 0: no bound */
+	int32_t pad_;
+} cvx_nav_params;
+typedef struct cvx_nav_step {     /* 32 bytes */
+	int32_t cell[3];              /* the stand cell the queried position resolves to; {-1,-1,-1}: none */
+	int32_t distance;             /* steps to the nearest goal; -1: no cell or unreached */
+	int32_t next[3];              /* the cell to step to (own cell at a goal); {-1,-1,-1} when distance < 0 */
+	int32_t direction;            /* 0,1,4,5 = -X,+X,-Z,+Z (the pick's face numbers); -1: at a goal or distance < 0 */
+} cvx_nav_step;
+typedef struct cvx_nav_summary {  /* 40 bytes */
+	int64_t nodes, reached;
+	int32_t goalsResolved, largestDistance;
+	int64_t columnsWithSeveralNodes;
+	int32_t launches, pad_;       /* relax launches made: informative, not part of the deterministic result */
+} cvx_nav_summary;
+typedef struct cvx_nav_field cvx_nav_field;
+int  cvx_world_nav_build(cvx_context *ctx, const cvx_nav_params *params, const int32_t *goals, int goalCount,
+                         cvx_nav_field **outField, cvx_nav_summary *summary, float *outDeviceMs);
+int  cvx_nav_field_goals(cvx_context *ctx, cvx_nav_field *field, const int32_t *goals, int goalCount, int maxSteps,
+                         cvx_nav_summary *summary, float *outDeviceMs);
+int  cvx_nav_query(cvx_context *ctx, const cvx_nav_field *field, int count, const int32_t *cells, cvx_nav_step *steps);
+int  cvx_nav_query_device(cvx_context *ctx, const cvx_nav_field *field, int count, const int32_t *cellsDevice,
+                          cvx_nav_step *stepsDevice, void *hipStream);
+void cvx_nav_field_destroy(cvx_nav_field *field);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
