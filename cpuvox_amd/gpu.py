@@ -36,6 +36,7 @@ EXPORTS = [
     "cvx_world_cavities",
     "cvx_world_light", "cvx_world_light_lamps", "cvx_world_move", "cvx_world_move_device",
     "cvx_world_nav_build", "cvx_nav_field_goals", "cvx_nav_query", "cvx_nav_query_device", "cvx_nav_field_destroy",
+    "cvx_world_surface", "cvx_world_surface_device", "cvx_surface_triangles",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -76,6 +77,8 @@ LIGHT_MAX_LAMPS, LAMP_MAX_RADIUS = 4096, 64      # cvx_world_light_lamps
 MOVE_UNIT = 256                                  # cvx_move_body: position units per LOD-0 voxel
 MOVE_SOLID_BELOW, MOVE_SOLID_SIDES = 1, 2        # cvx_move_body.flags
 MOVED_BLOCKED_MASK, MOVED_RESTING, MOVED_STARTS_SOLID, MOVED_STEPPED, MOVED_INVALID = 0x3F, 1 << 6, 1 << 7, 1 << 8, -(1 << 31)  # cvx_move_result.flags
+SURFACE_OUTSIDE_DEFAULT = 0x04                   # cvx_world_surface: solidOutside, the ground below y = 0 is solid
+SURFACE_IGNORE_COLOUR = 1                        # ... flags
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -151,6 +154,14 @@ class NavSummary(C.Structure):  # cvx_nav_summary
                 ("columnsWithSeveralNodes", C.c_int64), ("launches", C.c_int32), ("pad_", C.c_int32)]
 
 
+class SurfaceQuad(C.Structure):  # cvx_surface_quad
+    _fields_ = [("voxel", C.c_int32 * 3), ("face", C.c_int32), ("length", C.c_int32), ("argb", C.c_uint32)]
+
+
+class SurfaceSummary(C.Structure):  # cvx_surface_summary
+    _fields_ = [("quads", C.c_int64), ("unitFaces", C.c_int64), ("quadsPerFace", C.c_int64 * 6)]
+
+
 class _TextureStruct(C.Structure):  # cvx_mesh_texture
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
 
@@ -174,6 +185,20 @@ MOVE_RESULT_DTYPE = np.dtype([("pos", "<i4", 3), ("flags", "<i4")])  # cvx_move_
 NAV_STEP_DTYPE = np.dtype([("cell", "<i4", 3), ("distance", "<i4"), ("next", "<i4", 3), ("direction", "<i4")])  # cvx_nav_step
 NAV_SUMMARY_DTYPE = np.dtype([("nodes", "<i8"), ("reached", "<i8"), ("goalsResolved", "<i4"), ("largestDistance", "<i4"),
                               ("columnsWithSeveralNodes", "<i8"), ("launches", "<i4"), ("pad_", "<i4")])  # cvx_nav_summary
+SURFACE_QUAD_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("length", "<i4"), ("argb", "<u4")])  # cvx_surface_quad
+SURFACE_SUMMARY_DTYPE = np.dtype([("quads", "<i8"), ("unitFaces", "<i8"), ("quadsPerFace", "<i8", 6)])  # cvx_surface_summary
+
+
+def surface_triangles(quads):
+    """cvx_surface_triangles: a SURFACE_QUAD_DTYPE array -> (4 n vertices as a MESH_VERTEX_DTYPE array, 6 n int32 indices): every quad's rectangle
+    on its face plane, wound outward, with the vertex colour cvx_world_stamp_mesh turns back into the quad's colour word.  A pure host call."""
+    q = np.ascontiguousarray(quads, dtype=SURFACE_QUAD_DTYPE)
+    vertices = np.zeros(4 * q.size, dtype=MESH_VERTEX_DTYPE)
+    indices = np.zeros(6 * q.size, dtype=np.int32)
+    rc = lib().cvx_surface_triangles(q.ctypes.data if q.size else None, q.size, vertices.ctypes.data if q.size else None, indices.ctypes.data if q.size else None)
+    if rc != 0:
+        raise CvxError(f"cvx error {rc}: {lib().cvx_last_error(None).decode()}")
+    return vertices, indices
 
 
 def strokes_array(strokes) -> np.ndarray:
@@ -372,6 +397,9 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_nav_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.cvx_nav_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvx_nav_field_destroy.argtypes = [C.c_void_p]
+        L.cvx_world_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_surface_device.argtypes = L.cvx_world_surface.argtypes
+        L.cvx_surface_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -618,6 +646,34 @@ class Context:
                                              C.byref(ms)))
         totals = {name: int(summary[0][name]) for name in CAVITIES_SUMMARY_DTYPE.names}
         return out[:min(out.size, totals["selectedCavities"])].copy(), totals, ms.value
+
+    def _surface(self, entry, box_min, box_max, solid_outside, flags, quads_ptr, capacity):
+        lo, hi = np.ascontiguousarray(box_min, dtype=np.int32), np.ascontiguousarray(box_max, dtype=np.int32)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("world_surface: box_min and box_max are three integers each")
+        summary = np.zeros(1, dtype=SURFACE_SUMMARY_DTYPE)
+        ms = C.c_float()
+        self._check(entry(self._h, lo.ctypes.data, hi.ctypes.data, solid_outside, flags, quads_ptr, int(capacity), summary.ctypes.data, C.byref(ms)))
+        totals = {"quads": int(summary[0]["quads"]), "unitFaces": int(summary[0]["unitFaces"]), "quadsPerFace": [int(v) for v in summary[0]["quadsPerFace"]]}
+        return totals, ms.value
+
+    def world_surface(self, box_min, box_max, solid_outside: int = SURFACE_OUTSIDE_DEFAULT, flags: int = 0, capacity=None):
+        """The exposed faces of the solid LOD-0 voxels inside [box_min, box_max) as coloured quads (maximal vertical runs of one colour per column
+        and side face; SURFACE_IGNORE_COLOUR: of any colour; one quad per exposed -Y / +Y voxel face), in (x, z, face, descending y) order:
+        (the first `capacity` quads as a SURFACE_QUAD_DTYPE array, the totals of cvx_surface_summary as a dict, device milliseconds).
+        `solid_outside` bits 0..5 = -X,+X,-Y,+Y,-Z,+Z: what lies across a face of the world.  capacity=None asks for the count first and then
+        for every quad (the milliseconds are the second call's)."""
+        if capacity is None:
+            totals, _ = self._surface(lib().cvx_world_surface, box_min, box_max, solid_outside, flags, None, 0)
+            capacity = totals["quads"]
+        out = np.zeros(max(int(capacity), 0), dtype=SURFACE_QUAD_DTYPE)
+        totals, ms = self._surface(lib().cvx_world_surface, box_min, box_max, solid_outside, flags, out.ctypes.data if out.size else None, capacity)
+        return (out if out.size <= totals["quads"] else out[:totals["quads"]].copy()), totals, ms
+
+    def world_surface_device(self, box_min, box_max, quads_ptr: int, capacity: int, solid_outside: int = SURFACE_OUTSIDE_DEFAULT, flags: int = 0):
+        """world_surface into device memory (the address of `capacity` cvx_surface_quad, e.g. a torch tensor's data_ptr()): the first min(capacity,
+        quads) entries are written, the rest is left alone; returns (the totals, device milliseconds) once the summary is on the host."""
+        return self._surface(lib().cvx_world_surface_device, box_min, box_max, solid_outside, flags, quads_ptr or None, capacity)
 
     def debug_cavities(self) -> dict:
         """Diagnostics build only (include/cpuvox_gpu_diag.h): the last world_cavities' device ms split (analysis, edit), its air intervals and

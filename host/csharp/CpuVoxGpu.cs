@@ -145,6 +145,23 @@ namespace CpuVox.Gpu
 		public long EnclosedCavities, EnclosedVoxels, SelectedCavities, SelectedVoxels, OpenRegions, OpenVoxels;
 	}
 
+	// cvx_world_surface: one quad (24 bytes): its lowest voxel, Face 0 .. 5 = -X, +X, -Y, +Y, -Z, +Z, Length voxels along +Y (1 for -Y / +Y), the colour word
+	[StructLayout(LayoutKind.Sequential, Pack = 4)]
+	public unsafe struct SurfaceQuad
+	{
+		public fixed int Voxel[3];
+		public int Face, Length;
+		public uint Argb;
+	}
+
+	// cvx_world_surface: the totals (64 bytes): every quad whatever the capacity, the sum of their lengths (the exposed voxel faces), the quads per face
+	[StructLayout(LayoutKind.Sequential, Pack = 8)]
+	public unsafe struct SurfaceSummary
+	{
+		public long Quads, UnitFaces;
+		public fixed long QuadsPerFace[6];
+	}
+
 	// cvx_world_light: the call's parameters (64 bytes).  Box [BoxMin, BoxMax) in LOD-0 voxels; SunDir points TOWARDS the sun (integers, |.| <= 1024,
 	// all 0: no sun term); levels 0 .. 255; SunRange 0 .. 4096 voxels of the shadow walk, SkyRange 0 .. 32 voxels per sky direction; Target 0: the
 	// shade is multiplied into R, G, B (one-shot), 1: it is stored in A
@@ -315,6 +332,15 @@ namespace CpuVox.Gpu
 		[DllImport(Lib)] public static extern int cvx_nav_query(IntPtr ctx, IntPtr field, int count, int* cells, NavStep* steps);
 		[DllImport(Lib)] public static extern int cvx_nav_query_device(IntPtr ctx, IntPtr field, int count, IntPtr cellsDevice, IntPtr stepsDevice, IntPtr hipStream);
 		[DllImport(Lib)] public static extern void cvx_nav_field_destroy(IntPtr field);
+		// the exposed faces of LOD 0 inside a box as coloured quads in (x, z, face, descending y) order (solidOutside bits 0 .. 5: what lies across a face of
+		// the world; flags 1: colour does not end a quad); capacity 0 with no list asks for the count; the device call leaves the quads in device memory;
+		// cvx_surface_triangles (host only) expands quads into 4 vertices and 6 indices each, wound outward
+		public const int CVX_SURFACE_OUTSIDE_DEFAULT = 0x04, CVX_SURFACE_IGNORE_COLOUR = 1;
+		[DllImport(Lib)] public static extern int cvx_world_surface(IntPtr ctx, int* boxMin, int* boxMax, int solidOutside, int flags, SurfaceQuad* quads, long quadCapacity,
+		                                                            SurfaceSummary* summary, out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_world_surface_device(IntPtr ctx, int* boxMin, int* boxMax, int solidOutside, int flags, IntPtr quadsDevice, long quadCapacity,
+		                                                                   SurfaceSummary* summary, out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_surface_triangles(SurfaceQuad* quads, long quadCount, MeshVertex* vertices, int* indices);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

@@ -800,6 +800,59 @@ int  cvx_nav_query_device(cvx_context *ctx, const cvx_nav_field *field, int coun
                           cvx_nav_step *stepsDevice, void *hipStream);
 void cvx_nav_field_destroy(cvx_nav_field *field);
 
+/* ---- the exposed faces of the uploaded world as coloured quads ---------------------------------------------------------------------------------
+ * cvx_world_surface: the inverse of cvx_world_stamp_mesh -- a surface out of the edited world, for a physics engine's collision mesh, a
+ * rasterised preview or minimap, an OBJ export, an overlay of what a brush changed.  The rule is exact integers in LOD-0 voxels of the stored
+ * tile (a repeating world does not wrap the coordinates); the call only reads the arena.
+ *   Box.  The voxels considered are the solid voxels of LOD 0 inside [boxMin, boxMax) after clipping the box to the world.
+ *   Across a face.  Faces are numbered as the pick numbers them: 0..5 = -X,+X,-Y,+Y,-Z,+Z.  The voxel across face f of voxel v is read from the
+ *     arena whenever it lies inside the world, inside the box or not: the meshes of adjacent boxes tile, no face appears twice and none is
+ *     missing at the seam.  Outside the world it is solid iff bit f of solidOutside is set; CVX_SURFACE_OUTSIDE_DEFAULT makes the ground below
+ *     y = 0 solid and everything else air, above dimY too.
+ *   Exposed.  Face f of a solid voxel is exposed when the voxel across it is air.
+ *   Quads.  For a side face (f = 0, 1, 4, 5) a quad is a maximal vertical run of voxels of one column inside the box's y range that all have
+ *     face f exposed and all carry the same colour word (the arena's ARGB word, as cvx_world_pick reports it); how the column is encoded does
+ *     not show: a span split into two runs still gives one quad.  With CVX_SURFACE_IGNORE_COLOUR colour does not end a run and the quad carries
+ *     the colour of its top voxel: the collision mesh.  For f = 2, 3: one quad of length 1 per exposed voxel face.
+ *   Order.  Ascending x, then ascending z, then ascending face, then DESCENDING y of the quad's top.  The list is a function of the world and
+ *     the arguments: the same call twice gives the same bytes.
+ * `summary` (may be NULL): the total number of quads, the sum of their lengths (= the exposed voxel faces) and the quads per face, whatever
+ * the capacity.  `quads` receives the first min(quadCapacity, summary.quads) quads; a smaller capacity is not an error, and capacity 0 with
+ * quads NULL is the way to ask for the count.  outDeviceMs (may be NULL): device time of the call.
+ * cvx_world_surface is ordered on the context's stream behind everything enqueued before it, places unplaced levels first (as
+ * cvx_world_pieces does) and returns when the results are on the host.  cvx_world_surface_device leaves the quads in quadsDevice (device
+ * memory of quadCapacity entries; entries at and beyond min(quadCapacity, summary.quads) are not written); the summary still comes to the host
+ * and the call still waits for it.
+ * cvx_surface_triangles is a pure host function (no context, no device): four vertices and six indices per quad, quad k's vertices 4k .. 4k+3
+ * indexed 0,1,2, 0,2,3.  The corners are those of the quad's rectangle on its face plane -- face 0 on X = x, face 1 on X = x + 1, both
+ * spanning z .. z + 1 and y .. y + length; faces 2 / 3 on Y = y / Y = y + 1; faces 4 / 5 on Z = z / Z = z + 1 -- ordered so that
+ * (v1 - v0) x (v2 - v0) points along the face's outward axis.  rgba is the vertex colour for which cvx_world_stamp_mesh writes exactly the
+ * quad's colour word (alpha is ignored: 255); uv is 0 and material -1.  CVX_ERR_INVALID_ARGUMENT: a negative count, a NULL pointer with a
+ * count above 0, 2^29 or more quads, a face outside 0 .. 5.
+ * Errors of the two world calls, all checked on the host before anything is enqueued.  CVX_ERR_INVALID_ARGUMENT: a NULL box, boxMin >= boxMax
+ * on an axis, a box wholly outside the world, solidOutside bits above 0x3F, unknown flag bits, a negative capacity, quads NULL with a capacity
+ * above 0; CVX_ERR_NOT_READY: LOD 0 has not been uploaded; CVX_ERR_CAPACITY: the scratch does not fit in device memory, or the box holds 2^31
+ * or more (column, face) pairs or quads.  Device memory while it runs: 24 bytes per column of the clipped box (a count per face) and 8 bytes
+ * per 4096 (column, face) pairs for the scan; cvx_world_surface adds 24 bytes per quad it returns. */
+#define CVX_SURFACE_OUTSIDE_DEFAULT 0x04   /* -Y: the ground below y = 0 is solid, everything else outside the world is air */
+enum { CVX_SURFACE_IGNORE_COLOUR = 1 };    /* flags */
+typedef struct cvx_surface_quad {  /* 24 bytes */
+	int32_t voxel[3];  /* the quad's lowest voxel */
+	int32_t face;      /* 0..5 = -X,+X,-Y,+Y,-Z,+Z */
+	int32_t length;    /* voxels along +Y; 1 for the -Y / +Y faces */
+	uint32_t argb;     /* the colour word */
+} cvx_surface_quad;
+typedef struct cvx_surface_summary {  /* 64 bytes */
+	int64_t quads;            /* total quads */
+	int64_t unitFaces;        /* the sum of their lengths: the exposed voxel faces */
+	int64_t quadsPerFace[6];
+} cvx_surface_summary;
+int cvx_world_surface(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int solidOutside, int flags,
+                      cvx_surface_quad *quads, int64_t quadCapacity, cvx_surface_summary *summary, float *outDeviceMs);
+int cvx_world_surface_device(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int solidOutside, int flags,
+                             cvx_surface_quad *quadsDevice, int64_t quadCapacity, cvx_surface_summary *summary, float *outDeviceMs);
+int cvx_surface_triangles(const cvx_surface_quad *quads, int64_t quadCount, cvx_mesh_vertex *vertices, int32_t *indices);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
