@@ -1,0 +1,403 @@
+// cvx_dense.hip -- libcpuvox_gpu.so, dense voxel boxes out of and into the device-resident world (cvx_world_read_voxels[_device],
+// cvx_world_write_voxels[_device]).  See include/cpuvox_gpu.h for the contract and cvx_dense.h for the rules.
+//
+// A read is one kernel, a thread per element of the arrays: consecutive lanes are consecutive y of a column and go on into the next column (z,
+// then x) where the box is lower than a wave, so the stores are contiguous whatever the box's height.  Each lane finds its voxel with a binary
+// search of its column's runs (cvxb::DenseVoxel).
+// A write is a brush whose columns come from the dense arrays, step for step cvx_world_brush / cvx_world_copy:
+//   1. count  (a WAVE per LOD-0 column of the rounded rectangle): the column top-down, 64 voxels per step; every lane evaluates its voxel
+//             (cvxb::DenseFinal: the arrays inside the box, read contiguously, the arena elsewhere), a ballot gives the step's solid mask, its
+//             changes against itself shifted by one voxel the run starts, popcounts the run and colour counts; the steps between
+//             one run of the arena (or the box) and the next hold nothing but air and are taken in one go (a wave-uniform cursor over the
+//             column's runs), so a tall column costs its few live steps; columns the format cannot hold raise a flag
+//   2. the counts are prefix-scanned into element offsets; ONE copy brings the total and the flag to the host
+//   3. write  (same waves): the same walk; a lane that starts a run writes it when it ends at the next start of its step, prefix popcounts
+//             (mbcnt) give it its run slot and every solid lane its colour slot; the run that crosses a step is carried in wave-uniform state
+//   4. cvxi::EditFromDevice: the blob goes through cvx_world_edit's machinery (records, tails, growth, LOD 1 .. levelCount) unchanged.
+// Nothing in the arena is written before step 4, so a rejected write leaves the world as it was.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "cvx_context.h"
+#include "cvx_dense.h"
+
+using cvxi::Fail;
+
+namespace cvxdense {
+
+constexpr unsigned kThreads = 256;
+constexpr int kWavesPerBlock = kThreads / CVX_WAVE;
+
+struct ReadArgs {
+	cvxb::CopyWorld W;
+	cvxb::DenseBox box;
+	uint32_t n; // elements
+	uint32_t *argb;
+	uint8_t *solid;
+};
+
+__global__ __launch_bounds__(kThreads) void dense_read_kernel(ReadArgs A)
+{
+	const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+	if (i >= A.n) { return; }
+	const uint32_t sizeY = (uint32_t)A.box.size[1], sizeZ = (uint32_t)A.box.size[2];
+	const uint32_t column = i / sizeY, y = i - column * sizeY;
+	const uint32_t x = column / sizeZ, z = column - x * sizeZ;
+	const cvxb::Voxel v = cvxb::DenseVoxel(A.W, (int64_t)A.box.min[0] + x, (int64_t)A.box.min[1] + y, (int64_t)A.box.min[2] + z);
+	if (A.argb) { A.argb[i] = v.argb; }
+	if (A.solid) { A.solid[i] = v.solid ? 1 : 0; }
+}
+
+struct WriteArgs {
+	cvxb::CopyWorld W;
+	cvxb::DenseBox box;
+	const uint32_t *argb;
+	const uint8_t *solid;
+	int op;
+	int x0, z0, sizeZ, n;
+	uint32_t *counts;     // per column: elements (-> offset after the scan)
+	uint32_t *runCounts;  // per column: runs (0: the column is empty)
+	unsigned int *overLimit;
+	uint32_t *headers;    // write: the sub-world blob, n headers of 3 words
+	uint32_t *elements;
+};
+
+__device__ __forceinline__ uint32_t LanesBelow(uint64_t mask) // the set bits of `mask` below this lane
+{
+	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The wave's walk of column `i` of the rectangle (the steps of cvx_dense.h).  kWrite: runs go to outRuns, colours to outColours
+// (cvxb::DenseColumn's out arrays).  Everything but y, the voxel and the lane's slots is the same in all lanes.
+template <bool kWrite>
+__device__ __forceinline__ cvxb::BrushResult WalkColumn(const WriteArgs &A, int i, int lane, uint32_t *outRuns, uint32_t *outColours)
+{
+	const int64_t cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
+	const cvxb::ArenaColumn col = cvxb::CopyColumnAt(A.W, cx, cz);
+	const int dimY = A.W.dimY;
+	int64_t lo, hi, base;
+	cvxb::DenseSpan(A.box, cx, cz, dimY, &lo, &hi, &base);
+	const uint32_t count = col.Count();
+	uint32_t cursor = 0u;
+	uint32_t *lane0Runs = kWrite && lane == 0 ? outRuns : nullptr;
+	cvxb::DenseWalk w;
+	for (int yTop = dimY - 1; yTop >= 0; yTop -= CVX_WAVE) {
+		const int air = cvxb::DenseAirSteps(col, count, &cursor, lo, hi, yTop);
+		if (air > 0) { // nothing but air down to the next run of the arena or the box: all those steps at once
+			const int voxels = air * CVX_WAVE < yTop + 1 ? air * CVX_WAVE : yTop + 1;
+			cvxb::DenseAdvanceAir(w, (uint32_t)voxels, lane0Runs);
+			yTop -= (air - 1) * CVX_WAVE;
+			continue;
+		}
+		const int y = yTop - lane;
+		const uint32_t valid = (uint32_t)(yTop + 1 < CVX_WAVE ? yTop + 1 : CVX_WAVE);
+		cvxb::Voxel v{ false, 0u };
+		if (y >= 0) { v = cvxb::DenseFinal(col, A.W.colourSlots, A.W.colorShift, lo <= y && y < hi, base + y, A.argb, A.solid, A.op, y); }
+		const uint64_t mask = __ballot(v.solid); // bit l: the voxel yTop - l
+		const uint64_t starts = cvxb::DenseStarts(w, mask, valid);
+		if (kWrite) {
+			const uint32_t solidBelow = LanesBelow(mask);
+			cvxb::DenseLaneRun(w, mask, starts, lane, LanesBelow(starts), solidBelow, outRuns);
+			if (v.solid) { outColours[w.colours + solidBelow] = v.argb; }
+		}
+		cvxb::DenseAdvance(w, mask, starts, valid, yTop, lane0Runs);
+	}
+	return cvxb::DenseFinish(w, lane0Runs);
+}
+
+__global__ __launch_bounds__(kThreads) void dense_count_kernel(WriteArgs A)
+{
+	const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWavesPerBlock + threadIdx.x / CVX_WAVE));
+	const int lane = (int)(threadIdx.x % CVX_WAVE);
+	if (i >= A.n) { return; }
+	const cvxb::BrushResult r = WalkColumn<false>(A, i, lane, nullptr, nullptr);
+	if (lane != 0) { return; }
+	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
+	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.runCounts[i] = r.runCount;
+}
+
+__global__ __launch_bounds__(kThreads) void dense_write_kernel(WriteArgs A)
+{
+	const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWavesPerBlock + threadIdx.x / CVX_WAVE));
+	const int lane = (int)(threadIdx.x % CVX_WAVE);
+	if (i >= A.n) { return; }
+	const uint32_t off = A.counts[i], runCount = A.runCounts[i];
+	uint32_t *h = A.headers + 3 * (size_t)i;
+	if (runCount == 0u) {
+		if (lane < 3) { h[lane] = 0u; }
+		return;
+	}
+	uint32_t *e = A.elements + off;
+	// (the count kernel left the run count: the colours go behind the runs' second guard in the same walk)
+	const cvxb::BrushResult r = WalkColumn<true>(A, i, lane, e + 1, e + runCount + 2u);
+	if (lane != 0) { return; }
+	e[0] = 0u;
+	e[runCount + 1u] = 0u;
+	h[0] = off;
+	h[1] = runCount | (r.worldMin << 16);
+	h[2] = r.worldMax;
+}
+
+} // namespace cvxdense
+
+namespace {
+
+using cvxdense::kThreads;
+
+unsigned Grid(size_t n, unsigned per = kThreads) { return (unsigned)((n + per - 1) / per); }
+
+cvxb::CopyWorld WorldOf(const cvx_context *ctx)
+{
+	const DevWorldLevel &L = ctx->hostWorld.level[0];
+	cvxb::CopyWorld W;
+	W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
+	W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
+	W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
+	W.rowShift = L.rowShift;
+	W.colorShift = L.colorShift;
+	W.dimX = ctx->hostWorld.dimX;
+	W.dimY = ctx->hostWorld.dimY;
+	W.dimZ = ctx->hostWorld.dimZ;
+	return W;
+}
+
+// The checks both directions share; *elements receives the box's voxel count.
+int CheckBox(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], cvxb::DenseBox *box, int64_t *elements)
+{
+	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a NULL box", call); }
+	int64_t n = 1;
+	for (int a = 0; a < 3; a++) {
+		if (boxMin[a] < -(1 << 30) || boxMin[a] > (1 << 30) || boxMax[a] < -(1 << 30) || boxMax[a] > (1 << 30)) {
+			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d has a coordinate beyond 2^30", call, boxMin[a], boxMax[a], a);
+		}
+		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d is empty", call, boxMin[a], boxMax[a], a); }
+		box->min[a] = boxMin[a];
+		box->size[a] = (int32_t)((int64_t)boxMax[a] - boxMin[a]); // (at most 2^31 - 1: the product check below rejects it anyway)
+	}
+	for (int a = 0; a < 3; a++) {
+		n *= (int64_t)boxMax[a] - boxMin[a]; // (each factor at most 2^31, the running product below 2^31 before it: no overflow)
+		if (n >= ((int64_t)1 << 31)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a box of 2^31 or more voxels", call); }
+	}
+	*elements = n;
+	return CVX_OK;
+}
+
+int Prepare(cvx_context *ctx)
+{
+	CVX_HIP(ctx, hipSetDevice(ctx->device));
+	return cvxi::SyncWorld(ctx);
+}
+
+int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], uint32_t *argb, uint8_t *solid, bool device, void *hipStream,
+         float *outDeviceMs)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	cvxdense::ReadArgs A{};
+	int64_t n = 0;
+	int rc = CheckBox(ctx, call, boxMin, boxMax, &A.box, &n);
+	if (rc != CVX_OK) { return rc; }
+	if (!argb && !solid) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: argb and solid are both NULL", call); }
+	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	rc = Prepare(ctx);
+	if (rc != CVX_OK) { return rc; }
+	A.W = WorldOf(ctx);
+	A.n = (uint32_t)n;
+	if (device) {
+		A.argb = argb;
+		A.solid = solid;
+		hipStream_t stream = hipStream ? static_cast<hipStream_t>(hipStream) : ctx->stream;
+		hipLaunchKernelGGL(cvxdense::dense_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, stream, A);
+		CVX_HIP(ctx, hipGetLastError());
+		return CVX_OK;
+	}
+	hipEvent_t ev[2] = { nullptr, nullptr };
+	uint8_t *scratch = nullptr;
+	auto release = [&]() {
+		if (scratch) { (void)hipFree(scratch); }
+		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
+	};
+	const size_t argbBytes = argb ? (size_t)n * 4 : 0, solidBytes = solid ? (size_t)n : 0;
+	hipError_t e = hipEventCreate(&ev[0]);
+	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
+	if (e == hipSuccess) {
+		e = hipMalloc((void **)&scratch, argbBytes + solidBytes);
+		if (e == hipErrorOutOfMemory) {
+			release();
+			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the box", call, argbBytes + solidBytes);
+		}
+	}
+	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	if (e == hipSuccess) {
+		A.argb = argb ? reinterpret_cast<uint32_t *>(scratch) : nullptr;
+		A.solid = solid ? scratch + argbBytes : nullptr;
+		hipLaunchKernelGGL(cvxdense::dense_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess && argb) { e = hipMemcpyAsync(argb, A.argb, argbBytes, hipMemcpyDeviceToHost, ctx->stream); }
+	if (e == hipSuccess && solid) { e = hipMemcpyAsync(solid, A.solid, solidBytes, hipMemcpyDeviceToHost, ctx->stream); }
+	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
+	if (e != hipSuccess) {
+		release();
+		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
+	}
+	if (outDeviceMs) {
+		float ms = 0.f;
+		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+		*outDeviceMs = e == hipSuccess ? ms : 0.f;
+	}
+	release();
+	return CVX_OK;
+}
+
+// Both writes: `device` says where argb / solid live.
+int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], const uint32_t *argb, const uint8_t *solid, bool device, int op,
+          int levelCount, float *outDeviceMs)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	cvxdense::WriteArgs A{};
+	int64_t elements = 0;
+	int rc = CheckBox(ctx, call, boxMin, boxMax, &A.box, &elements);
+	if (rc != CVX_OK) { return rc; }
+	if (op < CVX_BRUSH_FILL || op > CVX_COPY_REPLACE) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: bad op %d", call, op); }
+	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
+	if (!argb && !(op == CVX_BRUSH_CARVE && solid)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: argb is NULL (only a CARVE with a solid mask may leave it out)", call); }
+	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	const int dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
+	// the rectangle: the box clipped to the world, its footprint rounded out to 2^levelCount, clipped again
+	int64_t lo[3], hi[3];
+	bool touches = true;
+	for (int a = 0; a < 3; a++) {
+		lo[a] = std::max<int64_t>(boxMin[a], 0);
+		hi[a] = std::min<int64_t>(boxMax[a], dim[a]);
+		touches = touches && lo[a] < hi[a];
+	}
+	if (outDeviceMs) { *outDeviceMs = 0.f; }
+	if (!touches) { return CVX_OK; }
+	const int64_t align = ((int64_t)1 << levelCount) - 1;
+	const int64_t x0 = lo[0] & ~align, z0 = lo[2] & ~align;
+	const int64_t x1 = std::min<int64_t>((hi[0] + align) & ~align, dim[0]), z1 = std::min<int64_t>((hi[2] + align) & ~align, dim[2]);
+	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
+		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dim[0], dim[2], (long long)align + 1);
+	}
+	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
+	const int n = sizeX * sizeZ;
+	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "a write over %d x %d columns", sizeX, sizeZ); }
+	rc = Prepare(ctx);
+	if (rc != CVX_OK) { return rc; }
+
+	hipEvent_t ev[2] = { nullptr, nullptr };
+	uint8_t *scratch = nullptr, *dSrc = nullptr, *dense = nullptr;
+	auto release = [&]() {
+		for (uint8_t *p : { scratch, dSrc, dense }) { if (p) { (void)hipFree(p); } }
+		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
+	};
+	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
+	size_t bytes = 0;
+	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	const size_t oCounts = carve((size_t)n * 4), oRunCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8);
+	const size_t argbBytes = argb ? ((size_t)elements * 4 + 15) & ~(size_t)15 : 0, solidBytes = solid ? (size_t)elements : 0;
+	struct { unsigned long long total, overLimit; } host = { 0, 0 };
+	hipError_t e = hipEventCreate(&ev[0]);
+	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
+	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
+	if (e == hipSuccess && !device) {
+		e = hipMalloc((void **)&dense, argbBytes + solidBytes);
+		if (e == hipErrorOutOfMemory) {
+			release();
+			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the box", call, argbBytes + solidBytes);
+		}
+	}
+	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	if (e == hipSuccess && !device) {
+		if (argb) { e = hipMemcpyAsync(dense, argb, (size_t)elements * 4, hipMemcpyHostToDevice, ctx->stream); }
+		if (e == hipSuccess && solid) { e = hipMemcpyAsync(dense + argbBytes, solid, solidBytes, hipMemcpyHostToDevice, ctx->stream); }
+		argb = argb ? reinterpret_cast<const uint32_t *>(dense) : nullptr;
+		solid = solid ? dense + argbBytes : nullptr;
+	}
+	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, 2 * 8, ctx->stream); }
+	if (e == hipSuccess) {
+		A.W = WorldOf(ctx);
+		A.argb = argb;
+		A.solid = solid;
+		A.op = op;
+		A.x0 = (int)x0;
+		A.z0 = (int)z0;
+		A.sizeZ = sizeZ;
+		A.n = n;
+		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
+		A.runCounts = reinterpret_cast<uint32_t *>(scratch + oRunCounts);
+		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
+		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
+		// 1, 2. count, scan, one copy back
+		hipLaunchKernelGGL(cvxdense::dense_count_kernel, dim3(Grid((size_t)n, cvxdense::kWavesPerBlock)), dim3(kThreads), 0, ctx->stream, A);
+		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
+		e = hipGetLastError();
+		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
+		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
+	}
+	if (e != hipSuccess) {
+		release();
+		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
+	}
+	if (host.overLimit) {
+		release();
+		return Fail(ctx, CVX_ERR_CAPACITY, "a written column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
+	}
+	if (host.total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) {
+		release();
+		return Fail(ctx, CVX_ERR_CAPACITY, "the written columns need %llu elements", host.total);
+	}
+	// 3. the sub-world blob
+	const size_t blobBytes = (size_t)n * 12 + (size_t)host.total * 4;
+	e = hipMalloc((void **)&dSrc, std::max<size_t>(blobBytes, 4));
+	if (e == hipSuccess) {
+		A.headers = reinterpret_cast<uint32_t *>(dSrc);
+		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
+		hipLaunchKernelGGL(cvxdense::dense_write_kernel, dim3(Grid((size_t)n, cvxdense::kWavesPerBlock)), dim3(kThreads), 0, ctx->stream, A);
+		e = hipGetLastError();
+	}
+	if (e != hipSuccess) {
+		release();
+		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
+	}
+	// 4. cvx_world_edit's machinery
+	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.total, n, levelCount, ev[1]);
+	if (rc == CVX_OK && outDeviceMs) {
+		float ms = 0.f;
+		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+		*outDeviceMs = e == hipSuccess ? ms : 0.f;
+	}
+	release();
+	return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int cvx_world_read_voxels(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], uint32_t *argb, uint8_t *solid, float *outDeviceMs)
+{
+	return Read(ctx, "cvx_world_read_voxels", boxMin, boxMax, argb, solid, false, nullptr, outDeviceMs);
+}
+
+int cvx_world_read_voxels_device(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], uint32_t *argbDevice, uint8_t *solidDevice, void *hipStream)
+{
+	return Read(ctx, "cvx_world_read_voxels_device", boxMin, boxMax, argbDevice, solidDevice, true, hipStream, nullptr);
+}
+
+int cvx_world_write_voxels(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], const uint32_t *argb, const uint8_t *solid, int op, int levelCount,
+                           float *outDeviceMs)
+{
+	return Write(ctx, "cvx_world_write_voxels", boxMin, boxMax, argb, solid, false, op, levelCount, outDeviceMs);
+}
+
+int cvx_world_write_voxels_device(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], const uint32_t *argbDevice, const uint8_t *solidDevice, int op,
+                                  int levelCount, float *outDeviceMs)
+{
+	return Write(ctx, "cvx_world_write_voxels_device", boxMin, boxMax, argbDevice, solidDevice, true, op, levelCount, outDeviceMs);
+}
+
+} // extern "C"

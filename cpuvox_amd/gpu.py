@@ -37,6 +37,7 @@ EXPORTS = [
     "cvx_world_light", "cvx_world_light_lamps", "cvx_world_move", "cvx_world_move_device",
     "cvx_world_nav_build", "cvx_nav_field_goals", "cvx_nav_query", "cvx_nav_query_device", "cvx_nav_field_destroy",
     "cvx_world_surface", "cvx_world_surface_device", "cvx_surface_triangles",
+    "cvx_world_read_voxels", "cvx_world_read_voxels_device", "cvx_world_write_voxels", "cvx_world_write_voxels_device",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -400,6 +401,10 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_surface_device.argtypes = L.cvx_world_surface.argtypes
         L.cvx_surface_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.cvx_world_read_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_read_voxels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvx_world_write_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.cvx_world_write_voxels_device.argtypes = L.cvx_world_write_voxels.argtypes
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -674,6 +679,61 @@ class Context:
         """world_surface into device memory (the address of `capacity` cvx_surface_quad, e.g. a torch tensor's data_ptr()): the first min(capacity,
         quads) entries are written, the rest is left alone; returns (the totals, device milliseconds) once the summary is on the host."""
         return self._surface(lib().cvx_world_surface_device, box_min, box_max, solid_outside, flags, quads_ptr or None, capacity)
+
+    # -- dense voxel boxes in and out of the world (cvx_world_read_voxels, cvx_world_write_voxels) --
+    @staticmethod
+    def _box(box_min, box_max):
+        lo, hi = np.ascontiguousarray(box_min, dtype=np.int32), np.ascontiguousarray(box_max, dtype=np.int32)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("box_min and box_max are three integers each")
+        return lo, hi
+
+    def read_voxels(self, box_min, box_max, want_argb: bool = True, want_solid: bool = True):
+        """The LOD-0 voxels of [box_min, box_max) (it may stick out of the world) as dense arrays of shape (X, Z, Y), y fastest: (argb uint32 --
+        the colour word of a solid voxel, 0 for air and outside the world -- or None, solid bool or None)."""
+        lo, hi = self._box(box_min, box_max)
+        shape = tuple(max(int(hi[a]) - int(lo[a]), 0) for a in (0, 2, 1))
+        if 0 < shape[0] * shape[1] * shape[2] < 1 << 31:  # (anything else: the call rejects it before it writes)
+            argb = np.zeros(shape, dtype=np.uint32) if want_argb else None
+            solid = np.zeros(shape, dtype=np.uint8) if want_solid else None
+        else:
+            argb = solid = None
+        self._check(lib().cvx_world_read_voxels(self._h, lo.ctypes.data, hi.ctypes.data, argb.ctypes.data if argb is not None else None,
+                                                solid.ctypes.data if solid is not None else None, None))
+        return argb, (solid.view(np.bool_) if solid is not None else None)
+
+    def read_voxels_device(self, box_min, box_max, argb_ptr: int, solid_ptr: int, stream: int | None = None) -> None:
+        """read_voxels into device memory (addresses of X * Z * Y uint32 / uint8, e.g. a torch tensor's data_ptr(); either may be 0), enqueued
+        on `stream` (None or 0: the context's) without waiting."""
+        lo, hi = self._box(box_min, box_max)
+        self._check(lib().cvx_world_read_voxels_device(self._h, lo.ctypes.data, hi.ctypes.data, argb_ptr or None, solid_ptr or None, stream or None))
+
+    def write_voxels(self, box_min, argb, solid=None, op: int = COPY_REPLACE, level_count: int = LOD_LEVELS - 1) -> float:
+        """Writes a dense box of voxels at box_min into LOD 0 and rebuilds LOD 1..level_count over its footprint.  `argb`: uint32 colour words of
+        shape (X, Z, Y) (None for a BRUSH_CARVE with a mask); `solid` (optional, same shape): which voxels are set -- without it the voxels
+        with a colour word other than 0.  op: COPY_REPLACE (the box replaces what is there, air included), BRUSH_FILL, BRUSH_CARVE, BRUSH_PAINT
+        (the set voxels fill, carve or recolour).  Returns the device milliseconds (0 when the box lies outside the world)."""
+        a = np.ascontiguousarray(argb, dtype=np.uint32) if argb is not None else None
+        m = np.ascontiguousarray(solid).astype(np.bool_, copy=False).view(np.uint8) if solid is not None else None
+        shape = a.shape if a is not None else (m.shape if m is not None else None)
+        if shape is None or len(shape) != 3 or (a is not None and m is not None and a.shape != m.shape):
+            raise ValueError("write_voxels: argb and solid are arrays of one shape (X, Z, Y)")
+        lo = np.ascontiguousarray(box_min, dtype=np.int64)
+        hi = lo + np.array([shape[0], shape[2], shape[1]], dtype=np.int64)
+        lo, hi = self._box(np.clip(lo, -(1 << 31), (1 << 31) - 1), np.clip(hi, -(1 << 31), (1 << 31) - 1))
+        ms = C.c_float()
+        self._check(lib().cvx_world_write_voxels(self._h, lo.ctypes.data, hi.ctypes.data, a.ctypes.data if a is not None else None,
+                                                 m.ctypes.data if m is not None else None, op, level_count, C.byref(ms)))
+        return ms.value
+
+    def write_voxels_device(self, box_min, box_max, argb_ptr: int, solid_ptr: int, op: int = COPY_REPLACE, level_count: int = LOD_LEVELS - 1) -> float:
+        """write_voxels from device memory (addresses of X * Z * Y uint32 / uint8; solid_ptr may be 0, argb_ptr only for a BRUSH_CARVE), read
+        on the context's stream: the arrays must be complete when the call is made.  Returns the device milliseconds."""
+        lo, hi = self._box(box_min, box_max)
+        ms = C.c_float()
+        self._check(lib().cvx_world_write_voxels_device(self._h, lo.ctypes.data, hi.ctypes.data, argb_ptr or None, solid_ptr or None, op, level_count,
+                                                        C.byref(ms)))
+        return ms.value
 
     def debug_cavities(self) -> dict:
         """Diagnostics build only (include/cpuvox_gpu_diag.h): the last world_cavities' device ms split (analysis, edit), its air intervals and

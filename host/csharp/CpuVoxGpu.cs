@@ -341,6 +341,15 @@ namespace CpuVox.Gpu
 		[DllImport(Lib)] public static extern int cvx_world_surface_device(IntPtr ctx, int* boxMin, int* boxMax, int solidOutside, int flags, IntPtr quadsDevice, long quadCapacity,
 		                                                                   SurfaceSummary* summary, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_surface_triangles(SurfaceQuad* quads, long quadCount, MeshVertex* vertices, int* indices);
+		// dense voxel boxes [boxMin, boxMax) out of and into LOD 0: element ((x - min.x) * size.z + (z - min.z)) * size.y + (y - min.y), colour words and / or a
+		// 0 / 1 mask (either may be null on a read; on a write argb only for a CARVE with a mask); op: CVX_COPY_REPLACE or a CVX_BRUSH_* op; the device
+		// calls take device arrays (a read enqueues on hipStream without waiting, a write reads them on the context's stream)
+		[DllImport(Lib)] public static extern int cvx_world_read_voxels(IntPtr ctx, int* boxMin, int* boxMax, uint* argb, byte* solid, out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_world_read_voxels_device(IntPtr ctx, int* boxMin, int* boxMax, IntPtr argbDevice, IntPtr solidDevice, IntPtr hipStream);
+		[DllImport(Lib)] public static extern int cvx_world_write_voxels(IntPtr ctx, int* boxMin, int* boxMax, uint* argb, byte* solid, int op, int levelCount,
+		                                                                 out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_world_write_voxels_device(IntPtr ctx, int* boxMin, int* boxMax, IntPtr argbDevice, IntPtr solidDevice, int op,
+		                                                                        int levelCount, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

@@ -853,6 +853,44 @@ int cvx_world_surface_device(cvx_context *ctx, const int32_t boxMin[3], const in
                              cvx_surface_quad *quadsDevice, int64_t quadCapacity, cvx_surface_summary *summary, float *outDeviceMs);
 int cvx_surface_triangles(const cvx_surface_quad *quads, int64_t quadCount, cvx_mesh_vertex *vertices, int32_t *indices);
 
+/* ---- dense voxel boxes in and out of the uploaded world --------------------------------------------------------------------------------------
+ * cvx_world_read_voxels / cvx_world_write_voxels: the world as everything outside this library holds voxels, a plain 3-D array -- terrain made
+ * by the caller's own kernels or torch ops, an imported volume, a prefab that is not in the world yet, the input of a simulation step or a model,
+ * an undo buffer that stays on the device.  No RLE columns are encoded or decoded on the host.
+ *   Box and layout.  Coordinates are LOD-0 voxels of the stored tile: a repeating world does not wrap them.  The box is [boxMin, boxMax) with
+ *     size s = boxMax - boxMin > 0 per axis, every |coordinate| <= 2^30 and s.x * s.y * s.z < 2^31; it may stick out of the world on any side.
+ *     Voxel (x, y, z) of the box is element ((x - boxMin.x) * s.z + (z - boxMin.z)) * s.y + (y - boxMin.y) of the arrays: the world's column
+ *     order (x, then z) with y ascending and fastest.  A C-contiguous array (a torch tensor) of shape (X, Z, Y) maps onto it directly.
+ *   Read.  solid[i] is 1 for a solid voxel, else 0; argb[i] is the arena's colour word of a solid voxel, as cvx_world_pick reports it, and 0 for
+ *     air and for everything outside the world.  Either pointer may be NULL, not both.  The call only reads the arena and places unplaced levels
+ *     first (as cvx_world_surface does).  cvx_world_read_voxels takes host arrays, is ordered on the context's stream behind everything enqueued
+ *     before it and returns when the data is on the host; outDeviceMs (may be NULL): device time of the kernel.  cvx_world_read_voxels_device
+ *     takes device arrays and enqueues on hipStream (NULL = the context's stream) without waiting; the caller orders that stream after the
+ *     context's work (cvx_world_pick_device's words).
+ *   Write.  A box voxel is SET iff solid[i] != 0 when `solid` is given, else iff argb[i] != 0; with a mask a set voxel may carry colour word 0.
+ *     Colour words are stored verbatim.  argb may be NULL only for CVX_BRUSH_CARVE, which then requires `solid`.  Let W be LOD 0 before the
+ *     call; for every box voxel v inside the world the op decides R(v): CVX_COPY_REPLACE R(v) = set ? solid(argb[i]) : air; CVX_BRUSH_FILL: set
+ *     -> R(v) = solid(argb[i]), solid voxels included; CVX_BRUSH_CARVE: set -> R(v) = air; CVX_BRUSH_PAINT: set and W(v) solid -> R(v) takes
+ *     argb[i].  Everything else is W.  The call edits the box's XZ footprint clipped to the world, rounded outward to multiples of 2^levelCount
+ *     and clipped again (cvx_world_brush's rectangle), and rebuilds LOD 1 .. levelCount (0 .. 5); columns of the rectangle outside the footprint
+ *     are re-encoded with the builder's rule, as the brush does (unchanged for every world the builder made); runs that come to touch merge
+ *     across the box's top and bottom.  A box that lies wholly outside the world (on any axis): CVX_OK, nothing is written, *outDeviceMs = 0.
+ *     Ordering, atomicity, outDeviceMs, CVX_ERR_CAPACITY (the brush's format limits, the arena limits) and CVX_ERR_NOT_READY are
+ *     cvx_world_brush's; every error leaves the world as it was.  cvx_world_write_voxels_device reads its device arrays on the context's stream:
+ *     the caller makes sure they are complete when it calls and leaves them alone until it returns (like the host call, when the edit is done).
+ * CVX_ERR_INVALID_ARGUMENT, all checked on the host before anything is enqueued: NULL box pointers, an empty box, a coordinate beyond 2^30,
+ * 2^31 or more voxels, a bad op, levelCount outside 0 .. 5, both arrays NULL on a read, argb NULL on a write unless the op is CARVE with `solid`
+ * given.  Device memory while a call runs: the host-array calls hold the box's arrays (4 bytes per voxel for argb, 1 for solid); a write adds
+ * cvx_world_brush's scratch for its rectangle, 4 more bytes per column of it (the run counts) and the rectangle's new columns.  The device calls
+ * of a read take none.  With several GPUs every rank applies the same write to its own context. */
+int cvx_world_read_voxels(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], uint32_t *argb, uint8_t *solid, float *outDeviceMs);
+int cvx_world_read_voxels_device(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], uint32_t *argbDevice, uint8_t *solidDevice,
+                                 void *hipStream);
+int cvx_world_write_voxels(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], const uint32_t *argb, const uint8_t *solid, int op,
+                           int levelCount, float *outDeviceMs);
+int cvx_world_write_voxels_device(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], const uint32_t *argbDevice,
+                                  const uint8_t *solidDevice, int op, int levelCount, float *outDeviceMs);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
