@@ -38,6 +38,7 @@ EXPORTS = [
     "cvx_world_nav_build", "cvx_nav_field_goals", "cvx_nav_query", "cvx_nav_query_device", "cvx_nav_field_destroy",
     "cvx_world_surface", "cvx_world_surface_device", "cvx_surface_triangles",
     "cvx_world_read_voxels", "cvx_world_read_voxels_device", "cvx_world_write_voxels", "cvx_world_write_voxels_device",
+    "cvx_world_distance", "cvx_world_distance_device",
     "cvx_shard_plan_create", "cvx_shard_plan_destroy", "cvx_shard_plan_tile_count", "cvx_shard_plan_sections", "cvx_shard_plan_tile_out", "cvx_shard_plan_transfer",
     "cvx_comm_unique_id", "cvx_comm_create", "cvx_comm_create_timeout", "cvx_comm_destroy", "cvx_exchange",
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
@@ -80,6 +81,8 @@ MOVE_SOLID_BELOW, MOVE_SOLID_SIDES = 1, 2        # cvx_move_body.flags
 MOVED_BLOCKED_MASK, MOVED_RESTING, MOVED_STARTS_SOLID, MOVED_STEPPED, MOVED_INVALID = 0x3F, 1 << 6, 1 << 7, 1 << 8, -(1 << 31)  # cvx_move_result.flags
 SURFACE_OUTSIDE_DEFAULT = 0x04                   # cvx_world_surface: solidOutside, the ground below y = 0 is solid
 SURFACE_IGNORE_COLOUR = 1                        # ... flags
+DISTANCE_FAR = 0x7FFFFFFF                        # cvx_world_distance: no such voxel within max_distance
+DISTANCE_TO_SOLID, DISTANCE_TO_AIR, DISTANCE_SIGNED = 0, 1, 2  # ... mode
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -405,6 +408,8 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_read_voxels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvx_world_write_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.cvx_world_write_voxels_device.argtypes = L.cvx_world_write_voxels.argtypes
+        L.cvx_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_distance_device.argtypes = L.cvx_world_distance.argtypes
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -733,6 +738,29 @@ class Context:
         ms = C.c_float()
         self._check(lib().cvx_world_write_voxels_device(self._h, lo.ctypes.data, hi.ctypes.data, argb_ptr or None, solid_ptr or None, op, level_count,
                                                         C.byref(ms)))
+        return ms.value
+
+    # -- exact squared-distance fields (cvx_world_distance) --
+    def distance(self, box_min, box_max, max_distance: int, mode: int = DISTANCE_TO_SOLID, solid_outside: int = SURFACE_OUTSIDE_DEFAULT):
+        """The squared Euclidean distance, in LOD-0 voxels, of every voxel of [box_min, box_max) (it may stick out of the world) to the nearest
+        solid voxel (DISTANCE_TO_SOLID), the nearest air voxel (DISTANCE_TO_AIR) or both (DISTANCE_SIGNED: negative inside the solid), as an
+        int32 array of shape (X, Z, Y), y fastest; DISTANCE_FAR where nothing lies within max_distance (1 .. 255).  `solid_outside` bits
+        0..5 = -X,+X,-Y,+Y,-Z,+Z: what lies beyond a face of the world."""
+        lo, hi = self._box(box_min, box_max)
+        shape = tuple(max(int(hi[a]) - int(lo[a]), 0) for a in (0, 2, 1))
+        out = np.zeros(shape, dtype=np.int32) if 0 < shape[0] * shape[1] * shape[2] < 1 << 31 else None  # (anything else: the call rejects it)
+        self._check(lib().cvx_world_distance(self._h, lo.ctypes.data, hi.ctypes.data, int(max_distance), int(mode), int(solid_outside),
+                                             out.ctypes.data if out is not None else None, None))
+        return out
+
+    def distance_device(self, box_min, box_max, max_distance: int, out_ptr: int, mode: int = DISTANCE_TO_SOLID,
+                        solid_outside: int = SURFACE_OUTSIDE_DEFAULT) -> float:
+        """distance into device memory (the address of X * Z * Y int32, e.g. a torch tensor's data_ptr()), ordered on the context's stream; the
+        field is complete when the call returns.  Returns the device milliseconds."""
+        lo, hi = self._box(box_min, box_max)
+        ms = C.c_float()
+        self._check(lib().cvx_world_distance_device(self._h, lo.ctypes.data, hi.ctypes.data, int(max_distance), int(mode), int(solid_outside),
+                                                    out_ptr or None, C.byref(ms)))
         return ms.value
 
     def debug_cavities(self) -> dict:

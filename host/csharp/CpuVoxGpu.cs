@@ -350,6 +350,13 @@ namespace CpuVox.Gpu
 		                                                                 out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_world_write_voxels_device(IntPtr ctx, int* boxMin, int* boxMax, IntPtr argbDevice, IntPtr solidDevice, int op,
 		                                                                        int levelCount, out float outDeviceMs);
+		// the exact squared distance (LOD-0 voxels) of every voxel of [boxMin, boxMax) to the nearest solid / air voxel within maxDistance (1 .. 255), in the
+		// dense layout above; CVX_DISTANCE_FAR where there is none; solidOutside as for cvx_world_surface; the device call leaves the field in device memory
+		public const int CVX_DISTANCE_FAR = 0x7FFFFFFF, CVX_DISTANCE_TO_SOLID = 0, CVX_DISTANCE_TO_AIR = 1, CVX_DISTANCE_SIGNED = 2;
+		[DllImport(Lib)] public static extern int cvx_world_distance(IntPtr ctx, int* boxMin, int* boxMax, int maxDistance, int mode, int solidOutside, int* @out,
+		                                                             out float outDeviceMs);
+		[DllImport(Lib)] public static extern int cvx_world_distance_device(IntPtr ctx, int* boxMin, int* boxMax, int maxDistance, int mode, int solidOutside,
+		                                                                    IntPtr outDevice, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_set_resolution(IntPtr ctx, int resolutionX, int resolutionY);
 		[DllImport(Lib)] public static extern int cvx_set_buffer_count(IntPtr ctx, int bufferCount);
 		[DllImport(Lib)] public static extern int cvx_draw_segments(IntPtr ctx, SegmentData* segments, CameraData* camera, int screenWidth, int screenHeight, float* vanishingPointScreenSpace, int bufferIndex, int flags);

@@ -891,6 +891,41 @@ int cvx_world_write_voxels(cvx_context *ctx, const int32_t boxMin[3], const int3
 int cvx_world_write_voxels_device(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], const uint32_t *argbDevice,
                                   const uint8_t *solidDevice, int op, int levelCount, float *outDeviceMs);
 
+/* ---- exact squared-distance fields of boxes of the uploaded world -----------------------------------------------------------------------------
+ * cvx_world_distance: how far every voxel of a box is from the nearest solid (or air) voxel -- sphere and capsule collision for particles and
+ * projectiles, clearance for AI and camera placement, contact shadows, fog that hugs the terrain, outlines, and the editor's grow, shrink, round
+ * off and shell: thresholds of the field written back through cvx_world_write_voxels.  The rule is exact integers in LOD-0 voxels of the stored
+ * tile (a repeating world does not wrap the coordinates); the calls only read the arena.
+ *   Box and layout.  cvx_world_read_voxels': the box is [boxMin, boxMax) with size s = boxMax - boxMin > 0 per axis, every |coordinate| <= 2^30
+ *     and s.x * s.y * s.z < 2^31; it may stick out of the world on any side or lie wholly outside it.  Voxel (x, y, z) of the box is element
+ *     ((x - boxMin.x) * s.z + (z - boxMin.z)) * s.y + (y - boxMin.y) of `out`: a C-contiguous int32 array (a torch tensor) of shape (X, Z, Y).
+ *   Solid(v).  Inside the world: what the arena holds at LOD 0.  Outside the world: solid iff, on some axis, v lies beyond the world on the side
+ *     of face f and bit f of solidOutside is set; faces are numbered as for cvx_world_surface, 0..5 = -X,+X,-Y,+Y,-Z,+Z.
+ *     CVX_SURFACE_OUTSIDE_DEFAULT (0x04) makes every voxel with y < 0 solid, an infinite ground, and everything else outside the world air.
+ *   Distances.  With R = maxDistance, 1 <= R <= 255: D_S(v) is the minimum of |s - v|^2 (the squared Euclidean distance between voxel centres,
+ *     an integer) over all s with Solid(s) and |s - v|^2 <= R^2, CVX_DISTANCE_FAR when there is none; s ranges over all of space, not only over
+ *     the box.  D_A(v) is the same over the s with !Solid(s).  CVX_DISTANCE_TO_SOLID: out = D_S(v), 0 on solid voxels; CVX_DISTANCE_TO_AIR:
+ *     out = D_A(v), 0 on air voxels; CVX_DISTANCE_SIGNED: out = Solid(v) ? -D_A(v) : D_S(v), -CVX_DISTANCE_FAR deep inside.
+ *   The result of a voxel depends on the world and the arguments only, not on the box: the fields of adjacent boxes tile, and the same call
+ *     twice gives the same bytes.
+ * Both calls are ordered on the context's stream behind everything enqueued before them, place unplaced levels first (as cvx_world_surface
+ * does), return when the result is complete and free their scratch before they return.  cvx_world_distance takes a host array;
+ * cvx_world_distance_device leaves the field in outDevice (device memory of s.x * s.y * s.z int32).  outDeviceMs (may be NULL): device time of
+ * the kernels.
+ * CVX_ERR_INVALID_ARGUMENT, all checked on the host before anything is enqueued: NULL pointers, an empty box, a coordinate beyond 2^30, 2^31
+ * or more voxels, maxDistance outside 1 .. 255, an unknown mode, solidOutside bits above 0x3F; CVX_ERR_NOT_READY: LOD 0 has not been uploaded;
+ * CVX_ERR_CAPACITY: the scratch does not fit in device memory.  Device memory while a call runs: 2 bytes per voxel of the box's XZ footprint
+ * grown by R on all four sides times its height (the distances along Y), 2 more per voxel of the footprint grown by R in X only -- together
+ * 2 * s.y * (s.x + 2R) * (2 * s.z + 2R) bytes: 4 per voxel of the box, 4 * s.y per halo column of the strips beside it in X, 2 * s.y per halo
+ * column of the strips and corners beyond it in Z; cvx_world_distance adds the 4 bytes per voxel of the field itself.  Every mode takes the
+ * same. */
+#define CVX_DISTANCE_FAR 0x7FFFFFFF
+enum { CVX_DISTANCE_TO_SOLID = 0, CVX_DISTANCE_TO_AIR = 1, CVX_DISTANCE_SIGNED = 2 };
+int cvx_world_distance(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int maxDistance, int mode, int solidOutside,
+                       int32_t *out, float *outDeviceMs);
+int cvx_world_distance_device(cvx_context *ctx, const int32_t boxMin[3], const int32_t boxMax[3], int maxDistance, int mode, int solidOutside,
+                              int32_t *outDevice, float *outDeviceMs);
+
 /* ---- reading the uploaded world back, and compacting its arena --------------------------------------------------------------------------
  * After edits and brushes the device holds the only up-to-date copy of the world; these calls bring it back (to save it, or to keep a rectangle
  * for undo) and reclaim the space edits left behind.  Every read-back column is in the builder's encoding (WordBuilder.cs:181-268, what
