@@ -4,6 +4,7 @@
 // tests/brush_rules.cpp and compares them with numpy models):
 //   ArenaColumn  what a LOD-0 record of the arena says about its column: the solid runs top-down (records with 1 .. 3 runs, run-list blocks),
 //                each with its colour index; colours at colorsBase + index << colorShift (blocks of 4 x 8 columns or column after column).
+//   StrokeSpan   the y interval a stroke (box, sphere, capsule, ellipsoid) covers in a column: exact integers decide every voxel.
 //   BrushColumn  a column after a list of strokes, emitted as the builder emits it (WordBuilder.cs:181-268): maximal runs from the top, the
 //                top air run first, ColorsIndex = solid voxels above, worldMin / worldMax as the RLEColumn constructor computes them.
 //   PickRay      the first solid voxel along a ray (a 2-D DDA over the columns, one record per step, the solid runs walked in the ray's y order).
@@ -60,13 +61,71 @@ CVX_HD inline int64_t ISqrt(int64_t v)
 	return h;
 }
 
-// The y interval [lo, hi) a stroke covers in column (cx, cz), clipped to [0, dimY); lo >= hi: none.
+// The unclipped box [lo, hi) per axis (x, y, z) that holds every voxel of a stroke of any shape: the host's rectangle (cvx_brush.hip, Footprint) and
+// the kernels' cull (StrokeMeetsStrip) both come from here, so they cannot disagree.  (A stroke cvx_world_brush accepted: nothing overflows.)
+CVX_HD inline void StrokeFootprint(const cvx_brush_stroke &s, int64_t lo[3], int64_t hi[3])
+{
+	for (int a = 0; a < 3; a++) {
+		const int64_t p = s.a[a], q = s.b[a];
+		if (s.shape == CVX_SHAPE_BOX) {
+			lo[a] = p;
+			hi[a] = q;
+		} else if (s.shape == CVX_SHAPE_CAPSULE) {
+			lo[a] = (p < q ? p : q) - s.pad_;
+			hi[a] = (p < q ? q : p) + s.pad_ + 1;
+		} else {
+			const int64_t r = s.shape == CVX_SHAPE_SPHERE ? s.b[0] : q;
+			lo[a] = p - r;
+			hi[a] = p + r + 1;
+		}
+	}
+}
+
+// floor(n / q) for q > 0, in 32 bits (the capsule's slab bounds: |n| < 2^30)
+CVX_HD inline int64_t FloorDiv32(int32_t n, int32_t q)
+{
+	const int32_t d = n / q;
+	return (int64_t)(n % q < 0 ? d - 1 : d);
+}
+
+// The part of a capsule's column strictly between its end planes, as offsets t = y - a[1]: the integers with 0 < p0 + t * dy < L (the slab) and
+// f(t) = a2 t^2 - 2 b1 t + c0 <= 0 (within r of the axis; a2 = dx^2 + dz^2 > 0, b1 = p0 * dy, c0 = (wx^2 + wz^2 - r^2) * L - p0^2), cut to [tMin, tMax].
+// f's roots need a discriminant of up to 85 bits: they are estimated in float64 (off by at most 8 / sqrt(a2) + 1, since p0^2 <= a2 (wx^2 + wz^2)) and
+// walked to the exact integers with f itself, which fits in int64 for |t| <= 16382 (a2 t^2 < 2^55, 2 b1 t < 2^57, c0 < 2^58).
+CVX_HD inline void CapsuleMiddle(int64_t a2, int64_t b1, int64_t c0, int64_t p0, int64_t dy, int64_t L, int64_t tMin, int64_t tMax, int64_t *outLo, int64_t *outHi)
+{
+	*outLo = 0;
+	*outHi = -1;
+	int64_t lo = tMin, hi = tMax;
+	if (dy == 0) {
+		if (!(p0 > 0 && p0 < L)) { return; }
+	} else {
+		const int32_t q = (int32_t)(dy > 0 ? dy : -dy);
+		const int64_t first = FloorDiv32((int32_t)(dy > 0 ? -p0 : p0 - L), q) + 1, last = FloorDiv32((int32_t)(dy > 0 ? L - p0 : p0) - 1, q);
+		lo = first > lo ? first : lo;
+		hi = last < hi ? last : hi;
+	}
+	if (lo > hi) { return; }
+	const double fa = (double)a2, fb = (double)b1, vertex = fb / fa, disc = fb * fb - fa * (double)c0;
+	const double reach = disc > 0.0 ? __builtin_sqrt(disc) / fa : 0.0;
+	const double from = __builtin_floor(vertex - reach) - 1.0, to = __builtin_ceil(vertex + reach) + 1.0; // (the integer nearest the vertex lies strictly between)
+	int64_t t1 = from < (double)lo ? lo : (from > (double)hi ? hi : (int64_t)from), t2 = to > (double)hi ? hi : (to < (double)lo ? lo : (int64_t)to);
+	while (t1 > lo && (a2 * (t1 - 1) - 2 * b1) * (t1 - 1) + c0 <= 0) { t1--; }
+	while (t1 <= t2 && (a2 * t1 - 2 * b1) * t1 + c0 > 0) { t1++; }
+	while (t2 < hi && (a2 * (t2 + 1) - 2 * b1) * (t2 + 1) + c0 <= 0) { t2++; }
+	while (t2 >= t1 && (a2 * t2 - 2 * b1) * t2 + c0 > 0) { t2--; }
+	*outLo = t1;
+	*outHi = t2;
+}
+
+// The y interval [lo, hi) a stroke covers in column (cx, cz), clipped to [0, dimY); lo >= hi: none.  The rules are those of include/cpuvox_gpu.h; a
+// capsule's and an ellipsoid's products are formed only for columns inside the footprint, which keeps them in int64 for strokes far from the world.
 CVX_HD inline void StrokeSpan(const cvx_brush_stroke &s, int64_t cx, int64_t cz, int64_t dimY, int64_t *lo, int64_t *hi)
 {
 	int64_t l = 0, h = 0;
 	if (s.shape == CVX_SHAPE_BOX) {
 		if (cx >= s.a[0] && cx < s.b[0] && cz >= s.a[2] && cz < s.b[2]) { l = s.a[1]; h = s.b[1]; }
-	} else {
+	} else if (s.shape == CVX_SHAPE_SPHERE) {
 		const int64_t r = s.b[0], dx = cx - s.a[0], dz = cz - s.a[2];
 		const int64_t left = r * r - dx * dx - dz * dz;
 		if (left >= 0) {
@@ -74,10 +133,107 @@ CVX_HD inline void StrokeSpan(const cvx_brush_stroke &s, int64_t cx, int64_t cz,
 			l = (int64_t)s.a[1] - e;
 			h = (int64_t)s.a[1] + e + 1;
 		}
+	} else if (s.shape == CVX_SHAPE_ELLIPSOID) {
+		// dy^2 rx^2 rz^2 <= left = rx^2 ry^2 rz^2 - dx^2 ry^2 rz^2 - dz^2 rx^2 ry^2 (each term at most 2^60 inside the footprint); the half height is
+		// ISqrt(left / (rx^2 rz^2)): a float64 estimate corrected with the integer predicate, as ISqrt does
+		const int64_t rx = s.b[0], ry = s.b[1], rz = s.b[2], dx = cx - s.a[0], dz = cz - s.a[2];
+		if (dx >= -rx && dx <= rx && dz >= -rz && dz <= rz) {
+			const int64_t xx = rx * rx, yy = ry * ry, zz = rz * rz, xz = xx * zz;
+			const int64_t left = xz * yy - dx * dx * (yy * zz) - dz * dz * (xx * yy);
+			if (left >= 0) {
+				int64_t e = (int64_t)__builtin_sqrt((double)left / (double)xz);
+				while (e > 0 && e * e * xz > left) { e--; }
+				while ((e + 1) * (e + 1) * xz <= left) { e++; }
+				l = (int64_t)s.a[1] - e;
+				h = (int64_t)s.a[1] + e + 1;
+			}
+		}
+	} else {
+		// the capsule: the hull of its end spheres' intervals and of the part between the end planes (the set is convex; a voxel of an end sphere
+		// on the far side of that end's plane satisfies the rule of the part it lies in, its distance to the segment being no larger)
+		const int64_t r = s.pad_, dx = (int64_t)s.b[0] - s.a[0], dy = (int64_t)s.b[1] - s.a[1], dz = (int64_t)s.b[2] - s.a[2];
+		const int64_t wx = cx - s.a[0], wz = cz - s.a[2];
+		if (wx >= (dx < 0 ? dx : 0) - r && wx <= (dx > 0 ? dx : 0) + r && wz >= (dz < 0 ? dz : 0) - r && wz <= (dz > 0 ? dz : 0) + r) {
+			const int64_t rr = r * r, ww = wx * wx + wz * wz, vv = (wx - dx) * (wx - dx) + (wz - dz) * (wz - dz);
+			int64_t t1 = 1, t2 = 0; // offsets from a[1], inclusive
+			if (ww <= rr) {
+				const int64_t e = ISqrt(rr - ww);
+				t1 = -e;
+				t2 = e;
+			}
+			if (vv <= rr) {
+				const int64_t e = ISqrt(rr - vv);
+				if (t1 > t2) { t1 = dy - e; t2 = dy + e; }
+				t1 = dy - e < t1 ? dy - e : t1;
+				t2 = dy + e > t2 ? dy + e : t2;
+			}
+			const int64_t a2 = dx * dx + dz * dz;
+			if (a2 > 0) { // (a vertical capsule, a point included: the end spheres' hull is all of it)
+				const int64_t L = a2 + dy * dy, p0 = wx * dx + wz * dz;
+				int64_t m1, m2;
+				CapsuleMiddle(a2, p0 * dy, (ww - rr) * L - p0 * p0, p0, dy, L, (dy < 0 ? dy : 0) - r, (dy > 0 ? dy : 0) + r, &m1, &m2);
+				if (m1 <= m2) {
+					if (t1 > t2) { t1 = m1; t2 = m2; }
+					t1 = m1 < t1 ? m1 : t1;
+					t2 = m2 > t2 ? m2 : t2;
+				}
+			}
+			if (t1 <= t2) {
+				l = (int64_t)s.a[1] + t1;
+				h = (int64_t)s.a[1] + t2 + 1;
+			}
+		}
 	}
 	*lo = l < 0 ? 0 : l;
 	*hi = h > dimY ? dimY : h;
 }
+
+// ---- the strokes a strip of columns can meet ----------------------------------------------------------------------------------------------------
+
+// The XZ box [x0, x1] x [z0, z1] (inclusive) of the columns first .. last of a rectangle whose columns are numbered i -> (rectX + i / sizeZ,
+// rectZ + i % sizeZ), the blob's column order: a wave's 64 columns in the brush kernels.  A strip that wraps into the next row takes the box of
+// both parts, the rectangle's whole width in z.
+CVX_HD inline void StripBox(int first, int last, int rectX, int rectZ, int sizeZ, int64_t *x0, int64_t *x1, int64_t *z0, int64_t *z1)
+{
+	const int rowA = first / sizeZ, rowB = last / sizeZ;
+	*x0 = (int64_t)rectX + rowA;
+	*x1 = (int64_t)rectX + rowB;
+	*z0 = (int64_t)rectZ + (rowA == rowB ? first - rowA * sizeZ : 0);
+	*z1 = (int64_t)rectZ + (rowA == rowB ? last - rowB * sizeZ : sizeZ - 1);
+}
+
+// Conservative: false only if the stroke's footprint misses every column of the box, where its span (StrokeSpan) is empty
+CVX_HD inline bool StrokeMeetsStrip(const cvx_brush_stroke &s, int64_t x0, int64_t x1, int64_t z0, int64_t z1)
+{
+	int64_t lo[3], hi[3];
+	StrokeFootprint(s, lo, hi);
+	return lo[0] <= x1 && hi[0] > x0 && lo[2] <= z1 && hi[2] > z0;
+}
+
+// The stroke list a column walks: all n strokes of the call, or those a cull kept (ascending indices into the call's list: the fold depends on order)
+// Walk(k) is the access of the column walk's loop over the strokes.  REQUIREMENT ON THE CALLER: on the device every active lane of the wave must call
+// Walk with the same k at the same time (ListedStrokes reads the entry through readfirstlane, i.e. from ONE lane, so that the stroke's fields come
+// through scalar loads).  BrushColumnOver keeps it: its stroke loop restarts at 0 in every iteration of the outer loop and runs to n in every lane,
+// with no per-lane exit.  A per-lane index (the last stroke that covered a voxel, say) goes through operator[] instead.
+struct AllStrokes {
+	const cvx_brush_stroke *strokes;
+	CVX_HD const cvx_brush_stroke &operator[](int k) const { return strokes[k]; }
+	CVX_HD const cvx_brush_stroke &Walk(int k) const { return strokes[k]; }
+};
+
+struct ListedStrokes {
+	const cvx_brush_stroke *strokes;
+	const uint16_t *list;
+	CVX_HD const cvx_brush_stroke &operator[](int k) const { return strokes[list[k]]; }
+	CVX_HD const cvx_brush_stroke &Walk(int k) const
+	{
+#if defined(__HIP_DEVICE_COMPILE__)
+		return strokes[__builtin_amdgcn_readfirstlane((int)list[k])]; // (k is wave-uniform: the requirement above)
+#else
+		return strokes[list[k]];
+#endif
+	}
+};
 
 // ---- one column after the strokes -------------------------------------------------------------------------------------------------------------
 
@@ -94,8 +250,11 @@ struct BrushResult {
 // next boundary of a stroke interval or an arena run below it.
 // Out (may be null): runs[r] = colorsIndex | length << 16 (colorsIndex 0xFFFF for air), colours[k] = the k-th solid voxel's colour from the top
 // (colourSlots: the arena's colour array, 4-byte slots, read at the column's colorsBase + index << (colorShift - 2)).
-CVX_HD inline BrushResult BrushColumn(const ArenaColumn &col, const uint32_t *colourSlots, int colorShift, const cvx_brush_stroke *strokes, int n,
-                                      int64_t cx, int64_t cz, int dimY, uint32_t *outRuns, uint32_t *outColours)
+// `strokes` is AllStrokes or ListedStrokes: strokes[k], k < n, in the order they apply.  A stroke a cull left out has an empty span in this
+// column, so the walk over the culled list gives what the walk over the whole list gives.
+template <class Strokes>
+CVX_HD inline BrushResult BrushColumnOver(const ArenaColumn &col, const uint32_t *colourSlots, int colorShift, const Strokes &strokes, int n,
+                                          int64_t cx, int64_t cz, int dimY, uint32_t *outRuns, uint32_t *outColours)
 {
 	BrushResult res{ 0u, 0u, 0u, 0u, false };
 	const uint32_t solidRuns = col.Count();
@@ -117,13 +276,16 @@ CVX_HD inline BrushResult BrushColumn(const ArenaColumn &col, const uint32_t *co
 		}
 		// the strokes: the last FILL / CARVE and the last FILL / PAINT that cover y, and where the span ends
 		int lastFC = -1, lastFP = -1;
+		// (Walk needs s to be the same in every active lane: this loop must keep running 0 .. n - 1 in every lane, whatever the lane's y -- no early
+		// exit, no per-lane start; see ListedStrokes)
 		for (int s = 0; s < n; s++) {
 			int64_t lo, hi;
-			StrokeSpan(strokes[s], cx, cz, dimY, &lo, &hi);
+			const cvx_brush_stroke &stroke = strokes.Walk(s);
+			StrokeSpan(stroke, cx, cz, dimY, &lo, &hi);
 			if (lo >= hi) { continue; }
 			if (lo <= y && y < hi) {
-				if (strokes[s].op != CVX_BRUSH_PAINT) { lastFC = s; }
-				if (strokes[s].op != CVX_BRUSH_CARVE) { lastFP = s; }
+				if (stroke.op != CVX_BRUSH_PAINT) { lastFC = s; }
+				if (stroke.op != CVX_BRUSH_CARVE) { lastFP = s; }
 				bottom = lo > bottom ? lo : bottom;
 			} else if (hi <= y) {
 				bottom = hi > bottom ? hi : bottom;
@@ -171,6 +333,12 @@ CVX_HD inline BrushResult BrushColumn(const ArenaColumn &col, const uint32_t *co
 	res.worldMin = (uint32_t)lowest & 0xFFFFu;
 	res.worldMax = (uint32_t)highest & 0xFFFFu;
 	return res;
+}
+
+CVX_HD inline BrushResult BrushColumn(const ArenaColumn &col, const uint32_t *colourSlots, int colorShift, const cvx_brush_stroke *strokes, int n,
+                                      int64_t cx, int64_t cz, int dimY, uint32_t *outRuns, uint32_t *outColours)
+{
+	return BrushColumnOver(col, colourSlots, colorShift, AllStrokes{ strokes }, n, cx, cz, dimY, outRuns, outColours);
 }
 
 // ---- picking ----------------------------------------------------------------------------------------------------------------------------------

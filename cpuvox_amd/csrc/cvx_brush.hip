@@ -2,7 +2,8 @@
 // world.  See include/cpuvox_gpu.h for the contract, cvx_brush.h for the per-column rules and DESIGN.md sections 3 and 4.
 //
 // A brush is cvx_world_edit with the sub-world built on the device instead of uploaded:
-//   1. count  (a thread per LOD-0 column of the rounded rectangle): the column from the arena, the strokes in order (cvxb::BrushColumn), the
+//   0. cull   (both kernels begin with it): each wave lists the strokes whose footprint meets its 64 columns, in stroke order, in LDS
+//   1. count  (a thread per LOD-0 column of the rounded rectangle): the column from the arena, the wave's strokes in order (cvxb::BrushColumnOver), the
 //             elements its new column needs ([guard][runs][guard][colours]); columns the format cannot hold raise a flag
 //   2. the counts are prefix-scanned into element offsets; ONE copy brings the total and the flag to the host
 //   3. write  (same threads): the sub-world blob in the reference's layout, 12-byte RLEColumn headers then the element pool
@@ -40,28 +41,66 @@ __device__ __forceinline__ cvxb::ArenaColumn Column(const BrushArgs &A, int cx, 
 	return cvxb::ArenaColumn{ r.x, r.y, r.z, r.w, reinterpret_cast<const uint32_t *>(A.arena + A.runsOff) };
 }
 
-__global__ __launch_bounds__(256) void brush_count_kernel(BrushArgs A)
+constexpr int kBrushThreads = 256, kBrushWaves = kBrushThreads / CVX_WAVE; // the one launch width of both brush kernels: bounds, grid and the lists' size
+
+// The strokes a wave's 64 columns can meet, as ascending indices into A.strokes (cvxb::ListedStrokes): the wave takes the XZ box of its strip of the
+// rectangle (cvxb::StripBox) and walks the call's list 64 strokes at a time, a lane per stroke; a ballot and the count of the kept lanes below
+// append the survivors in stroke order.  CVX_BRUSH_MAX_STROKES 16-bit indices per wave always fit: there is no overflow path.
+// A wave's list is written and read by that wave alone, so the waves of a workgroup do not wait for one another: a wave-scope fence orders the
+// lanes' stores before the other lanes' loads (LDS operations of one wave complete in order).  Returns the list's length.
+__device__ __forceinline__ int CullStrokes(const BrushArgs &A, uint16_t (*lists)[CVX_BRUSH_MAX_STROKES], const uint16_t **outList)
 {
+	const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / CVX_WAVE), lane = (int)threadIdx.x % CVX_WAVE;
+	const int first = (int)blockIdx.x * kBrushThreads + wave * CVX_WAVE, last = min(first + CVX_WAVE, A.n) - 1;
+	uint16_t *list = lists[wave];
+	int count = 0;
+	if (first <= last) {
+		int64_t x0, x1, z0, z1;
+		cvxb::StripBox(first, last, A.x0, A.z0, A.sizeZ, &x0, &x1, &z0, &z1);
+		for (int base = 0; base < A.strokeCount; base += CVX_WAVE) {
+			const int s = base + lane;
+			const bool keep = s < A.strokeCount && cvxb::StrokeMeetsStrip(A.strokes[s], x0, x1, z0, z1);
+			const unsigned long long kept = __ballot(keep);
+			if (keep) { list[count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(kept >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kept, 0u))] = (uint16_t)s; }
+			count += __popcll(kept);
+		}
+	}
+	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // (a lane reads what other lanes of its wave wrote)
+	__builtin_amdgcn_wave_barrier();
+	*outList = list;
+	return count;
+}
+
+__global__ __launch_bounds__(kBrushThreads) void brush_count_kernel(BrushArgs A)
+{
+	__shared__ uint16_t lists[kBrushWaves][CVX_BRUSH_MAX_STROKES];
+	const uint16_t *list;
+	const int listCount = CullStrokes(A, lists, &list);
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= A.n) { return; }
 	const int cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
 	const uint32_t *colours = reinterpret_cast<const uint32_t *>(A.arena + A.elementsOff);
-	const cvxb::BrushResult r = cvxb::BrushColumn(Column(A, cx, cz), colours, A.colorShift, A.strokes, A.strokeCount, cx, cz, A.dimY, nullptr, nullptr);
+	const cvxb::ListedStrokes strokes{ A.strokes, list };
+	const cvxb::BrushResult r = cvxb::BrushColumnOver(Column(A, cx, cz), colours, A.colorShift, strokes, listCount, cx, cz, A.dimY, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
 	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
 }
 
-__global__ __launch_bounds__(256) void brush_write_kernel(BrushArgs A)
+__global__ __launch_bounds__(kBrushThreads) void brush_write_kernel(BrushArgs A)
 {
+	__shared__ uint16_t lists[kBrushWaves][CVX_BRUSH_MAX_STROKES];
+	const uint16_t *list;
+	const int listCount = CullStrokes(A, lists, &list);
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= A.n) { return; }
 	const int cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
 	const uint32_t *colours = reinterpret_cast<const uint32_t *>(A.arena + A.elementsOff);
+	const cvxb::ListedStrokes strokes{ A.strokes, list };
 	const uint32_t off = A.counts[i];
 	uint32_t *e = A.elements + off;
 	// (the colours go behind the runs' second guard, a place known once the runs are counted: the walk runs twice, the second time writing)
 	const cvxb::ArenaColumn col = Column(A, cx, cz);
-	const cvxb::BrushResult r = cvxb::BrushColumn(col, colours, A.colorShift, A.strokes, A.strokeCount, cx, cz, A.dimY, nullptr, nullptr);
+	const cvxb::BrushResult r = cvxb::BrushColumnOver(col, colours, A.colorShift, strokes, listCount, cx, cz, A.dimY, nullptr, nullptr);
 	uint32_t *h = A.headers + 3 * (size_t)i;
 	if (r.runCount == 0u) {
 		h[0] = 0u;
@@ -69,7 +108,7 @@ __global__ __launch_bounds__(256) void brush_write_kernel(BrushArgs A)
 		h[2] = 0u;
 		return;
 	}
-	cvxb::BrushColumn(col, colours, A.colorShift, A.strokes, A.strokeCount, cx, cz, A.dimY, e + 1, e + r.runCount + 2u);
+	cvxb::BrushColumnOver(col, colours, A.colorShift, strokes, listCount, cx, cz, A.dimY, e + 1, e + r.runCount + 2u);
 	e[0] = 0u;
 	e[r.runCount + 1u] = 0u;
 	h[0] = off;
@@ -97,9 +136,9 @@ __global__ __launch_bounds__(CVX_WAVE) void pick_kernel(cvxb::PickWorld W, int r
 
 namespace {
 
-constexpr unsigned kThreads = 256;
+constexpr int kCapsuleMax = 8191, kEllipsoidMax = 1024; // the limits of include/cpuvox_gpu.h: the span rules (cvx_brush.h) are exact in int64 inside them
 
-unsigned Grid(size_t n, unsigned threads = kThreads) { return (unsigned)((n + threads - 1) / threads); }
+unsigned Grid(size_t n, unsigned threads) { return (unsigned)((n + threads - 1) / threads); }
 
 int Prepare(cvx_context *ctx)
 {
@@ -112,15 +151,7 @@ int Prepare(cvx_context *ctx)
 bool Footprint(const cvx_brush_stroke &s, int dimX, int dimY, int dimZ, int64_t *x0, int64_t *x1, int64_t *z0, int64_t *z1)
 {
 	int64_t lo[3], hi[3];
-	for (int a = 0; a < 3; a++) {
-		if (s.shape == CVX_SHAPE_BOX) {
-			lo[a] = s.a[a];
-			hi[a] = s.b[a];
-		} else {
-			lo[a] = (int64_t)s.a[a] - s.b[0];
-			hi[a] = (int64_t)s.a[a] + s.b[0] + 1;
-		}
-	}
+	cvxb::StrokeFootprint(s, lo, hi);
 	const int64_t dim[3] = { dimX, dimY, dimZ };
 	for (int a = 0; a < 3; a++) {
 		lo[a] = std::max<int64_t>(lo[a], 0);
@@ -174,9 +205,24 @@ int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strok
 	for (int s = 0; s < strokeCount; s++) {
 		const cvx_brush_stroke &k = strokes[s];
 		if (k.op < CVX_BRUSH_FILL || k.op > CVX_BRUSH_PAINT) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: bad op %d", s, k.op); }
-		if (k.shape != CVX_SHAPE_BOX && k.shape != CVX_SHAPE_SPHERE) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: bad shape %d", s, k.shape); }
+		if (k.shape != CVX_SHAPE_BOX && k.shape != CVX_SHAPE_SPHERE && k.shape != CVX_SHAPE_CAPSULE && k.shape != CVX_SHAPE_ELLIPSOID) {
+			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: bad shape %d", s, k.shape);
+		}
 		if (k.shape == CVX_SHAPE_SPHERE && (k.b[0] < 0 || k.b[0] > (1 << 30))) {
 			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: sphere radius %d outside 0 .. 2^30", s, k.b[0]);
+		}
+		if (k.shape == CVX_SHAPE_CAPSULE) {
+			if (k.pad_ < 0 || k.pad_ > kCapsuleMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: capsule radius %d outside 0 .. %d", s, k.pad_, kCapsuleMax); }
+			for (int a = 0; a < 3; a++) {
+				const int64_t d = (int64_t)k.b[a] - k.a[a];
+				if (d < -kCapsuleMax || d > kCapsuleMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: capsule ends %lld apart on axis %d, more than %d", s, (long long)d, a, kCapsuleMax); }
+				if (k.a[a] < -(1 << 30) || k.a[a] > (1 << 30)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: capsule end a[%d] = %d outside -2^30 .. 2^30", s, a, k.a[a]); }
+			}
+		}
+		if (k.shape == CVX_SHAPE_ELLIPSOID) {
+			for (int a = 0; a < 3; a++) {
+				if (k.b[a] < 1 || k.b[a] > kEllipsoidMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: ellipsoid radius b[%d] = %d outside 1 .. %d", s, a, k.b[a], kEllipsoidMax); }
+			}
 		}
 	}
 	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
@@ -247,7 +293,7 @@ int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strok
 		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
 		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
 		// 1, 2. count, scan, one copy back
-		hipLaunchKernelGGL(cvxbrush::brush_count_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
+		hipLaunchKernelGGL(cvxbrush::brush_count_kernel, dim3(Grid((size_t)n, cvxbrush::kBrushThreads)), dim3(cvxbrush::kBrushThreads), 0, ctx->stream, A);
 		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
 		e = hipGetLastError();
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
@@ -271,7 +317,7 @@ int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strok
 	if (e == hipSuccess) {
 		A.headers = reinterpret_cast<uint32_t *>(dSrc);
 		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
-		hipLaunchKernelGGL(cvxbrush::brush_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
+		hipLaunchKernelGGL(cvxbrush::brush_write_kernel, dim3(Grid((size_t)n, cvxbrush::kBrushThreads)), dim3(cvxbrush::kBrushThreads), 0, ctx->stream, A);
 		e = hipGetLastError();
 	}
 	if (e != hipSuccess) {

@@ -66,6 +66,7 @@ class Counters(C.Structure):
 
 BRUSH_FILL, BRUSH_CARVE, BRUSH_PAINT = 0, 1, 2  # cvx_brush_stroke.op
 SHAPE_BOX, SHAPE_SPHERE = 0, 1                  # cvx_brush_stroke.shape
+SHAPE_CAPSULE, SHAPE_ELLIPSOID = 16, 17         # (the codes 2 .. 15 are not shapes)
 BRUSH_MAX_STROKES = 4096
 COPY_REPLACE = 3                                # cvx_copy_placement.op, besides BRUSH_FILL / CARVE / PAINT
 COPY_MAX_PLACEMENTS = 1024
@@ -206,7 +207,9 @@ def surface_triangles(quads):
 
 
 def strokes_array(strokes) -> np.ndarray:
-    """A list of dicts {op, shape, a, b, argb} (b of a sphere may be just the radius) or a STROKE_DTYPE array -> a contiguous STROKE_DTYPE array."""
+    """A list of dicts {op, shape, a, b, argb} (b of a sphere may be just the radius) or a STROKE_DTYPE array -> a contiguous STROKE_DTYPE array.
+    A capsule is {op, shape: SHAPE_CAPSULE, a, b, radius, argb}: the voxels within `radius` (into pad_) of the segment from voxel a to voxel b;
+    an ellipsoid {op, shape: SHAPE_ELLIPSOID, a, b: (rx, ry, rz), argb}: centre a, radii b."""
     if isinstance(strokes, np.ndarray):
         return np.ascontiguousarray(strokes.astype(STROKE_DTYPE, copy=False))
     out = np.zeros(len(strokes), dtype=STROKE_DTYPE)
@@ -216,6 +219,8 @@ def strokes_array(strokes) -> np.ndarray:
         out[i]["a"] = s["a"]
         out[i]["b"] = [b, 0, 0] if np.isscalar(b) else b
         out[i]["argb"] = s.get("argb", 0) & 0xFFFFFFFF
+        if s["shape"] == SHAPE_CAPSULE:
+            out[i]["pad_"] = s["radius"]
     return out
 
 
@@ -570,7 +575,9 @@ class Context:
     # -- voxel brushes and ray picking (cvx_world_brush, cvx_world_pick) ------
     def brush(self, strokes, level_count: int = LOD_LEVELS - 1) -> float:
         """Applies the strokes (a list of dicts {op, shape, a, b or radius, argb} or a STROKE_DTYPE array) in order to LOD 0 and rebuilds
-        LOD 1..level_count over their footprint on the device.  Returns the device milliseconds."""
+        LOD 1..level_count over their footprint on the device.  Returns the device milliseconds.
+        Shapes (strokes_array): SHAPE_BOX [a, b), SHAPE_SPHERE (centre a, radius), SHAPE_CAPSULE (the voxels within radius 0 .. 8191 of the segment
+        from voxel a to voxel b, at most 8191 apart per axis, |a| <= 2^30) and SHAPE_ELLIPSOID (centre a, radii b = (rx, ry, rz), each 1 .. 1024)."""
         arr = strokes_array(strokes)
         ms = C.c_float()
         self._check(lib().cvx_world_brush(self._h, arr.ctypes.data if arr.size else None, arr.size, level_count, C.byref(ms)))

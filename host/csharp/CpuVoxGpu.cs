@@ -52,7 +52,9 @@ namespace CpuVox.Gpu
 		public int Rows, Kind;
 	}
 
-	// cvx_world_brush: one stroke (include/cpuvox_gpu.h, 40 bytes).  Op: 0 fill, 1 carve, 2 paint; Shape: 0 box [A, B), 1 sphere (centre A, radius B[0])
+	// cvx_world_brush: one stroke (include/cpuvox_gpu.h, 40 bytes).  Op: 0 fill, 1 carve, 2 paint; Shape: 0 box [A, B), 1 sphere (centre A, radius B[0]),
+	// 16 capsule (the voxels within radius Pad of the segment from voxel A to voxel B; 0 <= Pad <= 8191, |B[i] - A[i]| <= 8191, |A[i]| <= 2^30),
+	// 17 ellipsoid (centre A, radii B, each 1 .. 1024).  The codes 2 .. 15 are not shapes.  Pad (pad_): the capsule's radius, ignored by every other shape.
 	[StructLayout(LayoutKind.Sequential, Pack = 4)]
 	public unsafe struct BrushStroke
 	{
@@ -289,6 +291,7 @@ namespace CpuVox.Gpu
 		                                                         out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_world_edit_stats(IntPtr ctx, out long usedBytes, out long abandonedBytes, out long spareBytes);
 		// voxel brushes (a LOD-0 edit + its LOD refresh, computed on the device) and first-hit ray picking against LOD 0
+		public const int CVX_SHAPE_BOX = 0, CVX_SHAPE_SPHERE = 1, CVX_SHAPE_CAPSULE = 16, CVX_SHAPE_ELLIPSOID = 17;
 		[DllImport(Lib)] public static extern int cvx_world_brush(IntPtr ctx, BrushStroke* strokes, int strokeCount, int levelCount, out float outDeviceMs);
 		[DllImport(Lib)] public static extern int cvx_world_pick(IntPtr ctx, int rayCount, PickRay* rays, PickHit* hits);
 		[DllImport(Lib)] public static extern int cvx_world_pick_device(IntPtr ctx, int rayCount, IntPtr raysDevice, IntPtr hitsDevice, IntPtr hipStream);

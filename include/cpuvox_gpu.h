@@ -372,26 +372,37 @@ int cvx_world_edit_stats(cvx_context *ctx, int64_t *usedBytes, int64_t *abandone
  * Everything in LOD-0 voxel coordinates: voxel (x, y, z) is the unit cube [x, x+1) x [y, y+1) x [z, z+1), y = 0 at the bottom.
  * cvx_world_brush: voxel-level edits, computed on the device and handed to cvx_world_edit's machinery (records, tails, LOD refresh).  A stroke
  * acts on the voxels inside its shape, all integer: a box holds a <= (x, y, z) < b per axis; a sphere holds (x-a0)^2 + (y-a1)^2 + (z-a2)^2 <= r^2
- * (r = b[0] >= 0, 64-bit arithmetic).  FILL makes them solid with colour argb (solid ones included), CARVE makes them air, PAINT gives colour argb
+ * (r = b[0] >= 0, 64-bit arithmetic).
+ *   A capsule (CVX_SHAPE_CAPSULE) holds the voxels whose centre lies within r = pad_ of the segment from voxel a to voxel b.  With d = b - a,
+ *   w = v - a, L = d.d and p = w.d: L == 0 or p <= 0: w.w <= r^2; p >= L: |v - b|^2 <= r^2; otherwise (w.w) L - p^2 <= r^2 L.  Limits:
+ *   0 <= r <= 8191, |b[i] - a[i]| <= 8191 per axis, |a[i]| <= 2^30.  Footprint per axis: [min(a, b) - r, max(a, b) + r + 1).  A capsule with
+ *   a == b is the sphere of that radius.
+ *   An ellipsoid (CVX_SHAPE_ELLIPSOID) has the centre a and the radii (rx, ry, rz) = b, each 1 .. 1024 (pad_ ignored); with (dx, dy, dz) = v - a it
+ *   holds dx^2 ry^2 rz^2 + dy^2 rx^2 rz^2 + dz^2 rx^2 ry^2 <= rx^2 ry^2 rz^2.  Footprint per axis: [a - r_axis, a + r_axis + 1).  With equal
+ *   radii it is the sphere.
+ *   Both rules are exact in int64 at these limits (products of at most 58 and 62 bits); nothing but integers decides a voxel.
+ * FILL makes them solid with colour argb (solid ones included), CARVE makes them air, PAINT gives colour argb
  * to the solid ones and leaves air alone.  Strokes apply in array order (a later one sees what the earlier ones did) and are clipped to the world;
  * a stroke entirely outside it does nothing.  The call changes LOD 0 and rebuilds LOD 1 .. levelCount (0 .. 5) over the union of the strokes'
  * XZ footprints, rounded outward to multiples of 2^levelCount and clipped to the world: cvx_world_edit's rectangle.  Columns of that rectangle no
  * stroke touches are re-encoded with the builder's rule (WordBuilder.cs:181-268), which gives back the same column for every world the builder
  * made.  Ordering, atomicity and outDeviceMs are cvx_world_edit's.  CVX_ERR_INVALID_ARGUMENT: a bad op / shape, a negative radius, strokeCount
- * outside 1 .. CVX_BRUSH_MAX_STROKES, a sphere radius above 2^30
+ * outside 1 .. CVX_BRUSH_MAX_STROKES, a sphere radius above 2^30, a capsule or an ellipsoid outside its limits (the message names the stroke)
  * or levelCount outside 0 .. 5; CVX_ERR_CAPACITY: a column would need more than 65535 runs, a run longer than
  * 32767 voxels or a colour index above 32767 (World.cs:161-259 keeps them in ushort / short), or the arena limits of cvx_world_edit.  Either
  * leaves the world as it was.  With several GPUs every rank applies the same strokes to its own context. */
 enum { CVX_BRUSH_FILL = 0, CVX_BRUSH_CARVE = 1, CVX_BRUSH_PAINT = 2 };
 enum { CVX_SHAPE_BOX = 0, CVX_SHAPE_SPHERE = 1 };
+/* The codes 2 .. 15 are not shapes and stay rejected as "bad shape": callers and tests rely on 2 and 5 being invalid.  Do not renumber. */
+enum { CVX_SHAPE_CAPSULE = 16, CVX_SHAPE_ELLIPSOID = 17 };
 #define CVX_BRUSH_MAX_STROKES 4096
 typedef struct cvx_brush_stroke { /* 40 bytes */
 	int32_t op;    /* CVX_BRUSH_* */
 	int32_t shape; /* CVX_SHAPE_* */
-	int32_t a[3];  /* box: min corner (inclusive); sphere: centre voxel */
-	int32_t b[3];  /* box: max corner (exclusive); sphere: b[0] = radius, b[1], b[2] ignored */
+	int32_t a[3];  /* box: min corner (inclusive); sphere, ellipsoid: centre voxel; capsule: first end voxel */
+	int32_t b[3];  /* box: max corner (exclusive); sphere: b[0] = radius, b[1], b[2] ignored; ellipsoid: the radii; capsule: second end voxel */
 	uint32_t argb; /* FILL / PAINT colour (ColorARGB32 byte order, as the blobs hold it) */
-	int32_t pad_;
+	int32_t pad_;  /* capsule: the radius; every other shape: ignored */
 } cvx_brush_stroke;
 int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strokeCount, int levelCount, float *outDeviceMs);
 
