@@ -244,6 +244,29 @@ struct BrushResult {
 	bool overLimit;          // a run count, run length or colour index the format cannot hold
 };
 
+// The column in a sub-world blob (the reference's layout): its elements are [guard][runs][guard][colours], none for an empty column ...
+CVX_HD inline __attribute__((always_inline)) uint32_t BlobElements(const BrushResult &r) { return r.runCount ? r.runCount + 2u + r.colours : 0u; }
+// ... and what a write kernel ends with, the column counted as r: for an empty column the zero header h and nothing else; otherwise, once the
+// second walk has written the runs at e + 1 and the colours at e + r.runCount + 2 (behind the runs' second guard, a place known once the runs are
+// counted), the two guards and the 12-byte header.  e = the pool + off.
+// The test `r.runCount == 0u` stays in the kernels on purpose (`if (r.runCount == 0u) { BlobEmitEmpty(h); return; }`, h computed where it always
+// was): with the test inside a helper, or the second walk passed in as a callable, the compiler allocates the write kernels' registers differently
+// and their instruction lists change.  Keep the two helpers apart unless the kernels are meant to change.
+CVX_HD inline __attribute__((always_inline)) void BlobEmitEmpty(uint32_t *h)
+{
+	h[0] = 0u;
+	h[1] = 0u;
+	h[2] = 0u;
+}
+CVX_HD inline __attribute__((always_inline)) void BlobEmitHeader(uint32_t *h, uint32_t *e, uint32_t off, const BrushResult &r)
+{
+	e[0] = 0u;
+	e[r.runCount + 1u] = 0u;
+	h[0] = off;
+	h[1] = r.runCount | (r.worldMin << 16);
+	h[2] = r.worldMax;
+}
+
 // Walks the column (cx, cz) top-down after `n` strokes.  Every voxel ends as the fold of the strokes that cover it over what the arena holds:
 // FILL -> solid(argb), CARVE -> air, PAINT -> solid ? solid(argb) : air.  So within a y span where the same strokes cover the column and the
 // arena's column does not change between solid and air, every voxel has the same fate: the walk goes span by span, the span ends at the

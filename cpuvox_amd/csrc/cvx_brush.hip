@@ -1,7 +1,8 @@
 // cvx_brush.hip -- libcpuvox_gpu.so, voxel brushes (cvx_world_brush) and ray picking (cvx_world_pick, cvx_world_pick_device) on the device-resident
 // world.  See include/cpuvox_gpu.h for the contract, cvx_brush.h for the per-column rules and DESIGN.md sections 3 and 4.
 //
-// A brush is cvx_world_edit with the sub-world built on the device instead of uploaded:
+// A brush is cvx_world_edit with the sub-world built on the device instead of uploaded; steps 2 .. 4 are cvxi::ColumnEdit (cvx_edit.hip), the count and
+// the write kernel what it launches:
 //   0. cull   (both kernels begin with it): each wave lists the strokes whose footprint meets its 64 columns, in stroke order, in LDS
 //   1. count  (a thread per LOD-0 column of the rounded rectangle): the column from the arena, the wave's strokes in order (cvxb::BrushColumnOver), the
 //             elements its new column needs ([guard][runs][guard][colours]); columns the format cannot hold raise a flag
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(kBrushThreads) void brush_count_kernel(BrushArgs A)
 	const cvxb::ListedStrokes strokes{ A.strokes, list };
 	const cvxb::BrushResult r = cvxb::BrushColumnOver(Column(A, cx, cz), colours, A.colorShift, strokes, listCount, cx, cz, A.dimY, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
-	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.counts[i] = cvxb::BlobElements(r);
 }
 
 __global__ __launch_bounds__(kBrushThreads) void brush_write_kernel(BrushArgs A)
@@ -102,18 +103,9 @@ __global__ __launch_bounds__(kBrushThreads) void brush_write_kernel(BrushArgs A)
 	const cvxb::ArenaColumn col = Column(A, cx, cz);
 	const cvxb::BrushResult r = cvxb::BrushColumnOver(col, colours, A.colorShift, strokes, listCount, cx, cz, A.dimY, nullptr, nullptr);
 	uint32_t *h = A.headers + 3 * (size_t)i;
-	if (r.runCount == 0u) {
-		h[0] = 0u;
-		h[1] = 0u;
-		h[2] = 0u;
-		return;
-	}
+	if (r.runCount == 0u) { cvxb::BlobEmitEmpty(h); return; }
 	cvxb::BrushColumnOver(col, colours, A.colorShift, strokes, listCount, cx, cz, A.dimY, e + 1, e + r.runCount + 2u);
-	e[0] = 0u;
-	e[r.runCount + 1u] = 0u;
-	h[0] = off;
-	h[1] = r.runCount | (r.worldMin << 16);
-	h[2] = r.worldMax;
+	cvxb::BlobEmitHeader(h, e, off, r);
 }
 
 __global__ __launch_bounds__(CVX_WAVE) void pick_kernel(cvxb::PickWorld W, int rayCount, const cvx_pick_ray *rays, cvx_pick_hit *hits)
@@ -167,14 +159,13 @@ bool Footprint(const cvx_brush_stroke &s, int dimX, int dimY, int dimZ, int64_t 
 
 cvxb::PickWorld PickWorldOf(const cvx_context *ctx)
 {
-	const DevWorld &W = ctx->hostWorld;
-	const DevWorldLevel &L = W.level[0];
+	const cvxb::CopyWorld W = cvxi::WorldOf(ctx);
 	cvxb::PickWorld P;
-	P.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-	P.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-	P.colours = ctx->arena + L.elementsOff;
-	P.rowShift = L.rowShift;
-	P.colorShift = L.colorShift;
+	P.records = W.records;
+	P.runs = W.runs;
+	P.colours = reinterpret_cast<const uint8_t *>(W.colourSlots);
+	P.rowShift = W.rowShift;
+	P.colorShift = W.colorShift;
 	P.dimX = W.dimX;
 	P.dimY = W.dimY;
 	P.dimZ = W.dimZ;
@@ -241,98 +232,46 @@ int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strok
 	}
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	if (live.empty()) { return CVX_OK; }
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
-	x0 &= ~align;
-	z0 &= ~align;
-	x1 = std::min<int64_t>((x1 + align) & ~align, dimX);
-	z1 = std::min<int64_t>((z1 + align) & ~align, dimZ);
-	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
-		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dimX, dimZ, (long long)align + 1);
-	}
-	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-	const int n = sizeX * sizeZ;
-	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "a brush over %d x %d columns", sizeX, sizeZ); }
-	int rc = Prepare(ctx);
+	cvxi::EditRectangle R;
+	int rc = cvxi::RoundEditRectangle(ctx, x0, x1, z0, z1, levelCount, "a brush over", &R);
+	if (rc == CVX_OK) { rc = Prepare(ctx); }
 	if (rc != CVX_OK) { return rc; }
 
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	uint8_t *scratch = nullptr, *dSrc = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		if (dSrc) { (void)hipFree(dSrc); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
-	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
-	const size_t oStrokes = carve(live.size() * sizeof(cvx_brush_stroke)), oCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8);
-	struct { unsigned long long total, overLimit; } host = { 0, 0 };
+	const size_t strokeBytes = live.size() * sizeof(cvx_brush_stroke);
+	const DevWorldLevel &L = ctx->hostWorld.level[0];
 	cvxbrush::BrushArgs A{};
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
-	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oStrokes, live.data(), live.size() * sizeof(cvx_brush_stroke), hipMemcpyHostToDevice, ctx->stream); }
-	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, 2 * 8, ctx->stream); }
-	if (e == hipSuccess) {
-		const DevWorldLevel &L = ctx->hostWorld.level[0];
-		A.arena = ctx->arena;
-		A.recordsOff = L.recordsOff;
-		A.runsOff = L.runsOff;
-		A.elementsOff = L.elementsOff;
-		A.rowShift = L.rowShift;
-		A.colorShift = L.colorShift;
-		A.dimY = dimY;
-		A.x0 = (int)x0;
-		A.z0 = (int)z0;
-		A.sizeZ = sizeZ;
-		A.n = n;
-		A.strokes = reinterpret_cast<const cvx_brush_stroke *>(scratch + oStrokes);
-		A.strokeCount = (int)live.size();
-		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
-		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
-		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
-		// 1, 2. count, scan, one copy back
-		hipLaunchKernelGGL(cvxbrush::brush_count_kernel, dim3(Grid((size_t)n, cvxbrush::kBrushThreads)), dim3(cvxbrush::kBrushThreads), 0, ctx->stream, A);
-		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
-		e = hipGetLastError();
-		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "brush failed: %s", hipGetErrorString(e));
-	}
-	if (host.overLimit) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "a brushed column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
-	}
-	if (host.total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the brushed columns need %llu elements", host.total);
-	}
-	// 3. the sub-world blob
-	const size_t blobBytes = (size_t)n * 12 + (size_t)host.total * 4;
-	e = hipMalloc((void **)&dSrc, std::max<size_t>(blobBytes, 4));
-	if (e == hipSuccess) {
-		A.headers = reinterpret_cast<uint32_t *>(dSrc);
-		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
-		hipLaunchKernelGGL(cvxbrush::brush_write_kernel, dim3(Grid((size_t)n, cvxbrush::kBrushThreads)), dim3(cvxbrush::kBrushThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "brush failed: %s", hipGetErrorString(e));
-	}
-	// 4. cvx_world_edit's machinery
-	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.total, n, levelCount, ev[1]);
-	if (rc == CVX_OK && outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
-	return rc;
+	A.arena = ctx->arena;
+	A.recordsOff = L.recordsOff;
+	A.runsOff = L.runsOff;
+	A.elementsOff = L.elementsOff;
+	A.rowShift = L.rowShift;
+	A.colorShift = L.colorShift;
+	A.dimY = dimY;
+	A.x0 = R.x0;
+	A.z0 = R.z0;
+	A.sizeZ = R.sizeZ;
+	A.n = R.n;
+	A.strokeCount = (int)live.size();
+	const dim3 grid(Grid((size_t)R.n, cvxbrush::kBrushThreads)), block(cvxbrush::kBrushThreads);
+	cvxi::ColumnEditCall call{ "brush", nullptr, "a brushed column", "the brushed columns" };
+	call.extraScratchBytes = strokeBytes;
+	return cvxi::ColumnEdit(
+		ctx, R, levelCount, call,
+		[&](const cvxi::ColumnEditJob &J) {
+			A.strokes = reinterpret_cast<const cvx_brush_stroke *>(J.extra);
+			A.counts = J.counts;
+			A.overLimit = J.overLimit;
+			const hipError_t e = hipMemcpyAsync(J.extra, live.data(), strokeBytes, hipMemcpyHostToDevice, ctx->stream);
+			if (e == hipSuccess) { hipLaunchKernelGGL(cvxbrush::brush_count_kernel, grid, block, 0, ctx->stream, A); }
+			return e;
+		},
+		[&](const cvxi::ColumnEditJob &J) {
+			A.headers = J.headers;
+			A.elements = J.elements;
+			hipLaunchKernelGGL(cvxbrush::brush_write_kernel, grid, block, 0, ctx->stream, A);
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 int cvx_world_pick_device(cvx_context *ctx, int rayCount, const cvx_pick_ray *raysDevice, cvx_pick_hit *hitsDevice, void *hipStream)

@@ -13,12 +13,13 @@
 //             bounding box and open bits of every root; then the roots are flagged open / enclosed / selected (maxVoxels), totalled, and the
 //             selected ones ranked by a scan in index order = the order of the contract
 //   5. list   the first cavityCapacity selected cavities, copied to the host behind the totals
-//   6. FILL   count / scan / write of the sub-world blob of the selected cavities' rectangle (cvxb::CavityFillColumn), then
-//             cvxi::EditFromDevice, exactly as cvx_pieces.hip's REMOVE.  Nothing in the arena is written before that.
+//   6. FILL   cvxi::ColumnEdit (cvx_edit.hip) over the selected cavities' rectangle: count and write of the sub-world blob are
+//             cvxb::CavityFillColumn.  Nothing in the arena is written before its last step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(256) void cavity_fill_count_kernel(CavityArgs A)
 	const int cx = A.rx0 + i / A.rSizeZ, cz = A.rz0 + i % A.rSizeZ;
 	const cvxb::BrushResult r = cvxb::CavityFillColumn(A.W, cx, cz, A.B.y0, A.B.y1, ColumnNodes(A, cx, cz), A.argb, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(&A.totals->overLimit, 1u); }
-	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.counts[i] = cvxb::BlobElements(r);
 }
 
 __global__ __launch_bounds__(256) void cavity_fill_write_kernel(CavityArgs A)
@@ -289,18 +290,9 @@ __global__ __launch_bounds__(256) void cavity_fill_write_kernel(CavityArgs A)
 	uint32_t *e = A.elements + off;
 	const cvxb::BrushResult r = cvxb::CavityFillColumn(A.W, cx, cz, A.B.y0, A.B.y1, selected, A.argb, nullptr, nullptr);
 	uint32_t *h = A.headers + 3 * (size_t)i;
-	if (r.runCount == 0u) {
-		h[0] = 0u;
-		h[1] = 0u;
-		h[2] = 0u;
-		return;
-	}
+	if (r.runCount == 0u) { cvxb::BlobEmitEmpty(h); return; }
 	cvxb::CavityFillColumn(A.W, cx, cz, A.B.y0, A.B.y1, selected, A.argb, e + 1, e + r.runCount + 2u);
-	e[0] = 0u;
-	e[r.runCount + 1u] = 0u;
-	h[0] = off;
-	h[1] = r.runCount | (r.worldMin << 16);
-	h[2] = r.worldMax;
+	cvxb::BlobEmitHeader(h, e, off, r);
 }
 
 constexpr size_t kHead = 256; // cavities that come to the host with the totals, in one copy
@@ -344,9 +336,9 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 
 	const int n = (int)A.B.Columns();
 	hipEvent_t ev[3] = { nullptr, nullptr, nullptr }; // start, the analysis, the edit
-	uint8_t *columnScratch = nullptr, *nodeScratch = nullptr, *fillScratch = nullptr, *dSrc = nullptr;
+	uint8_t *columnScratch = nullptr, *nodeScratch = nullptr;
 	auto release = [&]() {
-		for (uint8_t *p : { columnScratch, nodeScratch, fillScratch, dSrc }) { if (p) { (void)hipFree(p); } }
+		for (uint8_t *p : { columnScratch, nodeScratch }) { if (p) { (void)hipFree(p); } }
 		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
 	};
 	size_t bytes = 0;
@@ -364,15 +356,7 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(columnScratch + oTotals, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) {
-		const DevWorldLevel &L = ctx->hostWorld.level[0];
-		A.W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-		A.W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-		A.W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-		A.W.rowShift = L.rowShift;
-		A.W.colorShift = L.colorShift;
-		A.W.dimX = dim[0];
-		A.W.dimY = dim[1];
-		A.W.dimZ = dim[2];
+		A.W = cvxi::WorldOf(ctx);
 		A.n = n;
 		A.openFaces = P.openFaces;
 		A.maxVoxels = (unsigned long long)P.maxVoxels;
@@ -466,62 +450,37 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 	(void)hipEventElapsedTime(&ms, ev[0], ev[1]);
 	const float analysisMs = ms;
 
-	// 6. FILL: the selected cavities' rectangle with them solid, through cvx_world_edit's machinery
+	// 6. FILL: the selected cavities' rectangle with them solid, through cvx_world_edit's machinery (cvxi::ColumnEdit)
 	if (P.op == CVX_CAVITIES_FILL && selected) {
-		const int64_t align = ((int64_t)1 << levelCount) - 1;
-		const int64_t x0 = host.x0 & ~align, z0 = host.z0 & ~align;
-		const int64_t x1 = std::min<int64_t>((host.x1 + align) & ~align, dim[0]), z1 = std::min<int64_t>((host.z1 + align) & ~align, dim[2]);
-		const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-		const int rn = sizeX * sizeZ;
-		if (((x1 - x0) & align) || ((z1 - z0) & align)) {
+		cvxi::EditRectangle E;
+		rc = cvxi::RoundEditRectangle(ctx, host.x0, host.x1, host.z0, host.z1, levelCount, "a fill over", &E);
+		if (rc != CVX_OK) {
 			release();
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dim[0], dim[2], (long long)align + 1);
+			return rc;
 		}
-		if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "a fill over %d x %d columns", sizeX, sizeZ);
-		}
-		bytes = 0;
-		const size_t oCounts = carve((size_t)rn * 4), oCountChunks = carve(chunksOf((size_t)rn) * 8);
-		e = hipMalloc((void **)&fillScratch, bytes);
-		if (e == hipSuccess) {
-			A.rx0 = (int)x0;
-			A.rz0 = (int)z0;
-			A.rSizeZ = sizeZ;
-			A.rn = rn;
-			A.counts = reinterpret_cast<uint32_t *>(fillScratch + oCounts);
-			const dim3 block(kThreads);
-			hipLaunchKernelGGL(cavity_mark_kernel, dim3(Grid(nodes)), block, 0, ctx->stream, A);
-			hipLaunchKernelGGL(cavity_fill_count_kernel, dim3(Grid((size_t)rn)), block, 0, ctx->stream, A);
-			cvxi::ExclusiveScan(ctx->stream, A.counts, rn, reinterpret_cast<unsigned long long *>(fillScratch + oCountChunks), &A.totals->elements);
-			e = hipGetLastError();
-			if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-			if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-		}
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
-		if (host.overLimit) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "a filled column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767 (one colour per voxel)");
-		}
-		if (host.elements >= ((unsigned long long)1 << 31) - (unsigned long long)rn * 3) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "the columns of the fill need %llu elements", host.elements);
-		}
-		e = hipMalloc((void **)&dSrc, std::max<size_t>((size_t)rn * 12 + (size_t)host.elements * 4, 4));
-		if (e == hipSuccess) {
-			A.headers = reinterpret_cast<uint32_t *>(dSrc);
-			A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)rn * 12);
-			hipLaunchKernelGGL(cavity_fill_write_kernel, dim3(Grid((size_t)rn)), dim3(kThreads), 0, ctx->stream, A);
-			e = hipGetLastError();
-		}
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
-		rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.elements, rn, levelCount, ev[2]);
+		A.rx0 = E.x0;
+		A.rz0 = E.z0;
+		A.rSizeZ = E.sizeZ;
+		A.rn = E.n;
+		const cvxi::ColumnEditTotals totals{ A.totals, &host, sizeof host, offsetof(Totals, elements), offsetof(Totals, overLimit) };
+		cvxi::ColumnEditCall edit{ call, FailHip, "a filled column", "the columns of the fill", " (one colour per voxel)" };
+		edit.totals = &totals;
+		edit.done = ev[2];
+		rc = cvxi::ColumnEdit(
+			ctx, E, levelCount, edit,
+			[&](const cvxi::ColumnEditJob &J) {
+				A.counts = J.counts;
+				hipLaunchKernelGGL(cavity_mark_kernel, dim3(Grid(nodes)), dim3(kThreads), 0, ctx->stream, A);
+				hipLaunchKernelGGL(cavity_fill_count_kernel, dim3(Grid((size_t)E.n)), dim3(kThreads), 0, ctx->stream, A);
+				return hipSuccess;
+			},
+			[&](const cvxi::ColumnEditJob &J) {
+				A.headers = J.headers;
+				A.elements = J.elements;
+				hipLaunchKernelGGL(cavity_fill_write_kernel, dim3(Grid((size_t)E.n)), dim3(kThreads), 0, ctx->stream, A);
+				return hipSuccess;
+			},
+			nullptr);
 		if (rc != CVX_OK) {
 			release();
 			return rc;

@@ -6,9 +6,11 @@
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "cpuvox_gpu.h"
+#include "cvx_copy.h" // cvxb::CopyWorld
 #include "cvx_device.h"
 
 struct RefHeader { // World.RLEColumn, World.cs:161-169
@@ -163,6 +165,8 @@ int ValidateRepeat(cvx_context *ctx);
 
 // cvx_gpu.hip: lays the uploaded levels out in the arena if any is pending (what the next draw would do first)
 int SyncWorld(cvx_context *ctx);
+// cvx_gpu.hip: LOD 0 of the arena as the kernels of the world calls read it (cvx_copy.h); valid from SyncWorld to the next call that lays the arena out again
+cvxb::CopyWorld WorldOf(const cvx_context *ctx);
 // cvx_world.hip: exclusive prefix sum of n counts in place on `stream`, *total (device) = their sum; chunkSums: (n + CVX_SCAN_CHUNK - 1) / CVX_SCAN_CHUNK words of 8 bytes
 void ExclusiveScan(hipStream_t stream, uint32_t *values, int n, unsigned long long *chunkSums, unsigned long long *total);
 int ScanChunk();
@@ -177,6 +181,68 @@ void FreeEditState(cvx_context *ctx);
 // patch.  Returns once the stream has run it.
 int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const uint8_t *dSrc, int64_t elementsOfColumns, int columnCount, int levelCount,
                    hipEvent_t done);
+
+// ---- the column-edit pipeline (cvx_edit.hip): what every call that builds its sub-world blob on the device goes through ----
+// The LOD-0 rectangle of an edit: n = sizeX * sizeZ columns, aligned to 2^levelCount
+struct EditRectangle {
+	int x0, z0, sizeX, sizeZ, n;
+};
+// Rounds the footprint [x0, x1) x [z0, z1) (inside the world) out to 2^levelCount and clips it to the world.  Fails with CVX_ERR_INVALID_ARGUMENT
+// when the world is too narrow for that rounding and with CVX_ERR_CAPACITY ("<what> %d x %d columns", e.g. "a brush over") when the headers of
+// that many columns would not fit the blob.
+int RoundEditRectangle(cvx_context *ctx, int64_t x0, int64_t x1, int64_t z0, int64_t z1, int levelCount, const char *what, EditRectangle *out);
+
+// What ColumnEdit owns and hands to the caller's two launchers
+struct ColumnEditJob {
+	EditRectangle R;
+	uint32_t *counts;             // R.n words: the count launcher's kernel leaves every column's elements there, the scan turns them into offsets
+	unsigned long long *total;    // device: the scan's total
+	unsigned int *overLimit;      // device, zero before the count launcher: its kernel raises it for a column the format cannot hold
+	uint8_t *extra;               // ColumnEditCall::extraScratchBytes of the same allocation, 16-byte aligned
+	uint32_t *headers, *elements; // the write launcher only: the blob, R.n headers of 3 words and the element pool
+};
+// A caller that keeps the total and the flag in a device struct of its own (already zeroed) and wants that struct back whole: the ONE copy
+// of the pipeline is `bytes` from `from` (device) to `to` (host); the total (8 bytes) and the flag (4 bytes) lie at these byte offsets in both.
+struct ColumnEditTotals {
+	void *from;
+	void *to;
+	size_t bytes;
+	size_t totalAt, overLimitAt;
+};
+struct ColumnEditCall {
+	const char *call;                      // HIP failures: "<call> failed: <error>" ...
+	int (*failHip)(cvx_context *, const char *call, hipError_t) = nullptr; // ... or what this returns (a call that reports hipErrorOutOfMemory its own way)
+	const char *overLimitSubject;          // "<a brushed column> would need ..." (what the format cannot hold)
+	const char *elementsSubject;           // "<the brushed columns> need %llu elements"
+	const char *overLimitNote = "";        // appended to the first message
+	size_t extraScratchBytes = 0;          // the caller's share of the pipeline's one scratch allocation (strokes, placements, lamps)
+	const ColumnEditTotals *totals = nullptr; // null: the pipeline's own pair, zeroed on the stream
+	hipEvent_t done = nullptr;             // null: the pipeline times itself, *outMs = device time from its first enqueue to the last patch;
+	                                       // else the caller's event, recorded behind the last patch: the caller recorded its start long before and
+	                                       // takes the time itself -- ColumnEdit then creates no events and does NOT write *outMs
+};
+// A reference to a caller's launcher (a lambda: hipError_t(const ColumnEditJob &)) for the length of the ColumnEdit call: nothing is owned or allocated.
+// The launcher enqueues on ctx->stream and returns the first error of its own uploads; launch errors are picked up by ColumnEdit.
+class ColumnEditLauncher {
+	void *object;
+	hipError_t (*invoke)(void *, const ColumnEditJob &);
+
+public:
+	template <class F, class = std::enable_if_t<!std::is_same_v<std::decay_t<F>, ColumnEditLauncher>>>
+	ColumnEditLauncher(F &&f)
+		: object(const_cast<void *>(static_cast<const void *>(&f))),
+		  invoke([](void *o, const ColumnEditJob &J) -> hipError_t { return (*static_cast<std::remove_reference_t<F> *>(o))(J); })
+	{
+	}
+	hipError_t operator()(const ColumnEditJob &J) const { return invoke(object, J); }
+};
+// Steps 2 .. 6 of the pipeline (cvx_edit.hip's header) on ctx->stream: scratch, launchCount (its uploads, then its count kernel), cvxi::ExclusiveScan, one
+// copy back and one synchronisation, the two capacity checks, the blob's allocation, launchWrite (its write kernel and whatever shades the blob),
+// EditFromDevice.  Everything the pipeline allocated is released on every path; nothing in the arena is written before EditFromDevice.
+// outMs (may be null) is written only when call.done is null, see there.
+int ColumnEdit(cvx_context *ctx, const EditRectangle &R, int levelCount, const ColumnEditCall &call, ColumnEditLauncher launchCount, ColumnEditLauncher launchWrite,
+               float *outMs);
+
 // cvx_brush.hip: releases the picking scratch (cvx_destroy)
 void FreeBrushState(cvx_context *ctx);
 } // namespace cvxi

@@ -1,7 +1,8 @@
 // cvx_copy.hip -- libcpuvox_gpu.so, copying, moving and rotating voxel boxes inside the device-resident world (cvx_world_copy).  See
 // include/cpuvox_gpu.h for the contract and cvx_copy.h for the column rule.
 //
-// A copy is a brush whose columns are composed from other columns of the arena, step for step cvx_world_brush:
+// A copy is a brush whose columns are composed from other columns of the arena; steps 2 .. 4 are cvxi::ColumnEdit (cvx_edit.hip), the count and the
+// write kernel what it launches:
 //   1. count  (a thread per LOD-0 column of the rounded rectangle): the column after the placements (cvxb::CopyColumn), the elements its new
 //             column needs ([guard][runs][guard][colours]); columns the format cannot hold raise a flag
 //   2. the counts are prefix-scanned into element offsets; ONE copy brings the total and the flag to the host
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(256) void copy_count_kernel(CopyArgs A)
 	const int cx = A.x0 + i / A.sizeZ, cz = A.z0 + i % A.sizeZ;
 	const cvxb::BrushResult r = cvxb::CopyColumn(A.W, A.placements, A.placementCount, cx, cz, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
-	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.counts[i] = cvxb::BlobElements(r);
 }
 
 __global__ __launch_bounds__(256) void copy_write_kernel(CopyArgs A)
@@ -52,18 +53,9 @@ __global__ __launch_bounds__(256) void copy_write_kernel(CopyArgs A)
 	// (the colours go behind the runs' second guard, a place known once the runs are counted: the walk runs twice, the second time writing)
 	const cvxb::BrushResult r = cvxb::CopyColumn(A.W, A.placements, A.placementCount, cx, cz, nullptr, nullptr);
 	uint32_t *h = A.headers + 3 * (size_t)i;
-	if (r.runCount == 0u) {
-		h[0] = 0u;
-		h[1] = 0u;
-		h[2] = 0u;
-		return;
-	}
+	if (r.runCount == 0u) { cvxb::BlobEmitEmpty(h); return; }
 	cvxb::CopyColumn(A.W, A.placements, A.placementCount, cx, cz, e + 1, e + r.runCount + 2u);
-	e[0] = 0u;
-	e[r.runCount + 1u] = 0u;
-	h[0] = off;
-	h[1] = r.runCount | (r.worldMin << 16);
-	h[2] = r.worldMax;
+	cvxb::BlobEmitHeader(h, e, off, r);
 }
 
 } // namespace cvxcopy
@@ -139,101 +131,40 @@ int cvx_world_copy(cvx_context *ctx, const cvx_copy_placement *placements, int p
 	}
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	if (live.empty()) { return CVX_OK; }
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
-	x0 &= ~align;
-	z0 &= ~align;
-	x1 = std::min<int64_t>((x1 + align) & ~align, dim[0]);
-	z1 = std::min<int64_t>((z1 + align) & ~align, dim[2]);
-	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
-		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dim[0], dim[2], (long long)align + 1);
-	}
-	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-	const int n = sizeX * sizeZ;
-	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "a copy over %d x %d columns", sizeX, sizeZ); }
+	cvxi::EditRectangle R;
+	int rc = cvxi::RoundEditRectangle(ctx, x0, x1, z0, z1, levelCount, "a copy over", &R);
+	if (rc != CVX_OK) { return rc; }
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	int rc = cvxi::SyncWorld(ctx);
+	rc = cvxi::SyncWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	uint8_t *scratch = nullptr, *dSrc = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		if (dSrc) { (void)hipFree(dSrc); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
-	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
-	const size_t oPlacements = carve(live.size() * sizeof(cvx_copy_placement)), oCounts = carve((size_t)n * 4), oTotals = carve(2 * 8),
-	             oChunks = carve(chunks * 8);
-	struct { unsigned long long total, overLimit; } host = { 0, 0 };
+	const size_t placementBytes = live.size() * sizeof(cvx_copy_placement);
 	cvxcopy::CopyArgs A{};
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
-	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oPlacements, live.data(), live.size() * sizeof(cvx_copy_placement), hipMemcpyHostToDevice, ctx->stream); }
-	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, 2 * 8, ctx->stream); }
-	if (e == hipSuccess) {
-		const DevWorldLevel &L = ctx->hostWorld.level[0];
-		A.W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-		A.W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-		A.W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-		A.W.rowShift = L.rowShift;
-		A.W.colorShift = L.colorShift;
-		A.W.dimX = dim[0];
-		A.W.dimY = dim[1];
-		A.W.dimZ = dim[2];
-		A.x0 = (int)x0;
-		A.z0 = (int)z0;
-		A.sizeZ = sizeZ;
-		A.n = n;
-		A.placements = reinterpret_cast<const cvx_copy_placement *>(scratch + oPlacements);
-		A.placementCount = (int)live.size();
-		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
-		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
-		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
-		// 1, 2. count, scan, one copy back
-		hipLaunchKernelGGL(cvxcopy::copy_count_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
-		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
-		e = hipGetLastError();
-		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "copy failed: %s", hipGetErrorString(e));
-	}
-	if (host.overLimit) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "a copied column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
-	}
-	if (host.total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the copied columns need %llu elements", host.total);
-	}
-	// 3. the sub-world blob
-	const size_t blobBytes = (size_t)n * 12 + (size_t)host.total * 4;
-	e = hipMalloc((void **)&dSrc, std::max<size_t>(blobBytes, 4));
-	if (e == hipSuccess) {
-		A.headers = reinterpret_cast<uint32_t *>(dSrc);
-		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
-		hipLaunchKernelGGL(cvxcopy::copy_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "copy failed: %s", hipGetErrorString(e));
-	}
-	// 4. cvx_world_edit's machinery
-	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.total, n, levelCount, ev[1]);
-	if (rc == CVX_OK && outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
-	return rc;
+	A.W = cvxi::WorldOf(ctx);
+	A.x0 = R.x0;
+	A.z0 = R.z0;
+	A.sizeZ = R.sizeZ;
+	A.n = R.n;
+	A.placementCount = (int)live.size();
+	cvxi::ColumnEditCall call{ "copy", nullptr, "a copied column", "the copied columns" };
+	call.extraScratchBytes = placementBytes;
+	return cvxi::ColumnEdit(
+		ctx, R, levelCount, call,
+		[&](const cvxi::ColumnEditJob &J) {
+			A.placements = reinterpret_cast<const cvx_copy_placement *>(J.extra);
+			A.counts = J.counts;
+			A.overLimit = J.overLimit;
+			const hipError_t e = hipMemcpyAsync(J.extra, live.data(), placementBytes, hipMemcpyHostToDevice, ctx->stream);
+			if (e == hipSuccess) { hipLaunchKernelGGL(cvxcopy::copy_count_kernel, dim3(Grid((size_t)R.n)), dim3(kThreads), 0, ctx->stream, A); }
+			return e;
+		},
+		[&](const cvxi::ColumnEditJob &J) {
+			A.headers = J.headers;
+			A.elements = J.elements;
+			hipLaunchKernelGGL(cvxcopy::copy_write_kernel, dim3(Grid((size_t)R.n)), dim3(kThreads), 0, ctx->stream, A);
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 } // extern "C"

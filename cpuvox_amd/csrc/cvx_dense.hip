@@ -4,7 +4,8 @@
 // A read is one kernel, a thread per element of the arrays: consecutive lanes are consecutive y of a column and go on into the next column (z,
 // then x) where the box is lower than a wave, so the stores are contiguous whatever the box's height.  Each lane finds its voxel with a binary
 // search of its column's runs (cvxb::DenseVoxel).
-// A write is a brush whose columns come from the dense arrays, step for step cvx_world_brush / cvx_world_copy:
+// A write is a brush whose columns come from the dense arrays; steps 2 .. 4 are cvxi::ColumnEdit (cvx_edit.hip), the count and the write kernel what
+// it launches:
 //   1. count  (a WAVE per LOD-0 column of the rounded rectangle): the column top-down, 64 voxels per step; every lane evaluates its voxel
 //             (cvxb::DenseFinal: the arrays inside the box, read contiguously, the arena elsewhere), a ballot gives the step's solid mask, its
 //             changes against itself shifted by one voxel the run starts, popcounts the run and colour counts; the steps between
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void dense_count_kernel(WriteArgs A)
 	const cvxb::BrushResult r = WalkColumn<false>(A, i, lane, nullptr, nullptr);
 	if (lane != 0) { return; }
 	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
-	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.counts[i] = cvxb::BlobElements(r);
 	A.runCounts[i] = r.runCount;
 }
 
@@ -147,21 +148,6 @@ namespace {
 using cvxdense::kThreads;
 
 unsigned Grid(size_t n, unsigned per = kThreads) { return (unsigned)((n + per - 1) / per); }
-
-cvxb::CopyWorld WorldOf(const cvx_context *ctx)
-{
-	const DevWorldLevel &L = ctx->hostWorld.level[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-	W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-	W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-	W.rowShift = L.rowShift;
-	W.colorShift = L.colorShift;
-	W.dimX = ctx->hostWorld.dimX;
-	W.dimY = ctx->hostWorld.dimY;
-	W.dimZ = ctx->hostWorld.dimZ;
-	return W;
-}
 
 // The checks both directions share; *elements receives the box's voxel count.
 int CheckBox(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], cvxb::DenseBox *box, int64_t *elements)
@@ -202,7 +188,7 @@ int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int3
 	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
 	rc = Prepare(ctx);
 	if (rc != CVX_OK) { return rc; }
-	A.W = WorldOf(ctx);
+	A.W = cvxi::WorldOf(ctx);
 	A.n = (uint32_t)n;
 	if (device) {
 		A.argb = argb;
@@ -276,102 +262,52 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	}
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	if (!touches) { return CVX_OK; }
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
-	const int64_t x0 = lo[0] & ~align, z0 = lo[2] & ~align;
-	const int64_t x1 = std::min<int64_t>((hi[0] + align) & ~align, dim[0]), z1 = std::min<int64_t>((hi[2] + align) & ~align, dim[2]);
-	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
-		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dim[0], dim[2], (long long)align + 1);
-	}
-	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-	const int n = sizeX * sizeZ;
-	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "a write over %d x %d columns", sizeX, sizeZ); }
-	rc = Prepare(ctx);
+	cvxi::EditRectangle R;
+	rc = cvxi::RoundEditRectangle(ctx, lo[0], hi[0], lo[2], hi[2], levelCount, "a write over", &R);
+	if (rc == CVX_OK) { rc = Prepare(ctx); }
 	if (rc != CVX_OK) { return rc; }
 
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	uint8_t *scratch = nullptr, *dSrc = nullptr, *dense = nullptr;
-	auto release = [&]() {
-		for (uint8_t *p : { scratch, dSrc, dense }) { if (p) { (void)hipFree(p); } }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
-	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
-	const size_t oCounts = carve((size_t)n * 4), oRunCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8);
+	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it
+	struct Dense {
+		uint8_t *p = nullptr;
+		~Dense() { if (p) { (void)hipFree(p); } }
+	} dense;
 	const size_t argbBytes = argb ? ((size_t)elements * 4 + 15) & ~(size_t)15 : 0, solidBytes = solid ? (size_t)elements : 0;
-	struct { unsigned long long total, overLimit; } host = { 0, 0 };
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
-	if (e == hipSuccess && !device) {
-		e = hipMalloc((void **)&dense, argbBytes + solidBytes);
-		if (e == hipErrorOutOfMemory) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the box", call, argbBytes + solidBytes);
-		}
+	if (!device) {
+		const hipError_t e = hipMalloc((void **)&dense.p, argbBytes + solidBytes);
+		if (e == hipErrorOutOfMemory) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the box", call, argbBytes + solidBytes); }
+		if (e != hipSuccess) { return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e)); }
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
-	if (e == hipSuccess && !device) {
-		if (argb) { e = hipMemcpyAsync(dense, argb, (size_t)elements * 4, hipMemcpyHostToDevice, ctx->stream); }
-		if (e == hipSuccess && solid) { e = hipMemcpyAsync(dense + argbBytes, solid, solidBytes, hipMemcpyHostToDevice, ctx->stream); }
-		argb = argb ? reinterpret_cast<const uint32_t *>(dense) : nullptr;
-		solid = solid ? dense + argbBytes : nullptr;
-	}
-	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, 2 * 8, ctx->stream); }
-	if (e == hipSuccess) {
-		A.W = WorldOf(ctx);
-		A.argb = argb;
-		A.solid = solid;
-		A.op = op;
-		A.x0 = (int)x0;
-		A.z0 = (int)z0;
-		A.sizeZ = sizeZ;
-		A.n = n;
-		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
-		A.runCounts = reinterpret_cast<uint32_t *>(scratch + oRunCounts);
-		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
-		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
-		// 1, 2. count, scan, one copy back
-		hipLaunchKernelGGL(cvxdense::dense_count_kernel, dim3(Grid((size_t)n, cvxdense::kWavesPerBlock)), dim3(kThreads), 0, ctx->stream, A);
-		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
-		e = hipGetLastError();
-		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
-	}
-	if (host.overLimit) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "a written column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
-	}
-	if (host.total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the written columns need %llu elements", host.total);
-	}
-	// 3. the sub-world blob
-	const size_t blobBytes = (size_t)n * 12 + (size_t)host.total * 4;
-	e = hipMalloc((void **)&dSrc, std::max<size_t>(blobBytes, 4));
-	if (e == hipSuccess) {
-		A.headers = reinterpret_cast<uint32_t *>(dSrc);
-		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
-		hipLaunchKernelGGL(cvxdense::dense_write_kernel, dim3(Grid((size_t)n, cvxdense::kWavesPerBlock)), dim3(kThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
-	}
-	// 4. cvx_world_edit's machinery
-	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.total, n, levelCount, ev[1]);
-	if (rc == CVX_OK && outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
-	return rc;
+	A.W = cvxi::WorldOf(ctx);
+	A.argb = device ? argb : (argb ? reinterpret_cast<const uint32_t *>(dense.p) : nullptr);
+	A.solid = device ? solid : (solid ? dense.p + argbBytes : nullptr);
+	A.op = op;
+	A.x0 = R.x0;
+	A.z0 = R.z0;
+	A.sizeZ = R.sizeZ;
+	A.n = R.n;
+	const dim3 grid(Grid((size_t)R.n, cvxdense::kWavesPerBlock)), block(kThreads);
+	cvxi::ColumnEditCall edit{ call, nullptr, "a written column", "the written columns" };
+	edit.extraScratchBytes = (size_t)R.n * 4; // the run counts
+	return cvxi::ColumnEdit(
+		ctx, R, levelCount, edit,
+		[&](const cvxi::ColumnEditJob &J) {
+			hipError_t e = hipSuccess;
+			if (!device && argb) { e = hipMemcpyAsync(dense.p, argb, (size_t)elements * 4, hipMemcpyHostToDevice, ctx->stream); }
+			if (e == hipSuccess && !device && solid) { e = hipMemcpyAsync(dense.p + argbBytes, solid, solidBytes, hipMemcpyHostToDevice, ctx->stream); }
+			A.counts = J.counts;
+			A.runCounts = reinterpret_cast<uint32_t *>(J.extra);
+			A.overLimit = J.overLimit;
+			if (e == hipSuccess) { hipLaunchKernelGGL(cvxdense::dense_count_kernel, grid, block, 0, ctx->stream, A); }
+			return e;
+		},
+		[&](const cvxi::ColumnEditJob &J) {
+			A.headers = J.headers;
+			A.elements = J.elements;
+			hipLaunchKernelGGL(cvxdense::dense_write_kernel, grid, block, 0, ctx->stream, A);
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 } // namespace

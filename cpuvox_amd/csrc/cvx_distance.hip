@@ -80,21 +80,6 @@ int CheckBox(cvx_context *ctx, const char *call, const int32_t boxMin[3], const 
 	return CVX_OK;
 }
 
-cvxb::CopyWorld WorldOf(const cvx_context *ctx)
-{
-	const DevWorldLevel &L = ctx->hostWorld.level[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-	W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-	W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-	W.rowShift = L.rowShift;
-	W.colorShift = L.colorShift;
-	W.dimX = ctx->hostWorld.dimX;
-	W.dimY = ctx->hostWorld.dimY;
-	W.dimZ = ctx->hostWorld.dimZ;
-	return W;
-}
-
 unsigned Grid(uint64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], int maxDistance, int mode, int solidOutside, int32_t *out,
@@ -140,7 +125,7 @@ int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const 
 	}
 	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
 	if (e == hipSuccess) {
-		A.W = WorldOf(ctx);
+		A.W = cvxi::WorldOf(ctx);
 		A.fromY = reinterpret_cast<uint16_t *>(scratch);
 		A.fromZ = reinterpret_cast<uint16_t *>(scratch + bytesY);
 		A.out = device ? out : reinterpret_cast<int32_t *>(scratch + bytesY + bytesZ);

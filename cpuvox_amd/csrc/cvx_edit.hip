@@ -10,6 +10,15 @@
 //   3. move   (a workgroup per moving block): the block's colours to its new place, the records of its columns outside the rectangle to it
 //   4. write  (a thread per replaced column): colours, run-list block, counts entry, record.
 // Nothing is written before step 3, so a failure up to there (validation, capacity) leaves the world as it was.
+//
+// The calls that build their sub-world on the device (brush, copy, dense write, light, stamp, pieces REMOVE, settle, cavities FILL) share one host
+// pipeline, written here beside the cvxi::EditFromDevice it ends with: cvxi::RoundEditRectangle, then cvxi::ColumnEdit --
+//   1. the footprint rounded out to 2^levelCount and clipped; a world narrower than that and a rectangle of 2^31 / 12 columns or more are refused
+//   2. one scratch allocation (counts, scan sums, {total, overLimit}, the caller's share), two events unless the caller has its own
+//   3. the caller's count launcher, cvxi::ExclusiveScan, ONE copy back, ONE synchronisation
+//   4. refused: a column the format cannot hold (the flag), 2^31 - 3 n elements or more
+//   5. the blob's allocation (n headers of 12 bytes, then the element pool), the caller's write launcher
+//   6. cvxi::EditFromDevice; the device time from the two events; everything released on every path.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -527,6 +536,94 @@ int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 	const hipError_t s = hipStreamSynchronize(ctx->stream);
 	if (rc == CVX_OK && (e != hipSuccess || s != hipSuccess)) { rc = Fail(ctx, CVX_ERR_HIP, "edit failed: %s", hipGetErrorString(e != hipSuccess ? e : s)); }
 	release();
+	return rc;
+}
+
+int RoundEditRectangle(cvx_context *ctx, int64_t x0, int64_t x1, int64_t z0, int64_t z1, int levelCount, const char *what, EditRectangle *out)
+{
+	const int dimX = ctx->hostWorld.dimX, dimZ = ctx->hostWorld.dimZ;
+	const int64_t align = ((int64_t)1 << levelCount) - 1;
+	x0 &= ~align;
+	z0 &= ~align;
+	x1 = std::min<int64_t>((x1 + align) & ~align, dimX);
+	z1 = std::min<int64_t>((z1 + align) & ~align, dimZ);
+	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
+		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dimX, dimZ, (long long)align + 1);
+	}
+	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
+	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "%s %d x %d columns", what, sizeX, sizeZ); }
+	*out = EditRectangle{ (int)x0, (int)z0, sizeX, sizeZ, sizeX * sizeZ };
+	return CVX_OK;
+}
+
+int ColumnEdit(cvx_context *ctx, const EditRectangle &R, int levelCount, const ColumnEditCall &call, ColumnEditLauncher launchCount, ColumnEditLauncher launchWrite,
+               float *outMs)
+{
+	struct Held { // what the pipeline allocates, released on every path
+		uint8_t *scratch = nullptr, *blob = nullptr;
+		hipEvent_t ev[2] = { nullptr, nullptr };
+		~Held()
+		{
+			if (scratch) { (void)hipFree(scratch); }
+			if (blob) { (void)hipFree(blob); }
+			for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
+		}
+	} held;
+	auto failHip = [&](hipError_t e) {
+		return call.failHip ? call.failHip(ctx, call.call, e) : Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call.call, hipGetErrorString(e));
+	};
+	const size_t n = (size_t)R.n, chunks = (n + ScanChunk() - 1) / ScanChunk();
+	size_t bytes = 0;
+	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	const size_t oExtra = carve(call.extraScratchBytes), oCounts = carve(n * 4), oTotals = carve(call.totals ? 0 : 2 * 8), oChunks = carve(chunks * 8);
+	struct { unsigned long long total, overLimit; } own = { 0, 0 };
+	// 2. the scratch, the events
+	hipError_t e = hipSuccess;
+	if (!call.done) {
+		e = hipEventCreate(&held.ev[0]);
+		if (e == hipSuccess) { e = hipEventCreate(&held.ev[1]); }
+	}
+	if (e == hipSuccess) { e = hipMalloc((void **)&held.scratch, bytes); }
+	if (e == hipSuccess && !call.done) { e = hipEventRecord(held.ev[0], ctx->stream); }
+	if (e == hipSuccess && !call.totals) { e = hipMemsetAsync(held.scratch + oTotals, 0, sizeof own, ctx->stream); }
+	if (e != hipSuccess) { return failHip(e); }
+	const ColumnEditTotals T = call.totals ? *call.totals : ColumnEditTotals{ held.scratch + oTotals, &own, sizeof own, 0, 8 };
+	ColumnEditJob J{ R, reinterpret_cast<uint32_t *>(held.scratch + oCounts), reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(T.from) + T.totalAt),
+	                 reinterpret_cast<unsigned int *>(static_cast<uint8_t *>(T.from) + T.overLimitAt), held.scratch + oExtra, nullptr, nullptr };
+	// 3. count, scan, one copy back, one synchronisation
+	e = launchCount(J);
+	if (e == hipSuccess) {
+		ExclusiveScan(ctx->stream, J.counts, R.n, reinterpret_cast<unsigned long long *>(held.scratch + oChunks), J.total);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) { e = hipMemcpyAsync(T.to, T.from, T.bytes, hipMemcpyDeviceToHost, ctx->stream); }
+	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
+	if (e != hipSuccess) { return failHip(e); }
+	// 4. what the blob's format cannot hold
+	unsigned long long total;
+	unsigned int overLimit;
+	std::memcpy(&total, static_cast<const uint8_t *>(T.to) + T.totalAt, sizeof total);
+	std::memcpy(&overLimit, static_cast<const uint8_t *>(T.to) + T.overLimitAt, sizeof overLimit);
+	if (overLimit) {
+		return Fail(ctx, CVX_ERR_CAPACITY, "%s would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767%s", call.overLimitSubject,
+		            call.overLimitNote);
+	}
+	if (total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) { return Fail(ctx, CVX_ERR_CAPACITY, "%s need %llu elements", call.elementsSubject, total); }
+	// 5. the sub-world blob
+	e = hipMalloc((void **)&held.blob, std::max<size_t>(n * 12 + (size_t)total * 4, 4));
+	if (e == hipSuccess) {
+		J.headers = reinterpret_cast<uint32_t *>(held.blob);
+		J.elements = reinterpret_cast<uint32_t *>(held.blob + n * 12);
+		e = launchWrite(J);
+	}
+	if (e == hipSuccess) { e = hipGetLastError(); }
+	if (e != hipSuccess) { return failHip(e); }
+	// 6. cvx_world_edit's machinery
+	const int rc = EditFromDevice(ctx, R.x0, R.z0, R.sizeX, R.sizeZ, held.blob, (int64_t)total, R.n, levelCount, call.done ? call.done : held.ev[1]);
+	if (rc == CVX_OK && !call.done && outMs) {
+		float ms = 0.f;
+		*outMs = hipEventElapsedTime(&ms, held.ev[0], held.ev[1]) == hipSuccess ? ms : 0.f;
+	}
 	return rc;
 }
 

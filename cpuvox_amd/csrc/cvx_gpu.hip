@@ -483,6 +483,21 @@ int Launch(cvx_context *ctx, int frameCount, int flags)
 
 int cvxi::SyncWorld(cvx_context *ctx) { return ::SyncWorld(ctx); }
 
+cvxb::CopyWorld cvxi::WorldOf(const cvx_context *ctx)
+{
+	const DevWorldLevel &L = ctx->hostWorld.level[0];
+	cvxb::CopyWorld W;
+	W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
+	W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
+	W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
+	W.rowShift = L.rowShift;
+	W.colorShift = L.colorShift;
+	W.dimX = ctx->hostWorld.dimX;
+	W.dimY = ctx->hostWorld.dimY;
+	W.dimZ = ctx->hostWorld.dimZ;
+	return W;
+}
+
 extern "C" {
 
 const char *cvx_version(void) { return "cpuvox_gpu 0.2 (gfx950)"; }

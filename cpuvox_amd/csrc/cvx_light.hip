@@ -1,8 +1,8 @@
 // cvx_light.hip -- libcpuvox_gpu.so, sky occlusion and sun shadows baked into the device-resident world (cvx_world_light).  See
 // include/cpuvox_gpu.h for the contract, cvx_light.h for the rules and DESIGN.md sections 3 and 4.
 //
-// The mechanics are cvx_world_brush's: count the elements of every column of the rounded rectangle, scan, write the sub-world blob in the
-// builder's encoding (cvxb::LightColumn: the colours verbatim), then -- new -- shade the blob's colours in place, then cvxi::EditFromDevice.
+// The mechanics are cvxi::ColumnEdit's (cvx_edit.hip): its count launcher counts the elements of every column of the rounded rectangle, its write
+// launcher writes the sub-world blob in the builder's encoding (cvxb::LightColumn: the colours verbatim) and then shades the blob's colours in place.
 // Nothing in the arena is written before that last step, and the blob has one colour per voxel, so runs that share colour slots are shaded once.
 //
 // The shade kernel (light_brick_kernel): a workgroup of 256 threads owns a tile of 16 x 16 columns of the clipped box and walks the y range its
@@ -51,18 +51,9 @@ __device__ __forceinline__ void WriteColumn(const LightArgs &A, int i, int cx, i
 	uint32_t *e = A.elements + off;
 	uint32_t *h = A.headers + 3 * (size_t)i;
 	const cvxb::BrushResult r = cvxb::LightColumn(A.W, cx, cz, nullptr, nullptr, cvxb::LightKeep{});
-	if (r.runCount == 0u) {
-		h[0] = 0u;
-		h[1] = 0u;
-		h[2] = 0u;
-		return;
-	}
+	if (r.runCount == 0u) { cvxb::BlobEmitEmpty(h); return; }
 	cvxb::LightColumn(A.W, cx, cz, e + 1, e + r.runCount + 2u, recolour);
-	e[0] = 0u;
-	e[r.runCount + 1u] = 0u;
-	h[0] = off;
-	h[1] = r.runCount | (r.worldMin << 16);
-	h[2] = r.worldMax;
+	cvxb::BlobEmitHeader(h, e, off, r);
 }
 
 __global__ __launch_bounds__(256) void light_count_kernel(LightArgs A)
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(256) void light_count_kernel(LightArgs A)
 	if (i >= A.n) { return; }
 	const cvxb::BrushResult r = cvxb::LightColumn(A.W, A.x0 + i / A.sizeZ, A.z0 + i % A.sizeZ, nullptr, nullptr, cvxb::LightKeep{});
 	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
-	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.counts[i] = cvxb::BlobElements(r);
 }
 
 __global__ __launch_bounds__(256) void light_write_kernel(LightArgs A)
@@ -329,112 +320,54 @@ static int Light(cvx_context *ctx, const cvx_light_params *params, const cvx_lam
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	cvxb::PiecesBox B;
 	if (!cvxb::PiecesClipBox(params->boxMin, params->boxMax, dimX, dimY, dimZ, &B)) { return CVX_OK; }
-	// the rectangle: the box's footprint rounded out to 2^levelCount, clipped to the world
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
-	const int64_t x0 = B.x0 & ~align, z0 = B.z0 & ~align;
-	const int64_t x1 = std::min<int64_t>((B.x1 + align) & ~align, dimX), z1 = std::min<int64_t>((B.z1 + align) & ~align, dimZ);
-	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
-		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dimX, dimZ, (long long)align + 1);
-	}
-	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-	const int n = sizeX * sizeZ;
-	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "lighting %d x %d columns", sizeX, sizeZ); }
+	cvxi::EditRectangle R;
+	int rc = cvxi::RoundEditRectangle(ctx, B.x0, B.x1, B.z0, B.z1, levelCount, "lighting", &R);
+	if (rc != CVX_OK) { return rc; }
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	int rc = cvxi::SyncWorld(ctx);
+	rc = cvxi::SyncWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	uint8_t *scratch = nullptr, *dSrc = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		if (dSrc) { (void)hipFree(dSrc); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
-	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
-	const size_t oCounts = carve((size_t)n * 4), oTotals = carve(2 * 8), oChunks = carve(chunks * 8), oLamps = carve((size_t)lampCount * sizeof(cvx_lamp));
-	struct { unsigned long long total, overLimit; } host = { 0, 0 };
+	const size_t lampBytes = (size_t)lampCount * sizeof(cvx_lamp);
 	cvxlight::LightArgs A{};
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
-	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, 2 * 8, ctx->stream); }
-	if (e == hipSuccess) {
-		const DevWorldLevel &L = ctx->hostWorld.level[0];
-		A.W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-		A.W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-		A.W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-		A.W.rowShift = L.rowShift;
-		A.W.colorShift = L.colorShift;
-		A.W.dimX = dimX;
-		A.W.dimY = dimY;
-		A.W.dimZ = dimZ;
-		A.B = B;
-		A.P = *params;
-		A.x0 = (int)x0;
-		A.z0 = (int)z0;
-		A.sizeZ = sizeZ;
-		A.n = n;
-		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
-		unsigned long long *totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
-		A.overLimit = reinterpret_cast<unsigned int *>(totals + 1);
-		A.lamps = reinterpret_cast<const cvx_lamp *>(scratch + oLamps);
-		A.lampCount = lampCount;
-		if (lampCount > 0) { e = hipMemcpyAsync(scratch + oLamps, lamps, (size_t)lampCount * sizeof(cvx_lamp), hipMemcpyHostToDevice, ctx->stream); }
-		// count, scan, one copy back
-		hipLaunchKernelGGL(cvxlight::light_count_kernel, dim3(Grid((size_t)n)), dim3(256), 0, ctx->stream, A);
-		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), totals);
-		if (e == hipSuccess) { e = hipGetLastError(); }
-		if (e == hipSuccess) { e = hipMemcpyAsync(&host, totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "light failed: %s", hipGetErrorString(e));
-	}
-	if (host.overLimit) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "a re-emitted column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
-	}
-	if (host.total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the lit columns need %llu elements", host.total);
-	}
-	// the sub-world blob, then its colours shaded in place
-	const size_t blobBytes = (size_t)n * 12 + (size_t)host.total * 4;
-	e = hipMalloc((void **)&dSrc, std::max<size_t>(blobBytes, 4));
-	if (e == hipSuccess) {
-		A.headers = reinterpret_cast<uint32_t *>(dSrc);
-		A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)n * 12);
-		hipLaunchKernelGGL(cvxlight::light_write_kernel, dim3(Grid((size_t)n)), dim3(256), 0, ctx->stream, A);
+	A.W = cvxi::WorldOf(ctx);
+	A.B = B;
+	A.P = *params;
+	A.x0 = R.x0;
+	A.z0 = R.z0;
+	A.sizeZ = R.sizeZ;
+	A.n = R.n;
+	A.lampCount = lampCount;
+	cvxi::ColumnEditCall call{ "light", nullptr, "a re-emitted column", "the lit columns" };
+	call.extraScratchBytes = lampBytes;
+	return cvxi::ColumnEdit(
+		ctx, R, levelCount, call,
+		[&](const cvxi::ColumnEditJob &J) {
+			A.counts = J.counts;
+			A.overLimit = J.overLimit;
+			A.lamps = reinterpret_cast<const cvx_lamp *>(J.extra);
+			const hipError_t e = lampCount > 0 ? hipMemcpyAsync(J.extra, lamps, lampBytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+			if (e == hipSuccess) { hipLaunchKernelGGL(cvxlight::light_count_kernel, dim3(Grid((size_t)R.n)), dim3(256), 0, ctx->stream, A); }
+			return e;
+		},
+		[&](const cvxi::ColumnEditJob &J) { // the sub-world blob, then its colours shaded in place
+			A.headers = J.headers;
+			A.elements = J.elements;
+			hipLaunchKernelGGL(cvxlight::light_write_kernel, dim3(Grid((size_t)R.n)), dim3(256), 0, ctx->stream, A);
 #ifndef CVX_LIGHT_RECORDS
-		const int tilesX = (B.SizeX() + cvxlight::kTile - 1) / cvxlight::kTile;
-		A.tilesZ = (B.SizeZ() + cvxlight::kTile - 1) / cvxlight::kTile;
-		A.brickSide = cvxlight::kTile + 2 * params->skyRange;
-		A.brickStride = A.brickSide | 1;
-		const size_t lds = (size_t)A.brickSide * A.brickStride * 8;
-		if (lampCount > 0) {
-			hipLaunchKernelGGL(cvxlight::light_brick_kernel<true>, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
-		} else {
-			hipLaunchKernelGGL(cvxlight::light_brick_kernel<false>, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
-		}
+			const int tilesX = (B.SizeX() + cvxlight::kTile - 1) / cvxlight::kTile;
+			A.tilesZ = (B.SizeZ() + cvxlight::kTile - 1) / cvxlight::kTile;
+			A.brickSide = cvxlight::kTile + 2 * params->skyRange;
+			A.brickStride = A.brickSide | 1;
+			const size_t lds = (size_t)A.brickSide * A.brickStride * 8;
+			if (lampCount > 0) {
+				hipLaunchKernelGGL(cvxlight::light_brick_kernel<true>, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
+			} else {
+				hipLaunchKernelGGL(cvxlight::light_brick_kernel<false>, dim3((unsigned)(tilesX * A.tilesZ)), dim3(cvxlight::kThreads), lds, ctx->stream, A);
+			}
 #endif
-		e = hipGetLastError();
-	}
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "light failed: %s", hipGetErrorString(e));
-	}
-	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.total, n, levelCount, ev[1]);
-	if (rc == CVX_OK && outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
-	return rc;
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 extern "C" int cvx_world_light(cvx_context *ctx, const cvx_light_params *params, int levelCount, float *outDeviceMs)

@@ -62,28 +62,12 @@ __global__ __launch_bounds__(kThreads) void move_kernel(cvxb::CopyWorld W, int r
 
 namespace {
 
-cvxb::CopyWorld MoveWorldOf(const cvx_context *ctx)
-{
-	const DevWorld &D = ctx->hostWorld;
-	const DevWorldLevel &L = D.level[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-	W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-	W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-	W.rowShift = L.rowShift;
-	W.colorShift = L.colorShift;
-	W.dimX = D.dimX;
-	W.dimY = D.dimY;
-	W.dimZ = D.dimZ;
-	return W;
-}
-
 template <int G>
 void Launch(hipStream_t stream, const cvx_context *ctx, int bodyCount, const cvx_move_body *bodies, cvx_move_result *results)
 {
 	const size_t threads = (size_t)bodyCount * G;
 	const unsigned grid = (unsigned)((threads + cvxmove::kThreads - 1) / cvxmove::kThreads);
-	hipLaunchKernelGGL(cvxmove::move_kernel<G>, dim3(grid), dim3(cvxmove::kThreads), 0, stream, MoveWorldOf(ctx), ctx->worldRepeat, bodyCount, bodies, results);
+	hipLaunchKernelGGL(cvxmove::move_kernel<G>, dim3(grid), dim3(cvxmove::kThreads), 0, stream, cvxi::WorldOf(ctx), ctx->worldRepeat, bodyCount, bodies, results);
 }
 
 } // namespace

@@ -495,15 +495,7 @@ int cvx_world_nav_build(cvx_context *ctx, const cvx_nav_params *params, const in
 	if (e == hipSuccess) { e = hipEventRecord(start, ctx->stream); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(F->columnMem, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) {
-		const DevWorldLevel &L = ctx->hostWorld.level[0];
-		A.W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-		A.W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-		A.W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-		A.W.rowShift = L.rowShift;
-		A.W.colorShift = L.colorShift;
-		A.W.dimX = dim[0];
-		A.W.dimY = dim[1];
-		A.W.dimZ = dim[2];
+		A.W = cvxi::WorldOf(ctx);
 		A.T.totals = reinterpret_cast<Totals *>(F->columnMem);
 		A.T.offsets = reinterpret_cast<uint32_t *>(F->columnMem + offsetsAt);
 		hipLaunchKernelGGL(nav_count_kernel, dim3(Grid((size_t)n + 1)), dim3(kThreads), 0, ctx->stream, A);

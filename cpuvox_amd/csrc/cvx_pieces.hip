@@ -13,13 +13,14 @@
 //   4. stats  (a thread per node, reduced per wave where a wave has one root): voxels, bounding box and anchor bits of every root; the largest
 //             piece by two reductions; floating roots flagged, totalled and ranked by a scan in index order = the order of the contract
 //   5. list   the first pieceCapacity floating pieces, copied to the host behind the totals
-//   6. REMOVE count / scan / write of the sub-world blob of the floating pieces' rectangle (cvxb::PiecesRemoveColumn), then
-//             cvxi::EditFromDevice, exactly as cvx_copy.hip.  Nothing in the arena is written before that.
+//   6. REMOVE cvxi::ColumnEdit (cvx_edit.hip) over the floating pieces' rectangle: count and write of the sub-world blob are
+//             cvxb::PiecesRemoveColumn.  Nothing in the arena is written before its last step.
 // Steps 1 .. 5 are cvxpieces::Analyse (cvx_pieces_nodes.h), which leaves the node tables on the device: cvx_world_settle (cvx_settle.hip) goes on from them too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(256) void pieces_remove_count_kernel(PiecesArgs A)
 	const uint32_t *floating = ColumnNodes(A, A.rank, cx, cz, &nodes);
 	const cvxb::BrushResult r = cvxb::PiecesRemoveColumn(A.W, cx, cz, A.B.y0, A.B.y1, floating, nodes, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(&A.totals->overLimit, 1u); }
-	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.counts[i] = cvxb::BlobElements(r);
 }
 
 __global__ __launch_bounds__(256) void pieces_remove_write_kernel(PiecesArgs A)
@@ -246,18 +247,9 @@ __global__ __launch_bounds__(256) void pieces_remove_write_kernel(PiecesArgs A)
 	uint32_t *e = A.elements + off;
 	const cvxb::BrushResult r = cvxb::PiecesRemoveColumn(A.W, cx, cz, A.B.y0, A.B.y1, floating, nodes, nullptr, nullptr);
 	uint32_t *h = A.headers + 3 * (size_t)i;
-	if (r.runCount == 0u) {
-		h[0] = 0u;
-		h[1] = 0u;
-		h[2] = 0u;
-		return;
-	}
+	if (r.runCount == 0u) { cvxb::BlobEmitEmpty(h); return; }
 	cvxb::PiecesRemoveColumn(A.W, cx, cz, A.B.y0, A.B.y1, floating, nodes, e + 1, e + r.runCount + 2u);
-	e[0] = 0u;
-	e[r.runCount + 1u] = 0u;
-	h[0] = off;
-	h[1] = r.runCount | (r.worldMin << 16);
-	h[2] = r.worldMax;
+	cvxb::BlobEmitHeader(h, e, off, r);
 }
 
 constexpr size_t kHead = 256; // pieces that come to the host with the totals, in one copy
@@ -325,15 +317,7 @@ int Analyse(cvx_context *ctx, const char *call, const int32_t boxMin[3], const i
 	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(columnScratch + oTotals, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) {
-		const DevWorldLevel &L = ctx->hostWorld.level[0];
-		A.W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-		A.W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-		A.W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-		A.W.rowShift = L.rowShift;
-		A.W.colorShift = L.colorShift;
-		A.W.dimX = dim[0];
-		A.W.dimY = dim[1];
-		A.W.dimZ = dim[2];
+		A.W = cvxi::WorldOf(ctx);
 		A.n = n;
 		A.anchors = anchors;
 		A.totals = reinterpret_cast<Totals *>(columnScratch + oTotals);
@@ -453,84 +437,48 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 	if (rc != CVX_OK) { return rc; }
 	PiecesArgs &A = R.A;
 	Totals &host = R.host;
-	const int *dim = R.dim;
 	const size_t nodes = R.nodes, floating = (size_t)host.summary.floatingPieces;
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
 	float ms = R.ms;
-	uint8_t *removeScratch = nullptr, *dSrc = nullptr;
-	auto release = [&]() {
-		for (uint8_t *p : { removeScratch, dSrc }) { if (p) { (void)hipFree(p); } }
-		R.Release();
-	};
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
-	auto chunksOf = [](size_t count) { return (count + cvxi::ScanChunk() - 1) / cvxi::ScanChunk(); };
+	struct Held { // (Analyse left its tables to this call)
+		Analysis &R;
+		~Held() { R.Release(); }
+	} held{ R };
 
-	// 6. REMOVE: the floating pieces' rectangle without them, through cvx_world_edit's machinery
+	// 6. REMOVE: the floating pieces' rectangle without them, through cvx_world_edit's machinery (cvxi::ColumnEdit)
 	if (op == CVX_PIECES_REMOVE && floating) {
-		const int64_t x0 = host.x0 & ~align, z0 = host.z0 & ~align;
-		const int64_t x1 = std::min<int64_t>((host.x1 + align) & ~align, dim[0]), z1 = std::min<int64_t>((host.z1 + align) & ~align, dim[2]);
-		const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-		const int rn = sizeX * sizeZ;
-		if (((x1 - x0) & align) || ((z1 - z0) & align)) {
-			release();
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dim[0], dim[2], (long long)align + 1);
-		}
-		if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "a removal over %d x %d columns", sizeX, sizeZ);
-		}
-		const size_t oCounts = carve((size_t)rn * 4), oCountChunks = carve(chunksOf((size_t)rn) * 8);
-		hipError_t e = hipMalloc((void **)&removeScratch, bytes);
-		if (e == hipSuccess) {
-			A.rx0 = (int)x0;
-			A.rz0 = (int)z0;
-			A.rSizeZ = sizeZ;
-			A.rn = rn;
-			A.counts = reinterpret_cast<uint32_t *>(removeScratch + oCounts);
-			const dim3 block(kThreads);
-			hipLaunchKernelGGL(pieces_mark_kernel, dim3(Grid(nodes)), block, 0, ctx->stream, A);
-			hipLaunchKernelGGL(pieces_remove_count_kernel, dim3(Grid((size_t)rn)), block, 0, ctx->stream, A);
-			cvxi::ExclusiveScan(ctx->stream, A.counts, rn, reinterpret_cast<unsigned long long *>(removeScratch + oCountChunks), &A.totals->elements);
-			e = hipGetLastError();
-			if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-			if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-		}
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
-		if (host.overLimit) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "a column without its floating runs would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
-		}
-		if (host.elements >= ((unsigned long long)1 << 31) - (unsigned long long)rn * 3) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "the columns of the removal need %llu elements", host.elements);
-		}
-		e = hipMalloc((void **)&dSrc, std::max<size_t>((size_t)rn * 12 + (size_t)host.elements * 4, 4));
-		if (e == hipSuccess) {
-			A.headers = reinterpret_cast<uint32_t *>(dSrc);
-			A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)rn * 12);
-			hipLaunchKernelGGL(pieces_remove_write_kernel, dim3(Grid((size_t)rn)), dim3(kThreads), 0, ctx->stream, A);
-			e = hipGetLastError();
-		}
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
-		rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)host.elements, rn, levelCount, R.ev[1]);
-		if (rc != CVX_OK) {
-			release();
-			return rc;
-		}
+		cvxi::EditRectangle E;
+		rc = cvxi::RoundEditRectangle(ctx, host.x0, host.x1, host.z0, host.z1, levelCount, "a removal over", &E);
+		if (rc != CVX_OK) { return rc; }
+		A.rx0 = E.x0;
+		A.rz0 = E.z0;
+		A.rSizeZ = E.sizeZ;
+		A.rn = E.n;
+		const cvxi::ColumnEditTotals totals{ A.totals, &host, sizeof host, offsetof(Totals, elements), offsetof(Totals, overLimit) };
+		cvxi::ColumnEditCall edit{ call, FailHip, "a column without its floating runs", "the columns of the removal" };
+		edit.totals = &totals;
+		edit.done = R.ev[1];
+		rc = cvxi::ColumnEdit(
+			ctx, E, levelCount, edit,
+			[&](const cvxi::ColumnEditJob &J) {
+				A.counts = J.counts;
+				hipLaunchKernelGGL(pieces_mark_kernel, dim3(Grid(nodes)), dim3(kThreads), 0, ctx->stream, A);
+				hipLaunchKernelGGL(pieces_remove_count_kernel, dim3(Grid((size_t)E.n)), dim3(kThreads), 0, ctx->stream, A);
+				return hipSuccess;
+			},
+			[&](const cvxi::ColumnEditJob &J) {
+				A.headers = J.headers;
+				A.elements = J.elements;
+				hipLaunchKernelGGL(pieces_remove_write_kernel, dim3(Grid((size_t)E.n)), dim3(kThreads), 0, ctx->stream, A);
+				return hipSuccess;
+			},
+			nullptr);
+		if (rc != CVX_OK) { return rc; }
 		(void)hipEventElapsedTime(&ms, R.ev[0], R.ev[1]);
 	}
 	// (nothing is handed out before the call can no longer fail)
 	if (!R.list.empty()) { std::memcpy(pieces, R.list.data(), R.list.size() * sizeof(cvx_piece)); }
 	if (summary) { *summary = host.summary; }
 	if (outDeviceMs) { *outDeviceMs = ms; }
-	release();
 	return CVX_OK;
 }
 

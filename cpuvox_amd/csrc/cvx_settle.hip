@@ -13,12 +13,13 @@
 //             larger box runs kSweepsPerLaunch sweeps per launch and the host reads the changed flag between launches.
 //   4. finish (a thread per node): the node's shift = its piece's drop; per floating root the drop in list order, and the totals and the XZ box of
 //             the pieces that fall
-//   5. count / scan / write of the sub-world blob of that box's rectangle (cvxb::SettleColumn), then cvxi::EditFromDevice, exactly as
-//             CVX_PIECES_REMOVE.  Nothing in the arena is written before that.
+//   5. cvxi::ColumnEdit (cvx_edit.hip) over that box's rectangle: count and write of the sub-world blob are cvxb::SettleColumn.  Nothing in
+//             the arena is written before its last step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(256) void settle_count_kernel(SettleArgs A)
 	const uint32_t *shift = cvxpieces::ColumnNodes(P, A.shift, cx, cz, &nodes);
 	const cvxb::BrushResult r = cvxb::SettleColumn(P.W, cx, cz, P.B.y0, P.B.y1, shift, nodes, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(&P.totals->overLimit, 1u); }
-	P.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	P.counts[i] = cvxb::BlobElements(r);
 }
 
 __global__ __launch_bounds__(256) void settle_write_kernel(SettleArgs A)
@@ -210,18 +211,9 @@ __global__ __launch_bounds__(256) void settle_write_kernel(SettleArgs A)
 	uint32_t *e = P.elements + off;
 	const cvxb::BrushResult r = cvxb::SettleColumn(P.W, cx, cz, P.B.y0, P.B.y1, shift, nodes, nullptr, nullptr);
 	uint32_t *h = P.headers + 3 * (size_t)i;
-	if (r.runCount == 0u) {
-		h[0] = 0u;
-		h[1] = 0u;
-		h[2] = 0u;
-		return;
-	}
+	if (r.runCount == 0u) { cvxb::BlobEmitEmpty(h); return; }
 	cvxb::SettleColumn(P.W, cx, cz, P.B.y0, P.B.y1, shift, nodes, e + 1, e + r.runCount + 2u);
-	e[0] = 0u;
-	e[r.runCount + 1u] = 0u;
-	h[0] = off;
-	h[1] = r.runCount | (r.worldMin << 16);
-	h[2] = r.worldMax;
+	cvxb::BlobEmitHeader(h, e, off, r);
 }
 
 #if defined(CVX_EXPERIMENTS) || defined(CVX_PROFILE_SECTIONS) /* include/cpuvox_gpu_diag.h: cvx_debug_settle */
@@ -248,24 +240,21 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 	cvxpieces::Analysis R;
 	int rc = cvxpieces::Analyse(ctx, call, boxMin, boxMax, anchors, maxDrop < 0 ? bad : nullptr, levelCount, pieces, pieceCapacity, &R);
 	if (rc != CVX_OK) { return rc; }
-	const int *dim = R.dim;
 	const size_t nodes = R.nodes, floating = (size_t)R.host.summary.floatingPieces, wanted = R.list.size();
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
 	cvx_settle_summary out{};
 	out.floatingPieces = R.host.summary.floatingPieces;
 	out.floatingVoxels = R.host.summary.floatingVoxels;
 	float ms = R.ms;
 	std::vector<int32_t> dropList(wanted, 0);
-	uint8_t *settleScratch = nullptr, *editScratch = nullptr, *dSrc = nullptr;
+	uint8_t *settleScratch = nullptr;
 	hipEvent_t relaxed = nullptr;
 	auto release = [&]() {
-		for (uint8_t *p : { settleScratch, editScratch, dSrc }) { if (p) { (void)hipFree(p); } }
+		if (settleScratch) { (void)hipFree(settleScratch); }
 		if (relaxed) { (void)hipEventDestroy(relaxed); }
 		R.Release();
 	};
 	size_t bytes = 0;
 	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
-	auto chunksOf = [](size_t count) { return (count + cvxi::ScanChunk() - 1) / cvxi::ScanChunk(); };
 	unsigned sweeps = 0, launches = 0;
 	bool single = nodes <= kSingleNodes;
 	float relaxMs = 0.f, editMs = 0.f;
@@ -341,61 +330,38 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		out.largestDrop = host.largestDrop;
 	}
 
-	// 5. the rectangle of the pieces that fall, with them where they land, through cvx_world_edit's machinery
+	// 5. the rectangle of the pieces that fall, with them where they land, through cvx_world_edit's machinery (cvxi::ColumnEdit)
 	if (out.fallenPieces) {
 		PiecesArgs &P = A.P;
-		const int64_t x0 = host.x0 & ~align, z0 = host.z0 & ~align;
-		const int64_t x1 = std::min<int64_t>((host.x1 + align) & ~align, dim[0]), z1 = std::min<int64_t>((host.z1 + align) & ~align, dim[2]);
-		const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-		const int rn = sizeX * sizeZ;
-		if (((x1 - x0) & align) || ((z1 - z0) & align)) {
+		cvxi::EditRectangle E;
+		rc = cvxi::RoundEditRectangle(ctx, host.x0, host.x1, host.z0, host.z1, levelCount, "a settle over", &E);
+		if (rc != CVX_OK) {
 			release();
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dim[0], dim[2], (long long)align + 1);
+			return rc;
 		}
-		if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "a settle over %d x %d columns", sizeX, sizeZ);
-		}
-		bytes = 0;
-		const size_t oCounts = carve((size_t)rn * 4), oCountChunks = carve(chunksOf((size_t)rn) * 8);
-		cvxpieces::Totals totals{};
-		hipError_t e = hipMalloc((void **)&editScratch, bytes);
-		if (e == hipSuccess) {
-			P.rx0 = (int)x0;
-			P.rz0 = (int)z0;
-			P.rSizeZ = sizeZ;
-			P.rn = rn;
-			P.counts = reinterpret_cast<uint32_t *>(editScratch + oCounts);
-			hipLaunchKernelGGL(settle_count_kernel, dim3(Grid((size_t)rn)), dim3(kThreads), 0, ctx->stream, A);
-			cvxi::ExclusiveScan(ctx->stream, P.counts, rn, reinterpret_cast<unsigned long long *>(editScratch + oCountChunks), &P.totals->elements);
-			e = hipGetLastError();
-			if (e == hipSuccess) { e = hipMemcpyAsync(&totals, P.totals, sizeof totals, hipMemcpyDeviceToHost, ctx->stream); }
-			if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-		}
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
-		if (totals.overLimit) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "a column with its pieces settled would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
-		}
-		if (totals.elements >= ((unsigned long long)1 << 31) - (unsigned long long)rn * 3) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "the columns of the settle need %llu elements", totals.elements);
-		}
-		e = hipMalloc((void **)&dSrc, std::max<size_t>((size_t)rn * 12 + (size_t)totals.elements * 4, 4));
-		if (e == hipSuccess) {
-			P.headers = reinterpret_cast<uint32_t *>(dSrc);
-			P.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)rn * 12);
-			hipLaunchKernelGGL(settle_write_kernel, dim3(Grid((size_t)rn)), dim3(kThreads), 0, ctx->stream, A);
-			e = hipGetLastError();
-		}
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
-		rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)totals.elements, rn, levelCount, R.ev[1]);
+		P.rx0 = E.x0;
+		P.rz0 = E.z0;
+		P.rSizeZ = E.sizeZ;
+		P.rn = E.n;
+		cvxpieces::Totals back{};
+		const cvxi::ColumnEditTotals totals{ P.totals, &back, sizeof back, offsetof(cvxpieces::Totals, elements), offsetof(cvxpieces::Totals, overLimit) };
+		cvxi::ColumnEditCall edit{ call, FailHip, "a column with its pieces settled", "the columns of the settle" };
+		edit.totals = &totals;
+		edit.done = R.ev[1];
+		rc = cvxi::ColumnEdit(
+			ctx, E, levelCount, edit,
+			[&](const cvxi::ColumnEditJob &J) {
+				P.counts = J.counts;
+				hipLaunchKernelGGL(settle_count_kernel, dim3(Grid((size_t)E.n)), dim3(kThreads), 0, ctx->stream, A);
+				return hipSuccess;
+			},
+			[&](const cvxi::ColumnEditJob &J) {
+				P.headers = J.headers;
+				P.elements = J.elements;
+				hipLaunchKernelGGL(settle_write_kernel, dim3(Grid((size_t)E.n)), dim3(kThreads), 0, ctx->stream, A);
+				return hipSuccess;
+			},
+			nullptr);
 		if (rc != CVX_OK) {
 			release();
 			return rc;

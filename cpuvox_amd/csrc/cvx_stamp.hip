@@ -12,8 +12,8 @@
 //   5. sort     LSD radix sort of the keys with their colours, 4 bits a pass (stable: the ranks come from wave ballots in item order)
 //   6. merge    the first of every run of equal keys averages them (cvxs::MergeStamped) into the stamped-voxel list, sorted by column and
 //               top-down within a column; the XZ box of the voxels comes back to the host with their number
-//   7. the rectangle's columns as cvx_world_brush does them (count, scan, write) with cvxs::StampColumn; a column finds its stamped voxels
-//      by binary search in the list; the sub-world blob goes to cvxi::EditFromDevice.
+//   7. the rectangle's columns through cvxi::ColumnEdit (cvx_edit.hip), count and write with cvxs::StampColumn; a column finds its stamped
+//      voxels by binary search in the list.
 // Nothing in the arena is written before step 7's hand-over, so a rejected stamp leaves the world as it was.
 #include <hip/hip_runtime.h>
 
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void column_count_kernel(ColumnArgs A)
 	if (i >= A.n) { return; }
 	const cvxb::BrushResult r = Stamp(A, i, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(A.overLimit, 1u); }
-	A.counts[i] = r.runCount ? r.runCount + 2u + r.colours : 0u;
+	A.counts[i] = cvxb::BlobElements(r);
 }
 
 __global__ __launch_bounds__(256) void column_write_kernel(ColumnArgs A)
@@ -317,18 +317,9 @@ __global__ __launch_bounds__(256) void column_write_kernel(ColumnArgs A)
 	// (the colours go behind the runs' second guard, a place known once the runs are counted: the walk runs twice, the second time writing)
 	const cvxb::BrushResult r = Stamp(A, i, nullptr, nullptr);
 	uint32_t *h = A.headers + 3 * (size_t)i;
-	if (r.runCount == 0u) {
-		h[0] = 0u;
-		h[1] = 0u;
-		h[2] = 0u;
-		return;
-	}
+	if (r.runCount == 0u) { cvxb::BlobEmitEmpty(h); return; }
 	Stamp(A, i, e + 1, e + r.runCount + 2u);
-	e[0] = 0u;
-	e[r.runCount + 1u] = 0u;
-	h[0] = off;
-	h[1] = r.runCount | (r.worldMin << 16);
-	h[2] = r.worldMax;
+	cvxb::BlobEmitHeader(h, e, off, r);
 }
 
 } // namespace cvxstamp
@@ -362,6 +353,16 @@ struct Scratch {
 		return e;
 	}
 };
+
+// (the pipeline's allocations report as the stamp's own do)
+int FailStampHip(cvx_context *ctx, const char *, hipError_t e)
+{
+	if (e == hipErrorOutOfMemory) {
+		(void)hipGetLastError();
+		return Fail(ctx, CVX_ERR_CAPACITY, "out of device memory for the stamp");
+	}
+	return Fail(ctx, CVX_ERR_HIP, "stamp failed: %s", hipGetErrorString(e));
+}
 
 } // namespace
 
@@ -551,18 +552,12 @@ int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int 
 	std::memcpy(box, &totals[6], sizeof box);
 
 	// 7. the rectangle: the voxels' XZ box rounded out to 2^levelCount, clipped
-	int64_t x0 = box[0], z0 = box[1], x1 = (int64_t)-box[2] + 1, z1 = (int64_t)-box[3] + 1;
-	const int64_t align = ((int64_t)1 << levelCount) - 1;
-	x0 &= ~align;
-	z0 &= ~align;
-	x1 = std::min<int64_t>((x1 + align) & ~align, dimX);
-	z1 = std::min<int64_t>((z1 + align) & ~align, dimZ);
-	if (((x1 - x0) & align) || ((z1 - z0) & align)) {
-		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the world (%d x %d columns) is narrower than 2^levelCount = %lld", dimX, dimZ, (long long)align + 1);
-	}
-	const int sizeX = (int)(x1 - x0), sizeZ = (int)(z1 - z0);
-	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "a stamp over %d x %d columns", sizeX, sizeZ); }
-	const int cols = sizeX * sizeZ;
+	cvxi::EditRectangle R;
+	rc = cvxi::RoundEditRectangle(ctx, box[0], (int64_t)-box[2] + 1, box[1], (int64_t)-box[3] + 1, levelCount, "a stamp over", &R);
+	if (rc != CVX_OK) { return rc; }
+#undef CVX_ST_HIP
+#undef CVX_ST_ALLOC
+#undef CVX_ST_CHUNKS
 	const DevWorldLevel &L = ctx->hostWorld.level[0];
 	cvxstamp::ColumnArgs A{};
 	A.arena = ctx->arena;
@@ -573,39 +568,35 @@ int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int 
 	A.colorShift = L.colorShift;
 	A.dimY = dimY;
 	A.dimZ = dimZ;
-	A.x0 = (int)x0;
-	A.z0 = (int)z0;
-	A.sizeZ = sizeZ;
-	A.n = cols;
+	A.x0 = R.x0;
+	A.z0 = R.z0;
+	A.sizeZ = R.sizeZ;
+	A.n = R.n;
 	A.op = op;
 	A.column = dColumn;
 	A.y = dY;
 	A.argb = dArgb;
 	A.voxels = voxels;
-	A.overLimit = reinterpret_cast<unsigned int *>(dTotals + 5);
-	CVX_ST_ALLOC(A.counts, (size_t)cols);
-	CVX_ST_CHUNKS((size_t)cols);
-	hipLaunchKernelGGL(cvxstamp::column_count_kernel, dim3(Grid((size_t)cols)), dim3(kThreads), 0, stream, A);
-	cvxi::ExclusiveScan(stream, A.counts, cols, dChunks, dTotals + 4);
-	CVX_ST_HIP(hipGetLastError());
-	CVX_ST_HIP(hipMemcpyAsync(totals, dTotals, sizeof totals, hipMemcpyDeviceToHost, stream));
-	CVX_ST_HIP(hipStreamSynchronize(stream));
-	if (totals[5]) {
-		return Fail(ctx, CVX_ERR_CAPACITY, "a stamped column would need more than 65535 runs, a run longer than 32767 voxels or a colour index above 32767");
-	}
-	const unsigned long long elements = totals[4];
-	if (elements >= ((unsigned long long)1 << 31) - (unsigned long long)cols * 3) { return Fail(ctx, CVX_ERR_CAPACITY, "the stamped columns need %llu elements", elements); }
-	uint8_t *dSrc = nullptr;
-	CVX_ST_ALLOC(dSrc, (size_t)cols * 12 + (size_t)elements * 4);
-	A.headers = reinterpret_cast<uint32_t *>(dSrc);
-	A.elements = reinterpret_cast<uint32_t *>(dSrc + (size_t)cols * 12);
-	hipLaunchKernelGGL(cvxstamp::column_write_kernel, dim3(Grid((size_t)cols)), dim3(kThreads), 0, stream, A);
-	CVX_ST_HIP(hipGetLastError());
-#undef CVX_ST_HIP
-#undef CVX_ST_ALLOC
-#undef CVX_ST_CHUNKS
-	// cvx_world_edit's machinery
-	rc = cvxi::EditFromDevice(ctx, (int)x0, (int)z0, sizeX, sizeZ, dSrc, (int64_t)elements, cols, levelCount, ev[1]);
+	// ... and its columns through cvx_world_edit's machinery (cvxi::ColumnEdit): the elements and the flag are dTotals[4] and [5]
+	const cvxi::ColumnEditTotals back{ dTotals, totals, sizeof totals, 4 * sizeof(unsigned long long), 5 * sizeof(unsigned long long) };
+	cvxi::ColumnEditCall edit{ "stamp", FailStampHip, "a stamped column", "the stamped columns" };
+	edit.totals = &back;
+	edit.done = ev[1];
+	rc = cvxi::ColumnEdit(
+		ctx, R, levelCount, edit,
+		[&](const cvxi::ColumnEditJob &J) {
+			A.counts = J.counts;
+			A.overLimit = J.overLimit;
+			hipLaunchKernelGGL(cvxstamp::column_count_kernel, dim3(Grid((size_t)R.n)), dim3(kThreads), 0, stream, A);
+			return hipSuccess;
+		},
+		[&](const cvxi::ColumnEditJob &J) {
+			A.headers = J.headers;
+			A.elements = J.elements;
+			hipLaunchKernelGGL(cvxstamp::column_write_kernel, dim3(Grid((size_t)R.n)), dim3(kThreads), 0, stream, A);
+			return hipSuccess;
+		},
+		nullptr);
 	if (rc == CVX_OK && outDeviceMs) {
 		float ms = 0.f;
 		*outDeviceMs = hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess ? ms : 0.f;

@@ -146,15 +146,7 @@ static int Surface(cvx_context *ctx, const char *call, const int32_t boxMin[3], 
 	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
 	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, sizeof(Totals), ctx->stream); }
 	if (e == hipSuccess) {
-		const DevWorldLevel &L = ctx->hostWorld.level[0];
-		A.W.records = reinterpret_cast<const uint32_t *>(ctx->arena + L.recordsOff);
-		A.W.runs = reinterpret_cast<const uint32_t *>(ctx->arena + L.runsOff);
-		A.W.colourSlots = reinterpret_cast<const uint32_t *>(ctx->arena + L.elementsOff);
-		A.W.rowShift = L.rowShift;
-		A.W.colorShift = L.colorShift;
-		A.W.dimX = dim[0];
-		A.W.dimY = dim[1];
-		A.W.dimZ = dim[2];
+		A.W = cvxi::WorldOf(ctx);
 		A.pairs = pairs;
 		A.solidOutside = solidOutside;
 		A.flags = flags;

@@ -8,7 +8,9 @@ height above two waves) for the runs that end at, start at and cross the steps. 
 property it is named for before it calls the device.
 
 The over-limit rejections (a run above 32767 voxels, a colour index above 32767, more than 65535 runs) are covered on the CPU
-(tests/test_world_dense_cpu.py) through the same step functions the kernels run: tests/limitworlds.py offers no world tall enough."""
+(tests/test_world_dense_cpu.py) through the same step functions the kernels run; on the device the run above 32767 voxels is rejected in
+tests/test_gpu_world_edit_rejections.py, on the 32 x 32768 x 32 world of the brush's and the copy's over-limit tests (tests/limitworlds.py
+offers no world tall enough)."""
 import numpy as np
 import pytest
 
