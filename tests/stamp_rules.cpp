@@ -1,8 +1,15 @@
-// Host build of the stamp rules (cpuvox_amd/csrc/cvx_stamp.h) for tests/test_world_stamp_cpu.py and tests/test_gpu_world_stamp.py.
+// Host build of the stamp rules (cpuvox_amd/csrc/cvx_stamp.h) for tests/test_world_stamp_cpu.py, tests/test_gpu_world_stamp.py and
+// tests/test_gpu_world_stamp_limits.py.
 //   stamp_rules voxelise <mesh in> <voxels out>
 //     mesh: int32 dimX dimY dimZ vertexCount indexCount materialCount, the cvx_mesh_vertex array, the int32 indices, then per material int32 width
 //     height (width 0: no texture) and width * height * 4 texel bytes.  Every triangle through cvxs::VoxelizeTriangle in order; out: int32
 //     (x, y, z, argb) per emitted voxel, in emission order.
+//   stamp_rules counts <mesh in> <counts out>
+//     What the device's pipeline (cvx_stamp.hip) makes of every triangle, from TriangleSetup / TriangleHit / TriangleColour in VoxelizeTriangle's
+//     loop order: int32 box columns (the device's pairs; 0 without area), hits, kept hits (capped at cvxs::kVoxelizeBufferMax), opaque kept
+//     hits, the most hits in one column, and 1 when the cap falls strictly inside a column (rank < cap < rank + hits).
+//   stamp_rules hits <mesh in> <hits out>
+//     The same loop: int32 (triangle, x, y, z) per hit, the hits past the cap and the transparent ones included.
 //   stamp_rules stamp <cases in> <results out>
 //     Each case is one column in the reference's layout plus stamped voxels (int32 words): dimY stride colorsBase runCount (colorsIndex length)*
 //     colourCount colour* op voxelCount (y argb)*.  The column gets its record as in brush_rules; the voxels (any order, duplicates allowed) are
@@ -38,43 +45,90 @@ static int WriteFile(const char *path, const std::vector<uint32_t> &words)
 	return 0;
 }
 
-static int Voxelise(const char *in, const char *outPath)
+// the mesh file of the voxelise / counts / hits modes
+struct MeshFile {
+	int dimX, dimY, dimZ, indexCount, materialCount;
+	std::vector<cvx_mesh_vertex> vertices;
+	std::vector<int32_t> indices;
+	std::vector<cvxs::Texture> textures;
+	std::vector<uint8_t> texels;
+	const cvx_mesh_vertex &Corner(int t, int k) const { return vertices[(size_t)indices[(size_t)t + (size_t)k]]; }
+};
+
+static MeshFile ReadMesh(const char *in)
 {
 	const std::vector<uint8_t> bytes = ReadFile(in);
 	const uint8_t *p = bytes.data();
 	int32_t head[6];
 	std::memcpy(head, p, sizeof head);
 	p += sizeof head;
-	const int dimX = head[0], dimY = head[1], dimZ = head[2], vertexCount = head[3], indexCount = head[4], materialCount = head[5];
-	std::vector<cvx_mesh_vertex> vertices((size_t)vertexCount);
-	std::memcpy(vertices.data(), p, vertices.size() * sizeof(cvx_mesh_vertex));
-	p += vertices.size() * sizeof(cvx_mesh_vertex);
-	std::vector<int32_t> indices((size_t)indexCount);
-	std::memcpy(indices.data(), p, indices.size() * 4);
-	p += indices.size() * 4;
-	std::vector<cvxs::Texture> textures;
-	std::vector<uint8_t> texels;
-	for (int m = 0; m < materialCount; m++) {
+	MeshFile m{ head[0], head[1], head[2], head[4], head[5], {}, {}, {}, {} };
+	m.vertices.resize((size_t)head[3]);
+	std::memcpy(m.vertices.data(), p, m.vertices.size() * sizeof(cvx_mesh_vertex));
+	p += m.vertices.size() * sizeof(cvx_mesh_vertex);
+	m.indices.resize((size_t)m.indexCount);
+	std::memcpy(m.indices.data(), p, m.indices.size() * 4);
+	p += m.indices.size() * 4;
+	for (int k = 0; k < m.materialCount; k++) {
 		int32_t wh[2];
 		std::memcpy(wh, p, sizeof wh);
 		p += sizeof wh;
 		if (wh[0] == 0) {
-			textures.push_back(cvxs::Texture{ 0, 0, -1 });
+			m.textures.push_back(cvxs::Texture{ 0, 0, -1 });
 			continue;
 		}
-		textures.push_back(cvxs::Texture{ wh[0], wh[1], (int64_t)texels.size() });
-		texels.insert(texels.end(), p, p + (size_t)wh[0] * wh[1] * 4);
+		m.textures.push_back(cvxs::Texture{ wh[0], wh[1], (int64_t)m.texels.size() });
+		m.texels.insert(m.texels.end(), p, p + (size_t)wh[0] * wh[1] * 4);
 		p += (size_t)wh[0] * wh[1] * 4;
 	}
+	return m;
+}
+
+static int Voxelise(const char *in, const char *outPath)
+{
+	const MeshFile m = ReadMesh(in);
 	std::vector<uint32_t> out;
-	for (int t = 0; t + 2 < indexCount; t += 3) {
-		cvxs::VoxelizeTriangle(vertices[(size_t)indices[(size_t)t]], vertices[(size_t)indices[(size_t)t + 1]], vertices[(size_t)indices[(size_t)t + 2]], dimX, dimY, dimZ,
-		                       textures.data(), materialCount, texels.data(), [&](int x, int y, int z, uint32_t argb) {
+	for (int t = 0; t + 2 < m.indexCount; t += 3) {
+		cvxs::VoxelizeTriangle(m.Corner(t, 0), m.Corner(t, 1), m.Corner(t, 2), m.dimX, m.dimY, m.dimZ, m.textures.data(), m.materialCount, m.texels.data(),
+		                       [&](int x, int y, int z, uint32_t argb) {
 			                       out.push_back((uint32_t)x);
 			                       out.push_back((uint32_t)y);
 			                       out.push_back((uint32_t)z);
 			                       out.push_back(argb);
 		                       });
+	}
+	return WriteFile(outPath, out);
+}
+
+// VoxelizeTriangle's loop (cvx_stamp.h) without its cap, counted per triangle; with allHits, every hit as (triangle, x, y, z) instead
+static int Counts(const char *in, const char *outPath, bool allHits)
+{
+	const MeshFile m = ReadMesh(in);
+	const uint32_t cap = (uint32_t)cvxs::kVoxelizeBufferMax;
+	std::vector<uint32_t> out;
+	for (int t = 0; t + 2 < m.indexCount; t += 3) {
+		const cvx_mesh_vertex &v0 = m.Corner(t, 0), &v1 = m.Corner(t, 1), &v2 = m.Corner(t, 2);
+		uint32_t columns = 0, hits = 0, opaque = 0, most = 0, inside = 0;
+		cvxs::TriSetup s;
+		if (cvxs::TriangleSetup(v0, v1, v2, m.dimX, m.dimY, m.dimZ, &s)) {
+			columns = (uint32_t)(s.hi[0] - s.lo[0] + 1) * (uint32_t)(s.hi[2] - s.lo[2] + 1);
+			for (int x = s.lo[0]; x <= s.hi[0]; x++) {
+				for (int z = s.lo[2]; z <= s.hi[2]; z++) {
+					const uint32_t rank = hits;
+					for (int y = s.lo[1]; y <= s.hi[1]; y++) {
+						float bx, by, bz;
+						if (!cvxs::TriangleHit(s, x, y, z, &bx, &by, &bz)) { continue; }
+						uint32_t argb;
+						if (hits < cap && cvxs::TriangleColour(v0, v1, v2, bx, by, bz, m.textures.data(), m.materialCount, m.texels.data(), &argb)) { opaque++; }
+						hits++;
+						if (allHits) { out.insert(out.end(), { (uint32_t)(t / 3), (uint32_t)x, (uint32_t)y, (uint32_t)z }); }
+					}
+					most = std::max(most, hits - rank);
+					if (rank < cap && cap < hits) { inside = 1; }
+				}
+			}
+		}
+		if (!allHits) { out.insert(out.end(), { columns, hits, std::min(hits, cap), opaque, most, inside }); }
 	}
 	return WriteFile(outPath, out);
 }
@@ -194,7 +248,9 @@ int main(int argc, char **argv)
 {
 	if (argc == 2 && std::strcmp(argv[1], "args") == 0) { return Args(); }
 	if (argc == 4 && std::strcmp(argv[1], "voxelise") == 0) { return Voxelise(argv[2], argv[3]); }
+	if (argc == 4 && std::strcmp(argv[1], "counts") == 0) { return Counts(argv[2], argv[3], false); }
+	if (argc == 4 && std::strcmp(argv[1], "hits") == 0) { return Counts(argv[2], argv[3], true); }
 	if (argc == 4 && std::strcmp(argv[1], "stamp") == 0) { return Stamp(argv[2], argv[3]); }
-	std::fprintf(stderr, "usage: stamp_rules voxelise <mesh> <voxels> | stamp <cases> <results> | args\n");
+	std::fprintf(stderr, "usage: stamp_rules voxelise <mesh> <voxels> | counts <mesh> <counts> | hits <mesh> <hits> | stamp <cases> <results> | args\n");
 	return 2;
 }

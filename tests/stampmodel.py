@@ -1,7 +1,9 @@
-"""Models and fixtures for the mesh-stamp tests (tests/test_world_stamp_cpu.py, tests/test_gpu_world_stamp.py).
+"""Models and fixtures for the mesh-stamp tests (tests/test_world_stamp_cpu.py, tests/test_gpu_world_stamp.py,
+tests/test_gpu_world_stamp_limits.py).
 
 - rules(): tests/stamp_rules.cpp compiled with g++ against cpuvox_amd/csrc/cvx_stamp.h (the rules the device runs).
 - voxelise(): a host.Mesh through the triangle rule, triangle after triangle: (x, y, z, argb) in emission order.
+- counts() / hits(): what the device's pipeline makes of every triangle (pairs, hits, kept hits, ...) and the hits themselves, uncapped.
 - apply_stamp(): a dense (solid, colour) volume after stamping voxels with FILL / CARVE / PAINT, duplicates merged with ToFinalColumn's
   average (per channel sum // count, alpha 255).
 - write_obj() / write_tga(): meshes and textures as files, for host.Mesh.from_obj and host.WorldSet.from_obj."""
@@ -35,8 +37,8 @@ def mill_obj(tmpdir) -> str:
     return path
 
 
-def voxelise(binary, mesh, dims, tmpdir):
-    """(x, y, z, argb) arrays of what the triangle rule emits for every triangle of `mesh` in a world of `dims`, in emission order."""
+def _mesh_file(mesh, dims, tmpdir) -> str:
+    """The mesh in the layout tests/stamp_rules.cpp reads."""
     v, idx = mesh.vertices, mesh.indices
     parts = [struct.pack("<6i", dims[0], dims[1], dims[2], v.size, idx.size, mesh.material_count), v.tobytes(), idx.astype("<i4").tobytes()]
     for k in range(mesh.material_count):
@@ -45,12 +47,41 @@ def voxelise(binary, mesh, dims, tmpdir):
             parts.append(struct.pack("<2i", 0, 0))
         else:
             parts.append(struct.pack("<2i", t.shape[1], t.shape[0]) + t.tobytes())
-    src, dst = os.path.join(str(tmpdir), "mesh.bin"), os.path.join(str(tmpdir), "voxels.bin")
+    src = os.path.join(str(tmpdir), "mesh.bin")
     with open(src, "wb") as f:
         f.write(b"".join(parts))
+    return src
+
+
+def voxelise(binary, mesh, dims, tmpdir):
+    """(x, y, z, argb) arrays of what the triangle rule emits for every triangle of `mesh` in a world of `dims`, in emission order."""
+    src, dst = _mesh_file(mesh, dims, tmpdir), os.path.join(str(tmpdir), "voxels.bin")
     subprocess.check_call([binary, "voxelise", src, dst])
     w = np.fromfile(dst, dtype="<u4").reshape(-1, 4)
     return w[:, 0].astype(np.int32), w[:, 1].astype(np.int32), w[:, 2].astype(np.int32), w[:, 3].copy()
+
+
+COUNTS_DTYPE = np.dtype([("pairs", "<i4"), ("hits", "<i4"), ("kept", "<i4"), ("opaque", "<i4"), ("column_max", "<i4"), ("midpair", "<i4")])
+
+
+def counts(binary, mesh, dims, tmpdir):
+    """Per triangle of `mesh`, what the device's pipeline makes of it (cvx_stamp.hip; the rule's `counts` mode): the columns of its box (the
+    device's pairs), its hits, the hits kept under the per-triangle cap, the opaque ones among those, the most hits in one column and whether
+    the cap falls strictly inside a column.  A COUNTS_DTYPE array."""
+    src, dst = _mesh_file(mesh, dims, tmpdir), os.path.join(str(tmpdir), "counts.bin")
+    subprocess.check_call([binary, "counts", src, dst])
+    out = np.fromfile(dst, dtype=COUNTS_DTYPE)
+    assert len(out) == mesh.indices.size // 3
+    return out
+
+
+def hits(binary, mesh, dims, tmpdir):
+    """Every hit of every triangle in the host's loop order, the ones past the cap and the transparent ones included: (triangle, x, y, z)
+    arrays.  A triangle's first 262144 are the ones it keeps."""
+    src, dst = _mesh_file(mesh, dims, tmpdir), os.path.join(str(tmpdir), "hits.bin")
+    subprocess.check_call([binary, "hits", src, dst])
+    w = np.fromfile(dst, dtype="<i4").reshape(-1, 4)
+    return w[:, 0], w[:, 1], w[:, 2], w[:, 3]
 
 
 def merge(x, y, z, argb):

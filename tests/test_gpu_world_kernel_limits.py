@@ -7,7 +7,10 @@ where a wave's nodes share a root, atomics per node otherwise) and the 256 piece
 
 Every case builds its volume in numpy (tests/limitworlds.py, no device needed) and asserts FROM THE VOLUME, before the device is called, that the
 count it is named after is exactly that; only then are the device's results compared, byte for byte, with the dense models (lightmodel,
-settlemodel, piecesmodel) and every level with the host-built LOD chain of the model's world."""
+settlemodel, piecesmodel) and every level with the host-built LOD chain of the model's world.
+
+cvx_world_stamp_mesh has a file of its own in the same manner: tests/test_gpu_world_stamp_limits.py (the pairs, the cap, the sort's tiles, the merge's
+runs, the early exits)."""
 import os
 
 import pytest

@@ -162,6 +162,31 @@ def test_mill_equals_the_host_voxeliser(work):
         assert mine.storage(k).tobytes() == ws.storage(k).tobytes(), f"LOD {k}"
 
 
+def test_counts_and_hits_modes_agree_with_the_voxeliser(work):
+    """stamp_rules counts / hits (what tests/test_gpu_world_stamp_limits.py names its cases after) on the three triangles that file is built
+    around, a triangle without area and a textured one: the figures, and hits == VoxelizeTriangle's voxels up to the cap."""
+    d, rules = work
+    f = np.float32
+    wall = [[10.3, 2, 10.2], [10.9, 60, 50.1], [11.4, 3, 52.7]]
+    ramp = np.float32([[0.2, 1.3, 0.4], [127.6, f(1.3) + f(36) * f(127.4), 3.1], [2.7, 9.9, 127.2]])
+    tall = [[3.5, -1, 3.2], [3.5, 100000, 5.0], [3.5, -1, 6.9]]
+    for tri, dims, want in ((wall, (128, 64, 128), (138, 1255, 1255, 1255, 45, 0)), (ramp, (128, 8192, 128), (16384, 290965, 262144, 262144, 37, 1)),
+                            (tall, (32, 32768, 32), (10, 103256, 103256, 103256, 32768, 0))):
+        mesh = host.Mesh.from_arrays({"position": np.float32([[1, 1, 1], [1, 1, 1], [5, 5, 5]] + [list(p) for p in tri])})
+        c = stampmodel.counts(rules, mesh, dims, d)
+        assert c[0].tolist() == (0, 0, 0, 0, 0, 0) and c[1].tolist() == want, c
+        t, hx, hy, hz = stampmodel.hits(rules, mesh, dims, d)
+        x, y, z, _ = stampmodel.voxelise(rules, mesh, dims, d)
+        assert len(t) == want[1] and (t == 1).all() and len(x) == want[2]
+        assert np.array_equal(hx[:len(x)], x) and np.array_equal(hy[:len(x)], y) and np.array_equal(hz[:len(x)], z)
+    rng = np.random.default_rng(21)
+    tex = rng.integers(0, 256, size=(8, 8, 4)).astype(np.uint8)
+    tex[..., 3] = np.where(rng.random((8, 8)) < 0.4, 17, 255)
+    mesh = host.Mesh.from_arrays({"position": np.float32(wall), "uv": np.float32([[0, 0], [1, 0], [0, 1]]), "material": 0}, textures=[tex])
+    c = stampmodel.counts(rules, mesh, (128, 64, 128), d)[0]
+    assert c["kept"] == 1255 and 0 < c["opaque"] < 1255 and c["opaque"] == len(stampmodel.voxelise(rules, mesh, (128, 64, 128), d)[0])
+
+
 # ---- the column rule --------------------------------------------------------------------------------------------------------------------------
 
 def _random_column(rng, dim_y):
