@@ -44,6 +44,8 @@ EXPORTS = [
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
     "cvx_image_plan_tile_out", "cvx_image_pack", "cvx_image_exchange", "cvx_image_unpack",
 ]
+# include/cpuvox_gpu_heights.h: terrain as height maps, exported by every build (checked by tests/test_world_heights_cpu.py)
+HEIGHTS_EXPORTS = ["cvx_world_read_heights", "cvx_world_read_heights_device", "cvx_world_write_heights", "cvx_world_write_heights_device"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -84,6 +86,7 @@ SURFACE_OUTSIDE_DEFAULT = 0x04                   # cvx_world_surface: solidOutsi
 SURFACE_IGNORE_COLOUR = 1                        # ... flags
 DISTANCE_FAR = 0x7FFFFFFF                        # cvx_world_distance: no such voxel within max_distance
 DISTANCE_TO_SOLID, DISTANCE_TO_AIR, DISTANCE_SIGNED = 0, 1, 2  # ... mode
+HEIGHTS_WALLED = 1                               # cvx_world_write_heights: flags, a neighbour outside the footprint counts as y0
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -415,6 +418,11 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_write_voxels_device.argtypes = L.cvx_world_write_voxels.argtypes
         L.cvx_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_distance_device.argtypes = L.cvx_world_distance.argtypes
+        L.cvx_world_read_heights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_read_heights_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvx_world_write_heights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(C.c_float)]
+        L.cvx_world_write_heights_device.argtypes = L.cvx_world_write_heights.argtypes
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -745,6 +753,66 @@ class Context:
         ms = C.c_float()
         self._check(lib().cvx_world_write_voxels_device(self._h, lo.ctypes.data, hi.ctypes.data, argb_ptr or None, solid_ptr or None, op, level_count,
                                                         C.byref(ms)))
+        return ms.value
+
+    # -- terrain as height maps (cvx_world_read_heights, cvx_world_write_heights) --
+    def read_heights(self, box_min, box_max, want_argb: bool = True, want_bottoms: bool = False):
+        """The terrain of the footprint of [box_min, box_max) (it may stick out of the world) inside the window [box_min.y, box_max.y), as arrays
+        of shape (X, Z), z fastest: (heights int32 -- 1 + the y of the highest solid voxel in the window, box_min.y when there is none --, argb
+        uint32 -- that voxel's colour word, 0 when there is none -- or None, bottoms int32 -- how far down the solid goes from there -- or None)."""
+        lo, hi = self._box(box_min, box_max)
+        shape = tuple(max(int(hi[a]) - int(lo[a]), 0) for a in (0, 2))
+        if 0 < shape[0] * shape[1] < 1 << 31:  # (anything else: the call rejects it before it writes)
+            heights = np.zeros(shape, dtype=np.int32)
+            argb = np.zeros(shape, dtype=np.uint32) if want_argb else None
+            bottoms = np.zeros(shape, dtype=np.int32) if want_bottoms else None
+        else:
+            heights = argb = bottoms = None
+        self._check(lib().cvx_world_read_heights(self._h, lo.ctypes.data, hi.ctypes.data, heights.ctypes.data if heights is not None else None,
+                                                 argb.ctypes.data if argb is not None else None, bottoms.ctypes.data if bottoms is not None else None, None))
+        return heights, argb, bottoms
+
+    def read_heights_device(self, box_min, box_max, heights_ptr: int, argb_ptr: int = 0, bottoms_ptr: int = 0, stream: int | None = None) -> None:
+        """read_heights into device memory (addresses of X * Z int32 / uint32 / int32, e.g. a torch tensor's data_ptr(); any may be 0, not all),
+        enqueued on `stream` (None or 0: the context's) without waiting."""
+        lo, hi = self._box(box_min, box_max)
+        self._check(lib().cvx_world_read_heights_device(self._h, lo.ctypes.data, hi.ctypes.data, heights_ptr or None, argb_ptr or None, bottoms_ptr or None,
+                                                        stream or None))
+
+    def write_heights(self, box_min, y_max: int, heights, argb, side_argb=None, thickness: int = 1, flags: int = 0, op: int = COPY_REPLACE,
+                      level_count: int = LOD_LEVELS - 1) -> float:
+        """Writes terrain into the window [box_min.y, y_max) of the columns at box_min and rebuilds LOD 1..level_count over them.  `heights`:
+        int32 of shape (X, Z), clamped into the window; a column's voxels from its crust's bottom up to its height are SET.  thickness 0: solid
+        down to the window's bottom; t: a crust of t voxels, thicker where a neighbour is lower (HEIGHTS_WALLED in `flags`: the rim counts as a
+        cliff down to the window's bottom).  `argb` (uint32, same shape; None for a BRUSH_CARVE): the top voxel's colour word, `side_argb`
+        (optional) that of the voxels below it.  op: COPY_REPLACE (the window becomes this terrain), BRUSH_FILL, BRUSH_CARVE, BRUSH_PAINT.
+        Returns the device milliseconds (0 when the box lies outside the world)."""
+        h = np.asarray(heights)
+        if h.ndim != 2 or h.dtype.kind not in "iu":
+            raise ValueError("write_heights: heights is an integer array of shape (X, Z)")
+        h = np.ascontiguousarray(h, dtype=np.int32)
+        a = np.ascontiguousarray(argb, dtype=np.uint32) if argb is not None else None
+        s = np.ascontiguousarray(side_argb, dtype=np.uint32) if side_argb is not None else None
+        if any(c is not None and c.shape != h.shape for c in (a, s)):
+            raise ValueError("write_heights: heights, argb and side_argb are arrays of one shape (X, Z)")
+        lo = np.ascontiguousarray(box_min, dtype=np.int64)
+        if lo.shape != (3,):
+            raise ValueError("box_min is three integers")
+        hi = np.array([lo[0] + h.shape[0], int(y_max), lo[2] + h.shape[1]], dtype=np.int64)
+        lo, hi = self._box(np.clip(lo, -(1 << 31), (1 << 31) - 1), np.clip(hi, -(1 << 31), (1 << 31) - 1))
+        ms = C.c_float()
+        self._check(lib().cvx_world_write_heights(self._h, lo.ctypes.data, hi.ctypes.data, h.ctypes.data, a.ctypes.data if a is not None else None,
+                                                  s.ctypes.data if s is not None else None, int(thickness), int(flags), int(op), int(level_count), C.byref(ms)))
+        return ms.value
+
+    def write_heights_device(self, box_min, box_max, heights_ptr: int, argb_ptr: int, side_argb_ptr: int = 0, thickness: int = 1, flags: int = 0,
+                             op: int = COPY_REPLACE, level_count: int = LOD_LEVELS - 1) -> float:
+        """write_heights from device memory (addresses of X * Z int32 / uint32 / uint32; side_argb_ptr may be 0, argb_ptr only for a
+        BRUSH_CARVE), read on the context's stream: the arrays must be complete when the call is made.  Returns the device milliseconds."""
+        lo, hi = self._box(box_min, box_max)
+        ms = C.c_float()
+        self._check(lib().cvx_world_write_heights_device(self._h, lo.ctypes.data, hi.ctypes.data, heights_ptr or None, argb_ptr or None, side_argb_ptr or None,
+                                                         int(thickness), int(flags), int(op), int(level_count), C.byref(ms)))
         return ms.value
 
     # -- exact squared-distance fields (cvx_world_distance) --
