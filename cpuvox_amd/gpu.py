@@ -46,6 +46,9 @@ EXPORTS = [
 ]
 # include/cpuvox_gpu_heights.h: terrain as height maps, exported by every build (checked by tests/test_world_heights_cpu.py)
 HEIGHTS_EXPORTS = ["cvx_world_read_heights", "cvx_world_read_heights_device", "cvx_world_write_heights", "cvx_world_write_heights_device"]
+# include/cpuvox_gpu_models.h: voxel models at any orientation and scale, exported by every build (checked by tests/test_world_models_cpu.py)
+MODELS_EXPORTS = ["cvx_world_place_models", "cvx_world_place_models_device", "cvx_world_read_model", "cvx_world_read_model_device",
+                  "cvx_model_instance_from_matrix"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -87,8 +90,22 @@ SURFACE_IGNORE_COLOUR = 1                        # ... flags
 DISTANCE_FAR = 0x7FFFFFFF                        # cvx_world_distance: no such voxel within max_distance
 DISTANCE_TO_SOLID, DISTANCE_TO_AIR, DISTANCE_SIGNED = 0, 1, 2  # ... mode
 HEIGHTS_WALLED = 1                               # cvx_world_write_heights: flags, a neighbour outside the footprint counts as y0
+MODELS_MAX_MODELS, MODELS_MAX_INSTANCES = 256, 4096  # cvx_world_place_models: modelCount, instanceCount
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
+
+
+class ModelMap(C.Structure):
+    """cvx_model_map: image_i = (m[i][0] (2 v0 + 1) + m[i][1] (2 v1 + 1) + m[i][2] (2 v2 + 1) + 2 t[i]) >> 17, m and t in units of 2^-16."""
+    _fields_ = [("m", (C.c_int32 * 3) * 3), ("pad_", C.c_int32), ("t", C.c_int64 * 3)]
+
+
+class Model(C.Structure):
+    _fields_ = [("size", C.c_int32 * 3), ("pad_", C.c_int32), ("argb", C.c_void_p), ("solid", C.c_void_p)]
+
+
+class ModelInstance(C.Structure):
+    _fields_ = [("toModel", ModelMap), ("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("model", C.c_int32), ("op", C.c_int32)]
 
 
 class BrushStroke(C.Structure):
@@ -423,6 +440,11 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_write_heights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.POINTER(C.c_float)]
         L.cvx_world_write_heights_device.argtypes = L.cvx_world_write_heights.argtypes
+        L.cvx_world_place_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.cvx_world_place_models_device.argtypes = L.cvx_world_place_models.argtypes
+        L.cvx_world_read_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_read_model_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvx_model_instance_from_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -454,6 +476,20 @@ def _bind(path: str) -> C.CDLL:
 
 class CvxError(RuntimeError):
     pass
+
+
+def model_instance(forward, size, model: int = 0, op: int = COPY_REPLACE) -> ModelInstance:
+    """cvx_model_instance_from_matrix: the instance that places a model of `size` (sx, sy, sz) under `forward`, the 3 x 4 matrix that takes model
+    coordinates (voxel s is the cube [s, s + 1)) to world voxel coordinates: its toModel is the rounded inverse, its box the mapped model's
+    bounds widened by a voxel.  For a read_model's to_world pass the INVERSE matrix and take the result's toModel."""
+    f = np.ascontiguousarray(forward, dtype=np.float64)
+    n = np.ascontiguousarray(size, dtype=np.int32)
+    if f.shape != (3, 4) or n.shape != (3,):
+        raise ValueError("model_instance: forward is a 3 x 4 matrix, size three integers")
+    out = ModelInstance()
+    if lib().cvx_model_instance_from_matrix(f.ctypes.data, n.ctypes.data, int(model), int(op), C.addressof(out)) != 0:
+        raise CvxError("cvx_model_instance_from_matrix: a non-finite or singular matrix, or a map or box beyond the limits")
+    return out
 
 
 class Context:
@@ -814,6 +850,88 @@ class Context:
         self._check(lib().cvx_world_write_heights_device(self._h, lo.ctypes.data, hi.ctypes.data, heights_ptr or None, argb_ptr or None, side_argb_ptr or None,
                                                          int(thickness), int(flags), int(op), int(level_count), C.byref(ms)))
         return ms.value
+
+    # -- voxel models at any orientation and scale (cvx_world_place_models, cvx_world_read_model) --
+    @staticmethod
+    def _instances(instances):
+        if isinstance(instances, C.Array) and instances._type_ is ModelInstance:
+            return instances
+        items = list(instances)
+        if not all(isinstance(i, ModelInstance) for i in items):
+            raise ValueError("instances are gpu.ModelInstance structures")
+        return (ModelInstance * len(items))(*items)
+
+    def place_models(self, models, instances, level_count: int = LOD_LEVELS - 1) -> float:
+        """Places instances of voxel models into LOD 0, in order, and rebuilds LOD 1..level_count over their boxes.  `models`: a list of
+        (argb, solid) -- uint32 colour words of shape (X, Z, Y) (None for a model only BRUSH_CARVE instances use) and an optional mask of the same
+        shape (without it the voxels with a colour word other than 0 are set).  `instances`: gpu.ModelInstance structures (gpu.model_instance
+        makes them from a matrix).  Returns the device milliseconds (0 when every box lies outside the world)."""
+        keep, descriptors = [], (Model * max(len(models), 1))()
+        for k, entry in enumerate(models):
+            if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+                raise ValueError("place_models: a model is a pair (argb, solid)")
+            argb, solid = entry
+            if argb is not None and np.asarray(argb).dtype.kind not in "iu":
+                raise ValueError("place_models: argb is an integer array of shape (X, Z, Y)")
+            a = np.ascontiguousarray(argb, dtype=np.uint32) if argb is not None else None
+            m = np.ascontiguousarray(solid).astype(np.bool_, copy=False).view(np.uint8) if solid is not None else None
+            shape = a.shape if a is not None else (m.shape if m is not None else None)
+            if shape is None or len(shape) != 3 or (a is not None and m is not None and a.shape != m.shape):
+                raise ValueError("place_models: argb and solid are arrays of one shape (X, Z, Y)")
+            keep += [a, m]
+            descriptors[k].size[:] = [shape[0], shape[2], shape[1]]
+            descriptors[k].argb = a.ctypes.data if a is not None else None
+            descriptors[k].solid = m.ctypes.data if m is not None else None
+        inst = self._instances(instances)
+        ms = C.c_float()
+        self._check(lib().cvx_world_place_models(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), int(level_count), C.byref(ms)))
+        return ms.value
+
+    def place_models_device(self, models, instances, level_count: int = LOD_LEVELS - 1) -> float:
+        """place_models from device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr), the addresses of sx * sz * sy uint32 /
+        uint8 laid out (X, Z, Y) (e.g. a torch tensor's data_ptr(); either may be 0, not both), read on the context's stream: the arrays must
+        be complete when the call is made."""
+        descriptors = (Model * max(len(models), 1))()
+        for k, entry in enumerate(models):
+            if not isinstance(entry, (tuple, list)) or len(entry) != 3 or len(tuple(entry[0])) != 3:
+                raise ValueError("place_models_device: a model is ((sx, sy, sz), argb_ptr, solid_ptr)")
+            descriptors[k].size[:] = [int(v) for v in entry[0]]
+            descriptors[k].argb = entry[1] or None
+            descriptors[k].solid = entry[2] or None
+        inst = self._instances(instances)
+        ms = C.c_float()
+        self._check(lib().cvx_world_place_models_device(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), int(level_count),
+                                                        C.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def _model_read(size, to_world):
+        n = np.ascontiguousarray(size, dtype=np.int32)
+        if n.shape != (3,):
+            raise ValueError("size is three integers (sx, sy, sz)")
+        if not isinstance(to_world, ModelMap):
+            raise ValueError("to_world is a gpu.ModelMap")
+        return n
+
+    def read_model(self, size, to_world, want_argb: bool = True, want_solid: bool = True):
+        """The world sampled as a model of `size` (sx, sy, sz): element (x, z, y) of the arrays, of shape (sx, sz, sy), is the LOD-0 voxel at
+        to_world(x, y, z) (a gpu.ModelMap), air outside the world: (argb uint32 or None, solid bool or None)."""
+        n = self._model_read(size, to_world)
+        shape = (max(int(n[0]), 0), max(int(n[2]), 0), max(int(n[1]), 0))
+        if 0 < shape[0] * shape[1] * shape[2] < 1 << 31:  # (anything else: the call rejects it before it writes)
+            argb = np.zeros(shape, dtype=np.uint32) if want_argb else None
+            solid = np.zeros(shape, dtype=np.uint8) if want_solid else None
+        else:
+            argb = solid = None
+        self._check(lib().cvx_world_read_model(self._h, n.ctypes.data, C.addressof(to_world), argb.ctypes.data if argb is not None else None,
+                                               solid.ctypes.data if solid is not None else None, None))
+        return argb, (solid.view(np.bool_) if solid is not None else None)
+
+    def read_model_device(self, size, to_world, argb_ptr: int, solid_ptr: int, stream: int | None = None) -> None:
+        """read_model into device memory (addresses of sx * sz * sy uint32 / uint8; either may be 0), enqueued on `stream` (None or 0: the
+        context's) without waiting."""
+        n = self._model_read(size, to_world)
+        self._check(lib().cvx_world_read_model_device(self._h, n.ctypes.data, C.addressof(to_world), argb_ptr or None, solid_ptr or None, stream or None))
 
     # -- exact squared-distance fields (cvx_world_distance) --
     def distance(self, box_min, box_max, max_distance: int, mode: int = DISTANCE_TO_SOLID, solid_outside: int = SURFACE_OUTSIDE_DEFAULT):
