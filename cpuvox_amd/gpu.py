@@ -49,6 +49,8 @@ HEIGHTS_EXPORTS = ["cvx_world_read_heights", "cvx_world_read_heights_device", "c
 # include/cpuvox_gpu_models.h: voxel models at any orientation and scale, exported by every build (checked by tests/test_world_models_cpu.py)
 MODELS_EXPORTS = ["cvx_world_place_models", "cvx_world_place_models_device", "cvx_world_read_model", "cvx_world_read_model_device",
                   "cvx_model_instance_from_matrix"]
+# include/cpuvox_gpu_spread.h: travel-distance fields through air or solid, exported by every build (checked by tests/test_world_spread_cpu.py)
+SPREAD_EXPORTS = ["cvx_world_spread", "cvx_world_spread_device"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -91,6 +93,10 @@ DISTANCE_FAR = 0x7FFFFFFF                        # cvx_world_distance: no such v
 DISTANCE_TO_SOLID, DISTANCE_TO_AIR, DISTANCE_SIGNED = 0, 1, 2  # ... mode
 HEIGHTS_WALLED = 1                               # cvx_world_write_heights: flags, a neighbour outside the footprint counts as y0
 MODELS_MAX_MODELS, MODELS_MAX_INSTANCES = 256, 4096  # cvx_world_place_models: modelCount, instanceCount
+SPREAD_AIR, SPREAD_SOLID = 0, 1                  # cvx_spread_params.medium
+SPREAD_UNREACHED, SPREAD_BLOCKED = -1, -2        # cvx_world_spread: passable but not reached within max_steps / not passable
+SPREAD_MAX_SEEDS, SPREAD_MAX_STEPS = 4096, 65534
+SPREAD_TILE = (8, 64, 8)                         # CVX_SPREAD_TILE_X / _Y / _Z: the (x, y, z) extents of the tile a workgroup relaxes
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -106,6 +112,20 @@ class Model(C.Structure):
 
 class ModelInstance(C.Structure):
     _fields_ = [("toModel", ModelMap), ("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("model", C.c_int32), ("op", C.c_int32)]
+
+
+class SpreadParams(C.Structure):  # cvx_spread_params
+    _fields_ = [("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("medium", C.c_int32), ("stepFaces", C.c_int32), ("maxSteps", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class SpreadSeed(C.Structure):  # cvx_spread_seed
+    _fields_ = [("voxel", C.c_int32 * 3), ("start", C.c_int32)]
+
+
+class SpreadSummary(C.Structure):  # cvx_spread_summary
+    _fields_ = [("passable", C.c_int64), ("reached", C.c_int64), ("largestDistance", C.c_int32), ("seedsUsed", C.c_int32), ("launches", C.c_int32),
+                ("pad_", C.c_int32), ("tileVisits", C.c_int64)]
 
 
 class BrushStroke(C.Structure):
@@ -210,6 +230,9 @@ MOVE_RESULT_DTYPE = np.dtype([("pos", "<i4", 3), ("flags", "<i4")])  # cvx_move_
 NAV_STEP_DTYPE = np.dtype([("cell", "<i4", 3), ("distance", "<i4"), ("next", "<i4", 3), ("direction", "<i4")])  # cvx_nav_step
 NAV_SUMMARY_DTYPE = np.dtype([("nodes", "<i8"), ("reached", "<i8"), ("goalsResolved", "<i4"), ("largestDistance", "<i4"),
                               ("columnsWithSeveralNodes", "<i8"), ("launches", "<i4"), ("pad_", "<i4")])  # cvx_nav_summary
+SPREAD_SEED_DTYPE = np.dtype([("voxel", "<i4", 3), ("start", "<i4")])  # cvx_spread_seed
+SPREAD_SUMMARY_DTYPE = np.dtype([("passable", "<i8"), ("reached", "<i8"), ("largestDistance", "<i4"), ("seedsUsed", "<i4"), ("launches", "<i4"),
+                                 ("pad_", "<i4"), ("tileVisits", "<i8")])  # cvx_spread_summary
 SURFACE_QUAD_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("length", "<i4"), ("argb", "<u4")])  # cvx_surface_quad
 SURFACE_SUMMARY_DTYPE = np.dtype([("quads", "<i8"), ("unitFaces", "<i8"), ("quadsPerFace", "<i8", 6)])  # cvx_surface_summary
 
@@ -242,6 +265,29 @@ def strokes_array(strokes) -> np.ndarray:
         if s["shape"] == SHAPE_CAPSULE:
             out[i]["pad_"] = s["radius"]
     return out
+
+
+def seeds_array(seeds) -> np.ndarray:
+    """A list of (x, y, z) or (x, y, z, start) or a SPREAD_SEED_DTYPE array -> a contiguous SPREAD_SEED_DTYPE array."""
+    if isinstance(seeds, np.ndarray) and seeds.dtype == SPREAD_SEED_DTYPE:
+        return np.ascontiguousarray(seeds)
+    out = np.zeros(len(seeds), dtype=SPREAD_SEED_DTYPE)
+    for i, s in enumerate(seeds):
+        if len(s) not in (3, 4):
+            raise ValueError("world_spread: a seed is (x, y, z) or (x, y, z, start)")
+        out[i]["voxel"] = [int(v) for v in s[:3]]
+        out[i]["start"] = int(s[3]) if len(s) == 4 else 0
+    return out
+
+
+def _spread_tensor_ptr(tensor, box) -> int:
+    lo, hi = box
+    n = 1
+    for a in range(3):
+        n *= max(int(hi[a]) - int(lo[a]), 0)
+    if str(getattr(tensor, "dtype", "")) != "torch.int32" or not tensor.is_contiguous() or tensor.numel() != n or not tensor.is_cuda:
+        raise ValueError("world_spread_device: out_tensor is a contiguous int32 device tensor of X * Z * Y elements")
+    return tensor.data_ptr()
 
 
 def bodies_array(bodies) -> np.ndarray:
@@ -445,6 +491,8 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_read_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_read_model_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvx_model_instance_from_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.cvx_world_spread.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_spread_device.argtypes = L.cvx_world_spread.argtypes
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -955,6 +1003,33 @@ class Context:
         self._check(lib().cvx_world_distance_device(self._h, lo.ctypes.data, hi.ctypes.data, int(max_distance), int(mode), int(solid_outside),
                                                     out_ptr or None, C.byref(ms)))
         return ms.value
+
+    # -- travel-distance fields through air or solid (cvx_world_spread) --
+    def _spread(self, fn, box_min, box_max, seeds, medium, step_faces, max_steps, out_ptr):
+        lo, hi = self._box(box_min, box_max)
+        p = SpreadParams((C.c_int32 * 3)(*lo.tolist()), (C.c_int32 * 3)(*hi.tolist()), int(medium), int(step_faces), int(max_steps), 0)
+        s = seeds_array(seeds)
+        summary, ms = SpreadSummary(), C.c_float()
+        self._check(fn(self._h, C.addressof(p), s.ctypes.data if s.size else None, s.size, out_ptr or None, C.addressof(summary), C.byref(ms)))
+        return {name: getattr(summary, name) for name, _ in SpreadSummary._fields_ if name != "pad_"}, ms.value
+
+    def world_spread(self, box_min, box_max, seeds, *, medium: int, step_faces: int = 0x3F, max_steps: int):
+        """The travel distance from `seeds` -- (x, y, z) or (x, y, z, start) each, or a SPREAD_SEED_DTYPE array -- to every voxel of [box_min,
+        box_max) (it may stick out of the world) through SPREAD_AIR or SPREAD_SOLID: steps of cost 1 between passable face neighbours, in the
+        directions `step_faces` allows (bits 0..5 = -X,+X,-Y,+Y,-Z,+Z: 0x3F all, 0x37 water, 0x3B smoke), cut at max_steps (1 .. 65534).
+        Returns (the field, int32 of shape (X, Z, Y), y fastest: the distance, SPREAD_UNREACHED, or SPREAD_BLOCKED where the voxel is not
+        passable; the summary as a dict: passable, reached, largestDistance, seedsUsed, launches, tileVisits; the device milliseconds)."""
+        lo, hi = self._box(box_min, box_max)
+        shape = tuple(max(int(hi[a]) - int(lo[a]), 0) for a in (0, 2, 1))
+        out = np.zeros(shape, dtype=np.int32) if 0 < shape[0] * shape[1] * shape[2] < 1 << 31 else None  # (anything else: the call rejects it)
+        summary, ms = self._spread(lib().cvx_world_spread, lo, hi, seeds, medium, step_faces, max_steps, out.ctypes.data if out is not None else None)
+        return out, summary, ms
+
+    def world_spread_device(self, box_min, box_max, seeds, out_tensor, *, medium: int, step_faces: int = 0x3F, max_steps: int):
+        """world_spread into device memory: `out_tensor` is a contiguous int32 torch tensor of X * Z * Y elements on the context's device (or the
+        address of such memory); the field is complete when the call returns.  `seeds` stays a host array.  Returns (summary, device ms)."""
+        ptr = out_tensor if isinstance(out_tensor, int) else _spread_tensor_ptr(out_tensor, self._box(box_min, box_max))
+        return self._spread(lib().cvx_world_spread_device, box_min, box_max, seeds, medium, step_faces, max_steps, ptr)
 
     def debug_cavities(self) -> dict:
         """Diagnostics build only (include/cpuvox_gpu_diag.h): the last world_cavities' device ms split (analysis, edit), its air intervals and
