@@ -51,6 +51,8 @@ MODELS_EXPORTS = ["cvx_world_place_models", "cvx_world_place_models_device", "cv
                   "cvx_model_instance_from_matrix"]
 # include/cpuvox_gpu_spread.h: travel-distance fields through air or solid, exported by every build (checked by tests/test_world_spread_cpu.py)
 SPREAD_EXPORTS = ["cvx_world_spread", "cvx_world_spread_device"]
+# include/cpuvox_gpu_surface_rects.h: the exposed faces merged into rectangles, exported by every build (checked by tests/test_world_surface_rects_cpu.py)
+SURFACE_RECTS_EXPORTS = ["cvx_world_surface_rects", "cvx_world_surface_rects_device", "cvx_surface_rect_triangles"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -207,6 +209,14 @@ class SurfaceSummary(C.Structure):  # cvx_surface_summary
     _fields_ = [("quads", C.c_int64), ("unitFaces", C.c_int64), ("quadsPerFace", C.c_int64 * 6)]
 
 
+class SurfaceRect(C.Structure):  # cvx_surface_rect
+    _fields_ = [("voxel", C.c_int32 * 3), ("size", C.c_int32 * 3), ("face", C.c_int32), ("argb", C.c_uint32)]
+
+
+class SurfaceRectsSummary(C.Structure):  # cvx_surface_rects_summary
+    _fields_ = [("rects", C.c_int64), ("strips", C.c_int64), ("unitFaces", C.c_int64), ("rectsPerFace", C.c_int64 * 6)]
+
+
 class _TextureStruct(C.Structure):  # cvx_mesh_texture
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
 
@@ -244,6 +254,23 @@ def surface_triangles(quads):
     vertices = np.zeros(4 * q.size, dtype=MESH_VERTEX_DTYPE)
     indices = np.zeros(6 * q.size, dtype=np.int32)
     rc = lib().cvx_surface_triangles(q.ctypes.data if q.size else None, q.size, vertices.ctypes.data if q.size else None, indices.ctypes.data if q.size else None)
+    if rc != 0:
+        raise CvxError(f"cvx error {rc}: {lib().cvx_last_error(None).decode()}")
+    return vertices, indices
+
+
+SURFACE_RECT_DTYPE = np.dtype([("voxel", "<i4", 3), ("size", "<i4", 3), ("face", "<i4"), ("argb", "<u4")])  # cvx_surface_rect
+SURFACE_RECTS_SUMMARY_DTYPE = np.dtype([("rects", "<i8"), ("strips", "<i8"), ("unitFaces", "<i8"), ("rectsPerFace", "<i8", 6)])  # cvx_surface_rects_summary
+
+
+def surface_rect_triangles(rects):
+    """cvx_surface_rect_triangles: a SURFACE_RECT_DTYPE array -> (4 n vertices as a MESH_VERTEX_DTYPE array, 6 n int32 indices): every rectangle
+    on its face plane, wound outward as surface_triangles winds a quad, with the same vertex colour.  A merged mesh has T-junctions.  A pure host
+    call."""
+    r = np.ascontiguousarray(rects, dtype=SURFACE_RECT_DTYPE)
+    vertices = np.zeros(4 * r.size, dtype=MESH_VERTEX_DTYPE)
+    indices = np.zeros(6 * r.size, dtype=np.int32)
+    rc = lib().cvx_surface_rect_triangles(r.ctypes.data if r.size else None, r.size, vertices.ctypes.data if r.size else None, indices.ctypes.data if r.size else None)
     if rc != 0:
         raise CvxError(f"cvx error {rc}: {lib().cvx_last_error(None).decode()}")
     return vertices, indices
@@ -493,6 +520,9 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_model_instance_from_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.cvx_world_spread.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_spread_device.argtypes = L.cvx_world_spread.argtypes
+        L.cvx_world_surface_rects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_surface_rects_device.argtypes = L.cvx_world_surface_rects.argtypes
+        L.cvx_surface_rect_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -783,6 +813,34 @@ class Context:
         """world_surface into device memory (the address of `capacity` cvx_surface_quad, e.g. a torch tensor's data_ptr()): the first min(capacity,
         quads) entries are written, the rest is left alone; returns (the totals, device milliseconds) once the summary is on the host."""
         return self._surface(lib().cvx_world_surface_device, box_min, box_max, solid_outside, flags, quads_ptr or None, capacity)
+
+    def _surface_rects(self, entry, box_min, box_max, solid_outside, flags, rects_ptr, capacity):
+        lo, hi = np.ascontiguousarray(box_min, dtype=np.int32), np.ascontiguousarray(box_max, dtype=np.int32)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("world_surface_rects: box_min and box_max are three integers each")
+        summary = np.zeros(1, dtype=SURFACE_RECTS_SUMMARY_DTYPE)
+        ms = C.c_float()
+        self._check(entry(self._h, lo.ctypes.data, hi.ctypes.data, solid_outside, flags, rects_ptr, int(capacity), summary.ctypes.data, C.byref(ms)))
+        totals = {"rects": int(summary[0]["rects"]), "strips": int(summary[0]["strips"]), "unitFaces": int(summary[0]["unitFaces"]),
+                  "rectsPerFace": [int(v) for v in summary[0]["rectsPerFace"]]}
+        return totals, ms.value
+
+    def world_surface_rects(self, box_min, box_max, solid_outside: int = SURFACE_OUTSIDE_DEFAULT, flags: int = 0, capacity=None):
+        """world_surface's quads merged into rectangles (side faces along the wall, -Y / +Y faces into rows along x that stack along z; colours
+        merge only with SURFACE_IGNORE_COLOUR), in (x, z, face, descending top) order of their lowest voxel: (the first `capacity` rectangles as a
+        SURFACE_RECT_DTYPE array, the totals of cvx_surface_rects_summary as a dict, device milliseconds).  capacity=None asks for the count
+        first and then for every rectangle (the milliseconds are the second call's)."""
+        if capacity is None:
+            totals, _ = self._surface_rects(lib().cvx_world_surface_rects, box_min, box_max, solid_outside, flags, None, 0)
+            capacity = totals["rects"]
+        out = np.zeros(max(int(capacity), 0), dtype=SURFACE_RECT_DTYPE)
+        totals, ms = self._surface_rects(lib().cvx_world_surface_rects, box_min, box_max, solid_outside, flags, out.ctypes.data if out.size else None, capacity)
+        return (out if out.size <= totals["rects"] else out[:totals["rects"]].copy()), totals, ms
+
+    def world_surface_rects_device(self, box_min, box_max, rects_ptr: int, capacity: int, solid_outside: int = SURFACE_OUTSIDE_DEFAULT, flags: int = 0):
+        """world_surface_rects into device memory (the address of `capacity` cvx_surface_rect, e.g. a torch tensor's data_ptr()): the first
+        min(capacity, rects) entries are written, the rest is left alone; returns (the totals, device milliseconds) once the summary is on the host."""
+        return self._surface_rects(lib().cvx_world_surface_rects_device, box_min, box_max, solid_outside, flags, rects_ptr or None, capacity)
 
     # -- dense voxel boxes in and out of the world (cvx_world_read_voxels, cvx_world_write_voxels) --
     @staticmethod
