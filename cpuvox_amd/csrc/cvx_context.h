@@ -147,7 +147,35 @@ namespace cvxi {
 // Records the message on the context (or for cvx_last_error(NULL) when ctx is null) and returns `code`.
 int Fail(cvx_context *ctx, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 
+// cvx_gpu.hip: hipErrorOutOfMemory -> CVX_ERR_CAPACITY ("the scratch of <call> does not fit in device memory"), anything else -> CVX_ERR_HIP
+int FailHip(cvx_context *ctx, const char *call, hipError_t e);
+
 inline bool IsPow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// the world calls' kernels: a thread per column, node or pair, kThreads to a workgroup
+constexpr unsigned kThreads = 256;
+inline unsigned Grid(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+// The layout of one scratch allocation: layout(b) is the offset of the next b bytes, every offset a multiple of 16; `bytes` is what to allocate.
+struct ScratchLayout {
+	size_t bytes = 0;
+	size_t operator()(size_t b)
+	{
+		const size_t at = bytes;
+		bytes = (bytes + b + 15) & ~(size_t)15;
+		return at;
+	}
+};
+
+#ifdef __HIPCC__
+__device__ inline uint32_t Load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+template <typename T, typename F> __device__ inline T WaveReduce(T v, F f)
+{
+	for (int d = 32; d > 0; d >>= 1) { v = f(v, __shfl_xor(v, d, 64)); }
+	return v;
+}
+#endif
 
 // One column of a world blob in the reference's layout (World.cs:161-209): element range inside the pool, both guards
 // present, positive run lengths that fit the column height, colours inside the pool.  Everything the kernels dereference
@@ -221,21 +249,22 @@ struct ColumnEditCall {
 	                                       // else the caller's event, recorded behind the last patch: the caller recorded its start long before and
 	                                       // takes the time itself -- ColumnEdit then creates no events and does NOT write *outMs
 };
-// A reference to a caller's launcher (a lambda: hipError_t(const ColumnEditJob &)) for the length of the ColumnEdit call: nothing is owned or allocated.
-// The launcher enqueues on ctx->stream and returns the first error of its own uploads; launch errors are picked up by ColumnEdit.
-class ColumnEditLauncher {
+// A reference to a caller's launcher (a lambda: hipError_t(const Job &)) for the length of the call it is handed to: nothing is owned or allocated.
+// The launcher enqueues on ctx->stream and returns the first error of its own uploads; launch errors are picked up by the driver that calls it.
+template <class Job> class Launcher {
 	void *object;
-	hipError_t (*invoke)(void *, const ColumnEditJob &);
+	hipError_t (*invoke)(void *, const Job &);
 
 public:
-	template <class F, class = std::enable_if_t<!std::is_same_v<std::decay_t<F>, ColumnEditLauncher>>>
-	ColumnEditLauncher(F &&f)
+	template <class F, class = std::enable_if_t<!std::is_same_v<std::decay_t<F>, Launcher>>>
+	Launcher(F &&f)
 		: object(const_cast<void *>(static_cast<const void *>(&f))),
-		  invoke([](void *o, const ColumnEditJob &J) -> hipError_t { return (*static_cast<std::remove_reference_t<F> *>(o))(J); })
+		  invoke([](void *o, const Job &J) -> hipError_t { return (*static_cast<std::remove_reference_t<F> *>(o))(J); })
 	{
 	}
-	hipError_t operator()(const ColumnEditJob &J) const { return invoke(object, J); }
+	hipError_t operator()(const Job &J) const { return invoke(object, J); }
 };
+using ColumnEditLauncher = Launcher<ColumnEditJob>;
 // Steps 2 .. 6 of the pipeline (cvx_edit.hip's header) on ctx->stream: scratch, launchCount (its uploads, then its count kernel), cvxi::ExclusiveScan, one
 // copy back and one synchronisation, the two capacity checks, the blob's allocation, launchWrite (its write kernel and whatever shades the blob),
 // EditFromDevice.  Everything the pipeline allocated is released on every path; nothing in the arena is written before EditFromDevice.

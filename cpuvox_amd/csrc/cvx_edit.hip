@@ -405,11 +405,10 @@ int ApplyJobs(cvx_context *ctx, std::vector<Job> &jobs)
 		A.elements = j.elements;
 		const size_t n = (size_t)A.n, T = (size_t)A.blockCount;
 		const size_t chunks = (std::max(n, T) + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-		size_t bytes = 0;
-		auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+		cvxi::ScratchLayout carve;
 		const size_t oRec = carve(n * 16), oCnt = carve(n * 8), oCol = carve(n * 4), oRun = carve(n * 4), oColReq = carve(n * 4), oFlags = carve(n * 4),
 		             oBlockReq = carve(T * 4 + 4), oBlockNeed = carve(T * 4 + 4), oTotals = carve(4 * 8 + chunks * 8);
-		CVX_HIP(ctx, hipMalloc((void **)&j.scratch, bytes));
+		CVX_HIP(ctx, hipMalloc((void **)&j.scratch, carve.bytes));
 		A.rec = reinterpret_cast<uint4 *>(j.scratch + oRec);
 		A.cnt = reinterpret_cast<uint2 *>(j.scratch + oCnt);
 		A.colours = reinterpret_cast<uint32_t *>(j.scratch + oCol);
@@ -573,8 +572,7 @@ int ColumnEdit(cvx_context *ctx, const EditRectangle &R, int levelCount, const C
 		return call.failHip ? call.failHip(ctx, call.call, e) : Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call.call, hipGetErrorString(e));
 	};
 	const size_t n = (size_t)R.n, chunks = (n + ScanChunk() - 1) / ScanChunk();
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	cvxi::ScratchLayout carve;
 	const size_t oExtra = carve(call.extraScratchBytes), oCounts = carve(n * 4), oTotals = carve(call.totals ? 0 : 2 * 8), oChunks = carve(chunks * 8);
 	struct { unsigned long long total, overLimit; } own = { 0, 0 };
 	// 2. the scratch, the events
@@ -583,7 +581,7 @@ int ColumnEdit(cvx_context *ctx, const EditRectangle &R, int levelCount, const C
 		e = hipEventCreate(&held.ev[0]);
 		if (e == hipSuccess) { e = hipEventCreate(&held.ev[1]); }
 	}
-	if (e == hipSuccess) { e = hipMalloc((void **)&held.scratch, bytes); }
+	if (e == hipSuccess) { e = hipMalloc((void **)&held.scratch, carve.bytes); }
 	if (e == hipSuccess && !call.done) { e = hipEventRecord(held.ev[0], ctx->stream); }
 	if (e == hipSuccess && !call.totals) { e = hipMemsetAsync(held.scratch + oTotals, 0, sizeof own, ctx->stream); }
 	if (e != hipSuccess) { return failHip(e); }

@@ -40,6 +40,15 @@ int Fail(cvx_context *ctx, int code, const char *fmt, ...)
 	return code;
 }
 
+int FailHip(cvx_context *ctx, const char *call, hipError_t e)
+{
+	if (e == hipErrorOutOfMemory) {
+		(void)hipGetLastError();
+		return Fail(ctx, CVX_ERR_CAPACITY, "the scratch of %s does not fit in device memory", call);
+	}
+	return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
+}
+
 int ValidateRepeat(cvx_context *ctx)
 {
 	const int minDim = 1 << (CVX_LOD_LEVELS - 1);

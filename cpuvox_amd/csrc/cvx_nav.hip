@@ -30,16 +30,15 @@
 
 #include "cvx_context.h"
 #include "cvx_nav.h"
-#include "cvx_pieces_nodes.h"
 
 using cvxi::Fail;
 
 namespace cvxnav {
 
-using cvxpieces::FailHip;
-using cvxpieces::Grid;
-using cvxpieces::kThreads;
-using cvxpieces::WaveReduce;
+using cvxi::FailHip;
+using cvxi::Grid;
+using cvxi::kThreads;
+using cvxi::WaveReduce;
 
 constexpr int kTile = 16;              // interior cell columns of a tile per axis: kTile * kTile = the workgroup's threads
 constexpr int kSide = kTile + 2;       // ... with the halo
@@ -170,7 +169,7 @@ struct FieldView {
 	int64_t x, z;
 	__device__ uint32_t Lo(uint32_t i) const { return lohi[2 * (size_t)i]; }
 	__device__ uint32_t Hi(uint32_t i) const { return lohi[2 * (size_t)i + 1]; }
-	__device__ uint32_t Dist(uint32_t i) const { return cvxpieces::Load(dist + i); }
+	__device__ uint32_t Dist(uint32_t i) const { return cvxi::Load(dist + i); }
 	__device__ void SetDist(uint32_t i, uint32_t d) const { __hip_atomic_store(dist + i, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 	__device__ void Range(int k, uint32_t *first, uint32_t *end) const
 	{
@@ -264,7 +263,7 @@ __global__ __launch_bounds__(256) void nav_relax_kernel(NavTables T, int tilesZ)
 			const uint32_t g = sRowGlobal[r] + (j - sRowBase[r]);
 			sLo[j] = T.lohi[2 * (size_t)g];
 			sHi[j] = T.lohi[2 * (size_t)g + 1];
-			sDist[j] = cvxpieces::Load(T.dist + g);
+			sDist[j] = cvxi::Load(T.dist + g);
 		}
 		__syncthreads();
 		const TileView V{ sLo, sHi, sDist, sStart, (ix + 1) * kRowStarts + iz + 1 };

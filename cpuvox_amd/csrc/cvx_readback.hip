@@ -204,8 +204,7 @@ int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, in
 		return oom ? Fail(ctx, CVX_ERR_CAPACITY, "read-back: out of device memory") : Fail(ctx, CVX_ERR_HIP, "read-back failed: %s", hipGetErrorString(e));
 	};
 	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	cvxi::ScratchLayout carve;
 	const size_t oCounts = carve((size_t)n * 4), oTotal = carve(8), oChunks = carve(chunks * 8);
 	const DevWorldLevel &L = ctx->hostWorld.level[lod];
 	cvxread::ReadArgs A{};
@@ -223,7 +222,7 @@ int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, in
 	A.n = n;
 	// 1, 2. count, scan, one copy back
 	unsigned long long total = 0;
-	hipError_t e = hipMalloc((void **)&scratch, bytes);
+	hipError_t e = hipMalloc((void **)&scratch, carve.bytes);
 	if (e == hipSuccess && n > 0) { // (n = 0: a level without columns, LOD 5 of a world 16 columns wide -- its blob is the zero headers alone)
 		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
 		unsigned long long *dTotal = reinterpret_cast<unsigned long long *>(scratch + oTotal);
@@ -391,10 +390,9 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 		A.blockDepth = E.blockDepth;
 		const size_t colEntries = A.blocked ? (size_t)A.blockCount : A.recordCount;
 		const size_t chunks = (std::max(A.recordCount, colEntries) + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-		size_t bytes = 0;
-		auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+		cvxi::ScratchLayout carve;
 		const size_t oRun = carve(A.recordCount * 4), oCol = carve(colEntries * 4 + 4), oDepth = carve((size_t)A.blockCount * 4 + 4), oTotals = carve(2 * 8 + chunks * 8);
-		e = hipMalloc((void **)&l.scratch, bytes);
+		e = hipMalloc((void **)&l.scratch, carve.bytes);
 		if (e != hipSuccess) { return failed(e, "scratch"); }
 		A.runOff = reinterpret_cast<uint32_t *>(l.scratch + oRun);
 		A.colOff = reinterpret_cast<uint32_t *>(l.scratch + oCol);

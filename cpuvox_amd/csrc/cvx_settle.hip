@@ -1,7 +1,8 @@
 // cvx_settle.hip -- libcpuvox_gpu.so, the floating pieces of the device-resident world fall until they rest (cvx_world_settle).  See
 // include/cpuvox_gpu.h for the contract and cvx_settle.h for the rules.
 //
-// The pieces and their node tables come from cvxpieces::Analyse (cvx_pieces.hip, steps 1 .. 5).  How far piece p falls is the largest d with
+// The pieces and their node tables come from cvxpieces::Analyse (cvx_pieces.hip: the component engine of cvx_components.h with the pieces' rule
+// and select kernels).  How far piece p falls is the largest d with
 // d_p <= g for every node of p over something static with g voxels of air between, and d_p <= d_q + g for every node of p over floating piece q:
 // the shortest-path distance to "static" in the piece graph, found by relaxation.
 //   1. init   (a thread per node): drop[root] = the piece's lowest y (the floor bounds every piece), or maxDrop if that is smaller
@@ -32,10 +33,10 @@ using cvxi::Fail;
 
 namespace cvxsettle {
 
-using cvxpieces::kFloats;
-using cvxpieces::Load;
-using cvxpieces::PiecesArgs;
-using cvxpieces::WaveReduce;
+using cvxi::Load;
+using cvxi::WaveReduce;
+using cvxcomp::kSelected; // (in a root's bits: its piece floats)
+using cvxcomp::NodeArgs;
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr unsigned kSingleThreads = 1024;
@@ -52,7 +53,7 @@ struct SettleTotals {
 };
 
 struct SettleArgs {
-	PiecesArgs P;
+	NodeArgs P;
 	uint32_t *drop;   // per root: how far its piece falls
 	uint32_t *below;  // per node: the root of the floating piece under it, kNone: no constraint to relax
 	uint32_t *gap;    // per node: the air under it
@@ -63,7 +64,7 @@ struct SettleArgs {
 	int sweeps;       // per launch of settle_relax_kernel
 };
 
-__device__ inline bool Floats(const PiecesArgs &P, uint32_t root) { return (P.bits[root] & kFloats) != 0u; }
+__device__ inline bool Floats(const NodeArgs &P, uint32_t root) { return (P.bits[root] & kSelected) != 0u; }
 
 __global__ __launch_bounds__(256) void settle_init_kernel(SettleArgs A)
 {
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void settle_init_kernel(SettleArgs A)
 
 __global__ __launch_bounds__(256) void settle_gap_kernel(SettleArgs A)
 {
-	const PiecesArgs &P = A.P;
+	const NodeArgs &P = A.P;
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	uint32_t root = kNone, bound = kNone;
 	bool active = false;
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(1024) void settle_relax_single_kernel(SettleArgs A)
 
 __global__ __launch_bounds__(256) void settle_finish_kernel(SettleArgs A)
 {
-	const PiecesArgs &P = A.P;
+	const NodeArgs &P = A.P;
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	bool falls = false;
 	long long voxels = 0;
@@ -188,12 +189,12 @@ __global__ __launch_bounds__(256) void settle_finish_kernel(SettleArgs A)
 
 __global__ __launch_bounds__(256) void settle_count_kernel(SettleArgs A)
 {
-	const PiecesArgs &P = A.P;
+	const NodeArgs &P = A.P;
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= P.rn) { return; }
 	const int cx = P.rx0 + i / P.rSizeZ, cz = P.rz0 + i % P.rSizeZ;
 	uint32_t nodes;
-	const uint32_t *shift = cvxpieces::ColumnNodes(P, A.shift, cx, cz, &nodes);
+	const uint32_t *shift = cvxcomp::ColumnNodes(P, A.shift, cx, cz, &nodes);
 	const cvxb::BrushResult r = cvxb::SettleColumn(P.W, cx, cz, P.B.y0, P.B.y1, shift, nodes, nullptr, nullptr);
 	if (r.overLimit) { atomicOr(&P.totals->overLimit, 1u); }
 	P.counts[i] = cvxb::BlobElements(r);
@@ -201,12 +202,12 @@ __global__ __launch_bounds__(256) void settle_count_kernel(SettleArgs A)
 
 __global__ __launch_bounds__(256) void settle_write_kernel(SettleArgs A)
 {
-	const PiecesArgs &P = A.P;
+	const NodeArgs &P = A.P;
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= P.rn) { return; }
 	const int cx = P.rx0 + i / P.rSizeZ, cz = P.rz0 + i % P.rSizeZ;
 	uint32_t nodes;
-	const uint32_t *shift = cvxpieces::ColumnNodes(P, A.shift, cx, cz, &nodes);
+	const uint32_t *shift = cvxcomp::ColumnNodes(P, A.shift, cx, cz, &nodes);
 	const uint32_t off = P.counts[i];
 	uint32_t *e = P.elements + off;
 	const cvxb::BrushResult r = cvxb::SettleColumn(P.W, cx, cz, P.B.y0, P.B.y1, shift, nodes, nullptr, nullptr);
@@ -231,9 +232,9 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
                      int pieceCapacity, cvx_settle_summary *summary, float *outDeviceMs)
 {
 	using namespace cvxsettle;
-	using cvxpieces::FailHip;
-	using cvxpieces::Grid;
-	using cvxpieces::kThreads;
+	using cvxi::FailHip;
+	using cvxi::Grid;
+	using cvxi::kThreads;
 	static const char *const call = "cvx_world_settle";
 	char bad[40];
 	std::snprintf(bad, sizeof bad, "maxDrop %d is negative", maxDrop);
@@ -253,8 +254,7 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		if (relaxed) { (void)hipEventDestroy(relaxed); }
 		R.Release();
 	};
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	cvxi::ScratchLayout carve;
 	unsigned sweeps = 0, launches = 0;
 	bool single = nodes <= kSingleNodes;
 	float relaxMs = 0.f, editMs = 0.f;
@@ -270,7 +270,7 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		host.x0 = host.z0 = INT_MAX;
 		host.x1 = host.z1 = INT_MIN;
 		hipError_t e = hipEventCreate(&relaxed);
-		if (e == hipSuccess) { e = hipMalloc((void **)&settleScratch, bytes); }
+		if (e == hipSuccess) { e = hipMalloc((void **)&settleScratch, carve.bytes); }
 		if (e == hipSuccess) { e = hipMemcpyAsync(settleScratch + oTotals, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
 		if (e == hipSuccess) {
 			A.P = R.A;
@@ -332,7 +332,7 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 
 	// 5. the rectangle of the pieces that fall, with them where they land, through cvx_world_edit's machinery (cvxi::ColumnEdit)
 	if (out.fallenPieces) {
-		PiecesArgs &P = A.P;
+		NodeArgs &P = A.P;
 		cvxi::EditRectangle E;
 		rc = cvxi::RoundEditRectangle(ctx, host.x0, host.x1, host.z0, host.z1, levelCount, "a settle over", &E);
 		if (rc != CVX_OK) {
@@ -344,7 +344,7 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		P.rSizeZ = E.sizeZ;
 		P.rn = E.n;
 		cvxpieces::Totals back{};
-		const cvxi::ColumnEditTotals totals{ P.totals, &back, sizeof back, offsetof(cvxpieces::Totals, elements), offsetof(cvxpieces::Totals, overLimit) };
+		const cvxi::ColumnEditTotals totals{ P.totals, &back, sizeof back, offsetof(cvxpieces::Totals, head.elements), offsetof(cvxpieces::Totals, head.overLimit) };
 		cvxi::ColumnEditCall edit{ call, FailHip, "a column with its pieces settled", "the columns of the settle" };
 		edit.totals = &totals;
 		edit.done = R.ev[1];

@@ -25,7 +25,6 @@
 #include <algorithm>
 
 #include "cvx_context.h"
-#include "cvx_pieces_nodes.h"
 #include "cvx_spread.h"
 
 using cvxi::Fail;
@@ -41,7 +40,7 @@ using cvxb::kSpreadTileX;
 using cvxb::kSpreadTileY;
 using cvxb::kSpreadTileZ;
 using cvxb::kSpreadUnreached;
-using cvxpieces::WaveReduce;
+using cvxi::WaveReduce;
 
 constexpr unsigned kThreads = 256;
 constexpr int kWaves = kThreads / CVX_WAVE;

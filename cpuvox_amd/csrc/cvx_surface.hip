@@ -17,16 +17,15 @@
 #include <vector>
 
 #include "cvx_context.h"
-#include "cvx_pieces_nodes.h"
 #include "cvx_surface.h"
 
 using cvxi::Fail;
 
 namespace cvxsurface {
 
-using cvxpieces::FailHip;
-using cvxpieces::Grid;
-using cvxpieces::kThreads;
+using cvxi::FailHip;
+using cvxi::Grid;
+using cvxi::kThreads;
 
 constexpr int kFaces = 6;
 
@@ -135,14 +134,13 @@ static int Surface(cvx_context *ctx, const char *call, const int32_t boxMin[3], 
 		for (uint8_t *p : { scratch, list }) { if (p) { (void)hipFree(p); } }
 		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
 	};
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	cvxi::ScratchLayout carve;
 	const size_t chunks = ((size_t)pairs + 1 + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	const size_t oTotals = carve(sizeof(Totals)), oOffsets = carve(((size_t)pairs + 1) * 4), oChunks = carve(chunks * 8);
 	Totals host{};
 	hipError_t e = hipSuccess;
 	for (hipEvent_t &event : ev) { if (e == hipSuccess) { e = hipEventCreate(&event); } }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
+	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, carve.bytes); }
 	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
 	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, sizeof(Totals), ctx->stream); }
 	if (e == hipSuccess) {

@@ -22,16 +22,15 @@
 #include <vector>
 
 #include "cvx_context.h"
-#include "cvx_pieces_nodes.h"
 #include "cvx_surface_rects.h"
 
 using cvxi::Fail;
 
 namespace cvxrects {
 
-using cvxpieces::FailHip;
-using cvxpieces::Grid;
-using cvxpieces::kThreads;
+using cvxi::FailHip;
+using cvxi::Grid;
+using cvxi::kThreads;
 
 constexpr int kFaces = 6;
 
@@ -198,15 +197,14 @@ static int Rects(cvx_context *ctx, const char *call, const int32_t boxMin[3], co
 		for (uint8_t *p : { scratch, stripScratch, list }) { if (p) { (void)hipFree(p); } }
 		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
 	};
-	size_t bytes = 0;
-	auto carve = [&](size_t b) { const size_t at = bytes; bytes = (bytes + b + 15) & ~(size_t)15; return at; };
+	cvxi::ScratchLayout carve;
 	const size_t chunks = ((size_t)pairs + 1 + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	const size_t oTotals = carve(sizeof(Totals)), oStripOffsets = carve(((size_t)pairs + 1) * 4), oRectOffsets = carve(((size_t)pairs + 1) * 4);
 	const size_t oChunks = carve(chunks * 8), oChunks2 = carve(chunks * 8);
 	Totals host{};
 	hipError_t e = hipSuccess;
 	for (hipEvent_t &event : ev) { if (e == hipSuccess) { e = hipEventCreate(&event); } }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, bytes); }
+	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, carve.bytes); }
 	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
 	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, sizeof(Totals), ctx->stream); }
 	if (e == hipSuccess) {
@@ -233,9 +231,9 @@ static int Rects(cvx_context *ctx, const char *call, const int32_t boxMin[3], co
 	}
 	const size_t strips = (size_t)host.strips;
 	if (strips) {
-		bytes = 0;
+		carve.bytes = 0;
 		const size_t oStrips = carve(strips * sizeof(cvxb::RectStrip)), oAlong = carve(strips * 4), oRows = carve(strips * 4);
-		e = hipMalloc((void **)&stripScratch, bytes);
+		e = hipMalloc((void **)&stripScratch, carve.bytes);
 		if (e == hipSuccess) {
 			A.strips = reinterpret_cast<cvxb::RectStrip *>(stripScratch + oStrips);
 			A.along = reinterpret_cast<uint32_t *>(stripScratch + oAlong);

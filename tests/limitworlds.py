@@ -1,7 +1,7 @@
 """Test infrastructure (numpy only, no device): the volumes of tests/test_gpu_world_kernel_limits.py and the counts they are named after.
 
 The size limits of the world kernels are constants of the .hip files (the LDS list of light_brick_kernel, the node count up to which one
-workgroup relaxes a settle, the sweeps per relax launch, the waves of pieces_stats_kernel, the list head that travels with the totals).  Every
+workgroup relaxes a settle, the sweeps per relax launch, the waves of cvxcomp::stats_kernel, the list head that travels with the totals).  Every
 builder here returns a volume TOGETHER with the count that decides which side of such a limit it lies on, computed from the volume alone by the
 counting functions below; the GPU test asserts the count before it calls the device."""
 from __future__ import annotations
