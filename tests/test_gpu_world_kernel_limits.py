@@ -4,7 +4,9 @@ The limits are constants of the .hip files, not of the rules, so the host builds
 entries of light_brick_kernel's LDS list (a tile slab of 16 x 16 x 32 voxels holds up to 8192 and is shaded in rounds), the 4096 nodes up to
 which ONE workgroup relaxes a settle and the 8 sweeps per launch above it, the waves of cvxcomp::stats_kernel / settle_gap_kernel (one reduction
 where a wave's nodes share a root, atomics per node otherwise) and the 256 pieces that come to the host with the totals.  The stats kernel,
-the list and its head belong to the component engine (cvx_components.h): cvx_world_cavities runs the same code.
+the list and its head belong to the component engine (cvx_components.h), whose kernels are templates: cvx_world_cavities runs instantiations of
+its own (CavityRule), which tests/test_gpu_world_kernel_limits_later.py takes through the same wave shapes -- with the cases that carry a non-zero
+bit through the stats kernel's wave reduction, for both rules, and the limits of cvx_world_spread and cvx_world_nav_build.
 
 Every case builds its volume in numpy (tests/limitworlds.py, no device needed) and asserts FROM THE VOLUME, before the device is called, that the
 count it is named after is exactly that; only then are the device's results compared, byte for byte, with the dense models (lightmodel,

@@ -4,7 +4,8 @@ of tests/navmodel.py (blocked voxels by OR-ed shifts, clear ranges by cumulative
 
 - World mode: the noise worlds and the terrain worlds of _pick_world uploaded into a host-only context; for the whole world, an inner box with
   odd bounds and random calls, over widths 1 .. 3, heights 1, 2, 5 and (stepUp, maxDrop) in (0, 0), (1, 3), (h, 4096), the cvx_nav_step of EVERY
-  voxel position of the world and the deterministic summary fields equal the model's exactly.
+  voxel position of the world and the deterministic summary fields equal the model's exactly.  Widths 8, 7 and 5 with heights 64, 63 and 1 (the
+  largest the rule allows) on the constructed wall of limitworlds.nav_wide_world.
 - The struct layouts of the header against the ctypes, numpy and C# mirrors; every argument error that needs no device.
 
 The noise worlds: noise_world's 70 % solid leaves little standing room for a body wider than a voxel, so width w draws the same generator at
@@ -18,6 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import limitworlds as LW
 import movemodel
 import navmodel
 from cpuvox_amd import gpu, host
@@ -155,6 +157,34 @@ def test_terrain_worlds_equal_the_model(rules, tmp_path, dims, sparse, seed):
                     assert want["reached"] > 100 and want["goalsResolved"] >= 2, (name, want)
                 if sparse and width == 1 and name == "whole world":
                     assert want["nodes"] >= empty  # an empty column is one node on y = 0
+    finally:
+        ws.close()
+
+
+def wide_world():
+    """limitworlds.nav_wide_world as (solid, ws)."""
+    solid = LW.nav_wide_world()
+    x, y, z = np.nonzero(solid)
+    ws = host.WorldSet.from_voxels(LW.NAV_WIDE_DIMS, x.astype(np.int32), y.astype(np.int32), z.astype(np.int32), np.full(len(x), 0xFF808080, dtype=np.uint32), threads=2)
+    return solid, ws
+
+
+def test_the_widest_and_tallest_body_equals_the_model(rules, tmp_path):
+    """Widths 8 (kNavMaxWidth), 7 and 5 with heights 64 (kNavMaxHeight), 63 and 1: the w x w union walk of NavNextInterval at its largest, on a
+    wall whose openings are exactly 8 and 7 wide and leave exactly 64 and 63 clear, with two steps behind it."""
+    solid, ws = wide_world()
+    try:
+        assert [LW.nav_wide_passable(w, h) for w, h, _, _ in LW.NAV_WIDE_RULES] == [[0], [0, 2], [0, 1], [0, 1], [0, 1, 2]]
+        near = {}
+        for width, height, step_up, max_drop in LW.NAV_WIDE_RULES:
+            for name, call in world_calls(LW.NAV_WIDE_DIMS, width, height, step_up, max_drop).items():
+                got, summary, _, _ = run_world(rules, tmp_path, ws, *call, [LW.NAV_WIDE_GOAL])
+                assert_field(got, summary, solid, call, [LW.NAV_WIDE_GOAL], f"{name}, w {width} h {height}")
+                if name == "whole world":
+                    LW.assert_wide_openings(got, width, height)
+                    near[width, height] = int(got[10, 1, 23]["distance"])
+        assert near[8, 63] < near[8, 64] and near[8, 63] > 0, "one voxel less of height opens the nearer doorway"
+        assert near[5, 1] == -1, "no step up: the goal on the steps is out of reach"
     finally:
         ws.close()
 
