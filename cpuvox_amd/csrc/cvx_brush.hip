@@ -253,7 +253,7 @@ int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strok
 	A.n = R.n;
 	A.strokeCount = (int)live.size();
 	const dim3 grid(Grid((size_t)R.n, cvxbrush::kBrushThreads)), block(cvxbrush::kBrushThreads);
-	cvxi::ColumnEditCall call{ "brush", nullptr, "a brushed column", "the brushed columns" };
+	cvxi::ColumnEditCall call{ "brush", CVX_ERR_HIP, "a brushed column", "the brushed columns" };
 	call.extraScratchBytes = strokeBytes;
 	return cvxi::ColumnEdit(
 		ctx, R, levelCount, call,

@@ -20,7 +20,6 @@
 #include "cvx_context.h"
 
 using cvxi::Fail;
-using cvxi::FailHip;
 using cvxi::Grid;
 using cvxi::kThreads;
 using cvxi::WaveReduce;
@@ -177,7 +176,7 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 	C.maxVoxels = (unsigned long long)P.maxVoxels;
 	C.argb = P.argb;
 	Totals host{};
-	cvxcomp::Analysis R;
+	cvxcomp::Analysis R(ctx, call);
 	int rc = cvxcomp::Analyse(
 		ctx, engine, P.boxMin, P.boxMax,
 		[&](const NodeArgs &A) {
@@ -201,9 +200,9 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 		A.rSizeZ = E.sizeZ;
 		A.rn = E.n;
 		const cvxi::ColumnEditTotals totals{ A.totals, &host, sizeof host, offsetof(Totals, head.elements), offsetof(Totals, head.overLimit) };
-		cvxi::ColumnEditCall edit{ call, FailHip, "a filled column", "the columns of the fill", " (one colour per voxel)" };
+		cvxi::ColumnEditCall edit{ call, CVX_ERR_CAPACITY, "a filled column", "the columns of the fill", " (one colour per voxel)" };
 		edit.totals = &totals;
-		edit.done = R.ev[1];
+		edit.done = R.device.Event(1);
 		rc = cvxi::ColumnEdit(
 			ctx, E, levelCount, edit,
 			[&](const cvxi::ColumnEditJob &J) {
@@ -220,8 +219,8 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 			},
 			nullptr);
 		if (rc != CVX_OK) { return rc; }
-		(void)hipEventElapsedTime(&ms, R.ev[0], R.ev[1]);
-		editMs = ms - R.ms; // (ev[1] is the end of the analysis first and the end of the edit then)
+		ms = R.device.Ms();
+		editMs = ms - R.ms; // (the second event is the end of the analysis first and the end of the edit then)
 	}
 #ifdef CVX_CAVITY_DIAG
 	g_lastMs[0] = R.ms;

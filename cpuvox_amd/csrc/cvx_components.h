@@ -91,22 +91,18 @@ struct Call {
 // call lists (rank = 0 for every other node) and total what the call reports, the selected components' XZ box among it.
 using SelectLauncher = cvxi::Launcher<NodeArgs>;
 
-// What Analyse leaves behind, released with the struct.  A.offsets / A.totals live in columnScratch; the node tables in nodeScratch (null when the
-// box holds no node).
+// What Analyse leaves behind.  `device` holds the analysis' events and its scratch until the struct goes: A.offsets / A.totals live in its first
+// block, the node tables in its second (none when the box holds no node).  A call that goes on to cvxi::ColumnEdit hands it device.Event(1) as
+// `done`; device.Ms() then spans the analysis and the edit.
 struct Analysis {
 	NodeArgs A{};
 	size_t nodes = 0;
 	int64_t rounds = 0;          // hook / flatten passes
 	std::vector<cvx_piece> list; // the first min(capacity, selected) selected components
-	float ms = 0.f;              // device time of the analysis: ev[0] .. ev[1]
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	uint8_t *columnScratch = nullptr, *nodeScratch = nullptr;
+	float ms = 0.f;              // device time of the analysis alone
+	cvxi::DeviceCall device;
 
-	Analysis() = default;
-	Analysis(const Analysis &) = delete;
-	Analysis &operator=(const Analysis &) = delete;
-	~Analysis() { Release(); }
-	void Release();
+	Analysis(cvx_context *ctx, const char *call) : device(ctx, call) {}
 };
 
 // Clips the box (CVX_ERR_INVALID_ARGUMENT when nothing of it is inside the world), lays the world out (cvxi::SyncWorld) and runs steps 1 .. 5.

@@ -9,7 +9,6 @@
 #include "cvx_components.h"
 
 using cvxi::Fail;
-using cvxi::FailHip;
 using cvxi::Grid;
 using cvxi::kThreads;
 
@@ -53,14 +52,6 @@ void MarkSelected(hipStream_t stream, const NodeArgs &A) { hipLaunchKernelGGL(ma
 
 constexpr size_t kHead = 256; // components that come to the host with the totals, in one copy
 
-void Analysis::Release()
-{
-	for (uint8_t *p : { columnScratch, nodeScratch }) { if (p) { (void)hipFree(p); } }
-	for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	columnScratch = nodeScratch = nullptr;
-	ev[0] = ev[1] = nullptr;
-}
-
 int Analyse(cvx_context *ctx, const Call &call, const int32_t boxMin[3], const int32_t boxMax[3], SelectLauncher select, void *hostTotals, Analysis *R)
 {
 	NodeArgs &A = R->A;
@@ -77,17 +68,15 @@ int Analyse(cvx_context *ctx, const Call &call, const int32_t boxMin[3], const i
 	const RuleKernels &K = call.kernels;
 	const size_t totalsBytes = call.totalsBytes;
 	TotalsHead &host = *static_cast<TotalsHead *>(hostTotals);
-	hipEvent_t *ev = R->ev;
-	uint8_t *&columnScratch = R->columnScratch, *&nodeScratch = R->nodeScratch;
+	cvxi::DeviceCall &D = R->device;
+	uint8_t *columnScratch = nullptr, *nodeScratch = nullptr;
 	auto chunksOf = [](size_t count) { return (count + cvxi::ScanChunk() - 1) / cvxi::ScanChunk(); };
 
 	// 1. the nodes of every column, their offsets, the total
 	cvxi::ScratchLayout columns;
 	const size_t oTotals = columns(totalsBytes), oOffsets = columns(((size_t)n + 1) * 4), oChunks = columns(chunksOf((size_t)n + 1) * 8);
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) { e = hipMalloc((void **)&columnScratch, columns.bytes); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&columnScratch, columns.bytes);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(columnScratch + oTotals, hostTotals, totalsBytes, hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) {
 		A.W = cvxi::WorldOf(ctx);
@@ -101,7 +90,7 @@ int Analyse(cvx_context *ctx, const Call &call, const int32_t boxMin[3], const i
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host.nodes, &A.totals->nodes, sizeof host.nodes, hipMemcpyDeviceToHost, ctx->stream); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	}
-	if (e != hipSuccess) { return FailHip(ctx, call.call, e); }
+	if (e != hipSuccess) { return D.Fail(e); }
 	if (host.nodes >= ((unsigned long long)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "the box holds %llu %s", host.nodes, call.nodeNoun); }
 	const size_t nodes = (size_t)host.nodes;
 	R->nodes = nodes;
@@ -115,8 +104,8 @@ int Analyse(cvx_context *ctx, const Call &call, const int32_t boxMin[3], const i
 	             oVoxels = table(nodes * 8), oBounds = table(nodes * 24), oBits = table(nodes * 4), oRank = table(nodes * 4), oRankChunks = table(chunksOf(nodes) * 8);
 	std::vector<uint8_t> back(totalsBytes + std::min(listed, kHead) * sizeof(cvx_piece));
 	if (nodes) {
-		e = hipMalloc((void **)&nodeScratch, table.bytes);
-		if (e != hipSuccess) { return FailHip(ctx, call.call, e); }
+		e = D.Allocate(&nodeScratch, table.bytes);
+		if (e != hipSuccess) { return D.Fail(e); }
 		A.list = reinterpret_cast<cvx_piece *>(nodeScratch + oList);
 		A.lohi = reinterpret_cast<uint32_t *>(nodeScratch + oLohi);
 		A.column = reinterpret_cast<uint32_t *>(nodeScratch + oColumn);
@@ -149,9 +138,9 @@ int Analyse(cvx_context *ctx, const Call &call, const int32_t boxMin[3], const i
 			if (e == hipSuccess) { e = hipMemcpyAsync(back.data(), nodeScratch + oHead, back.size(), hipMemcpyDeviceToHost, ctx->stream); }
 		}
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return FailHip(ctx, call.call, e); }
+	if (e != hipSuccess) { return D.Fail(e); }
 	if (nodes) { std::memcpy(hostTotals, back.data(), totalsBytes); }
 	const size_t wanted = std::min<size_t>((size_t)host.listed, (size_t)call.capacity);
 	R->list.assign(wanted, cvx_piece{});
@@ -160,11 +149,10 @@ int Analyse(cvx_context *ctx, const Call &call, const int32_t boxMin[3], const i
 		std::memcpy(R->list.data(), back.data() + totalsBytes, head * sizeof(cvx_piece));
 		if (wanted > head) {
 			e = hipMemcpy(R->list.data() + head, A.list + head, (wanted - head) * sizeof(cvx_piece), hipMemcpyDeviceToHost);
-			if (e != hipSuccess) { return FailHip(ctx, call.call, e); }
+			if (e != hipSuccess) { return D.Fail(e); }
 		}
 	}
-	R->ms = 0.f;
-	(void)hipEventElapsedTime(&R->ms, ev[0], ev[1]);
+	R->ms = D.Ms();
 	return CVX_OK;
 }
 

@@ -147,10 +147,101 @@ namespace cvxi {
 // Records the message on the context (or for cvx_last_error(NULL) when ctx is null) and returns `code`.
 int Fail(cvx_context *ctx, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 
-// cvx_gpu.hip: hipErrorOutOfMemory -> CVX_ERR_CAPACITY ("the scratch of <call> does not fit in device memory"), anything else -> CVX_ERR_HIP
-int FailHip(cvx_context *ctx, const char *call, hipError_t e);
-
 inline bool IsPow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// The runtime calls DeviceCall makes, as a table, so that its ownership rules compile and run without a device (tests/device_call_rules.cpp)
+struct DeviceApi {
+	hipError_t (*malloc)(void **, size_t);
+	hipError_t (*free)(void *);
+	hipError_t (*eventCreate)(hipEvent_t *);
+	hipError_t (*eventRecord)(hipEvent_t, hipStream_t);
+	hipError_t (*eventDestroy)(hipEvent_t);
+	hipError_t (*eventElapsedTime)(float *, hipEvent_t, hipEvent_t);
+	hipError_t (*getLastError)();
+	const char *(*getErrorString)(hipError_t);
+};
+const DeviceApi &HipApi(); // cvx_gpu.hip: the HIP runtime
+
+// What one world call borrows from the device -- its scratch blocks and the event pair around its work on ctx->stream -- given back by the
+// destructor on every path.  It owns nothing of the context's lifetime (the arena, the buffers grown on demand, the draw-time event pairs).
+class DeviceCall {
+public:
+	static constexpr int kBlocks = 24; // (the mesh stamp holds 19; every other call five at the most)
+
+	DeviceCall(cvx_context *ctx, const char *call) : DeviceCall(ctx, call, ctx->stream, HipApi()) {}
+	DeviceCall(cvx_context *ctx, const char *call, hipStream_t stream, const DeviceApi &api) : ctx(ctx), call(call), stream(stream), api(api) {}
+	DeviceCall(const DeviceCall &) = delete;
+	DeviceCall &operator=(const DeviceCall &) = delete;
+	~DeviceCall()
+	{
+		for (int i = 0; i < blockCount; i++) { if (blocks[i]) { (void)api.free(blocks[i]); } }
+		if (ev[0] && !adopted) { (void)api.eventDestroy(ev[0]); }
+		if (ev[1]) { (void)api.eventDestroy(ev[1]); }
+	}
+
+	// Creates the event pair and records the first event on the stream.  With `start`, an event the caller recorded earlier and goes on
+	// owning, only the second event is created.
+	hipError_t Begin(hipEvent_t start = nullptr)
+	{
+		adopted = start != nullptr;
+		ev[0] = start;
+		hipError_t e = adopted ? hipSuccess : api.eventCreate(&ev[0]);
+		if (e == hipSuccess) { e = api.eventCreate(&ev[1]); }
+		if (e == hipSuccess && !adopted) { e = api.eventRecord(ev[0], stream); }
+		return e;
+	}
+	// `bytes` of device memory that the destructor frees
+	template <class T> hipError_t Allocate(T **out, size_t bytes)
+	{
+		*out = nullptr;
+		if (blockCount == kBlocks) { return hipErrorInvalidValue; }
+		void *p = nullptr;
+		const hipError_t e = api.malloc(&p, bytes);
+		if (e == hipSuccess) {
+			blocks[blockCount++] = p;
+			*out = static_cast<T *>(p);
+		} else {
+			failedBytes = bytes;
+		}
+		return e;
+	}
+	// Hands the block to the caller: the destructor no longer frees it
+	template <class T> T *Keep(T *block)
+	{
+		for (int i = 0; i < blockCount; i++) { if (blocks[i] == block) { blocks[i] = nullptr; } }
+		return block;
+	}
+	// Records the second event on the stream
+	hipError_t End() { return api.eventRecord(ev[1], stream); }
+	// The pair's events, for a caller that records one itself or hands its start on (EditFromDevice's `done`, cvxnav::Solve's `start`)
+	hipEvent_t Event(int which) const { return ev[which]; }
+	// Device milliseconds between the two events once the stream has run both; 0 if the runtime cannot tell
+	float Ms() const
+	{
+		float ms = 0.f;
+		return ev[1] && api.eventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess ? ms : 0.f;
+	}
+	// The failure path of a world call: hipErrorOutOfMemory clears the thread's last error (hipGetLastError keeps returning it otherwise,
+	// also to the next call's launch checks) and returns oomCode, anything else is CVX_ERR_HIP "<call> failed: <error>"
+	int Fail(hipError_t e, int oomCode = CVX_ERR_CAPACITY)
+	{
+		if (e != hipErrorOutOfMemory) { return cvxi::Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, api.getErrorString(e)); }
+		(void)api.getLastError();
+		if (failedBytes) { return cvxi::Fail(ctx, oomCode, "%s: out of device memory (an allocation of %zu bytes)", call, failedBytes); }
+		return cvxi::Fail(ctx, oomCode, "%s: out of device memory", call);
+	}
+
+private:
+	cvx_context *ctx;
+	const char *call;
+	hipStream_t stream;
+	const DeviceApi &api;
+	void *blocks[kBlocks];
+	int blockCount = 0;
+	hipEvent_t ev[2] = { nullptr, nullptr };
+	bool adopted = false;
+	size_t failedBytes = 0;
+};
 
 // the world calls' kernels: a thread per column, node or pair, kThreads to a workgroup
 constexpr unsigned kThreads = 256;
@@ -238,8 +329,8 @@ struct ColumnEditTotals {
 	size_t totalAt, overLimitAt;
 };
 struct ColumnEditCall {
-	const char *call;                      // HIP failures: "<call> failed: <error>" ...
-	int (*failHip)(cvx_context *, const char *call, hipError_t) = nullptr; // ... or what this returns (a call that reports hipErrorOutOfMemory its own way)
+	const char *call;                      // HIP failures: DeviceCall::Fail under this name ...
+	int oomCode;                           // ... with this code for hipErrorOutOfMemory: CVX_ERR_HIP or CVX_ERR_CAPACITY, as the call's header promises
 	const char *overLimitSubject;          // "<a brushed column> would need ..." (what the format cannot hold)
 	const char *elementsSubject;           // "<the brushed columns> need %llu elements"
 	const char *overLimitNote = "";        // appended to the first message
@@ -265,6 +356,10 @@ public:
 	hipError_t operator()(const Job &J) const { return invoke(object, J); }
 };
 using ColumnEditLauncher = Launcher<ColumnEditJob>;
+// cvx_gpu.hip: the relaxations' "relaunch until a launch lowers nothing".  Per round: clears *changed (device), launch(k) enqueues launch k = 0, 1, ..
+// on ctx->stream, the word comes back, the stream is synchronised; a launch that leaves it 0 is the last.  Returns the number of launches, or -1
+// when `bound` launches did not settle it (the stream is synchronised then).  *error: the first HIP error, which ends the loop as well.
+int64_t LaunchUntilUnchanged(cvx_context *ctx, unsigned int *changed, int64_t bound, Launcher<int64_t> launch, hipError_t *error);
 // Steps 2 .. 6 of the pipeline (cvx_edit.hip's header) on ctx->stream: scratch, launchCount (its uploads, then its count kernel), cvxi::ExclusiveScan, one
 // copy back and one synchronisation, the two capacity checks, the blob's allocation, launchWrite (its write kernel and whatever shades the blob),
 // EditFromDevice.  Everything the pipeline allocated is released on every path; nothing in the arena is written before EditFromDevice.

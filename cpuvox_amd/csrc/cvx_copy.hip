@@ -146,7 +146,7 @@ int cvx_world_copy(cvx_context *ctx, const cvx_copy_placement *placements, int p
 	A.sizeZ = R.sizeZ;
 	A.n = R.n;
 	A.placementCount = (int)live.size();
-	cvxi::ColumnEditCall call{ "copy", nullptr, "a copied column", "the copied columns" };
+	cvxi::ColumnEditCall call{ "copy", CVX_ERR_HIP, "a copied column", "the copied columns" };
 	call.extraScratchBytes = placementBytes;
 	return cvxi::ColumnEdit(
 		ctx, R, levelCount, call,

@@ -198,43 +198,23 @@ int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int3
 		CVX_HIP(ctx, hipGetLastError());
 		return CVX_OK;
 	}
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
 	const size_t argbBytes = argb ? (size_t)n * 4 : 0, solidBytes = solid ? (size_t)n : 0;
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) {
-		e = hipMalloc((void **)&scratch, argbBytes + solidBytes);
-		if (e == hipErrorOutOfMemory) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the box", call, argbBytes + solidBytes);
-		}
-	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&scratch, argbBytes + solidBytes);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) {
 		A.argb = argb ? reinterpret_cast<uint32_t *>(scratch) : nullptr;
 		A.solid = solid ? scratch + argbBytes : nullptr;
 		hipLaunchKernelGGL(cvxdense::dense_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess && argb) { e = hipMemcpyAsync(argb, A.argb, argbBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess && solid) { e = hipMemcpyAsync(solid, A.solid, solidBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
-	}
-	if (outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return CVX_OK;
 }
 
@@ -268,33 +248,30 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	if (rc != CVX_OK) { return rc; }
 
 	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it
-	struct Dense {
-		uint8_t *p = nullptr;
-		~Dense() { if (p) { (void)hipFree(p); } }
-	} dense;
+	cvxi::DeviceCall upload(ctx, call);
+	uint8_t *dense = nullptr;
 	const size_t argbBytes = argb ? ((size_t)elements * 4 + 15) & ~(size_t)15 : 0, solidBytes = solid ? (size_t)elements : 0;
 	if (!device) {
-		const hipError_t e = hipMalloc((void **)&dense.p, argbBytes + solidBytes);
-		if (e == hipErrorOutOfMemory) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the box", call, argbBytes + solidBytes); }
-		if (e != hipSuccess) { return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e)); }
+		const hipError_t e = upload.Allocate(&dense, argbBytes + solidBytes);
+		if (e != hipSuccess) { return upload.Fail(e); }
 	}
 	A.W = cvxi::WorldOf(ctx);
-	A.argb = device ? argb : (argb ? reinterpret_cast<const uint32_t *>(dense.p) : nullptr);
-	A.solid = device ? solid : (solid ? dense.p + argbBytes : nullptr);
+	A.argb = device ? argb : (argb ? reinterpret_cast<const uint32_t *>(dense) : nullptr);
+	A.solid = device ? solid : (solid ? dense + argbBytes : nullptr);
 	A.op = op;
 	A.x0 = R.x0;
 	A.z0 = R.z0;
 	A.sizeZ = R.sizeZ;
 	A.n = R.n;
 	const dim3 grid(Grid((size_t)R.n, cvxdense::kWavesPerBlock)), block(kThreads);
-	cvxi::ColumnEditCall edit{ call, nullptr, "a written column", "the written columns" };
+	cvxi::ColumnEditCall edit{ call, CVX_ERR_HIP, "a written column", "the written columns" };
 	edit.extraScratchBytes = (size_t)R.n * 4; // the run counts
 	return cvxi::ColumnEdit(
 		ctx, R, levelCount, edit,
 		[&](const cvxi::ColumnEditJob &J) {
 			hipError_t e = hipSuccess;
-			if (!device && argb) { e = hipMemcpyAsync(dense.p, argb, (size_t)elements * 4, hipMemcpyHostToDevice, ctx->stream); }
-			if (e == hipSuccess && !device && solid) { e = hipMemcpyAsync(dense.p + argbBytes, solid, solidBytes, hipMemcpyHostToDevice, ctx->stream); }
+			if (!device && argb) { e = hipMemcpyAsync(dense, argb, (size_t)elements * 4, hipMemcpyHostToDevice, ctx->stream); }
+			if (e == hipSuccess && !device && solid) { e = hipMemcpyAsync(dense + argbBytes, solid, solidBytes, hipMemcpyHostToDevice, ctx->stream); }
 			A.counts = J.counts;
 			A.runCounts = reinterpret_cast<uint32_t *>(J.extra);
 			A.overLimit = J.overLimit;

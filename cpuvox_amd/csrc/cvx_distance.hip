@@ -108,22 +108,10 @@ int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const 
 	rc = cvxi::SyncWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) {
-		e = hipMalloc((void **)&scratch, bytesY + bytesZ + bytesOut);
-		if (e == hipErrorOutOfMemory) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the scratch", call, bytesY + bytesZ + bytesOut);
-		}
-	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&scratch, bytesY + bytesZ + bytesOut);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) {
 		A.W = cvxi::WorldOf(ctx);
 		A.fromY = reinterpret_cast<uint16_t *>(scratch);
@@ -137,19 +125,11 @@ int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const 
 		}
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess && !device) { e = hipMemcpyAsync(out, A.out, bytesOut, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
-	}
-	if (outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return CVX_OK;
 }
 

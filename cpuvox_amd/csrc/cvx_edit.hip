@@ -219,11 +219,10 @@ constexpr unsigned kThreads = 256;
 
 unsigned Grid(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-// one level's share of an edit: the rectangle, its columns on the device, and the scratch of the plan
+// one level's share of an edit: the rectangle, its columns on the device, and the plan's totals (its scratch is the call's, ApplyJobs)
 struct Job {
 	int lod = 0, x0 = 0, z0 = 0, sizeX = 0, sizeZ = 0;
 	const uint32_t *headers = nullptr, *elements = nullptr;
-	uint8_t *scratch = nullptr;
 	EditArgs A{};
 	unsigned long long *totals = nullptr; // device: [0] run entries, [1] colour slots (columns), [2] colour slots (blocks), [3] abandoned bytes, then chunk sums
 	unsigned long long host[4] = { 0, 0, 0, 0 };
@@ -320,12 +319,9 @@ int Relayout(cvx_context *ctx, const bool tail[CVX_LOD_LEVELS], const int64_t ne
 		return Fail(ctx, CVX_ERR_CAPACITY, "the edited world needs %.2f GiB of device tables: more than the 4 GiB the 32-bit offsets of the kernel can address", (double)cursor / (double)((size_t)1 << 30));
 	}
 	CVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	cvxi::DeviceCall D(ctx, "the arena layout of the edit");
 	uint8_t *arena = nullptr;
-	hipError_t e = hipMalloc((void **)&arena, cursor);
-	if (e == hipErrorOutOfMemory) {
-		(void)hipGetLastError();
-		return Fail(ctx, CVX_ERR_CAPACITY, "no device memory for an arena of %.2f GiB", (double)cursor / (double)((size_t)1 << 30));
-	}
+	hipError_t e = D.Allocate(&arena, cursor);
 	if (e == hipSuccess) { e = hipMemsetAsync(arena, 0, cursor, ctx->stream); }
 	for (int i = 0; i < CVX_LOD_LEVELS && e == hipSuccess; i++) {
 		const cvx_context::HostLevel &H = ctx->hostLevel[i];
@@ -336,12 +332,9 @@ int Relayout(cvx_context *ctx, const bool tail[CVX_LOD_LEVELS], const int64_t ne
 		if (e == hipSuccess) { e = hipMemcpyAsync(arena + elementsAt[i], ctx->arena + old.elementsOff, elementsCopy[i], hipMemcpyDeviceToDevice, ctx->stream); }
 	}
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		if (arena) { (void)hipFree(arena); }
-		return Fail(ctx, CVX_ERR_HIP, "arena layout for the edit failed: %s", hipGetErrorString(e));
-	}
+	if (e != hipSuccess) { return D.Fail(e); }
 	(void)hipFree(ctx->arena);
-	ctx->arena = arena;
+	ctx->arena = D.Keep(arena);
 	ctx->arenaBytes = cursor;
 	ctx->hostWorld.arena = arena;
 	for (int i = 0; i < CVX_LOD_LEVELS; i++) {
@@ -362,16 +355,8 @@ int Relayout(cvx_context *ctx, const bool tail[CVX_LOD_LEVELS], const int64_t ne
 	return CVX_OK;
 }
 
-void FreeJobs(std::vector<Job> &jobs)
-{
-	for (Job &j : jobs) {
-		if (j.scratch) { (void)hipFree(j.scratch); }
-		j.scratch = nullptr;
-	}
-}
-
-// Steps 1 .. 4 (file comment) for one rectangle per level; the columns of every job are on the device and valid.
-int ApplyJobs(cvx_context *ctx, std::vector<Job> &jobs)
+// Steps 1 .. 4 (file comment) for one rectangle per level; the columns of every job are on the device and valid.  D: the call, which owns the plans' scratch.
+int ApplyJobs(cvx_context *ctx, cvxi::DeviceCall &D, std::vector<Job> &jobs)
 {
 	const DevWorld &W = ctx->hostWorld;
 	// 1. plan
@@ -408,16 +393,18 @@ int ApplyJobs(cvx_context *ctx, std::vector<Job> &jobs)
 		cvxi::ScratchLayout carve;
 		const size_t oRec = carve(n * 16), oCnt = carve(n * 8), oCol = carve(n * 4), oRun = carve(n * 4), oColReq = carve(n * 4), oFlags = carve(n * 4),
 		             oBlockReq = carve(T * 4 + 4), oBlockNeed = carve(T * 4 + 4), oTotals = carve(4 * 8 + chunks * 8);
-		CVX_HIP(ctx, hipMalloc((void **)&j.scratch, carve.bytes));
-		A.rec = reinterpret_cast<uint4 *>(j.scratch + oRec);
-		A.cnt = reinterpret_cast<uint2 *>(j.scratch + oCnt);
-		A.colours = reinterpret_cast<uint32_t *>(j.scratch + oCol);
-		A.runReq = reinterpret_cast<uint32_t *>(j.scratch + oRun);
-		A.colReq = reinterpret_cast<uint32_t *>(j.scratch + oColReq);
-		A.flags = reinterpret_cast<uint32_t *>(j.scratch + oFlags);
-		A.blockReq = reinterpret_cast<uint32_t *>(j.scratch + oBlockReq);
-		A.blockNeed = reinterpret_cast<uint32_t *>(j.scratch + oBlockNeed);
-		j.totals = reinterpret_cast<unsigned long long *>(j.scratch + oTotals);
+		uint8_t *scratch = nullptr;
+		const hipError_t allocated = D.Allocate(&scratch, carve.bytes);
+		if (allocated != hipSuccess) { return D.Fail(allocated, CVX_ERR_HIP); }
+		A.rec = reinterpret_cast<uint4 *>(scratch + oRec);
+		A.cnt = reinterpret_cast<uint2 *>(scratch + oCnt);
+		A.colours = reinterpret_cast<uint32_t *>(scratch + oCol);
+		A.runReq = reinterpret_cast<uint32_t *>(scratch + oRun);
+		A.colReq = reinterpret_cast<uint32_t *>(scratch + oColReq);
+		A.flags = reinterpret_cast<uint32_t *>(scratch + oFlags);
+		A.blockReq = reinterpret_cast<uint32_t *>(scratch + oBlockReq);
+		A.blockNeed = reinterpret_cast<uint32_t *>(scratch + oBlockNeed);
+		j.totals = reinterpret_cast<unsigned long long *>(scratch + oTotals);
 		A.abandoned = j.totals + 3;
 		CVX_HIP(ctx, hipMemsetAsync(j.totals, 0, 4 * 8, ctx->stream));
 		if (A.blocked) {
@@ -502,21 +489,21 @@ namespace cvxi {
 int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const uint8_t *dSrc, int64_t elementsOfColumns, int columnCount, int levelCount,
                    hipEvent_t done)
 {
-	uint32_t *lodHeaders[CVX_LOD_LEVELS] = {}, *lodElements[CVX_LOD_LEVELS] = {};
+	struct Lods { // BuildLodChainOnDevice's levels, which it leaves to its caller to free
+		uint32_t *headers[CVX_LOD_LEVELS] = {}, *elements[CVX_LOD_LEVELS] = {};
+		~Lods()
+		{
+			for (int j = 0; j < CVX_LOD_LEVELS; j++) {
+				if (headers[j]) { (void)hipFree(headers[j]); }
+				if (elements[j]) { (void)hipFree(elements[j]); }
+			}
+		}
+	} lods;
+	DeviceCall D(ctx, "edit");
 	std::vector<Job> jobs;
-	auto release = [&]() {
-		FreeJobs(jobs);
-		for (int j = 0; j < CVX_LOD_LEVELS; j++) {
-			if (lodHeaders[j]) { (void)hipFree(lodHeaders[j]); }
-			if (lodElements[j]) { (void)hipFree(lodElements[j]); }
-		}
-	};
 	if (levelCount > 0) {
-		const int rc = BuildLodChainOnDevice(ctx, dSrc, elementsOfColumns, sizeX, ctx->hostWorld.dimY, sizeZ, columnCount, levelCount, lodHeaders + 1, lodElements + 1);
-		if (rc != CVX_OK) {
-			release();
-			return rc;
-		}
+		const int rc = BuildLodChainOnDevice(ctx, dSrc, elementsOfColumns, sizeX, ctx->hostWorld.dimY, sizeZ, columnCount, levelCount, lods.headers + 1, lods.elements + 1);
+		if (rc != CVX_OK) { return rc; }
 	}
 	for (int l = 0; l <= levelCount; l++) {
 		Job j;
@@ -525,16 +512,15 @@ int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 		j.z0 = z0 >> l;
 		j.sizeX = sizeX >> l;
 		j.sizeZ = sizeZ >> l;
-		j.headers = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc) : lodHeaders[l];
-		j.elements = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc + (size_t)columnCount * 12) : lodElements[l];
+		j.headers = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc) : lods.headers[l];
+		j.elements = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc + (size_t)columnCount * 12) : lods.elements[l];
 		jobs.push_back(j);
 	}
-	int rc = ApplyJobs(ctx, jobs);
+	int rc = ApplyJobs(ctx, D, jobs);
 	hipError_t e = hipSuccess;
 	if (rc == CVX_OK && done) { e = hipEventRecord(done, ctx->stream); }
 	const hipError_t s = hipStreamSynchronize(ctx->stream);
-	if (rc == CVX_OK && (e != hipSuccess || s != hipSuccess)) { rc = Fail(ctx, CVX_ERR_HIP, "edit failed: %s", hipGetErrorString(e != hipSuccess ? e : s)); }
-	release();
+	if (rc == CVX_OK && (e != hipSuccess || s != hipSuccess)) { rc = D.Fail(e != hipSuccess ? e : s, CVX_ERR_HIP); }
 	return rc;
 }
 
@@ -558,45 +544,29 @@ int RoundEditRectangle(cvx_context *ctx, int64_t x0, int64_t x1, int64_t z0, int
 int ColumnEdit(cvx_context *ctx, const EditRectangle &R, int levelCount, const ColumnEditCall &call, ColumnEditLauncher launchCount, ColumnEditLauncher launchWrite,
                float *outMs)
 {
-	struct Held { // what the pipeline allocates, released on every path
-		uint8_t *scratch = nullptr, *blob = nullptr;
-		hipEvent_t ev[2] = { nullptr, nullptr };
-		~Held()
-		{
-			if (scratch) { (void)hipFree(scratch); }
-			if (blob) { (void)hipFree(blob); }
-			for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-		}
-	} held;
-	auto failHip = [&](hipError_t e) {
-		return call.failHip ? call.failHip(ctx, call.call, e) : Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call.call, hipGetErrorString(e));
-	};
+	DeviceCall held(ctx, call.call); // what the pipeline allocates, released on every path
+	uint8_t *scratch = nullptr, *blob = nullptr;
 	const size_t n = (size_t)R.n, chunks = (n + ScanChunk() - 1) / ScanChunk();
 	cvxi::ScratchLayout carve;
 	const size_t oExtra = carve(call.extraScratchBytes), oCounts = carve(n * 4), oTotals = carve(call.totals ? 0 : 2 * 8), oChunks = carve(chunks * 8);
 	struct { unsigned long long total, overLimit; } own = { 0, 0 };
 	// 2. the scratch, the events
-	hipError_t e = hipSuccess;
-	if (!call.done) {
-		e = hipEventCreate(&held.ev[0]);
-		if (e == hipSuccess) { e = hipEventCreate(&held.ev[1]); }
-	}
-	if (e == hipSuccess) { e = hipMalloc((void **)&held.scratch, carve.bytes); }
-	if (e == hipSuccess && !call.done) { e = hipEventRecord(held.ev[0], ctx->stream); }
-	if (e == hipSuccess && !call.totals) { e = hipMemsetAsync(held.scratch + oTotals, 0, sizeof own, ctx->stream); }
-	if (e != hipSuccess) { return failHip(e); }
-	const ColumnEditTotals T = call.totals ? *call.totals : ColumnEditTotals{ held.scratch + oTotals, &own, sizeof own, 0, 8 };
-	ColumnEditJob J{ R, reinterpret_cast<uint32_t *>(held.scratch + oCounts), reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(T.from) + T.totalAt),
-	                 reinterpret_cast<unsigned int *>(static_cast<uint8_t *>(T.from) + T.overLimitAt), held.scratch + oExtra, nullptr, nullptr };
+	hipError_t e = held.Allocate(&scratch, carve.bytes);
+	if (e == hipSuccess && !call.done) { e = held.Begin(); }
+	if (e == hipSuccess && !call.totals) { e = hipMemsetAsync(scratch + oTotals, 0, sizeof own, ctx->stream); }
+	if (e != hipSuccess) { return held.Fail(e, call.oomCode); }
+	const ColumnEditTotals T = call.totals ? *call.totals : ColumnEditTotals{ scratch + oTotals, &own, sizeof own, 0, 8 };
+	ColumnEditJob J{ R, reinterpret_cast<uint32_t *>(scratch + oCounts), reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(T.from) + T.totalAt),
+	                 reinterpret_cast<unsigned int *>(static_cast<uint8_t *>(T.from) + T.overLimitAt), scratch + oExtra, nullptr, nullptr };
 	// 3. count, scan, one copy back, one synchronisation
 	e = launchCount(J);
 	if (e == hipSuccess) {
-		ExclusiveScan(ctx->stream, J.counts, R.n, reinterpret_cast<unsigned long long *>(held.scratch + oChunks), J.total);
+		ExclusiveScan(ctx->stream, J.counts, R.n, reinterpret_cast<unsigned long long *>(scratch + oChunks), J.total);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) { e = hipMemcpyAsync(T.to, T.from, T.bytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return failHip(e); }
+	if (e != hipSuccess) { return held.Fail(e, call.oomCode); }
 	// 4. what the blob's format cannot hold
 	unsigned long long total;
 	unsigned int overLimit;
@@ -608,20 +578,17 @@ int ColumnEdit(cvx_context *ctx, const EditRectangle &R, int levelCount, const C
 	}
 	if (total >= ((unsigned long long)1 << 31) - (unsigned long long)n * 3) { return Fail(ctx, CVX_ERR_CAPACITY, "%s need %llu elements", call.elementsSubject, total); }
 	// 5. the sub-world blob
-	e = hipMalloc((void **)&held.blob, std::max<size_t>(n * 12 + (size_t)total * 4, 4));
+	e = held.Allocate(&blob, std::max<size_t>(n * 12 + (size_t)total * 4, 4));
 	if (e == hipSuccess) {
-		J.headers = reinterpret_cast<uint32_t *>(held.blob);
-		J.elements = reinterpret_cast<uint32_t *>(held.blob + n * 12);
+		J.headers = reinterpret_cast<uint32_t *>(blob);
+		J.elements = reinterpret_cast<uint32_t *>(blob + n * 12);
 		e = launchWrite(J);
 	}
 	if (e == hipSuccess) { e = hipGetLastError(); }
-	if (e != hipSuccess) { return failHip(e); }
+	if (e != hipSuccess) { return held.Fail(e, call.oomCode); }
 	// 6. cvx_world_edit's machinery
-	const int rc = EditFromDevice(ctx, R.x0, R.z0, R.sizeX, R.sizeZ, held.blob, (int64_t)total, R.n, levelCount, call.done ? call.done : held.ev[1]);
-	if (rc == CVX_OK && !call.done && outMs) {
-		float ms = 0.f;
-		*outMs = hipEventElapsedTime(&ms, held.ev[0], held.ev[1]) == hipSuccess ? ms : 0.f;
-	}
+	const int rc = EditFromDevice(ctx, R.x0, R.z0, R.sizeX, R.sizeZ, blob, (int64_t)total, R.n, levelCount, call.done ? call.done : held.Event(1));
+	if (rc == CVX_OK && !call.done && outMs) { *outMs = held.Ms(); }
 	return rc;
 }
 
@@ -649,8 +616,10 @@ int cvx_world_set_columns(cvx_context *ctx, int lod, int x0, int z0, int sizeX, 
 	if (rc != CVX_OK) { return rc; }
 	rc = Prepare(ctx);
 	if (rc != CVX_OK) { return rc; }
+	cvxi::DeviceCall D(ctx, "cvx_world_set_columns");
 	uint8_t *dSrc = nullptr;
-	CVX_HIP(ctx, hipMalloc((void **)&dSrc, (size_t)std::max<int64_t>(byteLength, 4)));
+	hipError_t e = D.Allocate(&dSrc, (size_t)std::max<int64_t>(byteLength, 4));
+	if (e != hipSuccess) { return D.Fail(e, CVX_ERR_HIP); }
 	std::vector<Job> jobs(1);
 	jobs[0].lod = lod;
 	jobs[0].x0 = x0;
@@ -659,12 +628,10 @@ int cvx_world_set_columns(cvx_context *ctx, int lod, int x0, int z0, int sizeX, 
 	jobs[0].sizeZ = sizeZ;
 	jobs[0].headers = reinterpret_cast<const uint32_t *>(dSrc);
 	jobs[0].elements = reinterpret_cast<const uint32_t *>(dSrc + (size_t)columnCount * 12);
-	hipError_t e = hipMemcpyAsync(dSrc, storage, (size_t)byteLength, hipMemcpyHostToDevice, ctx->stream);
-	rc = e == hipSuccess ? ApplyJobs(ctx, jobs) : Fail(ctx, CVX_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e));
+	e = hipMemcpyAsync(dSrc, storage, (size_t)byteLength, hipMemcpyHostToDevice, ctx->stream);
+	rc = e == hipSuccess ? ApplyJobs(ctx, D, jobs) : D.Fail(e, CVX_ERR_HIP);
 	e = hipStreamSynchronize(ctx->stream);
-	if (rc == CVX_OK && e != hipSuccess) { rc = Fail(ctx, CVX_ERR_HIP, "edit failed: %s", hipGetErrorString(e)); }
-	FreeJobs(jobs);
-	(void)hipFree(dSrc);
+	if (rc == CVX_OK && e != hipSuccess) { rc = D.Fail(e, CVX_ERR_HIP); }
 	return rc;
 }
 
@@ -686,30 +653,16 @@ int cvx_world_edit(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 	if (rc != CVX_OK) { return rc; }
 	rc = Prepare(ctx);
 	if (rc != CVX_OK) { return rc; }
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	cvxi::DeviceCall D(ctx, "cvx_world_edit");
 	uint8_t *dSrc = nullptr;
-	auto release = [&]() {
-		if (dSrc) { (void)hipFree(dSrc); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) { e = hipMalloc((void **)&dSrc, (size_t)std::max<int64_t>(byteLength, 4)); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&dSrc, (size_t)std::max<int64_t>(byteLength, 4));
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(dSrc, storage, (size_t)byteLength, hipMemcpyHostToDevice, ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "edit upload failed: %s", hipGetErrorString(e));
-	}
-	rc = cvxi::EditFromDevice(ctx, x0, z0, sizeX, sizeZ, dSrc, elementsOfColumns, columnCount, levelCount, ev[1]);
-	const hipError_t s = hipStreamSynchronize(ctx->stream);
-	if (rc == CVX_OK && (e != hipSuccess || s != hipSuccess)) { rc = Fail(ctx, CVX_ERR_HIP, "edit failed: %s", hipGetErrorString(e != hipSuccess ? e : s)); }
-	if (rc == CVX_OK && outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
+	if (e != hipSuccess) { return D.Fail(e, CVX_ERR_HIP); }
+	rc = cvxi::EditFromDevice(ctx, x0, z0, sizeX, sizeZ, dSrc, elementsOfColumns, columnCount, levelCount, D.Event(1));
+	e = hipStreamSynchronize(ctx->stream);
+	if (rc == CVX_OK && e != hipSuccess) { rc = D.Fail(e, CVX_ERR_HIP); }
+	if (rc == CVX_OK && outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return rc;
 }
 

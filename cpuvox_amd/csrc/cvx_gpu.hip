@@ -40,13 +40,29 @@ int Fail(cvx_context *ctx, int code, const char *fmt, ...)
 	return code;
 }
 
-int FailHip(cvx_context *ctx, const char *call, hipError_t e)
+const DeviceApi &HipApi()
 {
-	if (e == hipErrorOutOfMemory) {
-		(void)hipGetLastError();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the scratch of %s does not fit in device memory", call);
+	static const DeviceApi api = { hipMalloc, hipFree, hipEventCreate, hipEventRecord, hipEventDestroy, hipEventElapsedTime, hipGetLastError, hipGetErrorString };
+	return api;
+}
+
+int64_t LaunchUntilUnchanged(cvx_context *ctx, unsigned int *changed, int64_t bound, Launcher<int64_t> launch, hipError_t *error)
+{
+	hipError_t &e = *error;
+	e = hipSuccess;
+	for (int64_t launches = 0;;) {
+		if (launches >= bound) {
+			(void)hipStreamSynchronize(ctx->stream);
+			return -1;
+		}
+		unsigned int host = 0;
+		e = hipMemsetAsync(changed, 0, sizeof host, ctx->stream);
+		if (e == hipSuccess) { e = launch(launches++); }
+		if (e == hipSuccess) { e = hipGetLastError(); }
+		if (e == hipSuccess) { e = hipMemcpyAsync(&host, changed, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
+		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
+		if (e != hipSuccess || !host) { return launches; }
 	}
-	return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
 }
 
 int ValidateRepeat(cvx_context *ctx)

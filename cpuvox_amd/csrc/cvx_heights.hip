@@ -139,27 +139,15 @@ int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int3
 		CVX_HIP(ctx, hipGetLastError());
 		return CVX_OK;
 	}
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	cvxi::DeviceCall D(ctx, call);
 	uint32_t *scratch = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
 	void *const host[3] = { heights, argb, bottoms };
 	uint32_t *dev[3] = { nullptr, nullptr, nullptr };
 	const size_t arrayBytes = (size_t)n * 4;
 	size_t arrays = 0;
 	for (void *p : host) { arrays += p ? 1 : 0; }
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) {
-		e = hipMalloc((void **)&scratch, arrays * arrayBytes);
-		if (e == hipErrorOutOfMemory) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the arrays", call, arrays * arrayBytes);
-		}
-	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&scratch, arrays * arrayBytes);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) {
 		size_t k = 0;
 		for (int a = 0; a < 3; a++) { if (host[a]) { dev[a] = scratch + (k++) * (size_t)n; } }
@@ -169,21 +157,13 @@ int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int3
 		hipLaunchKernelGGL(cvxheights::heights_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	for (int a = 0; a < 3; a++) {
 		if (e == hipSuccess && host[a]) { e = hipMemcpyAsync(host[a], dev[a], arrayBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	}
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
-	}
-	if (outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return CVX_OK;
 }
 
@@ -220,21 +200,18 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	if (rc != CVX_OK) { return rc; }
 
 	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it
-	struct Arrays {
-		uint32_t *p = nullptr;
-		~Arrays() { if (p) { (void)hipFree(p); } }
-	} copy;
+	cvxi::DeviceCall upload(ctx, call);
+	uint32_t *copy = nullptr;
 	const void *const host[3] = { heights, argb, sideArgb };
 	const uint32_t *dev[3] = { reinterpret_cast<const uint32_t *>(heights), argb, sideArgb };
 	const size_t arrayBytes = (size_t)columns * 4;
 	if (!device) {
 		size_t arrays = 0;
 		for (const void *p : host) { arrays += p ? 1 : 0; }
-		const hipError_t e = hipMalloc((void **)&copy.p, arrays * arrayBytes);
-		if (e == hipErrorOutOfMemory) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the arrays", call, arrays * arrayBytes); }
-		if (e != hipSuccess) { return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e)); }
+		const hipError_t e = upload.Allocate(&copy, arrays * arrayBytes);
+		if (e != hipSuccess) { return upload.Fail(e); }
 		size_t k = 0;
-		for (int a = 0; a < 3; a++) { dev[a] = host[a] ? copy.p + (k++) * (size_t)columns : nullptr; }
+		for (int a = 0; a < 3; a++) { dev[a] = host[a] ? copy + (k++) * (size_t)columns : nullptr; }
 	}
 	A.W = cvxi::WorldOf(ctx);
 	A.arrays = cvxb::HeightsArrays{ reinterpret_cast<const int32_t *>(dev[0]), dev[1], dev[2], thickness, flags };
@@ -244,7 +221,7 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	A.sizeZ = R.sizeZ;
 	A.n = R.n;
 	const dim3 grid(Grid((size_t)R.n)), block(kThreads);
-	cvxi::ColumnEditCall edit{ call, nullptr, "a written column", "the written columns" };
+	cvxi::ColumnEditCall edit{ call, CVX_ERR_HIP, "a written column", "the written columns" };
 	edit.extraScratchBytes = (size_t)R.n * 4; // the run counts
 	return cvxi::ColumnEdit(
 		ctx, R, levelCount, edit,

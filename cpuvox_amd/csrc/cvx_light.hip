@@ -337,7 +337,7 @@ static int Light(cvx_context *ctx, const cvx_light_params *params, const cvx_lam
 	A.sizeZ = R.sizeZ;
 	A.n = R.n;
 	A.lampCount = lampCount;
-	cvxi::ColumnEditCall call{ "light", nullptr, "a re-emitted column", "the lit columns" };
+	cvxi::ColumnEditCall call{ "light", CVX_ERR_HIP, "a re-emitted column", "the lit columns" };
 	call.extraScratchBytes = lampBytes;
 	return cvxi::ColumnEdit(
 		ctx, R, levelCount, call,

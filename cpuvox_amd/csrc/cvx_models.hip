@@ -222,43 +222,23 @@ int Read(cvx_context *ctx, const char *call, const int32_t size[3], const cvx_mo
 		CVX_HIP(ctx, hipGetLastError());
 		return CVX_OK;
 	}
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
 	const size_t argbBytes = argb ? n * 4 : 0, solidBytes = solid ? n : 0;
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) {
-		e = hipMalloc((void **)&scratch, argbBytes + solidBytes);
-		if (e == hipErrorOutOfMemory) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the model", call, argbBytes + solidBytes);
-		}
-	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&scratch, argbBytes + solidBytes);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) {
 		A.argb = argb ? reinterpret_cast<uint32_t *>(scratch) : nullptr;
 		A.solid = solid ? scratch + argbBytes : nullptr;
 		hipLaunchKernelGGL(cvxmodels::model_read_kernel, dim3(Grid(n)), dim3(kThreads), 0, ctx->stream, A);
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess && argb) { e = hipMemcpyAsync(argb, A.argb, argbBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess && solid) { e = hipMemcpyAsync(solid, A.solid, solidBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
-	}
-	if (outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return CVX_OK;
 }
 
@@ -295,10 +275,8 @@ int Place(cvx_context *ctx, const char *call, const cvx_model *models, int model
 	if (rc != CVX_OK) { return rc; }
 
 	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it
-	struct Arrays {
-		uint8_t *p = nullptr;
-		~Arrays() { if (p) { (void)hipFree(p); } }
-	} arrays;
+	cvxi::DeviceCall upload(ctx, call);
+	uint8_t *arrays = nullptr;
 	std::vector<cvx_model> deviceModels(models, models + modelCount);
 	struct Upload {
 		size_t at, bytes;
@@ -318,13 +296,12 @@ int Place(cvx_context *ctx, const char *call, const cvx_model *models, int model
 				total += Align16(n);
 			}
 		}
-		const hipError_t e = hipMalloc((void **)&arrays.p, total);
-		if (e == hipErrorOutOfMemory) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the models", call, total); }
-		if (e != hipSuccess) { return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e)); }
+		const hipError_t e = upload.Allocate(&arrays, total);
+		if (e != hipSuccess) { return upload.Fail(e); }
 		size_t u = 0;
 		for (int k = 0; k < modelCount; k++) {
-			if (models[k].argb) { deviceModels[k].argb = reinterpret_cast<const uint32_t *>(arrays.p + uploads[u++].at); }
-			if (models[k].solid) { deviceModels[k].solid = arrays.p + uploads[u++].at; }
+			if (models[k].argb) { deviceModels[k].argb = reinterpret_cast<const uint32_t *>(arrays + uploads[u++].at); }
+			if (models[k].solid) { deviceModels[k].solid = arrays + uploads[u++].at; }
 		}
 	}
 	cvxmodels::PlaceArgs A{};
@@ -337,14 +314,14 @@ int Place(cvx_context *ctx, const char *call, const cvx_model *models, int model
 	const size_t countsBytes = Align16((size_t)R.n * 4), modelsBytes = (size_t)modelCount * sizeof(cvx_model), instancesBytes = live.size() * sizeof(cvx_model_instance),
 	             boxesBytes = boxes.size() * sizeof(cvxb::ModelCullBox);
 	const dim3 grid(Grid((size_t)R.n, cvxmodels::kWaves)), block(kThreads);
-	cvxi::ColumnEditCall edit{ call, nullptr, "a column under the models", "the columns under the models" };
+	cvxi::ColumnEditCall edit{ call, CVX_ERR_HIP, "a column under the models", "the columns under the models" };
 	edit.extraScratchBytes = countsBytes + modelsBytes + instancesBytes + boxesBytes; // the run counts, the descriptors
 	return cvxi::ColumnEdit(
 		ctx, R, levelCount, edit,
 		[&](const cvxi::ColumnEditJob &J) {
 			hipError_t e = hipSuccess;
 			for (const Upload &u : uploads) {
-				if (e == hipSuccess) { e = hipMemcpyAsync(arrays.p + u.at, u.from, u.bytes, hipMemcpyHostToDevice, ctx->stream); }
+				if (e == hipSuccess) { e = hipMemcpyAsync(arrays + u.at, u.from, u.bytes, hipMemcpyHostToDevice, ctx->stream); }
 			}
 			A.counts = J.counts;
 			A.runCounts = reinterpret_cast<uint32_t *>(J.extra);

@@ -35,7 +35,6 @@ using cvxi::Fail;
 
 namespace cvxnav {
 
-using cvxi::FailHip;
 using cvxi::Grid;
 using cvxi::kThreads;
 using cvxi::WaveReduce;
@@ -347,8 +346,8 @@ static int CheckGoals(cvx_context *ctx, const int32_t *goals, int goalCount, int
 	return CVX_OK;
 }
 
-// Steps 3 and 4 on the field's tables.  `start` (may be null): an event already recorded in front of the caller's own passes.
-static int Solve(cvx_context *ctx, const char *call, cvx_nav_field *F, const int32_t *goals, int goalCount, int maxSteps, hipEvent_t start, cvx_nav_summary *summary,
+// Steps 3 and 4 on the field's tables, in the caller's DeviceCall: where the caller has begun it in front of its own passes, the time covers those too.
+static int Solve(cvx_context *ctx, const char *call, cvxi::DeviceCall &D, cvx_nav_field *F, const int32_t *goals, int goalCount, int maxSteps, cvx_nav_summary *summary,
                  float *outDeviceMs)
 {
 	cvx_nav_summary S{};
@@ -358,23 +357,12 @@ static int Solve(cvx_context *ctx, const char *call, cvx_nav_field *F, const int
 	if (F->T.nodes) {
 		NavTables &T = F->T;
 		T.maxSteps = (uint32_t)maxSteps;
-		hipEvent_t ev[2] = { start, nullptr };
 		int32_t *dGoals = nullptr;
-		auto release = [&]() {
-			if (dGoals) { (void)hipFree(dGoals); }
-			if (ev[0] && ev[0] != start) { (void)hipEventDestroy(ev[0]); }
-			if (ev[1]) { (void)hipEventDestroy(ev[1]); }
-		};
 		Totals host{};
 		host.nodes = T.nodes;
 		host.several = (unsigned long long)F->several;
-		hipError_t e = hipSuccess;
-		if (!start) {
-			e = hipEventCreate(&ev[0]);
-			if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
-		}
-		if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-		if (e == hipSuccess) { e = hipMalloc((void **)&dGoals, (size_t)goalCount * 12); }
+		hipError_t e = D.Event(0) ? hipSuccess : D.Begin();
+		if (e == hipSuccess) { e = D.Allocate(&dGoals, (size_t)goalCount * 12); }
 		if (e == hipSuccess) { e = hipMemcpyAsync(dGoals, goals, (size_t)goalCount * 12, hipMemcpyHostToDevice, ctx->stream); }
 		if (e == hipSuccess) { e = hipMemcpyAsync(T.totals, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
 		if (e == hipSuccess) {
@@ -385,33 +373,25 @@ static int Solve(cvx_context *ctx, const char *call, cvx_nav_field *F, const int
 		const int tilesX = (T.G.sizeX + kTile - 1) / kTile, tilesZ = (T.G.sizeZ + kTile - 1) / kTile;
 		const int64_t bound = (int64_t)T.nodes + 2;
 		int64_t launches = 0;
-		while (e == hipSuccess) { // until a launch lowers nothing
-			if (launches >= bound) {
-				release();
-				return Fail(ctx, CVX_ERR_HIP, "%s: the relaxation of %u nodes did not settle in %lld launches", call, T.nodes, (long long)bound);
-			}
-			e = hipMemsetAsync(&T.totals->changed, 0, sizeof(unsigned int), ctx->stream);
-			if (e != hipSuccess) { break; }
-			hipLaunchKernelGGL(nav_relax_kernel, dim3((unsigned)((int64_t)tilesX * tilesZ)), dim3(kThreads), 0, ctx->stream, T, tilesZ);
-			launches++;
-			e = hipGetLastError();
-			if (e == hipSuccess) { e = hipMemcpyAsync(&host.changed, &T.totals->changed, sizeof host.changed, hipMemcpyDeviceToHost, ctx->stream); }
-			if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-			if (e != hipSuccess || !host.changed) { break; }
+		if (e == hipSuccess) {
+			launches = cvxi::LaunchUntilUnchanged(
+				ctx, &T.totals->changed, bound,
+				[&](const int64_t &) {
+					hipLaunchKernelGGL(nav_relax_kernel, dim3((unsigned)((int64_t)tilesX * tilesZ)), dim3(kThreads), 0, ctx->stream, T, tilesZ);
+					return hipSuccess;
+				},
+				&e);
+			if (launches < 0) { return Fail(ctx, CVX_ERR_HIP, "%s: the relaxation of %u nodes did not settle in %lld launches", call, T.nodes, (long long)bound); }
 		}
 		if (e == hipSuccess) {
 			hipLaunchKernelGGL(nav_next_kernel, dim3(Grid((size_t)T.n)), dim3(kThreads), 0, ctx->stream, T);
 			e = hipGetLastError();
 		}
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host, T.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-		if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+		if (e == hipSuccess) { e = D.End(); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
-		(void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-		release();
+		if (e != hipSuccess) { return D.Fail(e); }
+		ms = D.Ms();
 		S.reached = (int64_t)host.reached;
 		S.goalsResolved = (int32_t)host.goalsResolved;
 		S.largestDistance = (int32_t)host.largest;
@@ -471,16 +451,14 @@ int cvx_world_nav_build(cvx_context *ctx, const cvx_nav_params *params, const in
 	const int n = (int)A.T.G.Columns();
 	A.T.n = n;
 	F->T = A.T;
+	cvxi::DeviceCall D(ctx, call);
 	if (n == 0) { // a box narrower than the body: the empty field
 		*outField = F;
-		return Solve(ctx, call, F, goals, goalCount, P.maxSteps, nullptr, summary, outDeviceMs);
+		return Solve(ctx, call, D, F, goals, goalCount, P.maxSteps, summary, outDeviceMs);
 	}
 
-	hipEvent_t start = nullptr;
-	uint8_t *scanMem = nullptr;
+	uint8_t *columnMem = nullptr, *nodeMem = nullptr, *scanMem = nullptr;
 	auto fail = [&](int code) {
-		if (scanMem) { (void)hipFree(scanMem); }
-		if (start) { (void)hipEventDestroy(start); }
 		cvx_nav_field_destroy(F);
 		return code;
 	};
@@ -488,46 +466,44 @@ int cvx_world_nav_build(cvx_context *ctx, const cvx_nav_params *params, const in
 	const size_t offsetsAt = (sizeof(Totals) + 15) & ~(size_t)15;
 	const size_t chunks = ((size_t)n + 1 + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	Totals host{};
-	hipError_t e = hipEventCreate(&start);
-	if (e == hipSuccess) { e = hipMalloc((void **)&F->columnMem, offsetsAt + ((size_t)n + 1) * 4); }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scanMem, chunks * 8); }
-	if (e == hipSuccess) { e = hipEventRecord(start, ctx->stream); }
-	if (e == hipSuccess) { e = hipMemcpyAsync(F->columnMem, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
+	hipError_t e = D.Allocate(&columnMem, offsetsAt + ((size_t)n + 1) * 4);
+	if (e == hipSuccess) { e = D.Allocate(&scanMem, chunks * 8); } // (a few KiB, held to the end of the call with the rest)
+	if (e == hipSuccess) { e = D.Begin(); }
+	if (e == hipSuccess) { e = hipMemcpyAsync(columnMem, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) {
 		A.W = cvxi::WorldOf(ctx);
-		A.T.totals = reinterpret_cast<Totals *>(F->columnMem);
-		A.T.offsets = reinterpret_cast<uint32_t *>(F->columnMem + offsetsAt);
+		A.T.totals = reinterpret_cast<Totals *>(columnMem);
+		A.T.offsets = reinterpret_cast<uint32_t *>(columnMem + offsetsAt);
 		hipLaunchKernelGGL(nav_count_kernel, dim3(Grid((size_t)n + 1)), dim3(kThreads), 0, ctx->stream, A);
 		cvxi::ExclusiveScan(ctx->stream, A.T.offsets, n + 1, reinterpret_cast<unsigned long long *>(scanMem), &A.T.totals->nodes);
 		e = hipGetLastError();
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host.nodes, &A.T.totals->nodes, sizeof host.nodes, hipMemcpyDeviceToHost, ctx->stream); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	}
-	if (e != hipSuccess) { return fail(FailHip(ctx, call, e)); }
+	if (e != hipSuccess) { return fail(D.Fail(e)); }
 	if (host.nodes >= ((unsigned long long)1 << 31) - 1) { return fail(Fail(ctx, CVX_ERR_CAPACITY, "the field holds %llu nodes", host.nodes)); }
-	(void)hipFree(scanMem);
-	scanMem = nullptr;
 	// 2. the node table
 	const size_t nodes = (size_t)host.nodes;
 	A.T.nodes = (uint32_t)nodes;
 	if (nodes) {
-		e = hipMalloc((void **)&F->nodeMem, nodes * 16);
-		if (e != hipSuccess) { return fail(FailHip(ctx, call, e)); }
-		A.T.lohi = reinterpret_cast<uint32_t *>(F->nodeMem);
-		A.T.dist = reinterpret_cast<uint32_t *>(F->nodeMem + nodes * 8);
-		A.T.next = reinterpret_cast<uint32_t *>(F->nodeMem + nodes * 12);
+		e = D.Allocate(&nodeMem, nodes * 16);
+		if (e != hipSuccess) { return fail(D.Fail(e)); }
+		A.T.lohi = reinterpret_cast<uint32_t *>(nodeMem);
+		A.T.dist = reinterpret_cast<uint32_t *>(nodeMem + nodes * 8);
+		A.T.next = reinterpret_cast<uint32_t *>(nodeMem + nodes * 12);
 		hipLaunchKernelGGL(nav_nodes_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
 		e = hipGetLastError();
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host.several, &A.T.totals->several, sizeof host.several, hipMemcpyDeviceToHost, ctx->stream); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-		if (e != hipSuccess) { return fail(FailHip(ctx, call, e)); }
+		if (e != hipSuccess) { return fail(D.Fail(e)); }
 	}
 	F->T = A.T;
 	F->several = (int64_t)host.several;
 	// 3, 4. the distances and the next cells
-	rc = Solve(ctx, call, F, goals, goalCount, P.maxSteps, start, summary, outDeviceMs);
+	rc = Solve(ctx, call, D, F, goals, goalCount, P.maxSteps, summary, outDeviceMs);
 	if (rc != CVX_OK) { return fail(rc); }
-	(void)hipEventDestroy(start);
+	F->columnMem = D.Keep(columnMem);
+	F->nodeMem = D.Keep(nodeMem);
 	*outField = F;
 	return CVX_OK;
 }
@@ -539,7 +515,9 @@ int cvx_nav_field_goals(cvx_context *ctx, cvx_nav_field *field, const int32_t *g
 	const int rc = cvxnav::CheckGoals(ctx, goals, goalCount, maxSteps);
 	if (rc != CVX_OK) { return rc; }
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxnav::Solve(ctx, "cvx_nav_field_goals", field, goals, goalCount, maxSteps, nullptr, summary, outDeviceMs);
+	static const char *const call = "cvx_nav_field_goals";
+	cvxi::DeviceCall D(ctx, call);
+	return cvxnav::Solve(ctx, call, D, field, goals, goalCount, maxSteps, summary, outDeviceMs);
 }
 
 int cvx_nav_query_device(cvx_context *ctx, const cvx_nav_field *field, int count, const int32_t *cellsDevice, cvx_nav_step *stepsDevice, void *hipStream)
@@ -564,16 +542,16 @@ int cvx_nav_query(cvx_context *ctx, const cvx_nav_field *field, int count, const
 	if (count == 0) { return CVX_OK; }
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
 	const size_t cellsBytes = ((size_t)count * 12 + 255) & ~(size_t)255, stepsBytes = (size_t)count * sizeof(cvx_nav_step);
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr;
-	hipError_t e = hipMalloc((void **)&scratch, cellsBytes + stepsBytes);
-	if (e != hipSuccess) { return cvxnav::FailHip(ctx, call, e); }
+	hipError_t e = D.Allocate(&scratch, cellsBytes + stepsBytes);
+	if (e != hipSuccess) { return D.Fail(e); }
 	int rc = CVX_OK;
 	e = hipMemcpyAsync(scratch, cells, (size_t)count * 12, hipMemcpyHostToDevice, ctx->stream);
 	if (e == hipSuccess) { rc = cvx_nav_query_device(ctx, field, count, reinterpret_cast<const int32_t *>(scratch), reinterpret_cast<cvx_nav_step *>(scratch + cellsBytes), nullptr); }
 	if (e == hipSuccess && rc == CVX_OK) { e = hipMemcpyAsync(steps, scratch + cellsBytes, stepsBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess && rc == CVX_OK) { e = hipStreamSynchronize(ctx->stream); }
-	(void)hipFree(scratch);
-	if (e != hipSuccess) { return cvxnav::FailHip(ctx, call, e); }
+	if (e != hipSuccess) { return D.Fail(e); }
 	return rc;
 }
 

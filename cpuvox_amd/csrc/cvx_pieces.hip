@@ -21,7 +21,6 @@
 #include "cvx_pieces_nodes.h"
 
 using cvxi::Fail;
-using cvxi::FailHip;
 using cvxi::Grid;
 using cvxi::kThreads;
 using cvxi::WaveReduce;
@@ -136,7 +135,6 @@ __global__ __launch_bounds__(256) void pieces_remove_write_kernel(NodeArgs A)
 int Analyse(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, const char *extraError, int levelCount,
             const cvx_piece *pieces, int pieceCapacity, Analysis *R)
 {
-	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box is NULL"); }
 	for (int a = 0; a < 3; a++) {
 		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box [%d, %d) on axis %d is empty", boxMin[a], boxMax[a], a); }
@@ -173,7 +171,8 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 	static const char *const call = "cvx_world_pieces";
 	char bad[32];
 	std::snprintf(bad, sizeof bad, "bad op %d", op);
-	Analysis R;
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	Analysis R(ctx, call);
 	int rc = Analyse(ctx, call, boxMin, boxMax, anchors, op != CVX_PIECES_REPORT && op != CVX_PIECES_REMOVE ? bad : nullptr, levelCount, pieces, pieceCapacity, &R);
 	if (rc != CVX_OK) { return rc; }
 	NodeArgs &A = R.A;
@@ -190,9 +189,9 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		A.rSizeZ = E.sizeZ;
 		A.rn = E.n;
 		const cvxi::ColumnEditTotals totals{ A.totals, &host, sizeof host, offsetof(Totals, head.elements), offsetof(Totals, head.overLimit) };
-		cvxi::ColumnEditCall edit{ call, FailHip, "a column without its floating runs", "the columns of the removal" };
+		cvxi::ColumnEditCall edit{ call, CVX_ERR_CAPACITY, "a column without its floating runs", "the columns of the removal" };
 		edit.totals = &totals;
-		edit.done = R.ev[1];
+		edit.done = R.device.Event(1);
 		rc = cvxi::ColumnEdit(
 			ctx, E, levelCount, edit,
 			[&](const cvxi::ColumnEditJob &J) {
@@ -209,7 +208,7 @@ int cvx_world_pieces(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 			},
 			nullptr);
 		if (rc != CVX_OK) { return rc; }
-		(void)hipEventElapsedTime(&ms, R.ev[0], R.ev[1]);
+		ms = R.device.Ms();
 	}
 	// (nothing is handed out before the call can no longer fail)
 	if (!R.list.empty()) { std::memcpy(pieces, R.list.data(), R.list.size() * sizeof(cvx_piece)); }

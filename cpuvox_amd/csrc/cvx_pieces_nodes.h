@@ -17,10 +17,11 @@ struct Totals {
 static_assert(sizeof(Totals) % 16 == 0, "the list follows the totals");
 
 struct Analysis : cvxcomp::Analysis {
+	using cvxcomp::Analysis::Analysis;
 	Totals host; // the totals, on the host
 };
 
-// `call`: the entry point's name for messages.  `extraError` (may be null): the message of the call's own argument check (op / maxDrop), reported
+// `call`: the entry point's name for messages; ctx is not null.  `extraError` (may be null): the message of the call's own argument check (op / maxDrop), reported
 // as CVX_ERR_INVALID_ARGUMENT in its place among the shared checks.
 int Analyse(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], int anchors, const char *extraError, int levelCount,
             const cvx_piece *pieces, int pieceCapacity, Analysis *R);

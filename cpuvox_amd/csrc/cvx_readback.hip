@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "cvx_context.h"
 #include "cvx_edit.h"
@@ -186,23 +187,13 @@ unsigned Grid(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 // The rectangle [x0, x0 + sizeX) x [z0, z0 + sizeZ) of level `lod` (validated) as a blob of `columnCount` headers (>= the rectangle's columns;
 // the ones behind it stay zero) and the element pool, in malloc'd memory.
-int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, int64_t columnCount, void **outStorage, int64_t *outByteLength,
+int ReadBack(cvx_context *ctx, const char *call, int lod, int x0, int z0, int sizeX, int sizeZ, int64_t columnCount, void **outStorage, int64_t *outByteLength,
              int32_t *outColumnCount)
 {
 	const int n = sizeX * sizeZ;
+	std::unique_ptr<void, void (*)(void *)> blob(nullptr, std::free); // (outlives D: freeing the device blocks waits for a copy still under way)
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr, *dBlob = nullptr;
-	void *blob = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		if (dBlob) { (void)hipFree(dBlob); }
-		std::free(blob);
-	};
-	auto failed = [&](hipError_t e) {
-		const bool oom = e == hipErrorOutOfMemory;
-		(void)hipGetLastError();
-		release();
-		return oom ? Fail(ctx, CVX_ERR_CAPACITY, "read-back: out of device memory") : Fail(ctx, CVX_ERR_HIP, "read-back failed: %s", hipGetErrorString(e));
-	};
 	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	cvxi::ScratchLayout carve;
 	const size_t oCounts = carve((size_t)n * 4), oTotal = carve(8), oChunks = carve(chunks * 8);
@@ -222,7 +213,7 @@ int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, in
 	A.n = n;
 	// 1, 2. count, scan, one copy back
 	unsigned long long total = 0;
-	hipError_t e = hipMalloc((void **)&scratch, carve.bytes);
+	hipError_t e = D.Allocate(&scratch, carve.bytes);
 	if (e == hipSuccess && n > 0) { // (n = 0: a level without columns, LOD 5 of a world 16 columns wide -- its blob is the zero headers alone)
 		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
 		unsigned long long *dTotal = reinterpret_cast<unsigned long long *>(scratch + oTotal);
@@ -232,19 +223,15 @@ int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, in
 		if (e == hipSuccess) { e = hipMemcpyAsync(&total, dTotal, sizeof total, hipMemcpyDeviceToHost, ctx->stream); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	}
-	if (e != hipSuccess) { return failed(e); }
+	if (e != hipSuccess) { return D.Fail(e); }
 	if (total >= ((unsigned long long)1 << 31)) { // (storageOffset is an int32)
-		release();
 		return Fail(ctx, CVX_ERR_CAPACITY, "LOD %d: the read-back needs %llu elements", lod, total);
 	}
 	// 3, 4. the blob on the device, one copy to the host
 	const size_t headerBytes = (size_t)columnCount * 12, blobBytes = headerBytes + (size_t)total * 4;
-	blob = std::malloc(std::max<size_t>(blobBytes, 1));
-	if (!blob) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "read-back: no host memory for %zu bytes", blobBytes);
-	}
-	e = hipMalloc((void **)&dBlob, std::max<size_t>(blobBytes, 4));
+	blob.reset(std::malloc(std::max<size_t>(blobBytes, 1)));
+	if (!blob) { return Fail(ctx, CVX_ERR_CAPACITY, "read-back: no host memory for %zu bytes", blobBytes); }
+	e = D.Allocate(&dBlob, std::max<size_t>(blobBytes, 4));
 	if (e == hipSuccess && headerBytes > (size_t)n * 12) { e = hipMemsetAsync(dBlob + (size_t)n * 12, 0, headerBytes - (size_t)n * 12, ctx->stream); }
 	if (e == hipSuccess && n > 0) {
 		A.headers = reinterpret_cast<uint32_t *>(dBlob);
@@ -252,14 +239,12 @@ int ReadBack(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ, in
 		hipLaunchKernelGGL(cvxread::read_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) { e = hipMemcpyAsync(blob, dBlob, blobBytes, hipMemcpyDeviceToHost, ctx->stream); }
+	if (e == hipSuccess) { e = hipMemcpyAsync(blob.get(), dBlob, blobBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return failed(e); }
-	*outStorage = blob;
+	if (e != hipSuccess) { return D.Fail(e); }
+	*outStorage = blob.release();
 	*outByteLength = (int64_t)blobBytes;
 	*outColumnCount = (int32_t)columnCount;
-	blob = nullptr;
-	release();
 	return CVX_OK;
 }
 
@@ -308,7 +293,7 @@ int cvx_world_read_region(cvx_context *ctx, int lod, int x0, int z0, int sizeX, 
 	if ((int64_t)sizeX * sizeZ >= ((int64_t)1 << 31) / 12) { return Fail(ctx, CVX_ERR_CAPACITY, "a read-back of %d x %d columns", sizeX, sizeZ); }
 	rc = Prepare(ctx, lod);
 	if (rc != CVX_OK) { return rc; }
-	return ReadBack(ctx, lod, x0, z0, sizeX, sizeZ, (int64_t)sizeX * sizeZ, outStorage, outByteLength, outColumnCount);
+	return ReadBack(ctx, "cvx_world_read_region", lod, x0, z0, sizeX, sizeZ, (int64_t)sizeX * sizeZ, outStorage, outByteLength, outColumnCount);
 }
 
 int cvx_world_read_level(cvx_context *ctx, int lod, void **outStorage, int64_t *outByteLength, int32_t *outColumnCount)
@@ -324,7 +309,7 @@ int cvx_world_read_level(cvx_context *ctx, int lod, void **outStorage, int64_t *
 	if ((int64_t)usedX * usedZ >= ((int64_t)1 << 31) / 12 || columnCount >= ((int64_t)1 << 31)) {
 		return Fail(ctx, CVX_ERR_CAPACITY, "a read-back of %d x %d columns", usedX, usedZ);
 	}
-	return ReadBack(ctx, lod, 0, 0, usedX, usedZ, columnCount, outStorage, outByteLength, outColumnCount);
+	return ReadBack(ctx, "cvx_world_read_level", lod, 0, 0, usedX, usedZ, columnCount, outStorage, outByteLength, outColumnCount);
 }
 
 int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDeviceMs)
@@ -344,23 +329,11 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 
 	const DevWorld &W = ctx->hostWorld;
 	Level lv[CVX_LOD_LEVELS];
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	static const char *const call = "cvx_world_compact";
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *arena = nullptr;
-	auto release = [&]() {
-		for (Level &l : lv) { if (l.scratch) { (void)hipFree(l.scratch); } }
-		if (arena) { (void)hipFree(arena); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
-	auto failed = [&](hipError_t e, const char *what) {
-		const bool oom = e == hipErrorOutOfMemory;
-		(void)hipGetLastError();
-		release();
-		return oom ? Fail(ctx, CVX_ERR_CAPACITY, "compaction: out of device memory (%s)", what) : Fail(ctx, CVX_ERR_HIP, "compaction failed (%s): %s", what, hipGetErrorString(e));
-	};
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
-	if (e != hipSuccess) { return failed(e, "events"); }
+	hipError_t e = D.Begin();
+	if (e != hipSuccess) { return D.Fail(e); }
 	// 1, 2. count and scan every edited level, one copy of its totals back
 	for (int i = 0; i < CVX_LOD_LEVELS; i++) {
 		const cvx_context::HostLevel &H = ctx->hostLevel[i];
@@ -382,18 +355,15 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 		A.blocksZ = (A.usedZ + CVX_COLOR_BLOCK_Z - 1) / CVX_COLOR_BLOCK_Z;
 		A.blockCount = A.blocked ? ((A.usedX + CVX_COLOR_BLOCK_X - 1) / CVX_COLOR_BLOCK_X) * A.blocksZ : 0;
 		A.recordCount = (size_t)A.usedX << H.rowShift;
-		if (A.blocked && ((size_t)A.blockCount > E.blockCap || !E.blockBase || !E.blockDepth)) {
-			release();
-			return Fail(ctx, CVX_ERR_HIP, "LOD %d: the edit's block tables are missing", i);
-		}
+		if (A.blocked && ((size_t)A.blockCount > E.blockCap || !E.blockBase || !E.blockDepth)) { return Fail(ctx, CVX_ERR_HIP, "LOD %d: the edit's block tables are missing", i); }
 		A.blockBase = E.blockBase;
 		A.blockDepth = E.blockDepth;
 		const size_t colEntries = A.blocked ? (size_t)A.blockCount : A.recordCount;
 		const size_t chunks = (std::max(A.recordCount, colEntries) + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 		cvxi::ScratchLayout carve;
 		const size_t oRun = carve(A.recordCount * 4), oCol = carve(colEntries * 4 + 4), oDepth = carve((size_t)A.blockCount * 4 + 4), oTotals = carve(2 * 8 + chunks * 8);
-		e = hipMalloc((void **)&l.scratch, carve.bytes);
-		if (e != hipSuccess) { return failed(e, "scratch"); }
+		e = D.Allocate(&l.scratch, carve.bytes);
+		if (e != hipSuccess) { return D.Fail(e); }
 		A.runOff = reinterpret_cast<uint32_t *>(l.scratch + oRun);
 		A.colOff = reinterpret_cast<uint32_t *>(l.scratch + oCol);
 		A.depth = reinterpret_cast<uint32_t *>(l.scratch + oDepth);
@@ -404,11 +374,11 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 		cvxi::ExclusiveScan(ctx->stream, A.colOff, (int)colEntries, l.dTotals + 2, l.dTotals + 1);
 		e = hipGetLastError();
 		if (e == hipSuccess) { e = hipMemcpyAsync(l.host, l.dTotals, sizeof l.host, hipMemcpyDeviceToHost, ctx->stream); }
-		if (e != hipSuccess) { return failed(e, "count"); }
+		if (e != hipSuccess) { return D.Fail(e); }
 	}
 	// (behind every draw enqueued before the call: the old arena may be freed once the new one is in place)
 	e = hipStreamSynchronize(ctx->stream);
-	if (e != hipSuccess) { return failed(e, "count"); }
+	if (e != hipSuccess) { return D.Fail(e); }
 	// the new layout: Relayout's placement (cvx_edit.hip), every compacted level with the headroom of a first edit
 	cvx_context::EditLevel next[CVX_LOD_LEVELS];
 	size_t runsBytes[CVX_LOD_LEVELS], elementsBytes[CVX_LOD_LEVELS];
@@ -421,10 +391,7 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 			n.runsCap = (n.runsUsed + std::max<int64_t>(n.runsUsed / 8, 4096) + 1) & ~(int64_t)1;
 			n.elementsCap = (n.elementsUsed + std::max<int64_t>(n.elementsUsed / 8, 16384) + 31) & ~(int64_t)31;
 			n.abandonedBytes = 0;
-			if (n.elementsCap + CVX_COLOR_STRIDE >= ((int64_t)1 << 30)) {
-				release();
-				return Fail(ctx, CVX_ERR_CAPACITY, "LOD %d: %.2f G colour slots (the records address 2^30)", i, (double)n.elementsCap / 1e9);
-			}
+			if (n.elementsCap + CVX_COLOR_STRIDE >= ((int64_t)1 << 30)) { return Fail(ctx, CVX_ERR_CAPACITY, "LOD %d: %.2f G colour slots (the records address 2^30)", i, (double)n.elementsCap / 1e9); }
 			runsBytes[i] = (size_t)n.runsCap * 8;
 			elementsBytes[i] = (size_t)(n.elementsCap + CVX_COLOR_STRIDE) * 4; // (a line of zeros behind the tail)
 		} else {
@@ -444,13 +411,10 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 		countsAt[i] = place(H.countsBytes);
 		elementsAt[i] = place(elementsBytes[i]);
 	}
-	if (cursor >= ((size_t)1 << 32)) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the compacted world needs %.2f GiB of device tables", (double)cursor / (double)((size_t)1 << 30));
-	}
+	if (cursor >= ((size_t)1 << 32)) { return Fail(ctx, CVX_ERR_CAPACITY, "the compacted world needs %.2f GiB of device tables", (double)cursor / (double)((size_t)1 << 30)); }
 	// 3. the new arena (old + new at the peak: out of memory leaves the world as it was)
-	e = hipMalloc((void **)&arena, cursor);
-	if (e != hipSuccess) { return failed(e, "arena"); }
+	e = D.Allocate(&arena, cursor);
+	if (e != hipSuccess) { return D.Fail(e); }
 	e = hipMemsetAsync(arena, 0, cursor, ctx->stream);
 	for (int i = 0; i < CVX_LOD_LEVELS && e == hipSuccess; i++) {
 		const cvx_context::HostLevel &H = ctx->hostLevel[i];
@@ -472,13 +436,12 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 		if (A.blocked && A.blockCount > 0) { hipLaunchKernelGGL(cvxread::compact_move_blocks_kernel, dim3((unsigned)A.blockCount), dim3(64), 0, ctx->stream, A); }
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return failed(e, "move"); }
+	if (e != hipSuccess) { return D.Fail(e); }
 	// the swap (the stream is idle: nothing reads the old arena any more)
 	(void)hipFree(ctx->arena);
-	ctx->arena = arena;
-	arena = nullptr;
+	ctx->arena = D.Keep(arena);
 	ctx->arenaBytes = cursor;
 	ctx->hostWorld.arena = ctx->arena;
 	for (int i = 0; i < CVX_LOD_LEVELS; i++) {
@@ -494,10 +457,8 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 	}
 	e = hipMemcpyAsync(ctx->devWorld, &ctx->hostWorld, sizeof(DevWorld), hipMemcpyHostToDevice, ctx->stream);
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	float ms = 0.f;
-	if (e == hipSuccess && outDeviceMs && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) { *outDeviceMs = ms; }
-	release();
-	if (e != hipSuccess) { return Fail(ctx, CVX_ERR_HIP, "compaction failed: %s", hipGetErrorString(e)); }
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	int64_t usedAfter = 0;
 	if ((rc = cvx_world_edit_stats(ctx, &usedAfter, nullptr, nullptr)) != CVX_OK) { return rc; }
 	if (outReclaimedBytes) { *outReclaimedBytes = usedBefore - usedAfter; }

@@ -232,13 +232,13 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
                      int pieceCapacity, cvx_settle_summary *summary, float *outDeviceMs)
 {
 	using namespace cvxsettle;
-	using cvxi::FailHip;
 	using cvxi::Grid;
 	using cvxi::kThreads;
 	static const char *const call = "cvx_world_settle";
 	char bad[40];
 	std::snprintf(bad, sizeof bad, "maxDrop %d is negative", maxDrop);
-	cvxpieces::Analysis R;
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	cvxpieces::Analysis R(ctx, call);
 	int rc = cvxpieces::Analyse(ctx, call, boxMin, boxMax, anchors, maxDrop < 0 ? bad : nullptr, levelCount, pieces, pieceCapacity, &R);
 	if (rc != CVX_OK) { return rc; }
 	const size_t nodes = R.nodes, floating = (size_t)R.host.summary.floatingPieces, wanted = R.list.size();
@@ -247,13 +247,10 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 	out.floatingVoxels = R.host.summary.floatingVoxels;
 	float ms = R.ms;
 	std::vector<int32_t> dropList(wanted, 0);
+	// the drops: their scratch, and the event pair from the analysis' start to the end of the relaxation
+	std::vector<uint8_t> back; // (outlives relax: freeing the device blocks waits for a copy still under way)
+	cvxi::DeviceCall relax(ctx, call);
 	uint8_t *settleScratch = nullptr;
-	hipEvent_t relaxed = nullptr;
-	auto release = [&]() {
-		if (settleScratch) { (void)hipFree(settleScratch); }
-		if (relaxed) { (void)hipEventDestroy(relaxed); }
-		R.Release();
-	};
 	cvxi::ScratchLayout carve;
 	unsigned sweeps = 0, launches = 0;
 	bool single = nodes <= kSingleNodes;
@@ -266,11 +263,11 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		const size_t oTotals = carve(sizeof(SettleTotals)), oDrops = carve(std::max<size_t>(wanted, 1) * 4), oDrop = carve(nodes * 4), oBelow = carve(nodes * 4),
 		             oGap = carve(nodes * 4), oShift = carve(nodes * 4);
 		static_assert(sizeof(SettleTotals) % 16 == 0, "the drops follow the totals");
-		std::vector<uint8_t> back(sizeof(SettleTotals) + wanted * 4);
+		back.resize(sizeof(SettleTotals) + wanted * 4);
 		host.x0 = host.z0 = INT_MAX;
 		host.x1 = host.z1 = INT_MIN;
-		hipError_t e = hipEventCreate(&relaxed);
-		if (e == hipSuccess) { e = hipMalloc((void **)&settleScratch, carve.bytes); }
+		hipError_t e = relax.Begin(R.device.Event(0));
+		if (e == hipSuccess) { e = relax.Allocate(&settleScratch, carve.bytes); }
 		if (e == hipSuccess) { e = hipMemcpyAsync(settleScratch + oTotals, &host, sizeof host, hipMemcpyHostToDevice, ctx->stream); }
 		if (e == hipSuccess) {
 			A.P = R.A;
@@ -313,18 +310,15 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 			}
 			// (the drops lie behind the totals: ONE copy brings both)
 			if (e == hipSuccess) { e = hipMemcpyAsync(back.data(), settleScratch + oTotals, back.size(), hipMemcpyDeviceToHost, ctx->stream); }
-			if (e == hipSuccess) { e = hipEventRecord(relaxed, ctx->stream); }
+			if (e == hipSuccess) { e = relax.End(); }
 			if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 		}
-		if (e != hipSuccess) {
-			release();
-			return FailHip(ctx, call, e);
-		}
+		if (e != hipSuccess) { return relax.Fail(e); }
 		std::memcpy(&host, back.data(), sizeof host);
 		if (wanted) { std::memcpy(dropList.data(), back.data() + sizeof host, wanted * 4); }
 		sweeps = single ? host.sweeps : launches * (unsigned)A.sweeps;
-		(void)hipEventElapsedTime(&relaxMs, R.ev[1], relaxed);
-		(void)hipEventElapsedTime(&ms, R.ev[0], relaxed);
+		ms = relax.Ms();
+		relaxMs = ms - R.ms; // (the analysis' end is the relaxation's start)
 		out.fallenPieces = host.fallenPieces;
 		out.fallenVoxels = host.fallenVoxels;
 		out.largestDrop = host.largestDrop;
@@ -335,19 +329,16 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 		NodeArgs &P = A.P;
 		cvxi::EditRectangle E;
 		rc = cvxi::RoundEditRectangle(ctx, host.x0, host.x1, host.z0, host.z1, levelCount, "a settle over", &E);
-		if (rc != CVX_OK) {
-			release();
-			return rc;
-		}
+		if (rc != CVX_OK) { return rc; }
 		P.rx0 = E.x0;
 		P.rz0 = E.z0;
 		P.rSizeZ = E.sizeZ;
 		P.rn = E.n;
 		cvxpieces::Totals back{};
 		const cvxi::ColumnEditTotals totals{ P.totals, &back, sizeof back, offsetof(cvxpieces::Totals, head.elements), offsetof(cvxpieces::Totals, head.overLimit) };
-		cvxi::ColumnEditCall edit{ call, FailHip, "a column with its pieces settled", "the columns of the settle" };
+		cvxi::ColumnEditCall edit{ call, CVX_ERR_CAPACITY, "a column with its pieces settled", "the columns of the settle" };
 		edit.totals = &totals;
-		edit.done = R.ev[1];
+		edit.done = R.device.Event(1);
 		rc = cvxi::ColumnEdit(
 			ctx, E, levelCount, edit,
 			[&](const cvxi::ColumnEditJob &J) {
@@ -362,12 +353,9 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 				return hipSuccess;
 			},
 			nullptr);
-		if (rc != CVX_OK) {
-			release();
-			return rc;
-		}
-		(void)hipEventElapsedTime(&ms, R.ev[0], R.ev[1]);
-		(void)hipEventElapsedTime(&editMs, relaxed, R.ev[1]);
+		if (rc != CVX_OK) { return rc; }
+		ms = R.device.Ms();
+		editMs = ms - relax.Ms(); // (the relaxation's end is the edit's start)
 	}
 #ifdef CVX_SETTLE_DIAG
 	g_lastMs[0] = R.ms;
@@ -387,7 +375,6 @@ int cvx_world_settle(cvx_context *ctx, const int32_t boxMin[3], const int32_t bo
 	if (wanted && drops) { std::memcpy(drops, dropList.data(), wanted * sizeof(int32_t)); }
 	if (summary) { *summary = out; }
 	if (outDeviceMs) { *outDeviceMs = ms; }
-	release();
 	return CVX_OK;
 }
 

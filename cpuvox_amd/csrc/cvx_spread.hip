@@ -319,24 +319,12 @@ int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, 
 	int rc = cvxi::SyncWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr;
-	auto release = [&]() {
-		if (scratch) { (void)hipFree(scratch); }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
 	cvxspread::Totals host{};
 	int64_t launches = 0;
-	hipError_t e = hipEventCreate(&ev[0]);
-	if (e == hipSuccess) { e = hipEventCreate(&ev[1]); }
-	if (e == hipSuccess) {
-		e = hipMalloc((void **)&scratch, bytes);
-		if (e == hipErrorOutOfMemory) {
-			release();
-			return Fail(ctx, CVX_ERR_CAPACITY, "%s: %zu bytes of device memory for the scratch", call, bytes);
-		}
-	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&scratch, bytes);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) { e = hipMemsetAsync(scratch, 0, bitsAt, ctx->stream); } // the totals and both flag arrays
 	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + seedsAt, seeds, (size_t)seedCount * sizeof(cvx_spread_seed), hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) {
@@ -351,20 +339,15 @@ int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, 
 		                   reinterpret_cast<const cvx_spread_seed *>(scratch + seedsAt), seedCount, flags[0]);
 		e = hipGetLastError();
 		const int64_t bound = (int64_t)A.G.maxSteps + 2;
-		while (e == hipSuccess) { // until a launch lowers nothing
-			if (launches >= bound) {
-				(void)hipStreamSynchronize(ctx->stream);
-				release();
-				return Fail(ctx, CVX_ERR_HIP, "%s: the relaxation did not settle in maxSteps + 2 = %lld launches", call, (long long)bound);
-			}
-			e = hipMemsetAsync(&A.totals->changed, 0, sizeof(unsigned int), ctx->stream);
-			if (e != hipSuccess) { break; }
-			hipLaunchKernelGGL(cvxspread::spread_relax_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, A, flags[launches & 1], flags[(launches & 1) ^ 1]);
-			launches++;
-			e = hipGetLastError();
-			if (e == hipSuccess) { e = hipMemcpyAsync(&host.changed, &A.totals->changed, sizeof host.changed, hipMemcpyDeviceToHost, ctx->stream); }
-			if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-			if (e != hipSuccess || !host.changed) { break; }
+		if (e == hipSuccess) {
+			launches = cvxi::LaunchUntilUnchanged(
+				ctx, &A.totals->changed, bound,
+				[&](const int64_t &k) {
+					hipLaunchKernelGGL(cvxspread::spread_relax_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, A, flags[k & 1], flags[(k & 1) ^ 1]);
+					return hipSuccess;
+				},
+				&e);
+			if (launches < 0) { return Fail(ctx, CVX_ERR_HIP, "%s: the relaxation did not settle in maxSteps + 2 = %lld launches", call, (long long)bound); }
 		}
 	}
 	if (e == hipSuccess) {
@@ -372,19 +355,11 @@ int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, 
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess && !device) { e = hipMemcpyAsync(out, A.out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return Fail(ctx, CVX_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e));
-	}
-	if (outDeviceMs) {
-		float ms = 0.f;
-		e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-		*outDeviceMs = e == hipSuccess ? ms : 0.f;
-	}
-	release();
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	if (summary) {
 		cvx_spread_summary S{};
 		S.passable = (int64_t)host.passable;

@@ -337,33 +337,6 @@ int BitWidth(uint64_t v)
 	return b;
 }
 
-// Device scratch of one stamp: every allocation goes through here and is released at the end.  A failed allocation is CVX_ERR_CAPACITY.
-struct Scratch {
-	std::vector<void *> blocks;
-	~Scratch()
-	{
-		for (void *p : blocks) { (void)hipFree(p); }
-	}
-	template <class T> hipError_t Get(T **out, size_t count)
-	{
-		void *p = nullptr;
-		const hipError_t e = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16));
-		if (e == hipSuccess) { blocks.push_back(p); }
-		*out = static_cast<T *>(p);
-		return e;
-	}
-};
-
-// (the pipeline's allocations report as the stamp's own do)
-int FailStampHip(cvx_context *ctx, const char *, hipError_t e)
-{
-	if (e == hipErrorOutOfMemory) {
-		(void)hipGetLastError();
-		return Fail(ctx, CVX_ERR_CAPACITY, "out of device memory for the stamp");
-	}
-	return Fail(ctx, CVX_ERR_HIP, "stamp failed: %s", hipGetErrorString(e));
-}
-
 } // namespace
 
 extern "C" {
@@ -413,29 +386,21 @@ int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int 
 	int rc = cvxi::SyncWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
-	Scratch S;
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	struct Events {
-		hipEvent_t *ev;
-		~Events() { for (int i = 0; i < 2; i++) { if (ev[i]) { (void)hipEventDestroy(ev[i]); } } }
-	} events{ ev };
+	static const char *const call = "cvx_world_stamp_mesh";
+	cvxi::DeviceCall D(ctx, call);
 	hipStream_t stream = ctx->stream;
 	const size_t chunk = (size_t)cvxi::ScanChunk();
 	auto chunksOf = [&](size_t n) { return (n + chunk - 1) / chunk; };
 #define CVX_ST_HIP(call)                                                                                         \
 	do {                                                                                                         \
 		const hipError_t e_ = (call);                                                                            \
-		if (e_ != hipSuccess) { return Fail(ctx, CVX_ERR_HIP, "stamp failed: %s", hipGetErrorString(e_)); } \
+		if (e_ != hipSuccess) { return D.Fail(e_); }                                                             \
 	} while (0)
-#define CVX_ST_ALLOC(ptr, count)                                                                                                       \
-	do {                                                                                                                               \
-		if (S.Get(&(ptr), (count)) != hipSuccess) {                                                                                    \
-			(void)hipGetLastError();                                                                                                   \
-			return Fail(ctx, CVX_ERR_CAPACITY, "out of device memory for the stamp (%llu entries)", (unsigned long long)(count)); \
-		}                                                                                                                              \
+#define CVX_ST_ALLOC(ptr, count)                                                                      \
+	do {                                                                                              \
+		const hipError_t e_ = D.Allocate(&(ptr), std::max<size_t>((count) * sizeof *(ptr), 16)); \
+		if (e_ != hipSuccess) { return D.Fail(e_); }                                                  \
 	} while (0)
-	CVX_ST_HIP(hipEventCreate(&ev[0]));
-	CVX_ST_HIP(hipEventCreate(&ev[1]));
 
 	// the mesh
 	cvx_mesh_vertex *dVertices = nullptr;
@@ -448,7 +413,7 @@ int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int 
 	CVX_ST_ALLOC(dTextures, (size_t)materialCount);
 	CVX_ST_ALLOC(dTexels, (size_t)texelBytes);
 	CVX_ST_ALLOC(dTotals, 9);
-	CVX_ST_HIP(hipEventRecord(ev[0], stream));
+	CVX_ST_HIP(D.Begin());
 	CVX_ST_HIP(hipMemcpyAsync(dVertices, vertices, (size_t)vertexCount * sizeof(cvx_mesh_vertex), hipMemcpyHostToDevice, stream));
 	CVX_ST_HIP(hipMemcpyAsync(dIndices, indices, (size_t)indexCount * sizeof(int32_t), hipMemcpyHostToDevice, stream));
 	if (materialCount > 0) { CVX_ST_HIP(hipMemcpyAsync(dTextures, textures.data(), textures.size() * sizeof(cvxs::Texture), hipMemcpyHostToDevice, stream)); }
@@ -579,9 +544,9 @@ int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int 
 	A.voxels = voxels;
 	// ... and its columns through cvx_world_edit's machinery (cvxi::ColumnEdit): the elements and the flag are dTotals[4] and [5]
 	const cvxi::ColumnEditTotals back{ dTotals, totals, sizeof totals, 4 * sizeof(unsigned long long), 5 * sizeof(unsigned long long) };
-	cvxi::ColumnEditCall edit{ "stamp", FailStampHip, "a stamped column", "the stamped columns" };
+	cvxi::ColumnEditCall edit{ call, CVX_ERR_CAPACITY, "a stamped column", "the stamped columns" };
 	edit.totals = &back;
-	edit.done = ev[1];
+	edit.done = D.Event(1);
 	rc = cvxi::ColumnEdit(
 		ctx, R, levelCount, edit,
 		[&](const cvxi::ColumnEditJob &J) {
@@ -597,10 +562,7 @@ int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int 
 			return hipSuccess;
 		},
 		nullptr);
-	if (rc == CVX_OK && outDeviceMs) {
-		float ms = 0.f;
-		*outDeviceMs = hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess ? ms : 0.f;
-	}
+	if (rc == CVX_OK && outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return rc;
 }
 

@@ -23,7 +23,6 @@ using cvxi::Fail;
 
 namespace cvxsurface {
 
-using cvxi::FailHip;
 using cvxi::Grid;
 using cvxi::kThreads;
 
@@ -128,20 +127,15 @@ static int Surface(cvx_context *ctx, const char *call, const int32_t boxMin[3], 
 	if (rc != CVX_OK) { return rc; }
 
 	const int pairs = (int)(A.B.Columns() * kFaces);
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	std::vector<cvx_surface_quad> back; // (outlives D: freeing the device blocks waits for a copy still under way)
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr, *list = nullptr;
-	auto release = [&]() {
-		for (uint8_t *p : { scratch, list }) { if (p) { (void)hipFree(p); } }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
 	cvxi::ScratchLayout carve;
 	const size_t chunks = ((size_t)pairs + 1 + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	const size_t oTotals = carve(sizeof(Totals)), oOffsets = carve(((size_t)pairs + 1) * 4), oChunks = carve(chunks * 8);
 	Totals host{};
-	hipError_t e = hipSuccess;
-	for (hipEvent_t &event : ev) { if (e == hipSuccess) { e = hipEventCreate(&event); } }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, carve.bytes); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&scratch, carve.bytes);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, sizeof(Totals), ctx->stream); }
 	if (e == hipSuccess) {
 		A.W = cvxi::WorldOf(ctx);
@@ -156,22 +150,15 @@ static int Surface(cvx_context *ctx, const char *call, const int32_t boxMin[3], 
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	}
-	if (e != hipSuccess) {
-		release();
-		return FailHip(ctx, call, e);
-	}
-	if (host.quads >= ((unsigned long long)1 << 31) - 1) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the box holds %llu quads", host.quads);
-	}
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (host.quads >= ((unsigned long long)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "the box holds %llu quads", host.quads); }
 	const size_t wanted = (size_t)std::min<unsigned long long>(host.quads, (unsigned long long)quadCapacity);
-	std::vector<cvx_surface_quad> back;
 	if (wanted) {
 		if (device) {
 			A.quads = quads;
 		} else {
 			back.resize(wanted);
-			e = hipMalloc((void **)&list, wanted * sizeof(cvx_surface_quad));
+			e = D.Allocate(&list, wanted * sizeof(cvx_surface_quad));
 			A.quads = reinterpret_cast<cvx_surface_quad *>(list);
 		}
 		if (e == hipSuccess) {
@@ -181,19 +168,13 @@ static int Surface(cvx_context *ctx, const char *call, const int32_t boxMin[3], 
 		}
 		if (e == hipSuccess && !device) { e = hipMemcpyAsync(back.data(), list, wanted * sizeof(cvx_surface_quad), hipMemcpyDeviceToHost, ctx->stream); }
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return FailHip(ctx, call, e);
-	}
-	float ms = 0.f;
-	(void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+	if (e != hipSuccess) { return D.Fail(e); }
 	// (nothing is handed out before the call can no longer fail)
 	if (!back.empty()) { std::memcpy(quads, back.data(), back.size() * sizeof(cvx_surface_quad)); }
 	if (summary) { std::memcpy(summary, &host, sizeof *summary); }
-	if (outDeviceMs) { *outDeviceMs = ms; }
-	release();
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return CVX_OK;
 }
 

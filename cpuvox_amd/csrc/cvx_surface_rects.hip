@@ -28,7 +28,6 @@ using cvxi::Fail;
 
 namespace cvxrects {
 
-using cvxi::FailHip;
 using cvxi::Grid;
 using cvxi::kThreads;
 
@@ -191,21 +190,16 @@ static int Rects(cvx_context *ctx, const char *call, const int32_t boxMin[3], co
 	if (rc != CVX_OK) { return rc; }
 
 	const int pairs = (int)(A.B.Columns() * kFaces);
-	hipEvent_t ev[2] = { nullptr, nullptr };
+	std::vector<cvx_surface_rect> back; // (outlives D: freeing the device blocks waits for a copy still under way)
+	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr, *stripScratch = nullptr, *list = nullptr;
-	auto release = [&]() {
-		for (uint8_t *p : { scratch, stripScratch, list }) { if (p) { (void)hipFree(p); } }
-		for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } }
-	};
 	cvxi::ScratchLayout carve;
 	const size_t chunks = ((size_t)pairs + 1 + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	const size_t oTotals = carve(sizeof(Totals)), oStripOffsets = carve(((size_t)pairs + 1) * 4), oRectOffsets = carve(((size_t)pairs + 1) * 4);
 	const size_t oChunks = carve(chunks * 8), oChunks2 = carve(chunks * 8);
 	Totals host{};
-	hipError_t e = hipSuccess;
-	for (hipEvent_t &event : ev) { if (e == hipSuccess) { e = hipEventCreate(&event); } }
-	if (e == hipSuccess) { e = hipMalloc((void **)&scratch, carve.bytes); }
-	if (e == hipSuccess) { e = hipEventRecord(ev[0], ctx->stream); }
+	hipError_t e = D.Allocate(&scratch, carve.bytes);
+	if (e == hipSuccess) { e = D.Begin(); }
 	if (e == hipSuccess) { e = hipMemsetAsync(scratch + oTotals, 0, sizeof(Totals), ctx->stream); }
 	if (e == hipSuccess) {
 		A.W = cvxi::WorldOf(ctx);
@@ -221,19 +215,13 @@ static int Rects(cvx_context *ctx, const char *call, const int32_t boxMin[3], co
 		if (e == hipSuccess) { e = hipMemcpyAsync(&host.strips, &A.totals->strips, sizeof host.strips, hipMemcpyDeviceToHost, ctx->stream); }
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	}
-	if (e != hipSuccess) {
-		release();
-		return FailHip(ctx, call, e);
-	}
-	if (host.strips >= ((unsigned long long)1 << 31) - 1) {
-		release();
-		return Fail(ctx, CVX_ERR_CAPACITY, "the box holds %llu strips", host.strips);
-	}
+	if (e != hipSuccess) { return D.Fail(e); }
+	if (host.strips >= ((unsigned long long)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "the box holds %llu strips", host.strips); }
 	const size_t strips = (size_t)host.strips;
 	if (strips) {
 		carve.bytes = 0;
 		const size_t oStrips = carve(strips * sizeof(cvxb::RectStrip)), oAlong = carve(strips * 4), oRows = carve(strips * 4);
-		e = hipMalloc((void **)&stripScratch, carve.bytes);
+		e = D.Allocate(&stripScratch, carve.bytes);
 		if (e == hipSuccess) {
 			A.strips = reinterpret_cast<cvxb::RectStrip *>(stripScratch + oStrips);
 			A.along = reinterpret_cast<uint32_t *>(stripScratch + oAlong);
@@ -247,18 +235,14 @@ static int Rects(cvx_context *ctx, const char *call, const int32_t boxMin[3], co
 	}
 	if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return FailHip(ctx, call, e);
-	}
+	if (e != hipSuccess) { return D.Fail(e); }
 	const size_t wanted = (size_t)std::min<unsigned long long>(host.rects, (unsigned long long)rectCapacity);
-	std::vector<cvx_surface_rect> back;
 	if (wanted) {
 		if (device) {
 			A.rects = rects;
 		} else {
 			back.resize(wanted);
-			e = hipMalloc((void **)&list, wanted * sizeof(cvx_surface_rect));
+			e = D.Allocate(&list, wanted * sizeof(cvx_surface_rect));
 			A.rects = reinterpret_cast<cvx_surface_rect *>(list);
 		}
 		if (e == hipSuccess) {
@@ -268,19 +252,13 @@ static int Rects(cvx_context *ctx, const char *call, const int32_t boxMin[3], co
 		}
 		if (e == hipSuccess && !device) { e = hipMemcpyAsync(back.data(), list, wanted * sizeof(cvx_surface_rect), hipMemcpyDeviceToHost, ctx->stream); }
 	}
-	if (e == hipSuccess) { e = hipEventRecord(ev[1], ctx->stream); }
+	if (e == hipSuccess) { e = D.End(); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) {
-		release();
-		return FailHip(ctx, call, e);
-	}
-	float ms = 0.f;
-	(void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+	if (e != hipSuccess) { return D.Fail(e); }
 	// (nothing is handed out before the call can no longer fail)
 	if (!back.empty()) { std::memcpy(rects, back.data(), back.size() * sizeof(cvx_surface_rect)); }
 	if (summary) { std::memcpy(summary, &host, sizeof *summary); }
-	if (outDeviceMs) { *outDeviceMs = ms; }
-	release();
+	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return CVX_OK;
 }
 
