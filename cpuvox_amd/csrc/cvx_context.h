@@ -293,6 +293,18 @@ int ScanChunk();
 // = level j (hipFree them), columnsZ as in the blob (dimZ >> j)
 int BuildLodChainOnDevice(cvx_context *ctx, const uint8_t *dSrc, int64_t elementsOfColumns, int dimX, int dimY, int dimZ, int columnCount, int levelCount,
                           uint32_t **headers, uint32_t **elements);
+// cvx_readback.hip: the device half of a read-back -- count, scan, write into a device blob -- in two steps around the caller's ONE
+// synchronisation, so that a caller with several rectangles (a snapshot's levels) brings all totals back at once.  The rectangle of level `lod`
+// is validated and the world laid out (SyncWorld).
+struct RegionRead {
+	int lod, x0, z0, sizeX, sizeZ;
+	uint32_t *offsets;        // RegionReadCount: per column its elements, scanned into offsets (in D's scratch)
+	unsigned long long total; // ... and their sum, valid once the stream has run the copy RegionReadCount enqueues: R must not move until then
+};
+// Allocates the scratch from D, enqueues the count, the scan and the copy of the total to R->total.  Does not wait.
+hipError_t RegionReadCount(cvx_context *ctx, DeviceCall &D, RegionRead *R);
+// Enqueues the write of the rectangle's headers to dBlob and of its element pool (R.total elements) to dBlob + headerBytes.  Does not wait.
+hipError_t RegionReadWrite(cvx_context *ctx, const RegionRead &R, uint8_t *dBlob, size_t headerBytes);
 // cvx_edit.hip: releases the edit state's device tables (cvx_destroy)
 void FreeEditState(cvx_context *ctx);
 // cvx_edit.hip: cvx_world_edit behind its host validation and upload, for a valid sub-world blob already on the device at dSrc (cvx_world_brush
@@ -300,6 +312,11 @@ void FreeEditState(cvx_context *ctx);
 // patch.  Returns once the stream has run it.
 int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const uint8_t *dSrc, int64_t elementsOfColumns, int columnCount, int levelCount,
                    hipEvent_t done);
+// cvx_edit.hip: the tail of EditFromDevice alone, for a caller that holds every level already (a snapshot's restore): the patch of LOD 0 ..
+// levelCount over (rectangle >> level) from valid blobs on the device, headers[l] / elements[l] = level l; nothing is downsampled.  `done` and the
+// return as EditFromDevice.
+int PatchLevelsFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const uint32_t *const *headers, const uint32_t *const *elements, int levelCount,
+                          hipEvent_t done);
 
 // ---- the column-edit pipeline (cvx_edit.hip): what every call that builds its sub-world blob on the device goes through ----
 // The LOD-0 rectangle of an edit: n = sizeX * sizeZ columns, aligned to 2^levelCount

@@ -499,12 +499,25 @@ int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 			}
 		}
 	} lods;
-	DeviceCall D(ctx, "edit");
-	std::vector<Job> jobs;
 	if (levelCount > 0) {
 		const int rc = BuildLodChainOnDevice(ctx, dSrc, elementsOfColumns, sizeX, ctx->hostWorld.dimY, sizeZ, columnCount, levelCount, lods.headers + 1, lods.elements + 1);
 		if (rc != CVX_OK) { return rc; }
 	}
+	const uint32_t *headers[CVX_LOD_LEVELS], *elements[CVX_LOD_LEVELS];
+	for (int l = 0; l <= levelCount; l++) {
+		headers[l] = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc) : lods.headers[l];
+		elements[l] = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc + (size_t)columnCount * 12) : lods.elements[l];
+	}
+	return PatchLevelsFromDevice(ctx, x0, z0, sizeX, sizeZ, headers, elements, levelCount, done);
+}
+
+// Steps 1 .. 4 for LOD 0 .. levelCount, one job per level, from blobs that hold every level already: EditFromDevice's tail, and all of a
+// snapshot's restore (cvx_snapshot.hip), which keeps the coarse columns it captured and therefore downsamples nothing.
+int PatchLevelsFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const uint32_t *const *headers, const uint32_t *const *elements, int levelCount,
+                          hipEvent_t done)
+{
+	DeviceCall D(ctx, "edit");
+	std::vector<Job> jobs;
 	for (int l = 0; l <= levelCount; l++) {
 		Job j;
 		j.lod = l;
@@ -512,8 +525,8 @@ int EditFromDevice(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 		j.z0 = z0 >> l;
 		j.sizeX = sizeX >> l;
 		j.sizeZ = sizeZ >> l;
-		j.headers = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc) : lods.headers[l];
-		j.elements = l == 0 ? reinterpret_cast<const uint32_t *>(dSrc + (size_t)columnCount * 12) : lods.elements[l];
+		j.headers = headers[l];
+		j.elements = elements[l];
 		jobs.push_back(j);
 	}
 	int rc = ApplyJobs(ctx, D, jobs);

@@ -6,6 +6,7 @@
 //   2. the counts are prefix-scanned into element offsets; ONE copy brings the total to the host
 //   3. write  (same threads): the headers and the element pool, in the reference's layout
 //   4. ONE device-to-host copy into the caller's buffer.
+// Steps 1 .. 3 are cvxi::RegionReadCount / RegionReadWrite: a snapshot's capture (cvx_snapshot.hip) runs them per level and keeps the blob on the device.
 // A compaction lays the arena out again with Relayout's placement (cvx_edit.hip) and fills it on the device, level by level:
 //   1. count  (a thread per record): the run-list entries of a listed column and, for a column-after-column level, the colours of every column;
 //             (a thread per 4 x 8 block, colour-block levels) the depth of the block = the most colours one of its columns holds
@@ -185,6 +186,62 @@ constexpr unsigned kThreads = 256;
 
 unsigned Grid(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
+// The read kernels' arguments for a rectangle, from the arena as it lies now
+cvxread::ReadArgs ArgsOf(const cvx_context *ctx, const cvxi::RegionRead &R)
+{
+	const DevWorldLevel &L = ctx->hostWorld.level[R.lod];
+	cvxread::ReadArgs A{};
+	A.arena = ctx->arena;
+	A.recordsOff = L.recordsOff;
+	A.runsOff = L.runsOff;
+	A.elementsOff = L.elementsOff;
+	A.rowShift = L.rowShift;
+	A.colorShift = L.colorShift;
+	A.lod = R.lod;
+	A.dimY = ctx->hostWorld.dimY;
+	A.x0 = R.x0;
+	A.z0 = R.z0;
+	A.sizeZ = R.sizeZ;
+	A.n = R.sizeX * R.sizeZ;
+	A.counts = R.offsets;
+	return A;
+}
+
+} // namespace
+
+// The device half of a read-back (cvx_context.h), shared by ReadBack below and the snapshot's capture (cvx_snapshot.hip)
+hipError_t cvxi::RegionReadCount(cvx_context *ctx, DeviceCall &D, RegionRead *R)
+{
+	const int n = R->sizeX * R->sizeZ;
+	uint8_t *scratch = nullptr;
+	const size_t chunks = ((size_t)n + ScanChunk() - 1) / ScanChunk();
+	ScratchLayout carve;
+	const size_t oCounts = carve((size_t)n * 4), oTotal = carve(8), oChunks = carve(chunks * 8);
+	R->total = 0;
+	hipError_t e = D.Allocate(&scratch, carve.bytes);
+	if (e != hipSuccess || n == 0) { return e; } // (n = 0: a level without columns, LOD 5 of a world 16 columns wide -- its blob is the zero headers alone)
+	R->offsets = reinterpret_cast<uint32_t *>(scratch + oCounts);
+	unsigned long long *dTotal = reinterpret_cast<unsigned long long *>(scratch + oTotal);
+	hipLaunchKernelGGL(cvxread::read_count_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, ArgsOf(ctx, *R));
+	ExclusiveScan(ctx->stream, R->offsets, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), dTotal);
+	e = hipGetLastError();
+	if (e == hipSuccess) { e = hipMemcpyAsync(&R->total, dTotal, sizeof R->total, hipMemcpyDeviceToHost, ctx->stream); }
+	return e;
+}
+
+hipError_t cvxi::RegionReadWrite(cvx_context *ctx, const RegionRead &R, uint8_t *dBlob, size_t headerBytes)
+{
+	const int n = R.sizeX * R.sizeZ;
+	if (n == 0) { return hipSuccess; }
+	cvxread::ReadArgs A = ArgsOf(ctx, R);
+	A.headers = reinterpret_cast<uint32_t *>(dBlob);
+	A.elements = reinterpret_cast<uint32_t *>(dBlob + headerBytes);
+	hipLaunchKernelGGL(cvxread::read_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
+	return hipGetLastError();
+}
+
+namespace {
+
 // The rectangle [x0, x0 + sizeX) x [z0, z0 + sizeZ) of level `lod` (validated) as a blob of `columnCount` headers (>= the rectangle's columns;
 // the ones behind it stay zero) and the element pool, in malloc'd memory.
 int ReadBack(cvx_context *ctx, const char *call, int lod, int x0, int z0, int sizeX, int sizeZ, int64_t columnCount, void **outStorage, int64_t *outByteLength,
@@ -193,37 +250,13 @@ int ReadBack(cvx_context *ctx, const char *call, int lod, int x0, int z0, int si
 	const int n = sizeX * sizeZ;
 	std::unique_ptr<void, void (*)(void *)> blob(nullptr, std::free); // (outlives D: freeing the device blocks waits for a copy still under way)
 	cvxi::DeviceCall D(ctx, call);
-	uint8_t *scratch = nullptr, *dBlob = nullptr;
-	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
-	cvxi::ScratchLayout carve;
-	const size_t oCounts = carve((size_t)n * 4), oTotal = carve(8), oChunks = carve(chunks * 8);
-	const DevWorldLevel &L = ctx->hostWorld.level[lod];
-	cvxread::ReadArgs A{};
-	A.arena = ctx->arena;
-	A.recordsOff = L.recordsOff;
-	A.runsOff = L.runsOff;
-	A.elementsOff = L.elementsOff;
-	A.rowShift = L.rowShift;
-	A.colorShift = L.colorShift;
-	A.lod = lod;
-	A.dimY = ctx->hostWorld.dimY;
-	A.x0 = x0;
-	A.z0 = z0;
-	A.sizeZ = sizeZ;
-	A.n = n;
+	uint8_t *dBlob = nullptr;
+	cvxi::RegionRead R{ lod, x0, z0, sizeX, sizeZ, nullptr, 0 };
 	// 1, 2. count, scan, one copy back
-	unsigned long long total = 0;
-	hipError_t e = D.Allocate(&scratch, carve.bytes);
-	if (e == hipSuccess && n > 0) { // (n = 0: a level without columns, LOD 5 of a world 16 columns wide -- its blob is the zero headers alone)
-		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
-		unsigned long long *dTotal = reinterpret_cast<unsigned long long *>(scratch + oTotal);
-		hipLaunchKernelGGL(cvxread::read_count_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
-		cvxi::ExclusiveScan(ctx->stream, A.counts, n, reinterpret_cast<unsigned long long *>(scratch + oChunks), dTotal);
-		e = hipGetLastError();
-		if (e == hipSuccess) { e = hipMemcpyAsync(&total, dTotal, sizeof total, hipMemcpyDeviceToHost, ctx->stream); }
-		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	}
+	hipError_t e = cvxi::RegionReadCount(ctx, D, &R);
+	if (e == hipSuccess && n > 0) { e = hipStreamSynchronize(ctx->stream); }
 	if (e != hipSuccess) { return D.Fail(e); }
+	const unsigned long long total = R.total;
 	if (total >= ((unsigned long long)1 << 31)) { // (storageOffset is an int32)
 		return Fail(ctx, CVX_ERR_CAPACITY, "LOD %d: the read-back needs %llu elements", lod, total);
 	}
@@ -233,12 +266,7 @@ int ReadBack(cvx_context *ctx, const char *call, int lod, int x0, int z0, int si
 	if (!blob) { return Fail(ctx, CVX_ERR_CAPACITY, "read-back: no host memory for %zu bytes", blobBytes); }
 	e = D.Allocate(&dBlob, std::max<size_t>(blobBytes, 4));
 	if (e == hipSuccess && headerBytes > (size_t)n * 12) { e = hipMemsetAsync(dBlob + (size_t)n * 12, 0, headerBytes - (size_t)n * 12, ctx->stream); }
-	if (e == hipSuccess && n > 0) {
-		A.headers = reinterpret_cast<uint32_t *>(dBlob);
-		A.elements = reinterpret_cast<uint32_t *>(dBlob + headerBytes);
-		hipLaunchKernelGGL(cvxread::read_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
+	if (e == hipSuccess) { e = cvxi::RegionReadWrite(ctx, R, dBlob, headerBytes); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(blob.get(), dBlob, blobBytes, hipMemcpyDeviceToHost, ctx->stream); }
 	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	if (e != hipSuccess) { return D.Fail(e); }

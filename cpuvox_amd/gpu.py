@@ -53,6 +53,9 @@ MODELS_EXPORTS = ["cvx_world_place_models", "cvx_world_place_models_device", "cv
 SPREAD_EXPORTS = ["cvx_world_spread", "cvx_world_spread_device"]
 # include/cpuvox_gpu_surface_rects.h: the exposed faces merged into rectangles, exported by every build (checked by tests/test_world_surface_rects_cpu.py)
 SURFACE_RECTS_EXPORTS = ["cvx_world_surface_rects", "cvx_world_surface_rects_device", "cvx_surface_rect_triangles"]
+# include/cpuvox_gpu_snapshot.h: snapshots of rectangles that stay on the device, exported by every build (checked by tests/test_world_snapshot_cpu.py)
+SNAPSHOT_EXPORTS = ["cvx_world_snapshot", "cvx_snapshot_info_get", "cvx_world_snapshot_restore", "cvx_world_snapshot_diff", "cvx_world_snapshot_diff_device",
+                    "cvx_snapshot_destroy"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -99,6 +102,7 @@ SPREAD_AIR, SPREAD_SOLID = 0, 1                  # cvx_spread_params.medium
 SPREAD_UNREACHED, SPREAD_BLOCKED = -1, -2        # cvx_world_spread: passable but not reached within max_steps / not passable
 SPREAD_MAX_SEEDS, SPREAD_MAX_STEPS = 4096, 65534
 SPREAD_TILE = (8, 64, 8)                         # CVX_SPREAD_TILE_X / _Y / _Z: the (x, y, z) extents of the tile a workgroup relaxes
+SNAPSHOT_IGNORE_COLOUR = 1                       # cvx_world_snapshot_diff: flags
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -128,6 +132,19 @@ class SpreadSeed(C.Structure):  # cvx_spread_seed
 class SpreadSummary(C.Structure):  # cvx_spread_summary
     _fields_ = [("passable", C.c_int64), ("reached", C.c_int64), ("largestDistance", C.c_int32), ("seedsUsed", C.c_int32), ("launches", C.c_int32),
                 ("pad_", C.c_int32), ("tileVisits", C.c_int64)]
+
+
+class SnapshotInfo(C.Structure):  # cvx_snapshot_info
+    _fields_ = [("x0", C.c_int32), ("z0", C.c_int32), ("sizeX", C.c_int32), ("sizeZ", C.c_int32), ("levelCount", C.c_int32), ("dimX", C.c_int32),
+                ("dimY", C.c_int32), ("dimZ", C.c_int32), ("deviceBytes", C.c_int64), ("elements", C.c_int64)]
+
+
+class SnapshotChange(C.Structure):  # cvx_snapshot_change
+    _fields_ = [("x", C.c_int32), ("z", C.c_int32), ("yMin", C.c_int32), ("yMax", C.c_int32)]
+
+
+class SnapshotDiffSummary(C.Structure):  # cvx_snapshot_diff_summary
+    _fields_ = [("changedColumns", C.c_int64), ("changedVoxels", C.c_int64), ("min", C.c_int32 * 3), ("max", C.c_int32 * 3), ("pad_", C.c_int32 * 2)]
 
 
 class BrushStroke(C.Structure):
@@ -243,6 +260,7 @@ NAV_SUMMARY_DTYPE = np.dtype([("nodes", "<i8"), ("reached", "<i8"), ("goalsResol
 SPREAD_SEED_DTYPE = np.dtype([("voxel", "<i4", 3), ("start", "<i4")])  # cvx_spread_seed
 SPREAD_SUMMARY_DTYPE = np.dtype([("passable", "<i8"), ("reached", "<i8"), ("largestDistance", "<i4"), ("seedsUsed", "<i4"), ("launches", "<i4"),
                                  ("pad_", "<i4"), ("tileVisits", "<i8")])  # cvx_spread_summary
+SNAPSHOT_CHANGE_DTYPE = np.dtype([("x", "<i4"), ("z", "<i4"), ("yMin", "<i4"), ("yMax", "<i4")])  # cvx_snapshot_change
 SURFACE_QUAD_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("length", "<i4"), ("argb", "<u4")])  # cvx_surface_quad
 SURFACE_SUMMARY_DTYPE = np.dtype([("quads", "<i8"), ("unitFaces", "<i8"), ("quadsPerFace", "<i8", 6)])  # cvx_surface_summary
 
@@ -523,6 +541,13 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_surface_rects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
         L.cvx_world_surface_rects_device.argtypes = L.cvx_world_surface_rects.argtypes
         L.cvx_surface_rect_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.cvx_world_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_float)]
+        L.cvx_snapshot_info_get.argtypes = [C.c_void_p, C.POINTER(SnapshotInfo)]
+        L.cvx_world_snapshot_restore.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_snapshot_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+        L.cvx_world_snapshot_diff_device.argtypes = L.cvx_world_snapshot_diff.argtypes
+        L.cvx_snapshot_destroy.argtypes = [C.c_void_p]
+        L.cvx_snapshot_destroy.restype = None
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -585,6 +610,7 @@ class Context:
             self._check(lib().cvx_set_buffer_count(self._h, buffer_count))
         self.buffer_count = buffer_count
         self._nav_fields = []  # the NavFields still open: closed with the context, which they must not outlive
+        self._snapshots = []   # ... and the Snapshots, under the same rule
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -594,6 +620,8 @@ class Context:
         if self._h:
             for field in list(getattr(self, "_nav_fields", ())):
                 field.close()
+            for snapshot in list(getattr(self, "_snapshots", ())):
+                snapshot.close()
             lib().cvx_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1062,6 +1090,16 @@ class Context:
                                                     out_ptr or None, C.byref(ms)))
         return ms.value
 
+    # -- snapshots that stay on the device (include/cpuvox_gpu_snapshot.h) --
+    def world_snapshot(self, x0: int, z0: int, size_x: int, size_z: int, level_count: int = 5) -> "Snapshot":
+        """cvx_world_snapshot: the columns of the rectangle (rounded outward to 2^level_count, clipped) at LOD 0 .. level_count, kept in device
+        memory -> a Snapshot (.info, .restore(), .diff(), .diff_device(), .close(); a context manager)."""
+        handle, ms = C.c_void_p(), C.c_float()
+        self._check(lib().cvx_world_snapshot(self._h, int(x0), int(z0), int(size_x), int(size_z), int(level_count), C.byref(handle), C.byref(ms)))
+        snapshot = Snapshot(self, handle, ms.value)
+        self._snapshots.append(snapshot)
+        return snapshot
+
     # -- travel-distance fields through air or solid (cvx_world_spread) --
     def _spread(self, fn, box_min, box_max, seeds, medium, step_faces, max_steps, out_ptr):
         lo, hi = self._box(box_min, box_max)
@@ -1371,6 +1409,63 @@ class Context:
         total = C.c_uint64()
         self._check(self._diag("cvx_selftest_scan")(self._h, v.size, v.ctypes.data, C.byref(total)))
         return v, int(total.value)
+
+
+class Snapshot:
+    """A cvx_snapshot: made by Context.world_snapshot, closed by .close(), by leaving its `with` block, or with its context.  It keeps its
+    context alive and must be destroyed before it (cvx_snapshot_destroy before cvx_destroy): Context.close() closes the snapshots still open."""
+
+    def __init__(self, ctx: "Context", handle, ms: float):
+        self._ctx, self._h, self.ms = ctx, handle, ms
+        info = SnapshotInfo()
+        ctx._check(lib().cvx_snapshot_info_get(handle, C.byref(info)))
+        self.info = {name: int(getattr(info, name)) for name, _ in SnapshotInfo._fields_}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def restore(self) -> float:
+        """cvx_world_snapshot_restore: every held level back over its rectangle -> device milliseconds."""
+        ms = C.c_float()
+        self._ctx._check(lib().cvx_world_snapshot_restore(self._ctx._h, self._h, C.byref(ms)))
+        return ms.value
+
+    def _diff(self, fn, flags, ptr, capacity):
+        summary, ms = SnapshotDiffSummary(), C.c_float()
+        self._ctx._check(fn(self._ctx._h, self._h, int(flags), C.c_void_p(ptr) if ptr else None, int(capacity), C.byref(summary), C.byref(ms)))
+        self.ms = ms.value
+        return {"changedColumns": int(summary.changedColumns), "changedVoxels": int(summary.changedVoxels), "min": tuple(summary.min), "max": tuple(summary.max)}
+
+    def diff(self, flags: int = 0, capacity: int | None = None):
+        """cvx_world_snapshot_diff: LOD 0 as it is now against the snapshot's -> (a SNAPSHOT_CHANGE_DTYPE array of the first min(capacity, changed
+        columns) changed columns in the rectangle's column order, the summary as a dict).  capacity None: every column of the rectangle."""
+        if capacity is None:
+            capacity = self.info["sizeX"] * self.info["sizeZ"]
+        changes = np.zeros(int(capacity), dtype=SNAPSHOT_CHANGE_DTYPE)
+        summary = self._diff(lib().cvx_world_snapshot_diff, flags, changes.ctypes.data if capacity else None, capacity)
+        return changes[:min(int(capacity), summary["changedColumns"])], summary
+
+    def diff_device(self, tensor_ptr, capacity: int, flags: int = 0) -> dict:
+        """cvx_world_snapshot_diff_device: the list goes to device memory at `tensor_ptr` (an address, e.g. a torch tensor's data_ptr(), with room for
+        `capacity` entries of 16 bytes; None with capacity 0) -> the summary."""
+        return self._diff(lib().cvx_world_snapshot_diff_device, flags, int(tensor_ptr) if tensor_ptr else None, capacity)
+
+    def close(self) -> None:
+        if self._h:
+            lib().cvx_snapshot_destroy(self._h)
+            self._h = C.c_void_p()
+            if self in self._ctx._snapshots:
+                self._ctx._snapshots.remove(self)
+
+    def __del__(self):
+        try:
+            if self._ctx._h:  # (a context that is gone has closed its snapshots)
+                self.close()
+        except Exception:
+            pass
 
 
 class NavField:
