@@ -20,19 +20,23 @@ def _split(ws: host.WorldSet, lod: int):
     return headers, blob[_table(dx, dz, lod) * 12:]
 
 
-def tile_blob(ws: host.WorldSet, lod: int, k: int) -> np.ndarray:
-    """LOD `lod` of W laid out k x k times: the header table tiled (x-major), every copy of a column pointing at the one pool."""
+def tile_blob(ws: host.WorldSet, lod: int, k: int, kz: int | None = None) -> np.ndarray:
+    """LOD `lod` of W laid out k x kz times (kz: k where not given): the header table tiled (x-major), every copy of a column pointing at the one
+    pool."""
     dx, _, dz = ws.dims
+    kz = k if kz is None else kz
     headers, pool = _split(ws, lod)
-    table = np.zeros(_table(dx * k, dz * k, lod), dtype=HEADER)
-    tiled = np.tile(headers, (k, k)).reshape(-1)
+    table = np.zeros(_table(dx * k, dz * kz, lod), dtype=HEADER)
+    tiled = np.tile(headers, (k, kz)).reshape(-1)
     table[: tiled.size] = tiled
     return np.concatenate([table.view(np.uint8), pool])
 
 
-def tile_world(ws: host.WorldSet, k: int) -> host.WorldSet:
+def tile_world(ws: host.WorldSet, k: int, kz: int | None = None) -> host.WorldSet:
+    """W laid out k times along X and kz times along Z (kz: k where not given)."""
     dx, dy, dz = ws.dims
-    return host.WorldSet.from_blobs((dx * k, dy, dz * k), [tile_blob(ws, lod, k) for lod in range(host.LOD_LEVELS)])
+    kz = k if kz is None else kz
+    return host.WorldSet.from_blobs((dx * k, dy, dz * kz), [tile_blob(ws, lod, k, kz) for lod in range(host.LOD_LEVELS)])
 
 
 def column(ws: host.WorldSet, lod: int, x: int, z: int, split=None):
