@@ -56,6 +56,8 @@ SURFACE_RECTS_EXPORTS = ["cvx_world_surface_rects", "cvx_world_surface_rects_dev
 # include/cpuvox_gpu_snapshot.h: snapshots of rectangles that stay on the device, exported by every build (checked by tests/test_world_snapshot_cpu.py)
 SNAPSHOT_EXPORTS = ["cvx_world_snapshot", "cvx_snapshot_info_get", "cvx_world_snapshot_restore", "cvx_world_snapshot_diff", "cvx_world_snapshot_diff_device",
                     "cvx_snapshot_destroy"]
+# include/cpuvox_gpu_lift.h: the floating pieces as models with mass moments, exported by every build (checked by tests/test_world_lift_cpu.py)
+LIFT_EXPORTS = ["cvx_world_lift_pieces", "cvx_world_lift_pieces_device", "cvx_lifted_piece_mass"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -103,6 +105,7 @@ SPREAD_UNREACHED, SPREAD_BLOCKED = -1, -2        # cvx_world_spread: passable bu
 SPREAD_MAX_SEEDS, SPREAD_MAX_STEPS = 4096, 65534
 SPREAD_TILE = (8, 64, 8)                         # CVX_SPREAD_TILE_X / _Y / _Z: the (x, y, z) extents of the tile a workgroup relaxes
 SNAPSHOT_IGNORE_COLOUR = 1                       # cvx_world_snapshot_diff: flags
+LIFT_COPY, LIFT_REMOVE = 0, 1                    # cvx_world_lift_pieces: op
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -170,6 +173,14 @@ class Piece(C.Structure):  # cvx_piece
 
 class PiecesSummary(C.Structure):  # cvx_pieces_summary
     _fields_ = [("floatingPieces", C.c_int64), ("floatingVoxels", C.c_int64), ("anchoredPieces", C.c_int64), ("anchoredVoxels", C.c_int64)]
+
+
+class LiftedPiece(C.Structure):  # cvx_lifted_piece
+    _fields_ = [("piece", Piece), ("offset", C.c_int64), ("sum", C.c_uint64 * 3), ("moment", C.c_uint64 * 6)]
+
+
+class LiftSummary(C.Structure):  # cvx_lift_summary
+    _fields_ = [("pieces", PiecesSummary), ("storedPieces", C.c_int64), ("storedVoxels", C.c_int64), ("neededVoxels", C.c_int64), ("pad_", C.c_int64)]
 
 
 class SettleSummary(C.Structure):  # cvx_settle_summary
@@ -261,6 +272,7 @@ SPREAD_SEED_DTYPE = np.dtype([("voxel", "<i4", 3), ("start", "<i4")])  # cvx_spr
 SPREAD_SUMMARY_DTYPE = np.dtype([("passable", "<i8"), ("reached", "<i8"), ("largestDistance", "<i4"), ("seedsUsed", "<i4"), ("launches", "<i4"),
                                  ("pad_", "<i4"), ("tileVisits", "<i8")])  # cvx_spread_summary
 SNAPSHOT_CHANGE_DTYPE = np.dtype([("x", "<i4"), ("z", "<i4"), ("yMin", "<i4"), ("yMax", "<i4")])  # cvx_snapshot_change
+LIFTED_PIECE_DTYPE = np.dtype([("piece", PIECE_DTYPE), ("offset", "<i8"), ("sum", "<u8", 3), ("moment", "<u8", 6)])  # cvx_lifted_piece
 SURFACE_QUAD_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("length", "<i4"), ("argb", "<u4")])  # cvx_surface_quad
 SURFACE_SUMMARY_DTYPE = np.dtype([("quads", "<i8"), ("unitFaces", "<i8"), ("quadsPerFace", "<i8", 6)])  # cvx_surface_summary
 
@@ -333,6 +345,37 @@ def _spread_tensor_ptr(tensor, box) -> int:
     if str(getattr(tensor, "dtype", "")) != "torch.int32" or not tensor.is_contiguous() or tensor.numel() != n or not tensor.is_cuda:
         raise ValueError("world_spread_device: out_tensor is a contiguous int32 device tensor of X * Z * Y elements")
     return tensor.data_ptr()
+
+
+def lifted_model(pieces, i: int, argb=None, solid=None):
+    """The cvx_model fields of stored piece i of a world_lift_pieces result: (size (sx, sy, sz), argb, solid).  With numpy pools the arrays are
+    views of shape (sx, sz, sy); with addresses (a device pool's data_ptr()) they are the addresses of the piece's first element, as
+    Context.place_models_device takes them.  ValueError for a piece that is listed but not stored."""
+    p = pieces[i]
+    offset = int(p["offset"])
+    if offset < 0:
+        raise ValueError(f"lifted_model: piece {i} is listed but not stored")
+    size = tuple(int(p["piece"]["max"][a]) - int(p["piece"]["min"][a]) for a in range(3))
+    n = size[0] * size[1] * size[2]
+
+    def part(pool, item_bytes):
+        if pool is None:
+            return None
+        if isinstance(pool, int):
+            return pool + offset * item_bytes if pool else 0
+        return pool[offset:offset + n].reshape(size[0], size[2], size[1])
+    return size, part(argb, 4), part(solid, 1)
+
+
+def lifted_piece_mass(piece):
+    """cvx_lifted_piece_mass of one LIFTED_PIECE_DTYPE element: (centre of mass (3,), inertia (Ixx, Iyy, Izz, Ixy, Iyz, Izx) about it) as float64
+    arrays, for unit cubes of unit mass."""
+    one = np.ascontiguousarray(np.asarray(piece, dtype=LIFTED_PIECE_DTYPE).reshape(1))
+    centre, inertia = np.zeros(3), np.zeros(6)
+    rc = lib().cvx_lifted_piece_mass(one.ctypes.data, centre.ctypes.data, inertia.ctypes.data)
+    if rc != 0:
+        raise ValueError("lifted_piece_mass: the piece has no voxels")
+    return centre, inertia
 
 
 def bodies_array(bodies) -> np.ndarray:
@@ -548,6 +591,10 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_world_snapshot_diff_device.argtypes = L.cvx_world_snapshot_diff.argtypes
         L.cvx_snapshot_destroy.argtypes = [C.c_void_p]
         L.cvx_snapshot_destroy.restype = None
+        L.cvx_world_lift_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.POINTER(LiftSummary), C.POINTER(C.c_float)]
+        L.cvx_world_lift_pieces_device.argtypes = L.cvx_world_lift_pieces.argtypes
+        L.cvx_lifted_piece_mass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvx_nav_field_destroy.restype = None
         L.cvx_free.restype = None
         L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -1099,6 +1146,62 @@ class Context:
         snapshot = Snapshot(self, handle, ms.value)
         self._snapshots.append(snapshot)
         return snapshot
+
+    # -- the floating pieces as models with mass moments (include/cpuvox_gpu_lift.h) --
+    def _lift(self, fn, box_min, box_max, anchors, op, level_count, capacity, argb_ptr, solid_ptr, voxel_capacity):
+        lo, hi = np.ascontiguousarray(box_min, dtype=np.int32), np.ascontiguousarray(box_max, dtype=np.int32)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("world_lift_pieces: box_min and box_max are three integers each")
+        out = np.zeros(max(int(capacity), 0), dtype=LIFTED_PIECE_DTYPE)
+        summary, ms = LiftSummary(), C.c_float()
+        self._check(fn(self._h, lo.ctypes.data, hi.ctypes.data, int(anchors), int(op), int(level_count), out.ctypes.data if out.size else None, int(capacity),
+                       argb_ptr or None, solid_ptr or None, int(voxel_capacity), C.byref(summary), C.byref(ms)))
+        totals = {name: int(getattr(summary.pieces, name)) for name, _ in PiecesSummary._fields_}
+        totals.update({name: int(getattr(summary, name)) for name in ("storedPieces", "storedVoxels", "neededVoxels")})
+        return out[:min(out.size, totals["floatingPieces"])].copy(), totals, ms.value
+
+    def world_lift_pieces(self, box_min, box_max, anchors: int, op: int = LIFT_COPY, level_count: int = LOD_LEVELS - 1, capacity: int = 1024,
+                          voxel_capacity: int = 0, want_argb: bool = True, want_solid: bool = True, argb=None, solid=None):
+        """cvx_world_lift_pieces: the floating pieces of world_pieces(box_min, box_max, anchors) as models.  Returns (the first `capacity` pieces
+        as a LIFTED_PIECE_DTYPE array -- cvx_piece, offset, sum, moment --, the totals as a dict: cvx_pieces_summary's four and storedPieces,
+        storedVoxels, neededVoxels, the argb pool (uint32, voxel_capacity elements, or None), the solid pool (uint8 or None), device
+        milliseconds).  The longest prefix of the listed pieces whose box volumes fit voxel_capacity is stored: lifted_model(pieces, i, argb,
+        solid) gives piece i's arrays.  op = LIFT_REMOVE turns the stored pieces into air and rebuilds LOD 1..level_count over their footprint.
+        With the capacities 0 the call is a report whose neededVoxels sizes the pools.  `argb` / `solid`: the caller's own pools (contiguous
+        uint32 / uint8 arrays of at least voxel_capacity elements) instead of fresh ones; elements from storedVoxels on keep what they held."""
+        n = max(int(voxel_capacity), 0)
+        for pool, dtype in ((argb, np.uint32), (solid, np.uint8)):
+            if pool is not None and (not isinstance(pool, np.ndarray) or pool.dtype != dtype or not pool.flags.c_contiguous or pool.size < n):
+                raise ValueError("world_lift_pieces: a pool is a contiguous uint32 / uint8 array of at least voxel_capacity elements")
+        if argb is None:
+            argb = np.zeros(n, dtype=np.uint32) if want_argb and n else None
+        if solid is None:
+            solid = np.zeros(n, dtype=np.uint8) if want_solid and n else None
+        pieces, totals, ms = self._lift(lib().cvx_world_lift_pieces, box_min, box_max, anchors, op, level_count, capacity,
+                                        argb.ctypes.data if argb is not None else None, solid.ctypes.data if solid is not None else None, voxel_capacity)
+        return pieces, totals, argb, solid, ms
+
+    def world_lift_pieces_device(self, box_min, box_max, anchors: int, argb_tensor, solid_tensor, op: int = LIFT_COPY, level_count: int = LOD_LEVELS - 1,
+                                 capacity: int = 1024, voxel_capacity: int | None = None):
+        """world_lift_pieces into device memory: argb_tensor / solid_tensor are contiguous torch tensors on the context's device, int32 (the colour
+        words' bits) and uint8 (either may be None), or addresses of such memory; voxel_capacity defaults to the smaller tensor's length.  The
+        pools are complete when the call returns.  Returns (pieces, totals, device milliseconds)."""
+        sizes, ptrs = [], []
+        for tensor, dtypes in ((argb_tensor, ("torch.int32", "torch.uint32")), (solid_tensor, ("torch.uint8",))):
+            if tensor is None or isinstance(tensor, int):
+                ptrs.append(tensor or None)
+                continue
+            if str(getattr(tensor, "dtype", "")) not in dtypes or not tensor.is_contiguous() or not tensor.is_cuda:
+                raise ValueError("world_lift_pieces_device: the pools are contiguous int32 / uint8 device tensors")
+            sizes.append(tensor.numel())
+            ptrs.append(tensor.data_ptr() if tensor.numel() else None)
+        if voxel_capacity is None:
+            if not sizes and any(ptrs):
+                raise ValueError("world_lift_pieces_device: voxel_capacity is needed with raw addresses")
+            voxel_capacity = min(sizes) if sizes else 0
+        elif sizes and voxel_capacity > min(sizes):
+            raise ValueError("world_lift_pieces_device: voxel_capacity exceeds a pool")
+        return self._lift(lib().cvx_world_lift_pieces_device, box_min, box_max, anchors, op, level_count, capacity, ptrs[0], ptrs[1], voxel_capacity)
 
     # -- travel-distance fields through air or solid (cvx_world_spread) --
     def _spread(self, fn, box_min, box_max, seeds, medium, step_faces, max_steps, out_ptr):
