@@ -1,9 +1,11 @@
-"""Test infrastructure (numpy and scipy only, no device): the volumes of tests/test_gpu_world_kernel_limits.py and
-tests/test_gpu_world_kernel_limits_later.py and the counts they are named after (tests/test_limit_worlds_cpu.py checks the later ones on the CPU).
+"""Test infrastructure (numpy and scipy only, no device): the volumes of tests/test_gpu_world_kernel_limits.py,
+tests/test_gpu_world_kernel_limits_later.py and tests/test_gpu_world_kernel_limits_newest.py and the counts they are named after
+(tests/test_limit_worlds_cpu.py checks the later and the newest ones on the CPU).
 
 The size limits of the world kernels are constants of the .hip files (the LDS list of light_brick_kernel, the node count up to which one
 workgroup relaxes a settle, the sweeps per relax launch, the waves of cvxcomp::stats_kernel, the list head that travels with the totals; the
-spread tile and its sweeps per launch, the nodes a nav tile keeps in LDS, the widest and tallest nav body).  Every
+spread tile and its sweeps per launch, the nodes a nav tile keeps in LDS, the widest and tallest nav body; the waves of lift_moments_kernel and
+lift_write_kernel, the 256 columns of a snapshot diff's count workgroup, the 256 partials a thread of its reduce kernel steps over).  Every
 builder here returns a volume TOGETHER with the count that decides which side of such a limit it lies on, computed from the volume alone by the
 counting functions below; the GPU test asserts the count before it calls the device."""
 from __future__ import annotations
@@ -583,3 +585,237 @@ def assert_one_node_in_its_wave(tops, roots, column, lane):
     i = node_at(tops, *column)
     assert (i // WAVE, i % WAVE) == (BITS_ROW, lane) and len(roots) == 9 * WAVE
     assert all(len(w) == WAVE and len(set(w)) == 1 for w in waves(roots)) and len(set(roots)) == 9
+
+
+# ---- lift: what the waves of the moments and the write kernel hold -----------------------------------------------------------------------------------------
+
+def node_lengths(solid, box_min, box_max):
+    """The voxels of every node (a maximal vertical run clipped to the box), in the device's node order."""
+    lo, hi = clip(solid.shape, box_min, box_max)
+    tops = run_tops(solid, box_min, box_max)
+    sub = solid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+    air = ~sub[tops[:, 0] - lo[0], :, tops[:, 2] - lo[2]]                   # (nodes, Y)
+    below = air & (np.arange(sub.shape[1])[None, :] < (tops[:, 1] - lo[1])[:, None])
+    # the highest air voxel below the top: the run starts above it (at the box's y0 when there is none)
+    start = np.where(below.any(axis=1), sub.shape[1] - np.argmax(below[:, ::-1], axis=1), 0)
+    return tops[:, 1] - lo[1] + 1 - start
+
+
+def node_ranks(solid, box_min, box_max, anchors=0):
+    """The place of every node's piece in the list of cvx_world_pieces / cvx_world_lift_pieces (piecesmodel.analyse's order), -1 for a node of an
+    anchored piece, in the device's node order."""
+    import piecesmodel
+
+    lo, hi = clip(solid.shape, box_min, box_max)
+    labels, _ = ndimage.label(solid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]], structure=SIX)
+    floating, _, _ = piecesmodel.analyse(solid, box_min, box_max, anchors)
+    rank_of = np.full(int(labels.max()) + 1, -1, dtype=np.int64)
+    for k, piece in enumerate(floating):
+        s = piece["seed"]
+        rank_of[labels[s[0] - lo[0], s[1] - lo[1], s[2] - lo[2]]] = k
+    tops = run_tops(solid, box_min, box_max)
+    return rank_of[labels[tops[:, 0] - lo[0], tops[:, 1] - lo[1], tops[:, 2] - lo[2]]]
+
+
+def lift_wave_kinds(ranks, piece_capacity):
+    """Per wave of lift_moments_kernel: (path, leader, active lanes).  A lane is active when its node's piece floats and is listed (rank below
+    piece_capacity).  path: "idle" (no active lane, the wave returns), "one root" (the active lanes share one piece: one reduction, the leader --
+    the FIRST ACTIVE lane -- adds it) or "atomics" (every active lane adds its own sums); leader is None on the other two paths."""
+    out = []
+    for w in waves(np.asarray(ranks)):
+        active = np.flatnonzero((w >= 0) & (w < piece_capacity))
+        if len(active) == 0:
+            out.append(("idle", None, 0))
+        elif len(set(w[active].tolist())) == 1:
+            out.append(("one root", int(active[0]), len(active)))
+        else:
+            out.append(("atomics", None, len(active)))
+    return out
+
+
+def pieces_late_leader(units=4):
+    """`units` times two rows of nodes.  The first row (x = 4 u) is a bar `pad` over z = 0 .. 62: 63 nodes.  The second (x = 4 u + 2) is a bar
+    `bar` over z = 0 .. 63 at y = 10 with a lone voxel `lone` ABOVE it in column z = 1 (y = 20): 65 nodes in the order bar, lone, bar x 63.  So
+    wave 2 u holds pad x 63 and the bar's first node, wave 2 u + 1 the lone voxel on LANE 0 and 63 nodes of the bar.  The list is in seed order
+    (first column, there the highest voxel): pad, bar, lone per unit -- the bar's seed lies a wave BEFORE the lone voxel, the only way a piece on
+    lane 0 can come later in the list than the piece on the lanes behind it.  With pieceCapacity 3 u + 2 wave 2 u + 1 has lane 0 unlisted and
+    lanes 1 .. 63 listed."""
+    solid = _floor(PIECES_DIMS)
+    for u in range(units):
+        solid[4 * u, 30, 0:WAVE - 1] = True
+        solid[4 * u + 2, 10, 0:WAVE] = True
+        solid[4 * u + 2, 20, 1] = True
+    return solid
+
+
+def pieces_two_roots_apart():
+    """Three rows at x = 0, 1, 2.  Row 0 is a bar `a` at y = 10 and row 2 a bar `b` at y = 14, one wave each.  Row 1 holds teeth of `a` (y = 10) on
+    the columns z % 3 == 0, teeth of `b` (y = 14) on z % 3 == 1 and lone voxels (y = 20) on z % 3 == 2: wave 1 is a, b, lone, a, b, lone, ...  The
+    list is a, b, then the 21 lone voxels: with pieceCapacity 2 the active lanes of wave 1 hold two roots with unlisted nodes between them."""
+    solid = _floor(PIECES_DIMS)
+    solid[0, 10, :] = True
+    solid[2, 14, :] = True
+    z = np.arange(WAVE)
+    solid[1, 10, z[z % 3 == 0]] = True
+    solid[1, 14, z[z % 3 == 1]] = True
+    solid[1, 20, z[z % 3 == 2]] = True
+    return solid
+
+
+# sums above 2^32: a pillar of k voxels has moment[1] = (k - 1) k (2 k - 1) / 6 about its lowest voxel, above 2^32 from k = 2345
+LIFT_TALL_DIMS = (32, 4096, 32)
+LIFT_TALL_BOX = ((0, 1, 0), LIFT_TALL_DIMS)  # above the floor, no anchor bit: everything in the box floats
+LIFT_TALL_WALL = 2400
+
+
+def pillar_moment(k):
+    return (k - 1) * k * (2 * k - 1) // 6
+
+
+def lift_tall_world():
+    """A floor and three floating pieces in 32 x 4096 x 32.
+    wall    the 64 columns of the rows x = 0 and 1 (the world is 32 columns deep: two rows are the 64 consecutive nodes of wave 0), y 5 .. 2404:
+            one piece, 64 nodes of 2400 voxels.
+    comb b  in the row x = 4: pillars y 5 .. 2410 on z % 4 == 0, joined by a beam along z at y = 2410.
+    comb c  in the same row: pillars y 3 .. 2402 on z % 4 == 2, joined by a beam along z at y = 3.
+    Every column of row 4 holds a node of b above a node of c: wave 1 is b, c, b, c, ... with pillars of 2406 and 2400 voxels among them."""
+    solid = _floor(LIFT_TALL_DIMS)
+    solid[0:2, 5:5 + LIFT_TALL_WALL, :] = True
+    z = np.arange(LIFT_TALL_DIMS[2])
+    solid[4, 2410, :] = True
+    solid[4, 3, :] = True
+    for k in z[z % 4 == 0]:
+        solid[4, 5:2411, k] = True
+    for k in z[z % 4 == 2]:
+        solid[4, 3:2403, k] = True
+    return solid
+
+
+def unique_colours(solid):
+    """A colour word of its own for every solid voxel of a volume of fewer than 2^24 voxels (alpha 0xFF, the voxel's linear index below it)."""
+    assert solid.size <= 1 << 24
+    x, y, z = np.nonzero(solid)
+    colour = np.zeros(solid.shape, dtype=np.uint32)
+    colour[x, y, z] = 0xFF000000 | ((x * solid.shape[1] + y) * solid.shape[2] + z)
+    return colour
+
+
+def brute_sums(solid, box_min, box_max, piece):
+    """sum[3] and moment[6] of one listed piece as Python integers, voxel by voxel from the volume: the judge between liftmodel and the kernel."""
+    lo, hi = clip(solid.shape, box_min, box_max)
+    labels, _ = ndimage.label(solid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]], structure=SIX)
+    s = [int(v) for v in piece["seed"]]
+    mn = [int(v) for v in piece["min"]]
+    pts = np.argwhere(labels == labels[s[0] - lo[0], s[1] - lo[1], s[2] - lo[2]])
+    rel = [[int(p[a]) + lo[a] - mn[a] for p in pts] for a in range(3)]
+    sums = [sum(c) for c in rel]
+    moments = [sum(v * v for v in c) for c in rel] + [sum(a * b for a, b in zip(rel[i], rel[j])) for i, j in ((0, 1), (1, 2), (2, 0))]
+    return sums, moments
+
+
+# the write kernel: chosen node lengths in node order
+LIFT_LENGTH_DIMS = (64, 128, 64)
+LIFT_LENGTH_BOX = ((0, 1, 0), LIFT_LENGTH_DIMS)  # with the anchor OUTSIDE: a pillar that stands on the floor (y = 0, outside the box) is anchored
+LIFT_LENGTH_BASE = 3                             # the lowest voxel of a floating pillar
+
+
+def lift_lengths(pattern):
+    """A floor and one pillar per entry of `pattern` on the columns (2 i, 2 j), in node order (no two touch: every pillar is a piece).  A positive
+    entry is a floating pillar of that many voxels from y = LIFT_LENGTH_BASE; 0 is a pillar of two voxels that stands on the floor -- anchored
+    under LIFT_LENGTH_BOX with OUTSIDE, so its node has length 0 in lift_write_kernel's scan.  -> solid"""
+    assert len(pattern) <= 32 * 32 and max(pattern) <= LIFT_LENGTH_DIMS[1] - LIFT_LENGTH_BASE
+    solid = _floor(LIFT_LENGTH_DIMS)
+    for n, length in enumerate(pattern):
+        x, z = 2 * (n // 32), 2 * (n % 32)
+        if length:
+            solid[x, LIFT_LENGTH_BASE:LIFT_LENGTH_BASE + length, z] = True
+        else:
+            solid[x, 1:3, z] = True
+    return solid
+
+
+def stored_lengths(solid, box_min, box_max, anchors, piece_capacity, voxel_capacity):
+    """What lift_write_kernel scans, from the volume and the prefix rule: per node its voxels when its piece is STORED (it floats, is listed, and
+    the box volumes of the list up to and including it fit voxel_capacity), else 0."""
+    import piecesmodel
+
+    floating, _, _ = piecesmodel.analyse(solid, box_min, box_max, anchors)
+    stored, used = 0, 0
+    for piece in floating[:piece_capacity]:
+        v = int(np.prod(piece["max"].astype(np.int64) - piece["min"]))
+        if used + v > voxel_capacity:
+            break
+        used, stored = used + v, stored + 1
+    ranks = node_ranks(solid, box_min, box_max, anchors)
+    return np.where((ranks >= 0) & (ranks < stored), node_lengths(solid, box_min, box_max), 0)
+
+
+_VARIED = [1 + (7 * k + k * k // 5) % 23 for k in range(64)]  # 64 lengths 1 .. 23 with no pattern in the lanes
+# name -> (the lengths in node order, the wave totals it is named after)
+LIFT_LENGTH_PATTERNS = {
+    "lane 0 zero": ([0] + _VARIED[1:], None),
+    "lane 63 zero": (_VARIED[:63] + [0], None),
+    "lanes 1 to 62 zero": ([7] + [0] * 62 + [9], [16]),
+    "63 zeros and 64 on lane 63": ([0] * 63 + [64], [64]),
+    "total 64: every lane its own owner": ([1] * 64, [64]),
+    "total 65": ([1] * 63 + [2], [65]),
+    "total 128": ([3, 1] * 32, [128]),
+    "total 4096": ([64] * 64, [4096]),
+    "an idle wave between two": (_VARIED + [0] * 64 + [5, 0, 11] * 7, [sum(_VARIED), 0, 112]),
+    "three waves and a partial one": ((_VARIED[::-1] + [0, 2, 65, 1]) * 3 + [9] * 5, None),
+}
+
+
+# ---- snapshot: rectangles above 256 workgroups of the diff's count kernel ---------------------------------------------------------------------------------
+
+SNAP_DIMS = (256, 32, 512)
+SNAP_GROUP, SNAP_CHUNK = 256, 4096  # the columns of a count workgroup and of a scan chunk
+# name -> (x0, z0, sizeX, sizeZ) at levelCount 0, and what the name says: (columns, workgroups, columns of the last workgroup)
+SNAP_RECTS = {
+    "257 groups, the last partial": ((1, 3, 255, 258), (65790, 257, 254)),
+    "257 full groups": ((0, 100, 256, 257), (65792, 257, 256)),
+    "256 groups": ((1, 200, 255, 257), (65535, 256, 255)),
+    "the whole world": ((0, 0, 256, 512), (131072, 512, 256)),
+}
+SNAP_ONE_RECT = SNAP_RECTS["257 groups, the last partial"][0]
+SNAP_ONE_INDICES = (0, 63, 64, 191, 192, 255, 256, 65535, 65536, 65789)
+
+
+def snap_terrain():
+    """Cheap terrain over SNAP_DIMS: every column solid from y = 0 up to a height of 5 .. 19 (no two neighbours alike)."""
+    x, z = np.arange(SNAP_DIMS[0])[:, None], np.arange(SNAP_DIMS[2])[None, :]
+    height = 5 + (3 * x + 5 * z + (x * z) % 11) % 15
+    return np.arange(SNAP_DIMS[1])[None, :, None] < height[:, None, :]
+
+
+def snap_counts(rect):
+    """(columns, workgroups of the count kernel, columns of its last workgroup, scan chunks) of a rectangle."""
+    n = rect[2] * rect[3]
+    groups = -(-n // SNAP_GROUP)
+    return n, groups, n - (groups - 1) * SNAP_GROUP, -(-n // SNAP_CHUNK)
+
+
+def snap_place(rect, index):
+    """Where linear column `index` of the rectangle lies: ((x, z), workgroup, wave of the workgroup, lane)."""
+    assert 0 <= index < rect[2] * rect[3]
+    return (rect[0] + index // rect[3], rect[1] + index % rect[3]), index // SNAP_GROUP, index % SNAP_GROUP // WAVE, index % WAVE
+
+
+def snap_scattered(rect):
+    """Edit pattern A: per scan chunk of the rectangle its first and its last column, one column in an even workgroup and one in an odd one
+    (at lanes that move from chunk to chunk), and the rectangle's last column -> the sorted linear indices."""
+    n, _, _, chunks = snap_counts(rect)
+    out = {n - 1}
+    for c in range(chunks):
+        base = c * SNAP_CHUNK
+        picks = [base, base + SNAP_CHUNK - 1, base + 2 * (c % 7) * SNAP_GROUP + (37 * c + 1) % SNAP_GROUP, base + (2 * (c % 5) + 3) * SNAP_GROUP + (91 * c + 5) % SNAP_GROUP]
+        out.update(i for i in picks if i < n)
+    return sorted(out)
+
+
+def snap_box_pair(rect):
+    """Two columns of SNAP_ONE_RECT and the y of the voxel changed in each: the first in workgroup 0 with the smaller x, the larger z and the higher
+    voxel, the second in the last (partial) workgroup with the larger x, the smaller z and the lower voxel.  min[0], max[1] and max[2] of the
+    box come from the first, max[0], min[1] and min[2] from the second.  -> ((index, y), (index, y))"""
+    n = rect[2] * rect[3]
+    return (100, 4), (n - rect[3] + 4, 1)  # (the fifth column of the rectangle's last row)

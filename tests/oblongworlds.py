@@ -172,6 +172,16 @@ def _floating(dims):
     return ("brush", dict(strokes=[_box(FILL, (dx - 3, 50, dz - 3), (dx, 53, dz), 0xFF778899)], label="a floating block over the far corner"))
 
 
+def beams(dims):
+    """Two floating beams for cvx_world_lift_pieces, each longer along the long axis than the short side is wide: 40 x 3 columns, two voxels high,
+    up to the far corner, and 45 x 1 columns, one voxel high, from the near end.  A swapped LiftElement stride or column decode lays their
+    voxels out otherwise in the pools."""
+    long_side, s = max(dims[0], dims[2]), short_side(dims)
+    (ax, az), (bx, bz) = along(dims, long_side - 40, s - 3), along(dims, long_side, s)
+    (cx, cz), (ex, ez) = along(dims, 6, 9), along(dims, 51, 10)
+    return ("brush", dict(strokes=[_box(FILL, (ax, 56, az), (bx, 58, bz), 0xFF778899), _box(FILL, (cx, 62, cz), (ex, 63, ez), 0xFF998877)], label="two floating beams along the long axis"))
+
+
 def tower_strokes(dims, count):
     """`count` towers with colours of their own and sphere carves, spread along the long axis (the strokes of the compaction test at these sizes)."""
     rng = np.random.default_rng(64)
@@ -246,7 +256,7 @@ def seam_rays(dims, n=600):
 # ---- the cases --------------------------------------------------------------------------------------------------------------------------------------
 
 WRITERS = ("brush", "shapes", "stamp", "copy", "write_heights", "place_models", "write_voxels", "fill_cavities", "lamps", "set_column",
-           "light", "settle", "remove", "edit", "set_columns", "snapshot_restore")
+           "light", "settle", "remove", "edit", "set_columns", "snapshot_restore", "lift_remove")
 
 
 def writer_cases(dims):
@@ -361,6 +371,13 @@ def writer_cases(dims):
             [("snapshot_restore", dict(rect=rect_of(O), strokes=[_box(PAINT, *W, 0xFF00C0FF), _sphere(CARVE, (dx - 6, 20, dz - 6), 9)], level_count=5,
                                        label="a snapshot of a rectangle that overhangs all four sides"))],
         ],
+        "lift_remove": [
+            # (boxes from y = 52: they cut the terrain's columns, whose tops float there with nothing at y = 0 to hold them, and hold a quarter of the
+            # world's single floating voxels)
+            [beams(dims), ("lift_remove", dict(box=corner(dims, 52), anchors=GROUND, level_count=0, label="lift REMOVE up to the far corner"))],
+            [beams(dims), ("lift_remove", dict(box=corner(dims, 52, 60), anchors=GROUND | OUTSIDE, level_count=2, label="lift REMOVE below y = 60 up to the far corner"))],
+            [beams(dims), ("lift_remove", dict(box=overhang(dims, 52), anchors=GROUND, label="lift REMOVE in a box that overhangs all four sides"))],
+        ],
         "rounds to the short side": [
             [("brush", dict(strokes=[_box(FILL, (dx - 3, 20, dz - 3), (dx, 30, dz), 0xFF00FF00)], label="three columns at the far corner, levelCount 5"))],
         ],
@@ -368,7 +385,7 @@ def writer_cases(dims):
     return cases
 
 
-NEEDS_SHELLS = ("report_cavities",)  # the reading cases that begin with writes: the dense world encloses no cavity
+NEEDS_SHELLS = ("report_cavities", "lift_copy")  # the reading cases that begin with writes: the dense world encloses no cavity and floats no long piece
 
 
 def reader_cases(dims):
@@ -396,6 +413,9 @@ def reader_cases(dims):
                 ("nav", dict(call=(*O, 1, 3, 1, 2, 0), goals=goals[::-1], label="nav in a box that overhangs all four sides"))],
         "report_pieces": three("report_pieces", "pieces REPORT", anchors=GROUND),
         "report_cavities": shell_steps(dims) + three("report_cavities", "cavities REPORT", open_faces=X_AND_Z),
+        "lift_copy": [beams(dims)] + [("lift_copy", dict(box=box, anchors=GROUND, label=f"lift COPY, {where}"))
+                                       for where, box in (("the whole footprint from y = 52", ((0, 52, 0), tuple(dims))), ("up to the far corner", corner(dims, 52)),
+                                                          ("overhanging all four sides", overhang(dims, 52)))],
     }
     return cases
 
@@ -462,6 +482,22 @@ class OblongModels(Models):
         want, summary, _ = piecesmodel.analyse(self.solid, *box, anchors)
         assert summary["floatingPieces"] > 0, f"{label}: nothing floats"
         return self.changed(piecesmodel.remove(self.solid, self.colour, *box, anchors), label)
+
+    def long_pieces(self, lift, label):
+        """The stored pieces of a lift that are longer along the long axis than the short side: there must be one, past the short side."""
+        axis = 0 if self.dims[0] > self.dims[2] else 2
+        stored = lift.pieces["piece"][:lift.summary["storedPieces"]]
+        long = [p for p in stored if int(p["max"][axis]) - int(p["min"][axis]) > short_side(self.dims)]
+        cols = np.zeros((self.dims[0], self.dims[2]), dtype=bool)
+        for p in long:
+            cols[p["min"][0]:p["max"][0], p["min"][2]:p["max"][2]] = True
+        assert long and beyond(self.dims, cols), f"{label}: no stored piece is longer than the short side and reaches past it"
+        return stored
+
+    def m_lift_remove(self, box, anchors, label, **kw):
+        after = super().m_lift_remove(box, anchors, label, **kw)
+        self.long_pieces(self.lift[0], label)
+        return after
 
     def m_fill_cavities(self, box, label, open_faces=0x3F, max_voxels=0, argb=0xFF123456, overlaps=False, **_):
         after = super().m_fill_cavities(box, label, open_faces, max_voxels, argb, overlaps)
@@ -548,6 +584,11 @@ class OblongModels(Models):
         steps = want[0].reshape(-1)
         reached = steps[steps["distance"] > 0]
         self.see(reached["cell"][:, 0], reached["cell"][:, 2])
+        return want
+
+    def m_lift_copy(self, box, anchors, label, capacity=8192, voxel_capacity=None, holds=None):
+        want = super().m_lift_copy(box, anchors, label, capacity, voxel_capacity, holds)
+        self.see_boxes(self.long_pieces(want[0], label))
         return want
 
     def m_report_pieces(self, box, anchors, label, holds=None):

@@ -69,7 +69,8 @@ class _Oblong(_Later, ob.OblongModels):
     Which parent supplies what (the MRO is _Oblong, _Later, _Sequence, OblongModels, Models):
     - _Later: the device calls of the newer writers and readers (stamp, copy, write_heights, ..., read_model), apply() and unchanged();
     - _Sequence: the device calls brush, light, settle, compact and check(); its remove() is replaced here by one that takes a levelCount;
-    - OblongModels: the models m_light, m_settle, m_remove, m_edit, m_snapshot_restore and the readers' m_* that record where a result reaches,
+    - OblongModels: the models m_light, m_settle, m_remove, m_edit, m_snapshot_restore (its own: snapshot, strokes and restore in one step, which
+      replaces the named snapshots of _Later / Models here), m_lift_remove, m_lift_copy and the readers' m_* that record where a result reaches,
       and changed(); Models below it: the other m_* that _Later's calls use;
     - here: run(), world(), the device calls remove, edit, set_columns, snapshot_restore, surface_rects and report_pieces.
     No parent constructor runs, as in _LaterTall: _Sequence's builds the square world and OblongModels' knows no context, so the state of both

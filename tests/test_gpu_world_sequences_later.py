@@ -10,8 +10,11 @@ and leave edit_stats() as they were.  Everything is integers and bytes: no compa
   A  the editor's loop across a compaction, on the terrain, the sparse world and (the stepped writers) the 32 x 256 x 32 world
   B  each newer writer directly behind a compaction, and a terrain over the whole footprint that makes the arena be laid out again
   C  foreign columns (a split solid run, a split air run, shared colours, air runs alone) under every newer reader, then every newer writer
-  D  heights, models, dense and cavities FILL at levelCount 2 in separate rectangles, a stamp at levelCount 5 over two of them, a full bake."""
+  D  heights, models, dense and cavities FILL at levelCount 2 in separate rectangles, a stamp at levelCount 5 over two of them, a full bake.
+_Later also holds the calls of the two newest, cvx_world_lift_pieces and cvx_world_snapshot, whose cases are tests/test_gpu_world_sequences_newest.py."""
+import numpy as np
 import pytest
+import torch
 
 import cavitymodel
 import lampmodel
@@ -19,11 +22,16 @@ from cpuvox_amd import gpu
 from test_gpu_world_cavities import _report as _cavities_report
 from test_gpu_world_dense import TALL, _any_world
 from test_gpu_world_distance import _same
+from test_gpu_world_lift import _assert_equals_model as _lift_equals
+from test_gpu_world_lift import _device_call as _lift_device
+from test_gpu_world_lift import _host_call as _lift_host
 from test_gpu_world_nav import _check as _nav_check
 from test_gpu_world_sequences import EVERYWHERE, SETUP, _Sequence
+from test_gpu_world_snapshot import held as _held
 from test_gpu_world_spread import _check as _spread_check
 from test_gpu_world_surface import _surface
 from test_world_light_cpu import model_world
+from test_world_models_cpu import identity_at
 from test_world_sequences_later_cpu import (BEHIND_A_COMPACTION, DIMS, LOOP_FIRST, LOOP_SECOND, LOOP_SETUP, PARTIAL, PARTIAL_LAMPS, PARTIAL_READS, PARTIAL_RECTS,
                                             PARTIAL_SETUP, PARTIAL_STAMP, READER_GROUPS, RELAYOUT, WRITER_GROUPS, Models, assert_foreign, group_plan, read_map, reader_plans, refreshed,
                                             relayout_need, rounded, sequence_world, strokes_plan, tall_loop, tall_world, work, writer_plans)  # noqa: F401  (work: the fixture)
@@ -182,6 +190,71 @@ class _Later(_Sequence, Models):
         argb, mask = self.ctx.read_model(dst_size, instance.toModel)
         assert (argb == want[0]).all() and (mask == want[1]).all(), label
         self.unchanged(stats, label)
+
+
+    # -- the newest calls (their plans: tests/test_world_sequences_newest_cpu.py) -------------------------------------------------------------------
+    def lift_copy(self, box, anchors, label, capacity=8192, voxel_capacity=None, holds=None):
+        """A reader: the list, the sums, the summary and both pools are the model's, through the host call and the _device variant."""
+        want, room = self.m_lift_copy(box, anchors, label, capacity, voxel_capacity, holds)
+        stats = self.ctx.edit_stats()
+        _lift_equals(_lift_host(self.ctx, box, anchors, gpu.LIFT_COPY, capacity, room), want, room, label)
+        pieces, summary, argb, mask = _lift_device(self.ctx, box, anchors, gpu.LIFT_COPY, capacity, room)
+        _lift_equals((pieces, summary, argb.cpu().numpy().view(np.uint32), mask.cpu().numpy()), want, room, f"{label}, _device")
+        self.unchanged(stats, label)
+
+    def lift_remove(self, box, anchors, label, capacity=8192, voxel_capacity=None, level_count=5, check=None, overlaps=False, holds=None, device=False):
+        """A writer.  device: into torch tensors, which place_lifted reads."""
+        after = self.m_lift_remove(box, anchors, label, capacity=capacity, voxel_capacity=voxel_capacity, overlaps=overlaps, holds=holds)
+        want, room = self.lift
+        if device:
+            pieces, summary, argb, mask = _lift_device(self.ctx, box, anchors, gpu.LIFT_REMOVE, capacity, room, level_count)
+            self.pools = (pieces, argb, mask)
+            got = (pieces, summary, argb.cpu().numpy().view(np.uint32), mask.cpu().numpy())
+        else:
+            got = _lift_host(self.ctx, box, anchors, gpu.LIFT_REMOVE, capacity, room, level_count)
+        _lift_equals(got, want, room, label)
+        self.apply(after, label, check)
+
+    def place_lifted(self, offset, label, op=None, level_count=5, check=None, overlaps=False):
+        """cvx_world_place_models_device of the largest piece of the last lift_remove, straight from its device pools."""
+        after = self.m_place_lifted(offset, label, op, overlaps)
+        pieces, argb, mask = self.pools
+        k = self.largest_lifted()
+        model = gpu.lifted_model(pieces, k, argb.data_ptr(), mask.data_ptr())
+        at = tuple(int(pieces[k]["piece"]["min"][a]) + offset[a] for a in range(3))
+        assert self.ctx.place_models_device([model], [identity_at(at, model[0], 0, gpu.BRUSH_FILL if op is None else op)], level_count) > 0.0
+        self.apply(after, label, check)
+
+    def snapshot(self, name, rect, label, levels=5):
+        """The capture changes nothing; the handle is kept under `name` and closes with the context."""
+        self.m_snapshot(name, rect, label, levels)
+        self.ctx.read_level(0)  # (places a fresh upload's levels in the arena: edit_stats() counts them from here on)
+        stats = self.ctx.edit_stats()
+        handle = self.ctx.world_snapshot(*rect, levels)
+        assert _held(handle) == self.taken()[name][2] and handle.info["levelCount"] == levels, label
+        self.__dict__.setdefault("handles", {})[name] = handle
+        self.unchanged(stats, label)
+
+    def snapshot_diff(self, name, label, flags=0, holds=None):
+        """A reader: the list and the summary are the model's, through the host call and the _device variant."""
+        want, want_summary = self.m_snapshot_diff(name, label, flags, holds)
+        stats = self.ctx.edit_stats()
+        handle = self.handles[name]
+        changes, summary = handle.diff(flags)
+        assert summary == want_summary, f"{label}: {summary} != {want_summary}"
+        assert changes.tobytes() == want.tobytes(), f"{label}: the list differs"
+        buffer = torch.full((len(want) + 2, 4), -7, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        assert handle.diff_device(buffer.data_ptr(), len(want) + 1, flags) == want_summary, f"{label}: _device"
+        torch.cuda.synchronize()
+        back = buffer.cpu().numpy()
+        assert back[:len(want)].tobytes() == want.tobytes() and (back[len(want):] == -7).all(), f"{label}: the device list"
+        self.unchanged(stats, label)
+
+    def snapshot_restore(self, name, label, check=None, overlaps=False):
+        after = self.m_snapshot_restore(name, label, overlaps)
+        assert self.handles[name].restore() > 0.0
+        self.apply(after, label, check)
 
 
 class _LaterTall(_Later):

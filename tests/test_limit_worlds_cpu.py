@@ -1,4 +1,5 @@
-"""CPU (no GPU needed): the worlds of tests/test_gpu_world_kernel_limits_later.py are what their names say.
+"""CPU (no GPU needed): the worlds of tests/test_gpu_world_kernel_limits_later.py and tests/test_gpu_world_kernel_limits_newest.py are what their
+names say.
 
 Every count the GPU cases assert before they call the device -- tile totals, wave compositions, cell counts, piece and cavity counts, element and
 word counts -- is asserted here from the numpy volumes alone (tests/limitworlds.py) and, where a dense model has a say (spreadmodel, navmodel,
@@ -176,3 +177,144 @@ def test_the_nav_tile_corridor():
         assert summary["reached"] == 135 and summary["largestDistance"] == 134 == want[cells[-1]]["distance"]
         assert LW.nav_corridor_row_sweeps(solid, call, cells) == 120 > LW.NAV_SWEEPS
     assert totals[LW.NAV_CORRIDOR_TILE] == 324 + 135 + 36 * 30
+
+
+# ---- lift: the waves of the moments kernel (tests/test_gpu_world_kernel_limits_newest.py) ---------------------------------------------------------------------
+
+def test_lift_wave_kinds_of_the_pieces_worlds():
+    """What lift_moments_kernel's waves hold in the worlds the pieces tests already use, for the pieceCapacity each GPU case passes."""
+    for last in (64, 1, 63):
+        ranks = LW.node_ranks(LW.pieces_bars(last=last), *BOX)
+        assert LW.lift_wave_kinds(ranks, 8192) == [("one root", 0, 64)] * 8 + [("one root", 0, last)]
+    ranks = LW.node_ranks(LW.pieces_checkerboard(), *BOX)
+    assert ranks.tolist() == list(range(2048)), "a piece per node: the list order is the node order"
+    assert LW.lift_wave_kinds(ranks, 8192) == [("atomics", None, 64)] * 32 and LW.lift_wave_kinds(ranks, 0) == [("idle", None, 0)] * 32
+    ranks = LW.node_ranks(LW.pieces_checkerboard(257), *BOX)
+    for capacity in (255, 256, 257):
+        assert [k[2] for k in LW.lift_wave_kinds(ranks, capacity)] == [64, 64, 64, min(capacity - 192, 64), max(capacity - 256, 0)]
+
+
+def test_the_lone_leader_always_comes_before_its_bar():
+    """In pieces_lone_leader lane 0's piece precedes the bar of its wave in the list, in every wave: a prefix of the list can leave the bar out
+    (the mirror case: lane 0 the only active lane) and never the lone voxel alone.  The node order and the list order are both the column order,
+    so a piece on lane 0 can come later than the one behind it only when that one has a node in an earlier wave: pieces_late_leader."""
+    solid = LW.pieces_lone_leader()
+    ranks = LW.node_ranks(solid, *BOX)
+    for r, w in enumerate(LW.waves(ranks)):
+        assert w[0] == 2 * r and set(w[1:].tolist()) == {2 * r + 1}
+    for capacity in range(13):
+        for path, leader, active in LW.lift_wave_kinds(ranks, capacity):
+            assert path == "idle" or (path == "one root" and (leader, active) == (0, 1)) or (path == "atomics" and active == 64)
+    assert LW.lift_wave_kinds(ranks, 5) == [("atomics", None, 64)] * 2 + [("one root", 0, 1)] + [("idle", None, 0)] * 3
+
+
+def test_the_late_leader():
+    solid = LW.pieces_late_leader()
+    floating, _, _ = piecesmodel.analyse(solid, *BOX, 0)
+    assert floating["voxels"].tolist() == [63, 64, 1] * 4 and LW.node_count(solid, *BOX) == 8 * 64
+    ranks = LW.node_ranks(solid, *BOX)
+    for u in range(4):
+        pad, bar, lone = 3 * u, 3 * u + 1, 3 * u + 2
+        assert LW.waves(ranks)[2 * u].tolist() == [pad] * 63 + [bar] and LW.waves(ranks)[2 * u + 1].tolist() == [lone] + [bar] * 63
+        kinds = LW.lift_wave_kinds(ranks, 3 * u + 2)  # pad and bar listed, the lone voxel not
+        assert kinds[2 * u + 1] == ("one root", 1, 63) and kinds[2 * u] == ("atomics", None, 64) and kinds[2 * u + 2:] == [("idle", None, 0)] * (6 - 2 * u)
+    assert LW.lift_wave_kinds(ranks, 8192) == [("atomics", None, 64)] * 8
+
+
+def test_two_roots_apart():
+    solid = LW.pieces_two_roots_apart()
+    floating, _, _ = piecesmodel.analyse(solid, *BOX, 0)
+    assert floating["voxels"].tolist() == [64 + 22, 64 + 21] + [1] * 21
+    ranks = LW.node_ranks(solid, *BOX)
+    wave = LW.waves(ranks)[1]
+    assert (wave[0::3] == 0).all() and (wave[1::3] == 1).all() and (wave[2::3] >= 2).all() and len(set(wave[2::3].tolist())) == 21
+    assert LW.lift_wave_kinds(ranks, 2) == [("one root", 0, 64), ("atomics", None, 43), ("one root", 0, 64)]
+    assert LW.lift_wave_kinds(ranks, 1) == [("one root", 0, 64), ("one root", 0, 22), ("idle", None, 0)]
+
+
+def test_the_tall_walls_have_sums_above_32_bits():
+    """The model's integers against sums taken voxel by voxel in Python integers, and against the closed form of a pillar."""
+    import liftmodel
+
+    solid, box = LW.lift_tall_world(), LW.LIFT_TALL_BOX
+    ranks, lengths = LW.node_ranks(solid, *box), LW.node_lengths(solid, *box)
+    assert LW.lift_wave_kinds(ranks, 8192) == [("one root", 0, 64), ("atomics", None, 64)] and LW.waves(ranks)[1].tolist() == [1, 2] * 32
+    assert LW.lift_wave_kinds(ranks, 2) == [("one root", 0, 64), ("one root", 0, 32)]
+    assert lengths[:64].tolist() == [2400] * 64 and lengths[64:].tolist() == ([2406, 1, 1, 1, 1, 2400, 1, 1] * 8)
+    assert LW.pillar_moment(2344) < 1 << 32 < LW.pillar_moment(2345) < LW.pillar_moment(2400)
+    colour = LW.unique_colours(solid)
+    assert len(np.unique(colour[solid])) == int(solid.sum())
+    want = liftmodel.lift(solid, colour, *box, 0, 8192, 1 << 62)
+    assert len(want.pieces) == 3 and want.pieces["sum"].dtype == np.uint64 and want.pieces["moment"].dtype == np.uint64
+    for p in want.pieces:
+        sums, moments = LW.brute_sums(solid, *box, p["piece"])
+        assert [int(v) for v in p["sum"]] == sums and [int(v) for v in p["moment"]] == moments
+        assert max(moments) > 1 << 32 and max(sums) < 1 << 32
+    assert int(want.pieces[0]["moment"][1]) == 64 * LW.pillar_moment(2400) == 294727705600
+
+
+# ---- lift: the lengths the write kernel scans ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", sorted(LW.LIFT_LENGTH_PATTERNS))
+def test_lift_lengths(name):
+    pattern, totals = LW.LIFT_LENGTH_PATTERNS[name]
+    solid = LW.lift_lengths(pattern)
+    box = LW.LIFT_LENGTH_BOX
+    assert LW.node_count(solid, *box) == len(pattern) == LW.piece_count(solid, *box), "a node and a piece per entry"
+    assert LW.stored_lengths(solid, *box, OUTSIDE, 8192, 1 << 62).tolist() == list(pattern)
+    assert (LW.node_lengths(solid, *box) == np.where(np.array(pattern) > 0, pattern, 2)).all()
+    _, summary, _ = piecesmodel.analyse(solid, *box, OUTSIDE)
+    assert summary["anchoredPieces"] == pattern.count(0) and summary["floatingVoxels"] == sum(pattern)
+    if totals is not None:
+        assert [sum(w) for w in LW.waves(pattern)] == totals
+
+
+def test_lift_length_patterns_cover_the_issue():
+    P = {name: pattern for name, (pattern, _) in LW.LIFT_LENGTH_PATTERNS.items()}
+    assert P["lane 0 zero"][0] == 0 and all(P["lane 0 zero"][1:]) and P["lane 63 zero"][63] == 0 and all(P["lane 63 zero"][:63])
+    assert P["lanes 1 to 62 zero"][0] and P["lanes 1 to 62 zero"][63] and not any(P["lanes 1 to 62 zero"][1:63])
+    assert P["63 zeros and 64 on lane 63"] == [0] * 63 + [64] and P["total 64: every lane its own owner"] == [1] * 64
+    assert {sum(P[name]) for name in ("total 64: every lane its own owner", "total 65", "total 128", "total 4096")} == {64, 65, 128, 4096}
+    assert [sum(w) > 0 for w in LW.waves(P["an idle wave between two"])] == [True, False, True]
+    assert max(max(p) for p in P.values()) == 65 and len(P["three waves and a partial one"]) % 64 == 17
+
+
+def test_lift_lengths_behind_a_short_prefix():
+    solid = LW.lift_lengths([5] * 100)
+    assert LW.stored_lengths(solid, *LW.LIFT_LENGTH_BOX, OUTSIDE, 8192, 354).tolist() == [5] * 70 + [0] * 30
+    assert LW.stored_lengths(solid, *LW.LIFT_LENGTH_BOX, OUTSIDE, 60, 1 << 62).tolist() == [5] * 60 + [0] * 40
+    assert LW.stored_lengths(solid, *LW.LIFT_LENGTH_BOX, OUTSIDE, 8192, 350).tolist() == [5] * 70 + [0] * 30, "room for exactly 70"
+    assert LW.stored_lengths(solid, *LW.LIFT_LENGTH_BOX, OUTSIDE, 8192, 349).tolist() == [5] * 69 + [0] * 31, "one short of 70"
+
+
+# ---- snapshot: the rectangles and the places of the changed columns ---------------------------------------------------------------------------------------------------
+
+def test_snapshot_rectangles():
+    for name, (rect, facts) in LW.SNAP_RECTS.items():
+        n, groups, last, chunks = LW.snap_counts(rect)
+        assert (n, groups, last) == facts, name
+        assert rect[0] + rect[2] <= LW.SNAP_DIMS[0] and rect[1] + rect[3] <= LW.SNAP_DIMS[2]
+        indices = LW.snap_scattered(rect)
+        assert indices[-1] == n - 1 and len(set(indices)) == len(indices)
+        for c in range(chunks):
+            groups_of = {i // LW.SNAP_GROUP % 2 for i in indices if i // LW.SNAP_CHUNK == c}
+            assert groups_of == {0, 1} or (c == chunks - 1 and n % LW.SNAP_CHUNK != 0 and groups_of), (name, c)
+            assert c * LW.SNAP_CHUNK in indices and (min((c + 1) * LW.SNAP_CHUNK, n) - 1) in indices, "both ends of every chunk"
+    assert sorted(facts[1] for _, facts in LW.SNAP_RECTS.values()) == [256, 257, 257, 512]
+    assert LW.SNAP_DIMS[1] >> 5 == 1, "six levels"
+
+
+def test_snapshot_places():
+    rect = LW.SNAP_ONE_RECT
+    places = {i: LW.snap_place(rect, i)[1:] for i in LW.SNAP_ONE_INDICES}
+    assert places == {0: (0, 0, 0), 63: (0, 0, 63), 64: (0, 1, 0), 191: (0, 2, 63), 192: (0, 3, 0), 255: (0, 3, 63), 256: (1, 0, 0), 65535: (255, 3, 63),
+                      65536: (256, 0, 0), 65789: (256, 3, 61)}
+    assert LW.snap_counts(rect)[:3] == (65790, 257, 254)
+    (ia, ya), (ib, yb) = LW.snap_box_pair(rect)
+    (xa, za), ga, _, _ = LW.snap_place(rect, ia)
+    (xb, zb), gb, _, _ = LW.snap_place(rect, ib)
+    assert (ga, gb) == (0, 256) and xa < xb and za > zb and ya > yb
+    terrain = LW.snap_terrain()
+    heights = terrain.sum(axis=1)
+    assert terrain.shape == LW.SNAP_DIMS and heights.min() == 5 and heights.max() == 19, "every voxel the cases paint or carve (y 1 .. 4) is solid"
+    assert (terrain == (np.arange(32)[None, :, None] < heights[:, None, :])).all()

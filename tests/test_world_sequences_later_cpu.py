@@ -21,11 +21,13 @@ import densemodel
 import distancemodel
 import heightsmodel
 import lampmodel
+import liftmodel
 import lightmodel
 import modelsmodel
 import navmodel
 import piecesmodel
 import shapemodel
+import snapshotmodel
 import spreadmodel
 import stampmodel
 import surfacemodel
@@ -44,7 +46,8 @@ IGNORE = gpu.SURFACE_IGNORE_COLOUR
 TO_SOLID, TO_AIR, SIGNED = gpu.DISTANCE_TO_SOLID, gpu.DISTANCE_TO_AIR, gpu.DISTANCE_SIGNED
 SPREAD_AIR, SPREAD_SOLID = gpu.SPREAD_AIR, gpu.SPREAD_SOLID
 UP_AND_DOWN = 0x0C  # spread's stepFaces: -Y and +Y alone
-WRITERS = ("brush", "shapes", "stamp", "copy", "write_heights", "place_models", "write_voxels", "fill_cavities", "lamps", "set_column")
+WRITERS = ("brush", "shapes", "stamp", "copy", "write_heights", "place_models", "write_voxels", "fill_cavities", "lamps", "set_column",
+           "lift_remove", "place_lifted", "snapshot_restore", "light")
 # (shapes: the brush with capsules and ellipsoids, through tests/shapemodel.py as tests/test_gpu_world_shapes.py does -- pickmodel.apply_strokes, the
 # model of `brush`, knows boxes and spheres alone)
 
@@ -186,6 +189,74 @@ class Models:
             dense = densemodel.read(self.solid, self.colour, (src_min, tuple(src_min[i] + size[i] for i in range(3))))
             assert (want[0] == dense[0]).all() and (want[1] == dense[1]).all(), f"{label}: the identity reads the dense box"
         return self.held(want, holds, label)
+
+    # -- the newest calls: cvx_world_lift_pieces and cvx_world_snapshot (tests/test_world_sequences_newest_cpu.py has their plans) ----------------------
+    def lifted(self, box, anchors, capacity, voxel_capacity, label):
+        """liftmodel's result; voxel_capacity None: exactly what the listed pieces need (the model's result with room for everything is the one
+        with exactly that room: the prefix rule stores every listed piece in both).  Something must be stored."""
+        want = liftmodel.lift(self.solid, self.colour, *box, anchors, capacity, (1 << 62) if voxel_capacity is None else voxel_capacity)
+        if voxel_capacity is None:
+            voxel_capacity = want.summary["storedVoxels"]
+        assert want.summary["storedPieces"] > 0, f"{label}: no piece is stored"
+        return want, voxel_capacity
+
+    def m_lift_copy(self, box, anchors, label, capacity=8192, voxel_capacity=None, holds=None):
+        """A reader: -> (liftmodel's Lift, the voxelCapacity of the call)."""
+        return self.held(self.lifted(box, anchors, capacity, voxel_capacity, label), holds, label)
+
+    def m_lift_remove(self, box, anchors, label, capacity=8192, voxel_capacity=None, overlaps=False, holds=None, **_):
+        """A writer: the world without the stored pieces.  self.lift keeps (the Lift, the voxelCapacity) for the call and for place_lifted."""
+        self.lift = self.held(self.lifted(box, anchors, capacity, voxel_capacity, label), holds, label)
+        return self.changed(self.lift[0].removed, label, overlaps)
+
+    def largest_lifted(self):
+        """The stored piece with the most voxels of the last lift_remove: its index in the list."""
+        want = self.lift[0]
+        return int(np.argmax(want.pieces["piece"]["voxels"][:want.summary["storedPieces"]]))
+
+    def m_place_lifted(self, offset, label, op=None, overlaps=False, **_):
+        """A writer: the largest piece of the last lift_remove placed as it lies, `offset` away from where it was."""
+        want, k = self.lift[0], self.largest_lifted()
+        piece = want.pieces["piece"][k]
+        size = tuple(int(piece["max"][a]) - int(piece["min"][a]) for a in range(3))
+        at = tuple(int(piece["min"][a]) + offset[a] for a in range(3))
+        argb, mask = want.models[k]
+        instance = identity_at(at, size, 0, FILL if op is None else op)
+        return self.changed(modelsmodel.place(self.solid, self.colour, [(argb, mask.astype(bool))], as_dicts([instance])), label, overlaps)
+
+    def taken(self):
+        """{name: (solid, colour, the held rectangle, levelCount)} of the snapshots of this run."""
+        return self.__dict__.setdefault("snapshots", {})
+
+    def m_snapshot(self, name, rect, label, levels=5):
+        """Neither reader nor writer: the volume as it is, and the rectangle rounded out to 2^levels and clipped.  (`levels`: the snapshot's
+        levelCount, under a name that a run on the models alone does not strip from the arguments.)"""
+        k = (1 << levels) - 1
+        x0, z0 = max(rect[0], 0) & ~k, max(rect[1], 0) & ~k
+        x1, z1 = min((rect[0] + rect[2] + k) & ~k, self.dims[0]), min((rect[1] + rect[3] + k) & ~k, self.dims[2])
+        self.taken()[name] = (self.solid, self.colour, (x0, z0, x1 - x0, z1 - z0), levels)
+
+    def m_snapshot_diff(self, name, label, flags=0, holds=None):
+        """A reader: snapshotmodel's (changes, summary) of the rectangle now against the snapshot."""
+        solid, colour, (x0, z0, sx, sz), _ = self.taken()[name]
+        cut = lambda a: a[x0:x0 + sx, :, z0:z0 + sz].transpose(0, 2, 1)  # noqa: E731
+        want = snapshotmodel.diff((cut(solid), cut(colour)), (cut(self.solid), cut(self.colour)), (x0, z0), flags)
+        return self.held(want, holds, label)
+
+    def m_snapshot_restore(self, name, label, overlaps=False, **_):
+        """A writer: the columns of the held rectangle as they were when the snapshot was taken."""
+        solid, colour, (x0, z0, sx, sz), _ = self.taken()[name]
+        s, c = self.solid.copy(), self.colour.copy()
+        s[x0:x0 + sx, :, z0:z0 + sz], c[x0:x0 + sx, :, z0:z0 + sz] = solid[x0:x0 + sx, :, z0:z0 + sz], colour[x0:x0 + sx, :, z0:z0 + sz]
+        return self.changed((s, c), label, overlaps)
+
+    def m_light(self, p, label, overlaps=False, **_):
+        mask, _ = lightmodel.shades(self.solid, p)
+        assert mask.any(), f"{label}: the box holds no voxel"
+        return self.changed((self.solid, lightmodel.light(self.solid, self.colour, p)), label, overlaps)
+
+    def m_compact(self, label, **_):
+        return None
 
     def held(self, want, holds, label):
         if holds is not None:
