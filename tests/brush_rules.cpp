@@ -1,9 +1,8 @@
 // Host build of the brush and pick rules (cpuvox_amd/csrc/cvx_brush.h) for tests/test_world_brush_cpu.py.
 //   brush_rules brush <cases in> <results out>
-//     Each case is one column in the reference's layout plus a stroke list (int32 words): dimY cx cz stride colorsBase runCount (colorsIndex length)*
-//     colourCount colour* strokeCount (op shape a0 a1 a2 b0 b1 b2 argb pad)*.  The column gets its record from the edit's record rule (cvx_edit.h;
-//     a listed column its run-list block at entry 2), its colours at colorsBase + k * stride, and goes through cvxb::BrushColumn.  Out per case:
-//     overLimit runCount colours worldMin worldMax, then (unless over the limits) the runs and the colours.
+//     Each case is one column plus a stroke list (int32 words): dimY cx cz stride, the column's words (tests/rules_world.h), strokeCount
+//     (op shape a0 a1 a2 b0 b1 b2 argb pad)*.  The column goes through cvxb::BrushColumn.  Out per case: the edited-column block
+//     (tests/rules_world.h).
 //   brush_rules pick <blob> <dimX> <dimY> <dimZ> <columnCount> <rays in> <hits out>
 //     Uploads the LOD-0 blob into a context that never touches a device (cvx_world_upload lays the level out on the host), then cvxb::PickRay on
 //     every ray (cvx_pick_ray in, cvx_pick_hit out) against the host copy of the level, with a guard row of zeros around its records.
@@ -13,17 +12,7 @@
 #include <vector>
 
 #include "cvx_brush.h"
-#include "cvx_context.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	for (int c; (c = std::fgetc(f)) != EOF;) { out.push_back((uint8_t)c); }
-	std::fclose(f);
-	return out;
-}
+#include "rules_world.h"
 
 static int Brush(const char *in, const char *outPath)
 {
@@ -32,76 +21,28 @@ static int Brush(const char *in, const char *outPath)
 	const int32_t *end = p + bytes.size() / 4;
 	std::vector<uint32_t> out;
 	while (p < end) {
-		const int dimY = *p++, cx = *p++, cz = *p++, stride = *p++, colorsBase = *p++, runCount = *p++;
-		// the column as a blob: header {0, runCount | worldMin << 16, worldMax}, elements [guard][runs][guard][colours]
-		std::vector<uint32_t> elements(1, 0u);
-		uint32_t start = 0;
-		int64_t lowest = -1, highest = -1;
-		for (int r = 0; r < runCount; r++) {
-			const int32_t ci = *p++, length = *p++;
-			elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-			if (ci >= 0) {
-				const int64_t top = (int64_t)dimY - start;
-				if (highest < 0) { highest = top; }
-				lowest = top - length;
-			}
-			start += (uint32_t)length;
-		}
-		elements.push_back(0u);
-		const int colourCount = *p++;
-		std::vector<uint32_t> slots((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u);
-		for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
+		const int dimY = *p++, cx = *p++, cz = *p++, stride = *p++;
+		CaseColumn C;
+		p = C.Read(p, dimY, stride);
 		const int strokeCount = *p++;
 		std::vector<cvx_brush_stroke> strokes((size_t)strokeCount);
 		std::memcpy(strokes.data(), p, (size_t)strokeCount * sizeof(cvx_brush_stroke));
 		p += (size_t)strokeCount * sizeof(cvx_brush_stroke) / 4;
-		const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
-		uint32_t x = 0, y = 0, z = 0, w = 0;
-		std::vector<uint32_t> runs(8, 0u);
-		if (runCount > 0) {
-			const cvxe::ColumnWords c = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-			x = c.x | (uint32_t)colorsBase;
-			y = c.y;
-			z = c.z;
-			w = c.w;
-			if (c.code == 0u) {
-				z = 2u;
-				runs.resize(2u * (2u + c.solid) + 8u, 0u);
-				cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 4);
-			}
-		}
-		const cvxb::ArenaColumn col{ x, y, z, w, runs.data() };
-		const int colorShift = stride == 1 ? 2 : 7;
-		const cvxb::BrushResult r = cvxb::BrushColumn(col, slots.data(), colorShift, strokes.data(), strokeCount, cx, cz, dimY, nullptr, nullptr);
-		out.push_back(r.overLimit ? 1u : 0u);
-		out.push_back(r.runCount);
-		out.push_back(r.colours);
-		out.push_back(r.worldMin);
-		out.push_back(r.worldMax);
-		if (!r.overLimit) {
-			std::vector<uint32_t> newRuns(r.runCount + 1u), newColours(r.colours + 1u);
-			const cvxb::BrushResult again = cvxb::BrushColumn(col, slots.data(), colorShift, strokes.data(), strokeCount, cx, cz, dimY, newRuns.data(), newColours.data());
-			if (again.runCount != r.runCount || again.colours != r.colours) { return 3; }
-			out.insert(out.end(), newRuns.begin(), newRuns.begin() + r.runCount);
-			out.insert(out.end(), newColours.begin(), newColours.begin() + r.colours);
-		}
+		const cvxb::ArenaColumn col = C.Column();
+		const int colorShift = CaseColorShift(stride);
+		if (!AppendEditedColumn(&out, [&](uint32_t *runs, uint32_t *colours) {
+			    return cvxb::BrushColumn(col, C.slots.data(), colorShift, strokes.data(), strokeCount, cx, cz, dimY, runs, colours);
+		    })) { return 3; }
 	}
-	FILE *f = std::fopen(outPath, "wb");
-	if (!f) { return 2; }
-	std::fwrite(out.data(), 4, out.size(), f);
-	std::fclose(f);
-	return 0;
+	return WriteFile(outPath, out);
 }
 
 static int Pick(char **argv)
 {
-	std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	const std::vector<uint8_t> rayBytes = ReadFile(argv[7]);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
+	const BlobWorld blob = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvx_context::HostLevel &H = *blob.H;
 	const size_t guard = ((size_t)1 << H.rowShift) + 4; // records
 	std::vector<uint4> records(guard + H.records.size() + guard, uint4{ 0u, 0u, 0u, 0u });
 	std::memcpy(records.data() + guard, H.records.data(), H.records.size() * sizeof(uint4));
@@ -126,10 +67,7 @@ static int Pick(char **argv)
 		hits[i].argb = r.argb;
 		hits[i].t = r.t;
 	}
-	FILE *f = std::fopen(argv[8], "wb");
-	if (!f) { return 2; }
-	std::fwrite(hits.data(), sizeof(cvx_pick_hit), n, f);
-	std::fclose(f);
+	if (WriteFile(argv[8], hits)) { return 2; }
 	std::printf("colorShift %d listed %lld\n", H.colorShift, (long long)H.listedColumns);
 	return 0;
 }

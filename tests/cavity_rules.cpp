@@ -1,10 +1,9 @@
 // Host build of the rules of cvx_world_cavities (cpuvox_amd/csrc/cvx_cavity.h) for tests/test_world_cavities_cpu.py, driven by a sequential
 // union-find: per-column air intervals, the edge rule, the open bits, the FILL column rule.
 //   cavity_rules columns <cases in> <results out>
-//     Each case is a small world of gx x gz columns in the reference's layout (int32 words, the format of tests/copy_rules.cpp): dimY gx gz stride,
-//     per column (x-major) colorsBase runCount (colorsIndex length)* colourCount colour*, then boxMin[3] boxMax[3] openFaces maxVoxels argb.  Out per
-//     case (uint32 words): the six totals of cvx_cavities_summary, per selected cavity min[3] max[3] seed[3] voxels, then for every column of the
-//     world with the selected cavities filled: overLimit runCount colours worldMin worldMax and (unless over the limits) the runs and the colours.
+//     Each case is a case world (int32 words, tests/rules_world.h), then boxMin[3] boxMax[3] openFaces maxVoxels argb.  Out per case (uint32
+//     words): the six totals of cvx_cavities_summary, per selected cavity min[3] max[3] seed[3] voxels, then for every column of the world with
+//     the selected cavities filled: the edited-column block (tests/rules_world.h).
 //   cavity_rules world <blob> <dimX> <dimY> <dimZ> <columnCount> <x0> <y0> <z0> <x1> <y1> <z1> <openFaces> <maxVoxels> <argb> <levelCount> <list out> <blob out>
 //     Uploads the LOD-0 blob into a context that never touches a device, analyses the box and writes the summary (48 bytes) and every selected
 //     cavity (48 bytes each), and the sub-world blob of the FILL rectangle as cvx_cavity.hip's write kernel makes it.  Prints the layout, the
@@ -18,28 +17,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_cavity.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t n; (n = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + n); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 struct Analysis {
 	std::vector<uint32_t> offsets, lohi, chosen; // per column + 1; per node lo, hi; per node: its cavity is selected
@@ -158,59 +137,16 @@ static int Columns(const char *in, const char *outPath)
 	const int32_t *end = p + bytes.size() / 4;
 	std::vector<uint32_t> out;
 	while (p < end) {
-		const int dimY = *p++, gx = *p++, gz = *p++, stride = *p++;
-		int rowShift = 0;
-		while ((1 << rowShift) < gz) { rowShift++; }
-		std::vector<uint4> records((size_t)gx << rowShift, uint4{ 0u, 0u, 0u, 0u });
-		std::vector<uint32_t> runs(8, 0u), slots(64, 0u);
-		for (int c = 0; c < gx * gz; c++) {
-			const int colorsBase = *p++, runCount = *p++;
-			std::vector<uint32_t> elements(1, 0u);
-			uint32_t start = 0;
-			int64_t lowest = -1, highest = -1;
-			for (int r = 0; r < runCount; r++) {
-				const int32_t ci = *p++, length = *p++;
-				elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-				if (ci >= 0) {
-					const int64_t top = (int64_t)dimY - start;
-					if (highest < 0) { highest = top; }
-					lowest = top - length;
-				}
-				start += (uint32_t)length;
-			}
-			elements.push_back(0u);
-			const int colourCount = *p++;
-			if (slots.size() < (size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64) { slots.resize((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u); }
-			for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
-			const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
-			uint4 rec{ 0u, 0u, 0u, 0u };
-			if (runCount > 0 && highest >= 0) {
-				const cvxe::ColumnWords w = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-				rec = uint4{ w.x | (uint32_t)colorsBase, w.y, w.z, w.w };
-				if (w.code == 0u) {
-					const size_t entry = runs.size() / 2;
-					rec.z = (uint32_t)entry;
-					runs.resize(runs.size() + 2u * w.solid + 8u, 0u);
-					cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 2 * entry);
-				}
-			}
-			records[((size_t)(c / gz) << rowShift) + (size_t)(c % gz)] = rec;
-		}
+		CaseWorld C;
+		p = C.Read(p);
+		const int dimY = C.dimY, gx = C.gx, gz = C.gz;
 		int32_t boxMin[3], boxMax[3];
 		for (int a = 0; a < 3; a++) { boxMin[a] = *p++; }
 		for (int a = 0; a < 3; a++) { boxMax[a] = *p++; }
 		const int openFaces = *p++;
 		const int64_t maxVoxels = *p++;
 		const uint32_t argb = (uint32_t)*p++;
-		cvxb::CopyWorld W;
-		W.records = reinterpret_cast<const uint32_t *>(records.data());
-		W.runs = runs.data();
-		W.colourSlots = slots.data();
-		W.rowShift = rowShift;
-		W.colorShift = stride == 1 ? 2 : 7;
-		W.dimX = gx;
-		W.dimY = dimY;
-		W.dimZ = gz;
+		const cvxb::CopyWorld W = C.View();
 		cvxb::PiecesBox B;
 		if (!cvxb::PiecesClipBox(boxMin, boxMax, gx, dimY, gz, &B)) { return 4; }
 		const Analysis R = Analyse(W, B, openFaces, maxVoxels);
@@ -226,19 +162,7 @@ static int Columns(const char *in, const char *outPath)
 		for (int c = 0; c < gx * gz; c++) {
 			const int64_t cx = c / gz, cz = c % gz;
 			const uint32_t *chosen = ColumnNodes(R, B, cx, cz);
-			const cvxb::BrushResult r = cvxb::CavityFillColumn(W, cx, cz, B.y0, B.y1, chosen, argb, nullptr, nullptr);
-			out.push_back(r.overLimit ? 1u : 0u);
-			out.push_back(r.runCount);
-			out.push_back(r.colours);
-			out.push_back(r.worldMin);
-			out.push_back(r.worldMax);
-			if (!r.overLimit) {
-				std::vector<uint32_t> newRuns(r.runCount + 1u), newColours(r.colours + 1u);
-				const cvxb::BrushResult again = cvxb::CavityFillColumn(W, cx, cz, B.y0, B.y1, chosen, argb, newRuns.data(), newColours.data());
-				if (again.runCount != r.runCount || again.colours != r.colours) { return 3; }
-				out.insert(out.end(), newRuns.begin(), newRuns.begin() + r.runCount);
-				out.insert(out.end(), newColours.begin(), newColours.begin() + r.colours);
-			}
+			if (!AppendEditedColumn(&out, [&](uint32_t *runs, uint32_t *colours) { return cvxb::CavityFillColumn(W, cx, cz, B.y0, B.y1, chosen, argb, runs, colours); })) { return 3; }
 		}
 	}
 	return WriteFile(outPath, out.data(), out.size() * 4);
@@ -246,7 +170,6 @@ static int Columns(const char *in, const char *outPath)
 
 static int World(char **argv)
 {
-	std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	int32_t boxMin[3], boxMax[3];
 	for (int a = 0; a < 3; a++) {
@@ -256,19 +179,9 @@ static int World(char **argv)
 	const int openFaces = std::atoi(argv[13]), levelCount = std::atoi(argv[16]);
 	const int64_t maxVoxels = std::atoll(argv[14]);
 	const uint32_t argb = (uint32_t)std::strtoul(argv[15], nullptr, 0);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W.runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W.colourSlots = H.elements.data();
-	W.rowShift = H.rowShift;
-	W.colorShift = H.colorShift;
-	W.dimX = dimX;
-	W.dimY = dimY;
-	W.dimZ = dimZ;
+	const BlobWorld blob = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvx_context::HostLevel &H = *blob.H;
+	const cvxb::CopyWorld &W = blob.W;
 	cvxb::PiecesBox B;
 	if (!cvxb::PiecesClipBox(boxMin, boxMax, dimX, dimY, dimZ, &B)) { return 4; }
 	const auto t0 = std::chrono::steady_clock::now();

@@ -1,10 +1,7 @@
 // Host build of the copy rule (cpuvox_amd/csrc/cvx_copy.h) for tests/test_world_copy_cpu.py.
 //   copy_rules columns <cases in> <results out>
-//     Each case is a small world of gx x gz columns in the reference's layout plus a placement list (int32 words): dimY gx gz stride, per column
-//     (x-major) colorsBase runCount (colorsIndex length)* colourCount colour*, then placementCount and the placements (cvx_copy_placement, 12 words
-//     each).  Every column gets its record from the edit's record rule (cvx_edit.h; a listed column its run-list block), its colours at
-//     colorsBase + k * stride, and every column of the world goes through cvxb::CopyColumn.  Out per case and column: overLimit runCount colours
-//     worldMin worldMax, then (unless over the limits) the runs and the colours.
+//     Each case is a case world (int32 words, tests/rules_world.h), then placementCount and the placements (cvx_copy_placement, 12 words each).
+//     Every column of the world goes through cvxb::CopyColumn.  Out per case and column: the edited-column block (tests/rules_world.h).
 //   copy_rules world <blob> <dimX> <dimY> <dimZ> <columnCount> <placements> <x0> <z0> <sizeX> <sizeZ> <blob out>
 //     Uploads the LOD-0 blob into a context that never touches a device (cvx_world_upload lays the level out on the host), runs cvxb::CopyColumn
 //     on every column of the rectangle and writes the sub-world blob cvx_copy.hip's write kernel makes (12-byte headers, then the element pool).
@@ -15,27 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
-#include "cvx_copy.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	for (int c; (c = std::fgetc(f)) != EOF;) { out.push_back((uint8_t)c); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 static int Columns(const char *in, const char *outPath)
 {
@@ -44,73 +21,16 @@ static int Columns(const char *in, const char *outPath)
 	const int32_t *end = p + bytes.size() / 4;
 	std::vector<uint32_t> out;
 	while (p < end) {
-		const int dimY = *p++, gx = *p++, gz = *p++, stride = *p++;
-		int rowShift = 0;
-		while ((1 << rowShift) < gz) { rowShift++; }
-		std::vector<uint4> records((size_t)gx << rowShift, uint4{ 0u, 0u, 0u, 0u });
-		std::vector<uint32_t> runs(8, 0u), slots(64, 0u);
-		for (int c = 0; c < gx * gz; c++) {
-			const int colorsBase = *p++, runCount = *p++;
-			// the column as a blob: header {0, runCount | worldMin << 16, worldMax}, elements [guard][runs][guard]
-			std::vector<uint32_t> elements(1, 0u);
-			uint32_t start = 0;
-			int64_t lowest = -1, highest = -1;
-			for (int r = 0; r < runCount; r++) {
-				const int32_t ci = *p++, length = *p++;
-				elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-				if (ci >= 0) {
-					const int64_t top = (int64_t)dimY - start;
-					if (highest < 0) { highest = top; }
-					lowest = top - length;
-				}
-				start += (uint32_t)length;
-			}
-			elements.push_back(0u);
-			const int colourCount = *p++;
-			if (slots.size() < (size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64) { slots.resize((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u); }
-			for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
-			const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
-			uint4 rec{ 0u, 0u, 0u, 0u };
-			if (runCount > 0) {
-				const cvxe::ColumnWords w = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-				rec = uint4{ w.x | (uint32_t)colorsBase, w.y, w.z, w.w };
-				if (w.code == 0u) {
-					const size_t entry = runs.size() / 2;
-					rec.z = (uint32_t)entry;
-					runs.resize(runs.size() + 2u * w.solid + 8u, 0u);
-					cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 2 * entry);
-				}
-			}
-			records[((size_t)(c / gz) << rowShift) + (size_t)(c % gz)] = rec;
-		}
+		CaseWorld C;
+		p = C.Read(p);
 		const int n = *p++;
 		std::vector<cvx_copy_placement> placements((size_t)n);
 		std::memcpy(placements.data(), p, (size_t)n * sizeof(cvx_copy_placement));
 		p += (size_t)n * sizeof(cvx_copy_placement) / 4;
-		cvxb::CopyWorld W;
-		W.records = reinterpret_cast<const uint32_t *>(records.data());
-		W.runs = runs.data();
-		W.colourSlots = slots.data();
-		W.rowShift = rowShift;
-		W.colorShift = stride == 1 ? 2 : 7;
-		W.dimX = gx;
-		W.dimY = dimY;
-		W.dimZ = gz;
-		for (int c = 0; c < gx * gz; c++) {
-			const int64_t cx = c / gz, cz = c % gz;
-			const cvxb::BrushResult r = cvxb::CopyColumn(W, placements.data(), n, cx, cz, nullptr, nullptr);
-			out.push_back(r.overLimit ? 1u : 0u);
-			out.push_back(r.runCount);
-			out.push_back(r.colours);
-			out.push_back(r.worldMin);
-			out.push_back(r.worldMax);
-			if (!r.overLimit) {
-				std::vector<uint32_t> newRuns(r.runCount + 1u), newColours(r.colours + 1u);
-				const cvxb::BrushResult again = cvxb::CopyColumn(W, placements.data(), n, cx, cz, newRuns.data(), newColours.data());
-				if (again.runCount != r.runCount || again.colours != r.colours) { return 3; }
-				out.insert(out.end(), newRuns.begin(), newRuns.begin() + r.runCount);
-				out.insert(out.end(), newColours.begin(), newColours.begin() + r.colours);
-			}
+		const cvxb::CopyWorld W = C.View();
+		for (int c = 0; c < C.gx * C.gz; c++) {
+			const int64_t cx = c / C.gz, cz = c % C.gz;
+			if (!AppendEditedColumn(&out, [&](uint32_t *runs, uint32_t *colours) { return cvxb::CopyColumn(W, placements.data(), n, cx, cz, runs, colours); })) { return 3; }
 		}
 	}
 	return WriteFile(outPath, out.data(), out.size() * 4);
@@ -118,23 +38,12 @@ static int Columns(const char *in, const char *outPath)
 
 static int World(char **argv)
 {
-	std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	const std::vector<uint8_t> placementBytes = ReadFile(argv[7]);
 	const int x0 = std::atoi(argv[8]), z0 = std::atoi(argv[9]), sizeX = std::atoi(argv[10]), sizeZ = std::atoi(argv[11]);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W.runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W.colourSlots = H.elements.data();
-	W.rowShift = H.rowShift;
-	W.colorShift = H.colorShift;
-	W.dimX = dimX;
-	W.dimY = dimY;
-	W.dimZ = dimZ;
+	const BlobWorld B = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvx_context::HostLevel &H = *B.H;
+	const cvxb::CopyWorld &W = B.W;
 	const int n = (int)(placementBytes.size() / sizeof(cvx_copy_placement));
 	const cvx_copy_placement *placements = reinterpret_cast<const cvx_copy_placement *>(placementBytes.data());
 	// count, scan, write: what copy_count_kernel, cvxi::ExclusiveScan and copy_write_kernel do

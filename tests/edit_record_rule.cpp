@@ -7,17 +7,12 @@
 #include <cstdlib>
 #include <vector>
 
-#include "cvx_context.h"
-#include "cvx_edit.h"
+#include "rules_world.h"
 
 int main(int argc, char **argv)
 {
 	if (argc != 7) { std::fprintf(stderr, "usage\n"); return 2; }
-	FILE *f = std::fopen(argv[1], "rb");
-	if (!f) { return 2; }
-	std::vector<uint8_t> blob;
-	for (int c; (c = std::fgetc(f)) != EOF;) { blob.push_back((uint8_t)c); }
-	std::fclose(f);
+	const std::vector<uint8_t> blob = ReadFile(argv[1]);
 	const int dimX = std::atoi(argv[2]), dimY = std::atoi(argv[3]), dimZ = std::atoi(argv[4]), lod = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	cvx_context *ctx = new cvx_context();
 	if (lod > 0) { // (upload checks the other levels against LOD 0's dimensions)
@@ -26,8 +21,7 @@ int main(int argc, char **argv)
 		ctx->hostWorld.dimY = dimY;
 		ctx->hostWorld.dimZ = dimZ;
 	}
-	const int rc = cvx_world_upload(ctx, lod, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
+	UploadBlobLevel(ctx, lod, blob, dimX, dimY, dimZ, columnCount);
 	const cvx_context::HostLevel &H = ctx->hostLevel[lod];
 	const uint32_t *headers = reinterpret_cast<const uint32_t *>(blob.data());
 	const uint32_t *elements = reinterpret_cast<const uint32_t *>(blob.data() + (size_t)columnCount * 12);

@@ -1,12 +1,10 @@
 // Host build of the height-map rules (cpuvox_amd/csrc/cvx_heights.h) for tests/test_world_heights_cpu.py.
 //   heights_rules columns <cases in> <results out>
-//     Each case is a small world of gx x gz columns in the reference's layout plus one write (int32 words): dimY gx gz stride, per column
-//     (x-major) colorsBase runCount (colorsIndex length)* colourCount colour*, then boxMin[3] boxSize[3] op thickness flags hasArgb hasSide, the
-//     heights and (if hasArgb / hasSide) the argb and sideArgb words, X * Z each.  Every column gets its record from the edit's record rule
-//     (cvx_edit.h; a listed column its run-list block), its colours at colorsBase + k * stride, and goes through cvxb::HeightsColumn -- the
+//     Each case is a case world (int32 words, tests/rules_world.h) plus one write: boxMin[3] boxSize[3] op thickness flags hasArgb hasSide, the
+//     heights and (if hasArgb / hasSide) the argb and sideArgb words, X * Z each.  Every column goes through cvxb::HeightsColumn -- the
 //     function the kernels run, counting and then writing -- AND through cvxb::DenseColumn on the write expanded into dense arrays, the call's
 //     definition; the two must agree word for word (exit code 3 otherwise).
-//     Out per case and column: overLimit runCount colours worldMin worldMax, then (unless over the limits) the runs and the colours.
+//     Out per case and column: the edited-column block (tests/rules_world.h).
 //   heights_rules read <blob> <dimX> <dimY> <dimZ> <columnCount> <minX> <minY> <minZ> <sizeX> <sizeY> <sizeZ> <out>
 //     Uploads the LOD-0 blob into a context that never touches a device and runs cvxb::HeightsTop over the footprint in the arrays' order: the
 //     heights, then the argb words, then the bottoms.
@@ -17,29 +15,9 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_dense.h"
 #include "cvx_heights.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t got; (got = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + got); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 // One write as the files hold it, and its expansion: the dense arrays of the cvx_world_write_voxels call that defines it.
 struct HeightsWrite {
@@ -130,55 +108,17 @@ static int Columns(const char *in, const char *outPath)
 	const int32_t *end = p + bytes.size() / 4;
 	std::vector<uint32_t> out;
 	while (p < end) {
-		const int dimY = *p++, gx = *p++, gz = *p++, stride = *p++;
-		int rowShift = 0;
-		while ((1 << rowShift) < gz) { rowShift++; }
-		std::vector<uint4> records((size_t)gx << rowShift, uint4{ 0u, 0u, 0u, 0u });
-		std::vector<uint32_t> runs(8, 0u), slots(64, 0u);
-		for (int c = 0; c < gx * gz; c++) {
-			const int colorsBase = *p++, runCount = *p++;
-			// the column as a blob: header {0, runCount | worldMin << 16, worldMax}, elements [guard][runs][guard]
-			std::vector<uint32_t> elements(1, 0u);
-			uint32_t start = 0;
-			int64_t lowest = -1, highest = -1;
-			for (int r = 0; r < runCount; r++) {
-				const int32_t ci = *p++, length = *p++;
-				elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-				if (ci >= 0) {
-					const int64_t top = (int64_t)dimY - start;
-					if (highest < 0) { highest = top; }
-					lowest = top - length;
-				}
-				start += (uint32_t)length;
-			}
-			elements.push_back(0u);
-			const int colourCount = *p++;
-			if (slots.size() < (size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64) { slots.resize((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u); }
-			for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
-			const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
-			uint4 rec{ 0u, 0u, 0u, 0u };
-			if (runCount > 0) {
-				const cvxe::ColumnWords w = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-				rec = uint4{ w.x | (uint32_t)colorsBase, w.y, w.z, w.w };
-				if (w.code == 0u) {
-					const size_t entry = runs.size() / 2;
-					rec.z = (uint32_t)entry;
-					runs.resize(runs.size() + 2u * w.solid + 8u, 0u);
-					cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 2 * entry);
-				}
-			}
-			records[((size_t)(c / gz) << rowShift) + (size_t)(c % gz)] = rec;
-		}
+		CaseWorld C;
+		p = C.Read(p);
+		const int dimY = C.dimY, gx = C.gx, gz = C.gz;
 		HeightsWrite W;
 		p = W.Parse(p);
-		const int colorShift = stride == 1 ? 2 : 7;
+		const cvxb::CopyWorld world = C.View();
 		for (int c = 0; c < gx * gz; c++) {
 			const int64_t cx = c / gz, cz = c % gz;
-			const uint4 rec = records[((size_t)cx << rowShift) + (size_t)cz];
-			const cvxb::ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, runs.data() };
 			cvxb::BrushResult r;
 			std::vector<uint32_t> newRuns, newColours;
-			if (!BothRules(col, slots.data(), colorShift, W, cx, cz, dimY, &r, &newRuns, &newColours)) { return 3; }
+			if (!BothRules(cvxb::CopyColumnAt(world, cx, cz), world.colourSlots, world.colorShift, W, cx, cz, dimY, &r, &newRuns, &newColours)) { return 3; }
 			out.push_back(r.overLimit ? 1u : 0u);
 			out.push_back(r.runCount);
 			out.push_back(r.colours);
@@ -195,21 +135,8 @@ static int Columns(const char *in, const char *outPath)
 
 static int Read(char **argv)
 {
-	const std::vector<uint8_t> blob = ReadFile(argv[2]);
-	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W.runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W.colourSlots = H.elements.data();
-	W.rowShift = H.rowShift;
-	W.colorShift = H.colorShift;
-	W.dimX = dimX;
-	W.dimY = dimY;
-	W.dimZ = dimZ;
+	const BlobWorld blob = LoadBlobWorld(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]));
+	const cvxb::CopyWorld &W = blob.W;
 	int32_t min[3], size[3];
 	for (int a = 0; a < 3; a++) {
 		min[a] = std::atoi(argv[7 + a]);

@@ -20,36 +20,7 @@
 #ifndef LIFT_RULES_NO_LIBRARY // (the sanitizer build: the rules alone, nothing of the library is linked)
 #include "cvx_context.h"
 #endif
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t got; (got = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + got); }
-	std::fclose(f);
-	return out;
-}
-
-template <class T>
-static std::vector<T> ReadWords(const char *path)
-{
-	const std::vector<uint8_t> raw = ReadFile(path);
-	std::vector<T> out(raw.size() / sizeof(T));
-	if (!out.empty()) { std::memcpy(out.data(), raw.data(), out.size() * sizeof(T)); }
-	return out;
-}
-
-template <class T>
-static int WriteFile(const char *path, const std::vector<T> &out)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(out.data(), sizeof(T), out.size(), f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_io.h"
 
 static int Sums(const char *in, const char *outPath)
 {

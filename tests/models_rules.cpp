@@ -3,11 +3,9 @@
 //   A call, as the files hold it (int32 words): modelCount, per model sx sy sz hasArgb hasSolid, the argb words (if hasArgb) and the mask, a
 //   word per voxel (if hasSolid), both in the (X, Z, Y) layout; instanceCount, per instance the 24 words of a cvx_model_instance.
 //   models_rules columns <cases in> <results out>
-//     Each case is a small world of gx x gz columns in the reference's layout plus one call: dimY gx gz stride, per column (x-major) colorsBase
-//     runCount (colorsIndex length)* colourCount colour*, then the call.  Every column goes through cvxb::ModelsColumn AND through the
-//     kernels' walk (WaveColumn below: the cull, then the steps of cvx_dense.h with cvxb::ModelsLaneVoxel, lane after lane); the two must
-//     agree word for word (exit code 3 otherwise).  Out per case and column: overLimit runCount colours worldMin worldMax, then (unless over
-//     the limits) the runs and the colours.
+//     Each case is a case world (int32 words, tests/rules_world.h), then the call.  Every column goes through cvxb::ModelsColumn AND through
+//     the kernels' walk (WaveColumn below: the cull, then the steps of cvx_dense.h with cvxb::ModelsLaneVoxel, lane after lane); the two must
+//     agree word for word (exit code 3 otherwise).  Out per case and column: the edited-column block (tests/rules_world.h).
 //   models_rules world <blob> <dimX> <dimY> <dimZ> <columnCount> <call> <x0> <z0> <sizeX> <sizeZ> <blob out> [dense]
 //     Uploads the LOD-0 blob into a context that never touches a device, runs both walks on every column of the rectangle (count, scan, write,
 //     as cvx_models.hip does) and writes the sub-world blob.  `dense`: the call is one instance with the identity map whose box is its model's;
@@ -21,28 +19,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_models.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t got; (got = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + got); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 struct ModelsCall {
 	std::vector<std::vector<uint32_t>> argbWords;
@@ -168,55 +146,17 @@ static int Columns(const char *in, const char *outPath)
 	const int32_t *end = p + bytes.size() / 4;
 	std::vector<uint32_t> out;
 	while (p < end) {
-		const int dimY = *p++, gx = *p++, gz = *p++, stride = *p++;
-		int rowShift = 0;
-		while ((1 << rowShift) < gz) { rowShift++; }
-		std::vector<uint4> records((size_t)gx << rowShift, uint4{ 0u, 0u, 0u, 0u });
-		std::vector<uint32_t> runs(8, 0u), slots(64, 0u);
-		for (int c = 0; c < gx * gz; c++) {
-			const int colorsBase = *p++, runCount = *p++;
-			// the column as a blob: header {0, runCount | worldMin << 16, worldMax}, elements [guard][runs][guard]
-			std::vector<uint32_t> elements(1, 0u);
-			uint32_t start = 0;
-			int64_t lowest = -1, highest = -1;
-			for (int r = 0; r < runCount; r++) {
-				const int32_t ci = *p++, length = *p++;
-				elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-				if (ci >= 0) {
-					const int64_t top = (int64_t)dimY - start;
-					if (highest < 0) { highest = top; }
-					lowest = top - length;
-				}
-				start += (uint32_t)length;
-			}
-			elements.push_back(0u);
-			const int colourCount = *p++;
-			if (slots.size() < (size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64) { slots.resize((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u); }
-			for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
-			const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
-			uint4 rec{ 0u, 0u, 0u, 0u };
-			if (runCount > 0) {
-				const cvxe::ColumnWords w = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-				rec = uint4{ w.x | (uint32_t)colorsBase, w.y, w.z, w.w };
-				if (w.code == 0u) {
-					const size_t entry = runs.size() / 2;
-					rec.z = (uint32_t)entry;
-					runs.resize(runs.size() + 2u * w.solid + 8u, 0u);
-					cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 2 * entry);
-				}
-			}
-			records[((size_t)(c / gz) << rowShift) + (size_t)(c % gz)] = rec;
-		}
+		CaseWorld world;
+		p = world.Read(p);
+		const int dimY = world.dimY, gx = world.gx, gz = world.gz;
 		ModelsCall C;
 		p = C.Parse(p);
-		const int colorShift = stride == 1 ? 2 : 7;
+		const cvxb::CopyWorld W = world.View();
 		for (int c = 0; c < gx * gz; c++) {
 			const int cx = c / gz, cz = c % gz;
-			const uint4 rec = records[((size_t)cx << rowShift) + (size_t)cz];
-			const cvxb::ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, runs.data() };
 			cvxb::BrushResult r;
 			std::vector<uint32_t> newRuns, newColours;
-			if (!BothWalks(col, slots.data(), colorShift, C, cx, cz, dimY, &r, &newRuns, &newColours)) { return 3; }
+			if (!BothWalks(cvxb::CopyColumnAt(W, cx, cz), W.colourSlots, W.colorShift, C, cx, cz, dimY, &r, &newRuns, &newColours)) { return 3; }
 			out.push_back(r.overLimit ? 1u : 0u);
 			out.push_back(r.runCount);
 			out.push_back(r.colours);
@@ -231,32 +171,13 @@ static int Columns(const char *in, const char *outPath)
 	return WriteFile(outPath, out.data(), out.size() * 4);
 }
 
-static cvx_context *Upload(char **argv, cvxb::CopyWorld *W)
-{
-	static std::vector<uint8_t> blob;
-	static cvx_context context;
-	blob = ReadFile(argv[2]);
-	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
-	cvx_context *ctx = &context;
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); std::exit(1); }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	W->records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W->runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W->colourSlots = H.elements.data();
-	W->rowShift = H.rowShift;
-	W->colorShift = H.colorShift;
-	W->dimX = dimX;
-	W->dimY = dimY;
-	W->dimZ = dimZ;
-	return ctx;
-}
+static BlobWorld Upload(char **argv) { return LoadBlobWorld(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6])); }
 
 static int World(char **argv, bool dense)
 {
-	cvxb::CopyWorld W;
-	cvx_context *ctx = Upload(argv, &W);
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
+	const BlobWorld blob = Upload(argv);
+	const cvx_context::HostLevel &H = *blob.H;
+	const cvxb::CopyWorld &W = blob.W;
 	const std::vector<uint8_t> callBytes = ReadFile(argv[7]);
 	ModelsCall C;
 	C.Parse(reinterpret_cast<const int32_t *>(callBytes.data()));
@@ -307,8 +228,8 @@ static int World(char **argv, bool dense)
 
 static int Read(char **argv)
 {
-	cvxb::CopyWorld W;
-	Upload(argv, &W);
+	const BlobWorld blob = Upload(argv);
+	const cvxb::CopyWorld &W = blob.W;
 	int64_t size[3];
 	for (int a = 0; a < 3; a++) { size[a] = std::atoll(argv[7 + a]); }
 	cvx_model_map M{};

@@ -12,20 +12,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_nav.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t n; (n = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + n); }
-	std::fclose(f);
-	return out;
-}
-
+#include "rules_world.h"
 struct HostNodes {
 	const uint32_t *lohi;
 	uint32_t Lo(uint32_t i) const { return lohi[2 * (size_t)i]; }
@@ -124,7 +112,6 @@ static Field Build(const cvxb::CopyWorld &W, const cvxb::PiecesBox &B, const cvx
 
 static int World(char **argv)
 {
-	std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	int32_t boxMin[3], boxMax[3];
 	for (int a = 0; a < 3; a++) {
@@ -137,19 +124,8 @@ static int World(char **argv)
 	const std::vector<uint8_t> goalBytes = ReadFile(argv[18]);
 	const int32_t *goals = reinterpret_cast<const int32_t *>(goalBytes.data());
 	const int goalCount = (int)(goalBytes.size() / 12);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W.runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W.colourSlots = H.elements.data();
-	W.rowShift = H.rowShift;
-	W.colorShift = H.colorShift;
-	W.dimX = dimX;
-	W.dimY = dimY;
-	W.dimZ = dimZ;
+	const BlobWorld blob = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvxb::CopyWorld &W = blob.W;
 	cvxb::PiecesBox B;
 	if (!cvxb::PiecesClipBox(boxMin, boxMax, dimX, dimY, dimZ, &B)) { return 4; }
 	const auto t0 = std::chrono::steady_clock::now();

@@ -1,9 +1,9 @@
 // Host build of the read-back rule (cpuvox_amd/csrc/cvx_readback.h) for tests/test_world_readback_cpu.py.
 //   readback_rules column <cases in> <results out>
 //     Each case is one column of a level in the reference's layout (int32 words): lod dimY stride colorsBase worldMin worldMax runCount
-//     (colorsIndex length)* colourCount colour*.  The column gets its record from the edit's record rule (cvx_edit.h; a listed column its run-list
-//     block at entry 2), its colours at colorsBase + k * stride, and goes through cvxr::ReadColumn.  Out per case: runCount colours worldMin
-//     worldMax, the runs, the colours, then the three header words cvxr::ReadHeader makes with storageOffset 7.
+//     (colorsIndex length)* colourCount colour*.  The column gets its record and its colour slots as a case world's columns do
+//     (tests/rules_world.h), with the stated bounds and at the level's scale, and goes through cvxr::ReadColumn.  Out per case: runCount colours
+//     worldMin worldMax, the runs, the colours, then the three header words cvxr::ReadHeader makes with storageOffset 7.
 //   readback_rules level <blob> <lod> <dimX> <dimY> <dimZ> <columnCount> <out>
 //     Uploads the level into a context that never touches a device (cvx_world_upload lays it out on the host; an empty LOD 0 first for lod > 0)
 //     and reads the whole level back from the host copy of its tables as cvx_world_read_level assembles it: World.ColumnCount headers, the pool
@@ -15,27 +15,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_readback.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	for (int c; (c = std::fgetc(f)) != EOF;) { out.push_back((uint8_t)c); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 static int Column(const char *in, const char *outPath)
 {
@@ -45,32 +26,13 @@ static int Column(const char *in, const char *outPath)
 	std::vector<uint32_t> out;
 	while (p < end) {
 		const int lod = *p++, dimY = *p++, stride = *p++, colorsBase = *p++, worldMin = *p++, worldMax = *p++, runCount = *p++;
-		std::vector<uint32_t> elements(1, 0u);
-		for (int r = 0; r < runCount; r++) {
-			const int32_t ci = *p++, length = *p++;
-			elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-		}
-		elements.push_back(0u);
-		const int colourCount = *p++;
-		std::vector<uint32_t> slots((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u);
-		for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
+		std::vector<uint32_t> elements, slots, runs(8, 0u);
+		p = ReadCaseRuns(p, runCount, dimY, &elements);
+		p = ReadCaseColours(p, colorsBase, stride, &slots);
 		const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)worldMin << 16), (uint32_t)worldMax };
-		uint32_t x = 0, y = 0, z = 0, w = 0;
-		std::vector<uint32_t> runs(8, 0u);
-		if (runCount > 0) {
-			const cvxe::ColumnWords c = cvxe::BuildColumnWords(header, elements.data(), lod, dimY);
-			x = c.x | (uint32_t)colorsBase;
-			y = c.y;
-			z = c.z;
-			w = c.w;
-			if (c.code == 0u) {
-				z = 2u;
-				runs.resize(2u * (2u + c.solid) + 8u, 0u);
-				cvxe::BuildListedRuns(header, elements.data(), lod, dimY, runs.data() + 4);
-			}
-		}
-		const cvxb::ArenaColumn col{ x, y, z, w, runs.data() };
-		const int colorShift = stride == 1 ? 2 : 7;
+		const uint4 rec = runCount > 0 ? CaseRecord(header, elements, lod, dimY, colorsBase, &runs) : uint4{ 0u, 0u, 0u, 0u };
+		const cvxb::ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, runs.data() };
+		const int colorShift = CaseColorShift(stride);
 		const cvxr::ReadResult r = cvxr::ReadColumn(col, slots.data(), colorShift, lod, dimY, nullptr, nullptr);
 		std::vector<uint32_t> newRuns(r.runCount + 1u), newColours(r.colours + 1u);
 		const cvxr::ReadResult again = cvxr::ReadColumn(col, slots.data(), colorShift, lod, dimY, newRuns.data(), newColours.data());
@@ -93,13 +55,8 @@ static int Level(char **argv)
 	const std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int lod = std::atoi(argv[3]), dimX = std::atoi(argv[4]), dimY = std::atoi(argv[5]), dimZ = std::atoi(argv[6]), columnCount = std::atoi(argv[7]);
 	cvx_context *ctx = new cvx_context();
-	if (lod > 0) {
-		const std::vector<uint8_t> empty((size_t)dimX * dimZ * 12, 0u);
-		const int rc = cvx_world_upload(ctx, 0, empty.data(), (int64_t)empty.size(), dimX, dimY, dimZ, dimX * dimZ);
-		if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	}
-	const int rc = cvx_world_upload(ctx, lod, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
+	if (lod > 0) { UploadBlobLevel(ctx, 0, std::vector<uint8_t>((size_t)dimX * dimZ * 12, 0u), dimX, dimY, dimZ, dimX * dimZ); }
+	UploadBlobLevel(ctx, lod, blob, dimX, dimY, dimZ, columnCount);
 	const cvx_context::HostLevel &H = ctx->hostLevel[lod];
 	const int usedX = dimX >> lod, usedZ = dimZ >> lod;
 	const int64_t count = ((int64_t)dimX * dimZ) / ((int64_t)(lod + 1) * (lod + 1)); // World.ColumnCount

@@ -14,29 +14,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_settle.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t n; (n = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + n); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
-
+#include "rules_world.h"
 struct Settled {
 	std::vector<uint32_t> offsets, lohi, column, root, shift; // per column + 1; per node: lo, hi; its column; its root; its piece's drop
 	std::vector<int64_t> place;                               // per node: its piece's place in the list, -1: the piece is anchored
@@ -182,7 +161,6 @@ static const uint32_t *ColumnNodes(const Settled &R, const cvxb::PiecesBox &B, i
 
 static int World(char **argv)
 {
-	std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	int32_t boxMin[3], boxMax[3];
 	for (int a = 0; a < 3; a++) {
@@ -190,19 +168,9 @@ static int World(char **argv)
 		boxMax[a] = std::atoi(argv[10 + a]);
 	}
 	const int anchors = std::atoi(argv[13]), maxDrop = std::atoi(argv[14]), levelCount = std::atoi(argv[15]);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W.runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W.colourSlots = H.elements.data();
-	W.rowShift = H.rowShift;
-	W.colorShift = H.colorShift;
-	W.dimX = dimX;
-	W.dimY = dimY;
-	W.dimZ = dimZ;
+	const BlobWorld blob = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvx_context::HostLevel &H = *blob.H;
+	const cvxb::CopyWorld &W = blob.W;
 	cvxb::PiecesBox B;
 	if (!cvxb::PiecesClipBox(boxMin, boxMax, dimX, dimY, dimZ, &B)) { return 4; }
 	const auto t0 = std::chrono::steady_clock::now();

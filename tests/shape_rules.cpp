@@ -5,42 +5,20 @@
 //   shape_rules points <cases in> <results out>     (int64 words; strokes at the limits, where there is no grid)
 //     Per case: dimY, the stroke's ten fields, columnCount, (cx cz)*.  Out: lo hi per column.
 //   shape_rules cull <case in>                      (int32 words)
-//     dimY x0 z0 sizeX sizeZ stride strokeCount stroke* and per column of the rectangle (blob order): colorsBase runCount (colorsIndex length)*
-//     colourCount colour*.  For every strip of 64 columns the stroke list is culled as the kernels cull it (cvxb::StripBox, 64 strokes at a
-//     time through cvxb::StrokeMeetsStrip, survivors appended in order); every column then goes through cvxb::BrushColumn over the whole list
-//     and cvxb::BrushColumnOver over the strip's list.  Prints: columns strips wrappedStrips listed mismatches.
+//     dimY x0 z0 sizeX sizeZ stride strokeCount stroke* and per column of the rectangle (blob order) the column's words (tests/rules_world.h).
+//     For every strip of 64 columns the stroke list is culled as the kernels cull it (cvxb::StripBox, 64 strokes at a time through
+//     cvxb::StrokeMeetsStrip, survivors appended in order); every column then goes through cvxb::BrushColumn over the whole list and
+//     cvxb::BrushColumnOver over the strip's list.  Prints: columns strips wrappedStrips listed mismatches.
 //   shape_rules args
 //     cvx_world_brush's argument checks on a context that never touched a device: one return code per call.
+//   -DSHAPE_RULES_NO_LIBRARY (the sanitizer build) leaves `args` out: the rest calls nothing of the library, so nothing of it is linked.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "cvx_brush.h"
-#ifndef SHAPE_RULES_NO_LIBRARY // (the sanitizer build: the rules alone, nothing of the library is linked)
-#include "cvx_context.h"
-#endif
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t got; (got = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + got); }
-	std::fclose(f);
-	return out;
-}
-
-template <class T>
-static int WriteFile(const char *path, const std::vector<T> &out)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(out.data(), sizeof(T), out.size(), f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 template <class T>
 static cvx_brush_stroke Stroke(const T *p)
@@ -98,50 +76,12 @@ static int Points(const char *in, const char *outPath)
 	return WriteFile(outPath, out);
 }
 
-// One arena column from the reference's encoding, as tests/brush_rules.cpp builds it (the edit's record rule; a listed column's run-list block at entry 2)
+// One arena column of the rectangle: its record and its own run list (tests/rules_world.h); the colour slots are shared
 struct HostColumn {
-	std::vector<uint32_t> runs;
-	uint32_t x = 0, y = 0, z = 0, w = 0;
-	cvxb::ArenaColumn Column() const { return cvxb::ArenaColumn{ x, y, z, w, runs.data() }; }
+	std::vector<uint32_t> runs = std::vector<uint32_t>(8, 0u);
+	uint4 rec{ 0u, 0u, 0u, 0u };
+	cvxb::ArenaColumn Column() const { return cvxb::ArenaColumn{ rec.x, rec.y, rec.z, rec.w, runs.data() }; }
 };
-
-static const int32_t *ReadColumn(const int32_t *p, int dimY, int stride, std::vector<uint32_t> &slots, HostColumn &col)
-{
-	const int colorsBase = *p++, runCount = *p++;
-	std::vector<uint32_t> elements(1, 0u);
-	uint32_t start = 0;
-	int64_t lowest = -1, highest = -1;
-	for (int r = 0; r < runCount; r++) {
-		const int32_t ci = *p++, length = *p++;
-		elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-		if (ci >= 0) {
-			const int64_t top = (int64_t)dimY - start;
-			if (highest < 0) { highest = top; }
-			lowest = top - length;
-		}
-		start += (uint32_t)length;
-	}
-	elements.push_back(0u);
-	const int colourCount = *p++;
-	const size_t need = (size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64;
-	if (slots.size() < need) { slots.resize(need, 0u); }
-	for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
-	const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
-	col.runs.assign(8, 0u);
-	if (runCount > 0) {
-		const cvxe::ColumnWords c = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-		col.x = c.x | (uint32_t)colorsBase;
-		col.y = c.y;
-		col.z = c.z;
-		col.w = c.w;
-		if (c.code == 0u) {
-			col.z = 2u;
-			col.runs.assign(2u * (2u + c.solid) + 8u, 0u);
-			cvxe::BuildListedRuns(header, elements.data(), 0, dimY, col.runs.data() + 4);
-		}
-	}
-	return p;
-}
 
 static int Cull(const char *in)
 {
@@ -154,8 +94,8 @@ static int Cull(const char *in)
 	const int n = sizeX * sizeZ;
 	std::vector<HostColumn> columns((size_t)n);
 	std::vector<uint32_t> slots;
-	for (int i = 0; i < n; i++) { p = ReadColumn(p, dimY, stride, slots, columns[(size_t)i]); }
-	const int colorShift = stride == 1 ? 2 : 7;
+	for (HostColumn &col : columns) { p = ReadCaseColumn(p, dimY, stride, &col.runs, &slots, &col.rec); }
+	const int colorShift = CaseColorShift(stride);
 	long long strips = 0, wrapped = 0, listed = 0, mismatches = 0;
 	std::vector<uint16_t> list((size_t)strokeCount + 1);
 	std::vector<uint32_t> runsA((size_t)dimY + 2), runsB((size_t)dimY + 2), coloursA((size_t)dimY + 2), coloursB((size_t)dimY + 2);

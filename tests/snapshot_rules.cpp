@@ -2,9 +2,9 @@
 //   snapshot_rules column <cases in> <results out>
 //     Each case is a pair of columns (int32 words): dimY stride colorsBase ignoreColour, then the ARENA's column in the reference's layout --
 //     worldMin worldMax runCount (colorsIndex length)* colourCount colour* -- and the SNAPSHOT's -- runCount (colorsIndex length)* colourCount
-//     colour*.  The arena's column gets its record from the edit's record rule (cvx_edit.h; a listed column its run-list block at entry 2) and its
-//     colours at colorsBase + k * stride, as tests/readback_rules.cpp builds it; the snapshot's column becomes a blob column behind 5 other
-//     elements.  Out per case: voxels yMin yMax of cvxs::DiffColumn.
+//     colour*.  The arena's column gets its record and its colour slots as a case world's columns do (tests/rules_world.h), with the stated
+//     bounds, as tests/readback_rules.cpp builds it; the snapshot's column becomes a blob column behind 5 other elements.  Out per case: voxels
+//     yMin yMax of cvxs::DiffColumn.
 //   snapshot_rules world <arena blob> <dimX> <dimY> <dimZ> <columnCount> <snapshot blob> <x0> <z0> <sizeX> <sizeZ> <ignoreColour> <out>
 //     Uploads LOD 0 into a context that never touches a device (cvx_world_upload lays it out on the host) and compares the rectangle with the
 //     columns of the second blob, a sub-world of sizeX x sizeZ columns, as the kernels do: count, scan, write.  Out: changedColumns changedVoxels
@@ -18,28 +18,8 @@
 #include <vector>
 
 #include "cpuvox_gpu_snapshot.h"
-#include "cvx_context.h"
 #include "cvx_snapshot.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t n; (n = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + n); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 static int Column(const char *in, const char *outPath)
 {
@@ -51,31 +31,12 @@ static int Column(const char *in, const char *outPath)
 		const int dimY = *p++, stride = *p++, colorsBase = *p++, ignoreColour = *p++;
 		// the arena's column
 		const int worldMin = *p++, worldMax = *p++, runCount = *p++;
-		std::vector<uint32_t> elements(1, 0u);
-		for (int r = 0; r < runCount; r++) {
-			const int32_t ci = *p++, length = *p++;
-			elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-		}
-		elements.push_back(0u);
-		const int colourCount = *p++;
-		std::vector<uint32_t> slots((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u);
-		for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
+		std::vector<uint32_t> elements, slots, runs(8, 0u);
+		p = ReadCaseRuns(p, runCount, dimY, &elements);
+		p = ReadCaseColours(p, colorsBase, stride, &slots);
 		const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)worldMin << 16), (uint32_t)worldMax };
-		uint32_t x = 0, y = 0, z = 0, w = 0;
-		std::vector<uint32_t> runs(8, 0u);
-		if (runCount > 0) {
-			const cvxe::ColumnWords c = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-			x = c.x | (uint32_t)colorsBase;
-			y = c.y;
-			z = c.z;
-			w = c.w;
-			if (c.code == 0u) {
-				z = 2u;
-				runs.resize(2u * (2u + c.solid) + 8u, 0u);
-				cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 4);
-			}
-		}
-		const cvxb::ArenaColumn col{ x, y, z, w, runs.data() };
+		const uint4 rec = runCount > 0 ? CaseRecord(header, elements, 0, dimY, colorsBase, &runs) : uint4{ 0u, 0u, 0u, 0u };
+		const cvxb::ArenaColumn col{ rec.x, rec.y, rec.z, rec.w, runs.data() };
 		// the snapshot's column
 		const int snapRuns = *p++;
 		std::vector<uint32_t> pool(5, 0xDEADBEEFu);
@@ -88,7 +49,7 @@ static int Column(const char *in, const char *outPath)
 		const int snapColours = *p++;
 		for (int k = 0; k < snapColours; k++) { pool.push_back((uint32_t)*p++); }
 		const uint32_t snapHeader[3] = { snapRuns ? 5u : 0u, (uint32_t)snapRuns, 0u };
-		const cvxs::ColumnDiff d = cvxs::DiffColumn(col, slots.data(), stride == 1 ? 2 : 7, dimY, snapHeader, pool.data(), ignoreColour != 0);
+		const cvxs::ColumnDiff d = cvxs::DiffColumn(col, slots.data(), CaseColorShift(stride), dimY, snapHeader, pool.data(), ignoreColour != 0);
 		out.push_back(d.voxels);
 		out.push_back(d.yMin);
 		out.push_back(d.yMax);
@@ -98,14 +59,11 @@ static int Column(const char *in, const char *outPath)
 
 static int World(char **argv)
 {
-	const std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	const std::vector<uint8_t> snap = ReadFile(argv[7]);
 	const int x0 = std::atoi(argv[8]), z0 = std::atoi(argv[9]), sizeX = std::atoi(argv[10]), sizeZ = std::atoi(argv[11]), ignoreColour = std::atoi(argv[12]);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
+	const BlobWorld arena = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvx_context::HostLevel &H = *arena.H;
 	const int n = sizeX * sizeZ;
 	const uint32_t *headers = reinterpret_cast<const uint32_t *>(snap.data());
 	const uint32_t *elements = headers + 3 * (size_t)n;

@@ -14,39 +14,15 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_spread.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t got; (got = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + got); }
-	std::fclose(f);
-	return out;
-}
-
+#include "rules_world.h"
 static int64_t Gcd(int64_t a, int64_t b) { return b == 0 ? a : Gcd(b, a % b); }
 
 static int Fields(char **argv)
 {
-	const std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W.runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W.colourSlots = H.elements.data();
-	W.rowShift = H.rowShift;
-	W.colorShift = H.colorShift;
-	W.dimX = dimX;
-	W.dimY = dimY;
-	W.dimZ = dimZ;
+	const BlobWorld blob = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvxb::CopyWorld &W = blob.W;
 	const std::vector<uint8_t> queryBytes = ReadFile(argv[7]);
 	const int32_t *q = reinterpret_cast<const int32_t *>(queryBytes.data());
 	const size_t words = queryBytes.size() / 4;

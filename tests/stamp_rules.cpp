@@ -11,10 +11,9 @@
 //   stamp_rules hits <mesh in> <hits out>
 //     The same loop: int32 (triangle, x, y, z) per hit, the hits past the cap and the transparent ones included.
 //   stamp_rules stamp <cases in> <results out>
-//     Each case is one column in the reference's layout plus stamped voxels (int32 words): dimY stride colorsBase runCount (colorsIndex length)*
-//     colourCount colour* op voxelCount (y argb)*.  The column gets its record as in brush_rules; the voxels (any order, duplicates allowed) are
-//     sorted top-down and merged with cvxs::MergeStamped, then cvxs::StampColumn.  Out per case: overLimit runCount colours worldMin worldMax,
-//     then (unless over the limits) the runs and the colours.
+//     Each case is one column plus stamped voxels (int32 words): dimY stride, the column's words (tests/rules_world.h), op voxelCount
+//     (y argb)*.  The voxels (any order, duplicates allowed) are sorted top-down and merged with cvxs::MergeStamped, then cvxs::StampColumn.
+//     Out per case: the edited-column block (tests/rules_world.h).
 //   stamp_rules args
 //     The argument checks of cvx_world_stamp_mesh on a context that never touched a device (no world): one return code per call.
 #include <algorithm>
@@ -23,27 +22,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_stamp.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	for (int c; (c = std::fgetc(f)) != EOF;) { out.push_back((uint8_t)c); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const std::vector<uint32_t> &words)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(words.data(), 4, words.size(), f);
-	std::fclose(f);
-	return 0;
-}
+#include "rules_world.h"
 
 // the mesh file of the voxelise / counts / hits modes
 struct MeshFile {
@@ -140,24 +120,9 @@ static int Stamp(const char *in, const char *outPath)
 	const int32_t *end = p + bytes.size() / 4;
 	std::vector<uint32_t> out;
 	while (p < end) {
-		const int dimY = *p++, stride = *p++, colorsBase = *p++, runCount = *p++;
-		std::vector<uint32_t> elements(1, 0u);
-		uint32_t start = 0;
-		int64_t lowest = -1, highest = -1;
-		for (int r = 0; r < runCount; r++) {
-			const int32_t ci = *p++, length = *p++;
-			elements.push_back(((uint32_t)ci & 0xFFFFu) | ((uint32_t)length << 16));
-			if (ci >= 0) {
-				const int64_t top = (int64_t)dimY - start;
-				if (highest < 0) { highest = top; }
-				lowest = top - length;
-			}
-			start += (uint32_t)length;
-		}
-		elements.push_back(0u);
-		const int colourCount = *p++;
-		std::vector<uint32_t> slots((size_t)colorsBase + (size_t)stride * (colourCount + 1) + 64, 0u);
-		for (int k = 0; k < colourCount; k++) { slots[(size_t)colorsBase + (size_t)k * stride] = (uint32_t)*p++; }
+		const int dimY = *p++, stride = *p++;
+		CaseColumn C;
+		p = C.Read(p, dimY, stride);
 		const int op = *p++, voxelCount = *p++;
 		std::vector<std::pair<uint32_t, uint32_t>> voxels((size_t)voxelCount);
 		for (int v = 0; v < voxelCount; v++) {
@@ -176,37 +141,12 @@ static int Stamp(const char *in, const char *outPath)
 			argbs.push_back(cvxs::MergeStamped(group.data(), (int)group.size()));
 			i = e;
 		}
-		const uint32_t header[3] = { 0u, (uint32_t)runCount | ((uint32_t)(lowest < 0 ? 0 : lowest) << 16), (uint32_t)(highest < 0 ? 0 : highest) };
-		uint32_t x = 0, y = 0, z = 0, w = 0;
-		std::vector<uint32_t> runs(8, 0u);
-		if (runCount > 0) {
-			const cvxe::ColumnWords c = cvxe::BuildColumnWords(header, elements.data(), 0, dimY);
-			x = c.x | (uint32_t)colorsBase;
-			y = c.y;
-			z = c.z;
-			w = c.w;
-			if (c.code == 0u) {
-				z = 2u;
-				runs.resize(2u * (2u + c.solid) + 8u, 0u);
-				cvxe::BuildListedRuns(header, elements.data(), 0, dimY, runs.data() + 4);
-			}
-		}
-		const cvxb::ArenaColumn col{ x, y, z, w, runs.data() };
-		const int colorShift = stride == 1 ? 2 : 7;
+		const cvxb::ArenaColumn col = C.Column();
+		const int colorShift = CaseColorShift(stride);
 		const int m = (int)ys.size();
-		const cvxb::BrushResult r = cvxs::StampColumn(col, slots.data(), colorShift, ys.data(), argbs.data(), m, op, dimY, nullptr, nullptr);
-		out.push_back(r.overLimit ? 1u : 0u);
-		out.push_back(r.runCount);
-		out.push_back(r.colours);
-		out.push_back(r.worldMin);
-		out.push_back(r.worldMax);
-		if (!r.overLimit) {
-			std::vector<uint32_t> newRuns(r.runCount + 1u), newColours(r.colours + 1u);
-			const cvxb::BrushResult again = cvxs::StampColumn(col, slots.data(), colorShift, ys.data(), argbs.data(), m, op, dimY, newRuns.data(), newColours.data());
-			if (again.runCount != r.runCount || again.colours != r.colours) { return 3; }
-			out.insert(out.end(), newRuns.begin(), newRuns.begin() + r.runCount);
-			out.insert(out.end(), newColours.begin(), newColours.begin() + r.colours);
-		}
+		if (!AppendEditedColumn(&out, [&](uint32_t *runs, uint32_t *colours) {
+			    return cvxs::StampColumn(col, C.slots.data(), colorShift, ys.data(), argbs.data(), m, op, dimY, runs, colours);
+		    })) { return 3; }
 	}
 	return WriteFile(outPath, out);
 }

@@ -14,6 +14,7 @@ import subprocess
 
 import numpy as np
 
+import ruleslib
 from cpuvox_amd import gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,11 +22,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def rules(tmpdir) -> str:
-    out = os.path.join(str(tmpdir), "stamp_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "stamp_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("stamp_rules", tmpdir)
 
 
 def mill_obj(tmpdir) -> str:

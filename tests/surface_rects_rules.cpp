@@ -11,29 +11,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
 #include "cvx_surface_rects.h"
-
-static std::vector<uint8_t> ReadFile(const char *path)
-{
-	std::vector<uint8_t> out;
-	FILE *f = std::fopen(path, "rb");
-	if (!f) { std::exit(2); }
-	uint8_t buffer[65536];
-	for (size_t n; (n = std::fread(buffer, 1, sizeof buffer, f)) > 0;) { out.insert(out.end(), buffer, buffer + n); }
-	std::fclose(f);
-	return out;
-}
-
-static int WriteFile(const char *path, const void *data, size_t bytes)
-{
-	FILE *f = std::fopen(path, "wb");
-	if (!f) { return 2; }
-	std::fwrite(data, 1, bytes, f);
-	std::fclose(f);
-	return 0;
-}
-
+#include "rules_world.h"
 struct CountSink {
 	uint32_t strips;
 	int64_t unitFaces;
@@ -115,7 +94,6 @@ static void Walk(const cvxb::CopyWorld &W, const cvxb::PiecesBox &B, int solidOu
 
 static int World(char **argv)
 {
-	std::vector<uint8_t> blob = ReadFile(argv[2]);
 	const int dimX = std::atoi(argv[3]), dimY = std::atoi(argv[4]), dimZ = std::atoi(argv[5]), columnCount = std::atoi(argv[6]);
 	int32_t boxMin[3], boxMax[3];
 	for (int a = 0; a < 3; a++) {
@@ -123,19 +101,8 @@ static int World(char **argv)
 		boxMax[a] = std::atoi(argv[10 + a]);
 	}
 	const int solidOutside = std::atoi(argv[13]), flags = std::atoi(argv[14]);
-	cvx_context *ctx = new cvx_context();
-	const int rc = cvx_world_upload(ctx, 0, blob.data(), (int64_t)blob.size(), dimX, dimY, dimZ, columnCount);
-	if (rc != CVX_OK) { std::printf("upload failed %d: %s\n", rc, ctx->error.c_str()); return 1; }
-	const cvx_context::HostLevel &H = ctx->hostLevel[0];
-	cvxb::CopyWorld W;
-	W.records = reinterpret_cast<const uint32_t *>(H.records.data());
-	W.runs = reinterpret_cast<const uint32_t *>(H.runs.data());
-	W.colourSlots = H.elements.data();
-	W.rowShift = H.rowShift;
-	W.colorShift = H.colorShift;
-	W.dimX = dimX;
-	W.dimY = dimY;
-	W.dimZ = dimZ;
+	const BlobWorld blob = LoadBlobWorld(argv[2], dimX, dimY, dimZ, columnCount);
+	const cvxb::CopyWorld &W = blob.W;
 	cvxb::PiecesBox B;
 	if (!cvxb::PiecesClipBox(boxMin, boxMax, dimX, dimY, dimZ, &B)) { return 4; }
 	std::vector<uint8_t> out;

@@ -7,17 +7,13 @@ built with -fsanitize=address,undefined (nothing is loaded into Python), and che
 - a kept block is not released and an adopted start event is not destroyed;
 - the failure path maps hipErrorOutOfMemory to CVX_ERR_CAPACITY (or the caller's code), clears the thread's last error then and only then, and
   maps everything else to CVX_ERR_HIP."""
-import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ruleslib
 
 
 def test_device_call_ownership(tmp_path):
-    program = str(tmp_path / "device_call_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
-                           "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc", os.path.join(ROOT, "tests", "device_call_rules.cpp"),
-                           "-o", program])
+    program = ruleslib.build("device_call_rules", tmp_path, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", link_library=False)
     run = subprocess.run([program], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
     assert run.stdout.strip().endswith("0 failed")

@@ -9,11 +9,12 @@ import pytest
 import torch
 
 import movemodel
+import ruleslib
 import scenes
 from cpuvox_amd import gpu
 from test_gpu_world_edit import DIMS, _check_world, _context, _frames
 from test_world_brush_cpu import _pick_world
-from test_world_move_cpu import WORLDS, bodies_to_array, build_rules, model_results, random_body, run_world, world_bodies
+from test_world_move_cpu import WORLDS, bodies_to_array, model_results, random_body, run_world, world_bodies
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,7 @@ LANES = (0, 1, 4, 16, 64)
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    return build_rules(str(tmp_path_factory.mktemp("move") / "move_rules"))
+    return ruleslib.build("move_rules", tmp_path_factory.mktemp("move"), "-O2")
 
 
 def _device_move(ctx, bodies, lanes):

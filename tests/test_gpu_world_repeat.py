@@ -188,12 +188,9 @@ def test_negative_coordinates_wrap():
 
 def _host_picks(tmp_path, ws, rays):
     """Bounded picks with the host build of PickRay (tests/brush_rules.cpp, the harness of tests/test_world_brush_cpu.py)."""
-    import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "brush_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{root}/include", f"-I{root}/cpuvox_amd/csrc",
-                           os.path.join(root, "tests", "brush_rules.cpp"), "-o", exe, f"-L{root}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{root}/cpuvox_amd"])
+    import ruleslib
+    exe = ruleslib.build("brush_rules", tmp_path)
     blob, rays_in, hits_out = tmp_path / "blob.bin", tmp_path / "rays.bin", tmp_path / "hits.bin"
     np.array(ws.storage(0)).tofile(blob)
     rays.tofile(rays_in)

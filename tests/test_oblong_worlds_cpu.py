@@ -28,6 +28,7 @@ import lightmodel
 import oblongworlds as ob
 import pickmodel
 import piecesmodel
+import ruleslib
 import settlemodel
 import scenes
 import snapshotmodel
@@ -61,33 +62,24 @@ from test_world_spread_cpu import run_fields, same_totals
 from test_world_surface_cpu import _check_calls as check_surface
 from test_world_surface_rects_cpu import check_call as check_surface_rects
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SANITIZE = ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")
 SAN_ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime the library links keeps its own allocations to the end)
 WRITER_NAMES = sorted(ob.writer_cases(LONG_Z))
 READER_NAMES = sorted(ob.reader_cases(LONG_Z))
 
 
-def _compile(directory, name, *flags):
-    """tests/<name>.cpp as a stand-alone program of its own (its own main; nothing is loaded into Python)."""
-    out = str(directory / (name + ("_san" if flags else "")))
-    subprocess.check_call(["g++", "-std=c++17", "-O1", *flags, "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", name + ".cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
-
-
 SANITIZED = ("snapshot_rules", "spread_rules")  # (the test files of these two build them so themselves)
 
 
 class _Programs:
-    """tests/<name>_rules.cpp compiled on first use: programs["move"]."""
+    """tests/<name>_rules.cpp compiled on first use, each a stand-alone program (its own main; nothing is loaded into Python): programs["move"]."""
 
     def __init__(self, directory):
         self.directory, self.built = directory, {}
 
     def __getitem__(self, name):
         if name not in self.built:
-            self.built[name] = _compile(self.directory, name + "_rules", *(SANITIZE if name + "_rules" in SANITIZED else ()))
+            self.built[name] = ruleslib.build(name + "_rules", self.directory, *(SANITIZE if name + "_rules" in SANITIZED else ()))
         return self.built[name]
 
 

@@ -18,6 +18,7 @@ import pytest
 
 import pickmodel
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu, host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,11 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("brush") / "brush_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "brush_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("brush_rules", tmp_path_factory.mktemp("brush"))
 
 
 # ---- the brush column rule ---------------------------------------------------------------------------------------------------------------------
@@ -107,11 +104,7 @@ def _model_column(solid, dense, strokes, cx, cz, dim_y):
 
 
 def _case_words(dim_y, cx, cz, stride, base, runs, colours, strokes):
-    w = [dim_y, cx, cz, stride, base, len(runs)]
-    for ci, n in runs:
-        w += [ci, n]
-    w += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
-    w += [len(strokes)]
+    w = [dim_y, cx, cz, stride] + ruleslib.column_words(base, runs, colours) + [len(strokes)]
     for s in strokes:
         w += [s["op"], s["shape"], *s["a"], *s["b"], int(np.int32(np.uint32(s["argb"]))), 0]
     return w
@@ -121,22 +114,8 @@ def _run_brush(rules, tmp_path, cases):
     words = []
     for case in cases:
         words += _case_words(*case)
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
-    subprocess.check_call([rules, "brush", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
-    results, at = [], 0
-    for _ in cases:
-        over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
-        at += 5
-        if over:
-            results.append((True, None, None, None, None))
-            continue
-        runs = out[at:at + rc].tolist()
-        at += rc
-        colours = out[at:at + nc].tolist()
-        at += nc
-        results.append((False, runs, colours, wmin, wmax))
+    out = ruleslib.run_cases(rules, "brush", tmp_path, words)
+    results, at = ruleslib.edited_columns(out, 0, len(cases))
     assert at == len(out)
     return results
 

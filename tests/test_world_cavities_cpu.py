@@ -19,6 +19,7 @@ import pytest
 import cavitymodel
 import piecesmodel
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world, _random_column
 from test_world_pieces_cpu import pieces_rows
@@ -30,11 +31,7 @@ NOISE_DIMS = [(32, 32, 32), (16, 64, 32)]
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("cavity") / "cavity_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "cavity_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("cavity_rules", tmp_path_factory.mktemp("cavity"))
 
 
 def noise_world(dims):
@@ -82,17 +79,8 @@ def _model_case(solid, colour, box_min, box_max, open_faces, max_voxels):
 def _run_columns(rules, tmp_path, cases):
     words = []
     for dim_y, gx, gz, stride, columns, box_min, box_max, open_faces, max_voxels in cases:
-        words += [dim_y, gx, gz, stride]
-        for base, runs, colours in columns:
-            words += [base, len(runs)]
-            for ci, n in runs:
-                words += [ci, n]
-            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
-        words += list(box_min) + list(box_max) + [open_faces, max_voxels, int(np.int32(np.uint32(ARGB)))]
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
-    subprocess.check_call([rules, "columns", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+        words += ruleslib.world_words(dim_y, gx, gz, stride, columns) + list(box_min) + list(box_max) + [open_faces, max_voxels, int(np.int32(np.uint32(ARGB)))]
+    out = ruleslib.run_cases(rules, "columns", tmp_path, words)
     results, at = [], 0
     for dim_y, gx, gz, *_ in cases:
         totals = [int(v) for v in out[at:at + 6]]
@@ -102,18 +90,7 @@ def _run_columns(rules, tmp_path, cases):
             w = out[at:at + 10].astype(np.int32).tolist()
             at += 10
             rows.append((w[0:3], w[3:6], w[6:9], w[9]))
-        columns = []
-        for _ in range(gx * gz):
-            over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
-            at += 5
-            if over:
-                columns.append((True, None, None, None, None))
-                continue
-            runs = out[at:at + rc].tolist()
-            at += rc
-            colours = out[at:at + nc].tolist()
-            at += nc
-            columns.append((False, runs, colours, wmin, wmax))
+        columns, at = ruleslib.edited_columns(out, at, gx * gz)
         results.append((dict(zip(cavitymodel.SUMMARY_NAMES, totals)), rows, columns))
     assert at == len(out)
     return results

@@ -19,6 +19,7 @@ import pytest
 
 import copymodel
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world, _random_column
 
@@ -28,11 +29,7 @@ FILL, CARVE, PAINT, REPLACE = gpu.BRUSH_FILL, gpu.BRUSH_CARVE, gpu.BRUSH_PAINT, 
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("copy") / "copy_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "copy_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("copy_rules", tmp_path_factory.mktemp("copy"))
 
 
 def _placement(src_min, src_max, dst, transform=0, op=REPLACE, move=0):
@@ -78,13 +75,6 @@ def _random_placements(rng, gx, dim_y, gz):
     return out
 
 
-def _encode(runs, colours):
-    w = []
-    for ci, n in runs:
-        w += [ci, n]
-    return w, [int(np.int32(np.uint32(c))) for c in colours]
-
-
 def _model_columns(solid, colour, placements):
     """Per column (x-major): (over_limit, runs words, colours, worldMin, worldMax) of the model's result re-encoded by the builder's rule."""
     s, c = copymodel.apply_copies(solid, colour, gpu.copy_placements_array(placements))
@@ -107,30 +97,12 @@ def _run_columns(rules, tmp_path, cases):
     """cases: (dim_y, gx, gz, stride, [(colorsBase, runs, colours)] x-major, placements) -> per case, per column (over, runs, colours, wmin, wmax)."""
     words = []
     for dim_y, gx, gz, stride, columns, placements in cases:
-        words += [dim_y, gx, gz, stride]
-        for base, runs, colours in columns:
-            rw, cw = _encode(runs, colours)
-            words += [base, len(runs)] + rw + [len(cw)] + cw
         arr = gpu.copy_placements_array(placements)
-        words += [len(arr)] + np.frombuffer(arr.tobytes(), dtype=np.int32).tolist()
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
-    subprocess.check_call([rules, "columns", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+        words += ruleslib.world_words(dim_y, gx, gz, stride, columns) + [len(arr)] + np.frombuffer(arr.tobytes(), dtype=np.int32).tolist()
+    out = ruleslib.run_cases(rules, "columns", tmp_path, words)
     results, at = [], 0
     for dim_y, gx, gz, *_ in cases:
-        per = []
-        for _ in range(gx * gz):
-            over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
-            at += 5
-            if over:
-                per.append((True, None, None, None, None))
-                continue
-            runs = out[at:at + rc].tolist()
-            at += rc
-            colours = out[at:at + nc].tolist()
-            at += nc
-            per.append((False, runs, colours, wmin, wmax))
+        per, at = ruleslib.edited_columns(out, at, gx * gz)
         results.append(per)
     assert at == len(out)
     return results

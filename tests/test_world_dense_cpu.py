@@ -19,6 +19,7 @@ import pytest
 
 import densemodel
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world, _random_column
 
@@ -29,11 +30,7 @@ OPS = {"fill": FILL, "carve": CARVE, "paint": PAINT, "replace": REPLACE}
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("dense") / "dense_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "dense_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("dense_rules", tmp_path_factory.mktemp("dense"))
 
 
 def _write_words(box_min, argb, mask, op):
@@ -91,32 +88,11 @@ def _run_columns(rules, tmp_path, cases):
     colours, wmin, wmax)."""
     parts = []
     for dim_y, gx, gz, stride, columns, write in cases:
-        words = [dim_y, gx, gz, stride]
-        for base, runs, colours in columns:
-            words += [base, len(runs)]
-            for ci, n in runs:
-                words += [ci, n]
-            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
-        parts.append(np.array(words, dtype=np.int64).astype(np.int32))
-        parts.append(_write_words(*write))
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.concatenate(parts).tobytes())
-    subprocess.check_call([rules, "columns", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+        parts += [ruleslib.world_words(dim_y, gx, gz, stride, columns), _write_words(*write)]
+    out = ruleslib.run_cases(rules, "columns", tmp_path, *parts)
     results, at = [], 0
     for dim_y, gx, gz, *_ in cases:
-        per = []
-        for _ in range(gx * gz):
-            over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
-            at += 5
-            if over:
-                per.append((True, None, None, None, None))
-                continue
-            runs = out[at:at + rc].tolist()
-            at += rc
-            colours = out[at:at + nc].tolist()
-            at += nc
-            per.append((False, runs, colours, wmin, wmax))
+        per, at = ruleslib.edited_columns(out, at, gx * gz)
         results.append(per)
     assert at == len(out)
     return results

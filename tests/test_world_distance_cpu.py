@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import distancemodel
+import ruleslib
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world
 
@@ -27,11 +28,7 @@ OUTSIDES = (0, 0x04, 0x3F, 0x02)  # nothing, the ground (the default), every sid
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("distance") / "distance_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "distance_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("distance_rules", tmp_path_factory.mktemp("distance"))
 
 
 def test_constants_are_the_headers():

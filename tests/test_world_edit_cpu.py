@@ -6,7 +6,6 @@
 - cvxh_world_extract_region against tests/pyworld.py.
 - The three new entry points fail cleanly without a context / device."""
 import ctypes as C
-import os
 import struct
 import subprocess
 
@@ -14,18 +13,13 @@ import numpy as np
 import pytest
 
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu, host
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def rule_binary(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("rule") / "edit_record_rule")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "edit_record_rule.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("edit_record_rule", tmp_path_factory.mktemp("rule"))
 
 
 def _random_column(rng, height, kind, lod):

@@ -19,6 +19,7 @@ import pytest
 import lampmodel
 import lightmodel
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu
 from test_world_brush_cpu import _random_column
 from test_world_light_cpu import random_params
@@ -29,13 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
     """{"lamp": tests/lamp_rules.cpp, "light": tests/light_rules.cpp}, built for the host."""
-    out = {}
-    for name in ("lamp", "light"):
-        out[name] = str(tmp_path_factory.mktemp(name) / f"{name}_rules")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                               os.path.join(ROOT, "tests", f"{name}_rules.cpp"), "-o", out[name], f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                               f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return {name: ruleslib.build(f"{name}_rules", tmp_path_factory.mktemp(name)) for name in ("lamp", "light")}
 
 
 DIRECTIONS = {
@@ -108,33 +103,13 @@ def _model_case(solid, colour, p, lamps):
 def _run_columns(binary, tmp_path, cases, with_lamps=True):
     words = []
     for dim_y, gx, gz, stride, columns, p, lamps in cases:
-        words += [dim_y, gx, gz, stride]
-        for base, runs, colours in columns:
-            words += [base, len(runs)]
-            for ci, n in runs:
-                words += [ci, n]
-            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
-        words += lightmodel.words(p)
+        words += ruleslib.world_words(dim_y, gx, gz, stride, columns) + lightmodel.words(p)
         if with_lamps:
             words += lampmodel.words(lamps)
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
-    subprocess.check_call([binary, "columns", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+    out = ruleslib.run_cases(binary, "columns", tmp_path, words)
     results, at = [], 0
     for dim_y, gx, gz, *_ in cases:
-        columns = []
-        for _ in range(gx * gz):
-            over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
-            at += 5
-            if over:
-                columns.append((True, None, None, None, None))
-                continue
-            runs = out[at:at + rc].tolist()
-            at += rc
-            colours = out[at:at + nc].tolist()
-            at += nc
-            columns.append((False, runs, colours, wmin, wmax))
+        columns, at = ruleslib.edited_columns(out, at, gx * gz)
         results.append(columns)
     assert at == len(out)
     return results

@@ -21,19 +21,16 @@ import pytest
 
 import liftmodel
 import piecesmodel
+import ruleslib
 from cpuvox_amd import gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MOD = 1 << 64
-COMMON = ["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-          os.path.join(ROOT, "tests", "lift_rules.cpp")]
 
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("lift") / "lift_rules")
-    subprocess.check_call(COMMON + ["-O1", "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("lift_rules", tmp_path_factory.mktemp("lift"))
 
 
 def run(program, mode, tmp_path, words, in_dtype, out_dtype, env=None):
@@ -235,8 +232,7 @@ def test_a_single_voxel_has_its_centre_in_the_middle_and_a_third_on_the_diagonal
 def test_the_rules_are_clean_under_the_address_and_undefined_behaviour_sanitizers(tmp_path):
     """The same stand-alone program (its own main; nothing is loaded into Python, nothing of the library is linked) built with
     -fsanitize=address,undefined: every check above runs to the end with the same results."""
-    program = str(tmp_path / "lift_rules_san")
-    subprocess.check_call(COMMON + ["-O1", "-g", "-DLIFT_RULES_NO_LIBRARY", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", program])
+    program = ruleslib.build("lift_rules", tmp_path, "-g", "-DLIFT_RULES_NO_LIBRARY", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", link_library=False)
     check_node_sums(program, tmp_path)
     check_sums_wrap(program, tmp_path)
     check_plan(program, tmp_path)

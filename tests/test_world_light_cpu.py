@@ -20,6 +20,7 @@ import pytest
 
 import lightmodel
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world, _random_column
 
@@ -29,11 +30,7 @@ RGB, ALPHA = gpu.LIGHT_TO_RGB, gpu.LIGHT_TO_ALPHA
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("light") / "light_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "light_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("light_rules", tmp_path_factory.mktemp("light"))
 
 
 def random_params(rng, dims, whole=0.3):
@@ -88,31 +85,11 @@ def _model_case(solid, colour, p):
 def _run_columns(rules, tmp_path, cases):
     words = []
     for dim_y, gx, gz, stride, columns, p in cases:
-        words += [dim_y, gx, gz, stride]
-        for base, runs, colours in columns:
-            words += [base, len(runs)]
-            for ci, n in runs:
-                words += [ci, n]
-            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
-        words += lightmodel.words(p)
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
-    subprocess.check_call([rules, "columns", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+        words += ruleslib.world_words(dim_y, gx, gz, stride, columns) + lightmodel.words(p)
+    out = ruleslib.run_cases(rules, "columns", tmp_path, words)
     results, at = [], 0
     for dim_y, gx, gz, *_ in cases:
-        columns = []
-        for _ in range(gx * gz):
-            over, rc, nc, wmin, wmax = [int(v) for v in out[at:at + 5]]
-            at += 5
-            if over:
-                columns.append((True, None, None, None, None))
-                continue
-            runs = out[at:at + rc].tolist()
-            at += rc
-            colours = out[at:at + nc].tolist()
-            at += nc
-            columns.append((False, runs, colours, wmin, wmax))
+        columns, at = ruleslib.edited_columns(out, at, gx * gz)
         results.append(columns)
     assert at == len(out)
     return results

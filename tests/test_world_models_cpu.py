@@ -20,6 +20,7 @@ import pytest
 import copymodel
 import densemodel
 import modelsmodel
+import ruleslib
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world
 from test_world_dense_cpu import FILL, CARVE, PAINT, REPLACE, _builder_column, _compare, random_dense
@@ -32,11 +33,7 @@ ONE = 65536
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("models") / "models_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "models_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("models_rules", tmp_path_factory.mktemp("models"))
 
 
 # ---- building calls (the GPU test uses these too) -----------------------------------------------------------------------------------------------
@@ -336,17 +333,8 @@ def test_rule_rejects_what_the_format_cannot_hold(rules, tmp_path):
         cases.append((height, [(32, runs, colours)], [inst]))
     parts = []
     for dim_y, columns, insts in cases:
-        words = [dim_y, 1, 1, 1]
-        for base, rr, cc in columns:
-            words += [base, len(rr)]
-            for ci, n in rr:
-                words += [ci, n]
-            words += [len(cc)] + [int(np.int32(np.uint32(v))) for v in cc]
-        parts += [np.array(words, dtype=np.int64).astype(np.int32), call_words([model], insts)]
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.concatenate(parts).tobytes())
-    subprocess.check_call([rules, "columns", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=np.uint32)
+        parts += [ruleslib.world_words(dim_y, 1, 1, 1, columns), call_words([model], insts)]
+    out = ruleslib.run_cases(rules, "columns", tmp_path, *parts)
     assert out[0] == 1, "a run of 32769 voxels is over the limit"
     over, rc, nc, wmin, wmax = [int(v) for v in out[5:10]]
     results = [[(True, None, None, None, None)], [(bool(over), out[10:10 + rc].tolist(), out[10 + rc:10 + rc + nc].tolist(), wmin, wmax)]]

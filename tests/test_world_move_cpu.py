@@ -18,6 +18,7 @@ import pytest
 
 import movemodel
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu
 from movemodel import RESTING, STARTS_SOLID, STEPPED, UNIT
 from test_world_brush_cpu import _pick_world, _random_column
@@ -27,17 +28,9 @@ U = UNIT
 MINUS_X, PLUS_X, MINUS_Y, PLUS_Y, MINUS_Z, PLUS_Z = 1, 2, 4, 8, 16, 32
 
 
-def build_rules(out):
-    """tests/move_rules.cpp compiled for the host (the GPU test and tools/move_bench.py build it too)."""
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "move_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
-
-
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    return build_rules(str(tmp_path_factory.mktemp("move") / "move_rules"))
+    return ruleslib.build("move_rules", tmp_path_factory.mktemp("move"), "-O2")  # (the GPU test and tools/move_bench.py build it so too)
 
 
 # ---- random bodies ---------------------------------------------------------------------------------------------------------------------------------
@@ -117,19 +110,10 @@ def _run_cases(rules, tmp_path, cases):
     """cases: (dim_y, gx, gz, stride, columns [(base, runs, colours)], repeat, bodies) -> a MOVE_RESULT_DTYPE array per case"""
     words = []
     for dim_y, gx, gz, stride, columns, repeat, bodies in cases:
-        words += [dim_y, gx, gz, stride]
-        for base, runs, colours in columns:
-            words += [base, len(runs)]
-            for ci, n in runs:
-                words += [ci, n]
-            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
-        words += [int(repeat), len(bodies)]
+        words += ruleslib.world_words(dim_y, gx, gz, stride, columns) + [int(repeat), len(bodies)]
         for b in bodies:
             words += body_words(b)
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
-    subprocess.check_call([rules, "cases", str(src), str(dst)])
-    out = np.frombuffer(dst.read_bytes(), dtype=gpu.MOVE_RESULT_DTYPE)
+    out = ruleslib.run_cases(rules, "cases", tmp_path, words, dtype=gpu.MOVE_RESULT_DTYPE)
     assert len(out) == sum(len(c[6]) for c in cases)
     results, at = [], 0
     for c in cases:

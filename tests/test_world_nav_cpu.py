@@ -22,6 +22,7 @@ import pytest
 import limitworlds as LW
 import movemodel
 import navmodel
+import ruleslib
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world
 
@@ -33,11 +34,7 @@ RULES = [(h, s, m) for h in (1, 2, 5) for s, m in ((0, 0), (1, 3), (h, 4096))]
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("nav") / "nav_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "nav_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("nav_rules", tmp_path_factory.mktemp("nav"))
 
 
 def nav_noise_world(dims, density):

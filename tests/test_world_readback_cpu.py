@@ -10,7 +10,6 @@ through tests/readback_rules.cpp.
   byte-identical to the uploaded blobs at every level, both colour layouts.
 - The new calls without a context / world: bad arguments first, then CVX_ERR_NOT_READY."""
 import ctypes as C
-import os
 import struct
 import subprocess
 
@@ -18,18 +17,13 @@ import numpy as np
 import pytest
 
 import pyworld
+import ruleslib
 from cpuvox_amd import gpu, host
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("readback") / "readback_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "readback_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("readback_rules", tmp_path_factory.mktemp("readback"))
 
 
 # ---- the column rule ---------------------------------------------------------------------------------------------------------------------------

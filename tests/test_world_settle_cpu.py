@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import piecesmodel
+import ruleslib
 import settlemodel
 from cpuvox_amd import gpu, host
 from test_world_brush_cpu import _pick_world
@@ -27,11 +28,7 @@ SUMMARY_NAMES = ("floatingPieces", "floatingVoxels", "fallenPieces", "fallenVoxe
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("settle") / "settle_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "settle_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("settle_rules", tmp_path_factory.mktemp("settle"))
 
 
 def settle_rectangle(pieces, drops, dims, level_count):

@@ -13,21 +13,18 @@ import subprocess
 import numpy as np
 import pytest
 
+import ruleslib
 import shapemodel
 from cpuvox_amd import gpu
 from test_world_brush_cpu import _random_column
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAPSULE, ELLIPSOID, SPHERE, BOX = gpu.SHAPE_CAPSULE, gpu.SHAPE_ELLIPSOID, gpu.SHAPE_SPHERE, gpu.SHAPE_BOX
-COMMON = ["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-          os.path.join(ROOT, "tests", "shape_rules.cpp")]
 
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("shapes") / "shape_rules")
-    subprocess.check_call(COMMON + ["-O1", "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("shape_rules", tmp_path_factory.mktemp("shapes"))
 
 
 def _capsule(a, b, r, op=0, argb=0):
@@ -228,8 +225,7 @@ def test_spans_at_the_limits_match_the_integer_predicates(rules, tmp_path):
 def test_the_limits_under_ubsan_and_asan(tmp_path):
     """The same program built a second time with the sanitizers and run stand-alone on the limits: a signed overflow at the documented limits
     (or a read out of bounds) ends it with an error."""
-    program = str(tmp_path / "shape_rules_san")
-    subprocess.check_call(COMMON + ["-O1", "-g", "-DSHAPE_RULES_NO_LIBRARY", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-o", program])
+    program = ruleslib.build("shape_rules", tmp_path, "-g", "-DSHAPE_RULES_NO_LIBRARY", "-fsanitize=undefined,address", "-fno-sanitize-recover=all", link_library=False)
     cases = _limit_cases(np.random.default_rng(8191))
     got = _run_points(program, tmp_path, cases)
     assert _check_points(cases, got) > 2000
@@ -267,10 +263,7 @@ def test_the_culled_walk_equals_the_whole_list(rules, tmp_path, size_x, size_z, 
     base = 32
     for _ in range(size_x * size_z):
         runs, colours, _, _ = _random_column(rng, dim_y)
-        words += [base, len(runs)]
-        for ci, n in runs:
-            words += [ci, n]
-        words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
+        words += ruleslib.column_words(base, runs, colours)
         base += stride * (len(colours) + 1)
     src = tmp_path / "cull.bin"
     src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import piecesmodel
+import ruleslib
 import snapshotmodel
 from cpuvox_amd import gpu
 from test_gpu_world_brush import _box, _brushed, _sphere
@@ -31,15 +32,9 @@ FILL, CARVE, PAINT = gpu.BRUSH_FILL, gpu.BRUSH_CARVE, gpu.BRUSH_PAINT
 ENCODINGS = ("builder", "split solid run", "split air run", "shared colours")
 
 
-def _compile(out, *flags):
-    subprocess.check_call(["g++", "-std=c++17", "-O1", *flags, "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "snapshot_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
-
-
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    return _compile(str(tmp_path_factory.mktemp("snapshot") / "snapshot_rules"))
+    return ruleslib.build("snapshot_rules", tmp_path_factory.mktemp("snapshot"))
 
 
 # ---- columns: dense (solid[Y], colour[Y], y upward) <-> runs from the top ------------------------------------------------------------------------
@@ -317,7 +312,7 @@ def test_worlds_against_the_model_list_order_and_summary(rules, tmp_path, sparse
 def test_the_rules_are_clean_under_the_address_and_undefined_behaviour_sanitizers(tmp_path):
     """The same stand-alone program (its own main; nothing is loaded into Python) built with -fsanitize=address,undefined: the hand-made pairs,
     a world and the argument checks run to the end with the same results."""
-    out = _compile(str(tmp_path / "snapshot_rules_san"), "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")
+    out = ruleslib.build("snapshot_rules", tmp_path, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime the library links keeps its own allocations to the end)
     check_hand_made_pairs(out, tmp_path, env)
     check_worlds(out, tmp_path, False, env)

@@ -17,6 +17,7 @@ import time
 import numpy as np
 import pytest
 
+import ruleslib
 import spreadmodel
 from cpuvox_amd import gpu, host
 
@@ -29,11 +30,7 @@ TOTALS = ("passable", "reached", "largestDistance", "seedsUsed")
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("spread") / "spread_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "spread_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("spread_rules", tmp_path_factory.mktemp("spread"))
 
 
 # ---- worlds the GPU tests share ------------------------------------------------------------------------------------------------------------------
@@ -197,10 +194,7 @@ def test_the_serpentine_needs_unsigned_sixteen_bits(rules, tmp_path):
 def test_the_rules_are_clean_under_the_address_and_undefined_behaviour_sanitizers(tmp_path):
     """The same stand-alone program (its own main; nothing is loaded into Python) built with -fsanitize=address,undefined: the argument checks and
     a small field in both orders run to the end, and the field is still the model's."""
-    out = str(tmp_path / "spread_rules_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
-                           "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc", os.path.join(ROOT, "tests", "spread_rules.cpp"), "-o", out,
-                           f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
+    out = ruleslib.build("spread_rules", tmp_path, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")  # (the HIP runtime the library links keeps its own allocations to the end)
     assert len(subprocess.check_output([out, "args"], text=True, env=env).splitlines()) == 28
     solid = noise_world(5, (16, 128, 16), 0.4)

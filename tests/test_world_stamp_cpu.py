@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import pyworld
+import ruleslib
 import stampmodel
 from cpuvox_amd import gpu, host
 
@@ -227,10 +228,7 @@ def test_stamp_column_rule_against_a_dense_model(work, tmp_path):
         vc = rng.integers(0, 2**32, size=len(ys), dtype=np.uint64).astype(np.uint32)
         stride = int(rng.choice([1, 32]))
         base = int(rng.integers(1, 50))  # (colorsBase 0 is never a column's: the arena starts with a line of zeros)
-        words = [dim_y, stride, base, len(runs)]
-        for ci, n in runs:
-            words += [ci, n]
-        words += [len(colours)] + [int(c) for c in colours] + [op, len(ys)]
+        words = [dim_y, stride] + ruleslib.column_words(base, runs, colours) + [op, len(ys)]
         for y, c in zip(ys, vc):
             words += [int(y), int(c)]
         cases.append(struct.pack(f"<{len(words)}I", *[w & 0xFFFFFFFF for w in words]))

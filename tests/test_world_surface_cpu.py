@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import piecesmodel
+import ruleslib
 import surfacemodel
 from cpuvox_amd import gpu
 from test_world_brush_cpu import _pick_world, _random_column
@@ -30,11 +31,7 @@ IGNORE = surfacemodel.IGNORE_COLOUR
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("surface") / "surface_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "surface_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("surface_rules", tmp_path_factory.mktemp("surface"))
 
 
 def random_call(rng, dims):
@@ -64,17 +61,8 @@ def parse(raw, count=None):
 def _run_columns(rules, tmp_path, cases):
     words = []
     for dim_y, gx, gz, stride, columns, box_min, box_max, solid_outside, flags in cases:
-        words += [dim_y, gx, gz, stride]
-        for base, runs, colours in columns:
-            words += [base, len(runs)]
-            for ci, n in runs:
-                words += [ci, n]
-            words += [len(colours)] + [int(np.int32(np.uint32(c))) for c in colours]
-        words += list(box_min) + list(box_max) + [solid_outside, flags]
-    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
-    src.write_bytes(np.array(words, dtype=np.int64).astype(np.int32).tobytes())
-    subprocess.check_call([rules, "columns", str(src), str(dst)])
-    return parse(dst.read_bytes(), len(cases))
+        words += ruleslib.world_words(dim_y, gx, gz, stride, columns) + list(box_min) + list(box_max) + [solid_outside, flags]
+    return parse(ruleslib.run_cases(rules, "columns", tmp_path, words, dtype=np.uint8).tobytes(), len(cases))
 
 
 def _fold(c):

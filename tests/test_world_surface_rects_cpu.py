@@ -18,6 +18,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import ruleslib
 import surfacemodel
 import surfacerectsmodel as model
 from cpuvox_amd import gpu, host
@@ -30,11 +31,7 @@ SLAB = ((10, 5, 3), (140, 8, 73))  # solid x 10..139, y 5..7, z 3..72
 
 @pytest.fixture(scope="module")
 def rules(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("surface_rects") / "surface_rects_rules")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", "surface_rects_rules.cpp"), "-o", out, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu",
-                           f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
-    return out
+    return ruleslib.build("surface_rects_rules", tmp_path_factory.mktemp("surface_rects"))
 
 
 def built_world(dims, solid, colour):

@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import scenes  # noqa: E402
+import ruleslib  # noqa: E402
 from cpuvox_amd import gpu, host  # noqa: E402
 
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
@@ -25,9 +26,7 @@ repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 OPEN = gpu.CAVITY_OPEN_DEFAULT
 ARGB = 0xFF808080
 work = tempfile.mkdtemp(prefix="cavity_bench")
-rules = os.path.join(work, "cavity_rules")
-subprocess.check_call(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                       os.path.join(ROOT, "tests", "cavity_rules.cpp"), "-o", rules, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
+rules = ruleslib.build("cavity_rules", work, "-O2")
 
 
 def bench(name, ws):

@@ -26,6 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import scenes  # noqa: E402
+import ruleslib  # noqa: E402
 from cpuvox_amd import gpu, host  # noqa: E402
 
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
@@ -33,10 +34,7 @@ repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 VARIANT = os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_lightrec.so")
 LIGHT = dict(sun_dir=(3, 5, 2), sun_level=140, sun_range=256, sky_level=90, sky_range=6, floor_level=25, target=gpu.LIGHT_TO_ALPHA)
 work = tempfile.mkdtemp(prefix="light_bench")
-rules, lamp_rules = os.path.join(work, "light_rules"), os.path.join(work, "lamp_rules")
-for source, binary in (("light_rules.cpp", rules), ("lamp_rules.cpp", lamp_rules)):
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                           os.path.join(ROOT, "tests", source), "-o", binary, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
+rules, lamp_rules = ruleslib.build("light_rules", work, "-O2"), ruleslib.build("lamp_rules", work, "-O2")
 
 
 def device(ws, boxes, library):

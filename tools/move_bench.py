@@ -22,7 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from cpuvox_amd import gpu, host  # noqa: E402
-from test_world_move_cpu import build_rules, run_world  # noqa: E402
+import ruleslib  # noqa: E402
+from test_world_move_cpu import run_world  # noqa: E402
 
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -30,7 +31,7 @@ U = gpu.MOVE_UNIT
 LANES = (1, 4, 16, 64)
 WORKLOADS = {"debris": (65536, (U, U, U)), "players": (4096, (154, 461, 154)), "boxes": (256, (16 * U, 4 * U, 16 * U))}
 work = tempfile.mkdtemp(prefix="move_bench")
-rules = build_rules(os.path.join(work, "move_rules"))
+rules = ruleslib.build("move_rules", work, "-O2")
 
 
 def picked(bodies):

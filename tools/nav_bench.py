@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
+import ruleslib  # noqa: E402
 from cpuvox_amd import gpu, host  # noqa: E402
 
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
@@ -24,9 +25,7 @@ repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "nav.md")
 QUERIES = 65536
 work = tempfile.mkdtemp(prefix="nav_bench")
-rules = os.path.join(work, "nav_rules")
-subprocess.check_call(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT}/include", f"-I{ROOT}/cpuvox_amd/csrc",
-                       os.path.join(ROOT, "tests", "nav_rules.cpp"), "-o", rules, f"-L{ROOT}/cpuvox_amd", "-lcpuvox_gpu", f"-Wl,-rpath,{ROOT}/cpuvox_amd"])
+rules = ruleslib.build("nav_rules", work, "-O2")
 
 
 def timed(call):
