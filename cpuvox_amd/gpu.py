@@ -23,7 +23,9 @@ DRAW_SYNC = 0
 DRAW_ASYNC = 1
 LATENCY_AUTO, LATENCY_NEVER, LATENCY_ALWAYS = 0, 1, 2  # cvx_set_latency_kernel
 
-# every symbol include/cpuvox_gpu.h declares (checked by tests/test_abi.py)
+# The export lists, one per header under include/ that declares cvx_ entry points, and ABI_HEADERS, the table of them.
+# tests/test_abi_mirrors.py checks every list against its header, the libraries, the C# file and the argtypes of _bind.
+# include/cpuvox_gpu.h: the list its hosts were built against
 EXPORTS = [
     "cvx_create", "cvx_destroy", "cvx_last_error", "cvx_set_stream", "cvx_world_upload", "cvx_set_resolution",
     "cvx_set_buffer_count", "cvx_draw_segments", "cvx_draw_segments_batch", "cvx_set_shard", "cvx_set_latency_kernel", "cvx_set_world_repeat", "cvx_synchronize",
@@ -44,23 +46,34 @@ EXPORTS = [
     "cvx_image_plan_create", "cvx_image_plan_destroy", "cvx_image_plan_tile_count", "cvx_image_plan_sizes", "cvx_image_plan_transfer",
     "cvx_image_plan_tile_out", "cvx_image_pack", "cvx_image_exchange", "cvx_image_unpack",
 ]
-# include/cpuvox_gpu_heights.h: terrain as height maps, exported by every build (checked by tests/test_world_heights_cpu.py)
+# include/cpuvox_gpu_heights.h: terrain as height maps
 HEIGHTS_EXPORTS = ["cvx_world_read_heights", "cvx_world_read_heights_device", "cvx_world_write_heights", "cvx_world_write_heights_device"]
-# include/cpuvox_gpu_models.h: voxel models at any orientation and scale, exported by every build (checked by tests/test_world_models_cpu.py)
+# include/cpuvox_gpu_models.h: voxel models at any orientation and scale
 MODELS_EXPORTS = ["cvx_world_place_models", "cvx_world_place_models_device", "cvx_world_read_model", "cvx_world_read_model_device",
                   "cvx_model_instance_from_matrix"]
-# include/cpuvox_gpu_spread.h: travel-distance fields through air or solid, exported by every build (checked by tests/test_world_spread_cpu.py)
+# include/cpuvox_gpu_spread.h: travel-distance fields through air or solid
 SPREAD_EXPORTS = ["cvx_world_spread", "cvx_world_spread_device"]
-# include/cpuvox_gpu_surface_rects.h: the exposed faces merged into rectangles, exported by every build (checked by tests/test_world_surface_rects_cpu.py)
+# include/cpuvox_gpu_surface_rects.h: the exposed faces merged into rectangles
 SURFACE_RECTS_EXPORTS = ["cvx_world_surface_rects", "cvx_world_surface_rects_device", "cvx_surface_rect_triangles"]
-# include/cpuvox_gpu_snapshot.h: snapshots of rectangles that stay on the device, exported by every build (checked by tests/test_world_snapshot_cpu.py)
+# include/cpuvox_gpu_snapshot.h: snapshots of rectangles that stay on the device
 SNAPSHOT_EXPORTS = ["cvx_world_snapshot", "cvx_snapshot_info_get", "cvx_world_snapshot_restore", "cvx_world_snapshot_diff", "cvx_world_snapshot_diff_device",
                     "cvx_snapshot_destroy"]
-# include/cpuvox_gpu_lift.h: the floating pieces as models with mass moments, exported by every build (checked by tests/test_world_lift_cpu.py)
+# include/cpuvox_gpu_lift.h: the floating pieces as models with mass moments
 LIFT_EXPORTS = ["cvx_world_lift_pieces", "cvx_world_lift_pieces_device", "cvx_lifted_piece_mass"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
+# (header, its export list, its file under host/csharp/ or None), in the order the headers came; every build exports all but the last list
+ABI_HEADERS = [
+    ("cpuvox_gpu.h", EXPORTS, "CpuVoxGpu.cs"),
+    ("cpuvox_gpu_heights.h", HEIGHTS_EXPORTS, "CpuVoxGpuHeights.cs"),
+    ("cpuvox_gpu_models.h", MODELS_EXPORTS, "CpuVoxGpuModels.cs"),
+    ("cpuvox_gpu_spread.h", SPREAD_EXPORTS, "CpuVoxGpuSpread.cs"),
+    ("cpuvox_gpu_surface_rects.h", SURFACE_RECTS_EXPORTS, "CpuVoxGpuSurfaceRects.cs"),
+    ("cpuvox_gpu_snapshot.h", SNAPSHOT_EXPORTS, "CpuVoxGpuSnapshot.cs"),
+    ("cpuvox_gpu_lift.h", LIFT_EXPORTS, "CpuVoxGpuLift.cs"),
+    ("cpuvox_gpu_diag.h", DIAG_EXPORTS, None),
+]
 # cvx_debug_last_launch: out[0], the kernel instance a draw went to
 INSTANCE_COUNTING, INSTANCE_BATCH, INSTANCE_LONE, INSTANCE_LONE_WIDE = 0, 1, 2, 3
 LAUNCH_FIELDS = ("instance", "tiles", "waves", "min_rays", "max_rays", "max_dup_shift", "split", "lds_words")
@@ -249,32 +262,21 @@ class _TextureStruct(C.Structure):  # cvx_mesh_texture
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgba", C.c_void_p)]
 
 
-# numpy views of the same layouts
-STROKE_DTYPE = np.dtype([("op", "<i4"), ("shape", "<i4"), ("a", "<i4", 3), ("b", "<i4", 3), ("argb", "<u4"), ("pad_", "<i4")])
-PICK_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("maxT", "<f4"), ("pad_", "<f4")])
-PICK_HIT_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("argb", "<u4"), ("t", "<f4")])
-MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex
+# numpy views of the same layouts: one declaration each, the structure's
+STROKE_DTYPE, PICK_RAY_DTYPE, PICK_HIT_DTYPE = np.dtype(BrushStroke), np.dtype(PickRay), np.dtype(PickHit)
+COPY_PLACEMENT_DTYPE = np.dtype(CopyPlacement)
+PIECE_DTYPE, PIECES_SUMMARY_DTYPE = np.dtype(Piece), np.dtype(PiecesSummary)
+LIFTED_PIECE_DTYPE = np.dtype(LiftedPiece)
+SETTLE_SUMMARY_DTYPE = np.dtype(SettleSummary)
+CAVITIES_SUMMARY_DTYPE = np.dtype(CavitiesSummary)
+MOVE_BODY_DTYPE, MOVE_RESULT_DTYPE = np.dtype(MoveBody), np.dtype(MoveResult)
+NAV_STEP_DTYPE, NAV_SUMMARY_DTYPE = np.dtype(NavStep), np.dtype(NavSummary)
+SPREAD_SEED_DTYPE, SPREAD_SUMMARY_DTYPE = np.dtype(SpreadSeed), np.dtype(SpreadSummary)
+SNAPSHOT_CHANGE_DTYPE = np.dtype(SnapshotChange)
+SURFACE_QUAD_DTYPE, SURFACE_SUMMARY_DTYPE = np.dtype(SurfaceQuad), np.dtype(SurfaceSummary)
+SURFACE_RECT_DTYPE, SURFACE_RECTS_SUMMARY_DTYPE = np.dtype(SurfaceRect), np.dtype(SurfaceRectsSummary)
+MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
-COPY_PLACEMENT_DTYPE = np.dtype([("srcMin", "<i4", 3), ("srcMax", "<i4", 3), ("dst", "<i4", 3), ("transform", "<i4"), ("op", "<i4"),
-                                 ("move", "<i4")])  # cvx_copy_placement
-PIECE_DTYPE = np.dtype([("min", "<i4", 3), ("max", "<i4", 3), ("seed", "<i4", 3), ("pad_", "<i4"), ("voxels", "<i8")])  # cvx_piece
-PIECES_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("anchoredPieces", "<i8"), ("anchoredVoxels", "<i8")])
-SETTLE_SUMMARY_DTYPE = np.dtype([("floatingPieces", "<i8"), ("floatingVoxels", "<i8"), ("fallenPieces", "<i8"), ("fallenVoxels", "<i8"),
-                                 ("largestDrop", "<i4"), ("pad_", "<i4")])  # cvx_settle_summary
-CAVITIES_SUMMARY_DTYPE = np.dtype([("enclosedCavities", "<i8"), ("enclosedVoxels", "<i8"), ("selectedCavities", "<i8"), ("selectedVoxels", "<i8"),
-                                   ("openRegions", "<i8"), ("openVoxels", "<i8")])  # cvx_cavities_summary
-MOVE_BODY_DTYPE = np.dtype([("pos", "<i4", 3), ("size", "<i4", 3), ("delta", "<i4", 3), ("stepUp", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])  # cvx_move_body
-MOVE_RESULT_DTYPE = np.dtype([("pos", "<i4", 3), ("flags", "<i4")])  # cvx_move_result
-NAV_STEP_DTYPE = np.dtype([("cell", "<i4", 3), ("distance", "<i4"), ("next", "<i4", 3), ("direction", "<i4")])  # cvx_nav_step
-NAV_SUMMARY_DTYPE = np.dtype([("nodes", "<i8"), ("reached", "<i8"), ("goalsResolved", "<i4"), ("largestDistance", "<i4"),
-                              ("columnsWithSeveralNodes", "<i8"), ("launches", "<i4"), ("pad_", "<i4")])  # cvx_nav_summary
-SPREAD_SEED_DTYPE = np.dtype([("voxel", "<i4", 3), ("start", "<i4")])  # cvx_spread_seed
-SPREAD_SUMMARY_DTYPE = np.dtype([("passable", "<i8"), ("reached", "<i8"), ("largestDistance", "<i4"), ("seedsUsed", "<i4"), ("launches", "<i4"),
-                                 ("pad_", "<i4"), ("tileVisits", "<i8")])  # cvx_spread_summary
-SNAPSHOT_CHANGE_DTYPE = np.dtype([("x", "<i4"), ("z", "<i4"), ("yMin", "<i4"), ("yMax", "<i4")])  # cvx_snapshot_change
-LIFTED_PIECE_DTYPE = np.dtype([("piece", PIECE_DTYPE), ("offset", "<i8"), ("sum", "<u8", 3), ("moment", "<u8", 6)])  # cvx_lifted_piece
-SURFACE_QUAD_DTYPE = np.dtype([("voxel", "<i4", 3), ("face", "<i4"), ("length", "<i4"), ("argb", "<u4")])  # cvx_surface_quad
-SURFACE_SUMMARY_DTYPE = np.dtype([("quads", "<i8"), ("unitFaces", "<i8"), ("quadsPerFace", "<i8", 6)])  # cvx_surface_summary
 
 
 def surface_triangles(quads):
@@ -287,10 +289,6 @@ def surface_triangles(quads):
     if rc != 0:
         raise CvxError(f"cvx error {rc}: {lib().cvx_last_error(None).decode()}")
     return vertices, indices
-
-
-SURFACE_RECT_DTYPE = np.dtype([("voxel", "<i4", 3), ("size", "<i4", 3), ("face", "<i4"), ("argb", "<u4")])  # cvx_surface_rect
-SURFACE_RECTS_SUMMARY_DTYPE = np.dtype([("rects", "<i8"), ("strips", "<i8"), ("unitFaces", "<i8"), ("rectsPerFace", "<i8", 6)])  # cvx_surface_rects_summary
 
 
 def surface_rect_triangles(rects):
@@ -484,143 +482,142 @@ def use_library(path: str | None) -> None:
 
 
 def _bind(path: str) -> C.CDLL:
-    if True:
-        if not os.path.exists(path):
-            raise RuntimeError(f"{path} missing: the HIP extension is required (build with `make -C cpuvox_amd/csrc`); there is no CPU fallback")
-        _load_torch_hip_runtime_first()
-        L = C.CDLL(path)
-        L.cvx_version.restype = C.c_char_p
-        L.cvx_last_error.restype = C.c_char_p
-        L.cvx_last_error.argtypes = [C.c_void_p]
-        L.cvx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.cvx_destroy.argtypes = [C.c_void_p]
-        L.cvx_destroy.restype = None
-        L.cvx_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.cvx_world_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.cvx_set_resolution.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.cvx_set_buffer_count.argtypes = [C.c_void_p, C.c_int]
-        L.cvx_draw_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
-        L.cvx_draw_segments_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
-        L.cvx_draw_segments_placed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
-        L.cvx_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.cvx_set_latency_kernel.argtypes = [C.c_void_p, C.c_int]
-        L.cvx_set_world_repeat.argtypes = [C.c_void_p, C.c_int]
-        L.cvx_synchronize.argtypes = [C.c_void_p]
-        L.cvx_clear_raybuffer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
-        L.cvx_read_raybuffer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.cvx_blit_segments.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.cvx_blit_segments_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-        L.cvx_raybuffer_device_ptr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-        L.cvx_screen_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-        L.cvx_last_draw_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_draw_time_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
-        L.cvx_enable_counters.argtypes = [C.c_void_p, C.c_int]
-        L.cvx_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
-        L.cvx_get_raybuffer_layout.argtypes = [C.c_void_p, C.c_int, C.POINTER(RaybufferLayout)]
-        L.cvx_bind_raybuffers.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-        L.cvx_copy_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
-        if hasattr(L, "cvx_selftest_math"):  # a diagnostics build (include/cpuvox_gpu_diag.h)
-            L.cvx_debug_section_cycles.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
-            L.cvx_debug_section_histogram.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
-            L.cvx_debug_occupancy.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int)]
-            L.cvx_debug_last_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-            L.cvx_debug_settle.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
-            L.cvx_debug_cavities.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
-            L.cvx_selftest_math.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.cvx_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
-            L.cvx_selftest_lone.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_world_downsample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
-        L.cvx_world_build_lods.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
-        L.cvx_free.argtypes = [C.c_void_p]
-        L.cvx_world_set_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int]
-        L.cvx_world_edit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.cvx_world_edit_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.cvx_world_brush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.cvx_world_pick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.cvx_world_pick_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_world_read_region.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                                            C.POINTER(C.c_int32)]
-        L.cvx_world_read_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.cvx_world_compact.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
-        L.cvx_world_stamp_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                           C.POINTER(C.c_float)]
-        L.cvx_world_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.cvx_world_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_settle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} missing: the HIP extension is required (build with `make -C cpuvox_amd/csrc`); there is no CPU fallback")
+    _load_torch_hip_runtime_first()
+    L = C.CDLL(path)
+    L.cvx_version.restype = C.c_char_p
+    L.cvx_last_error.restype = C.c_char_p
+    L.cvx_last_error.argtypes = [C.c_void_p]
+    L.cvx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.cvx_destroy.argtypes = [C.c_void_p]
+    L.cvx_destroy.restype = None
+    L.cvx_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.cvx_world_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.cvx_set_resolution.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.cvx_set_buffer_count.argtypes = [C.c_void_p, C.c_int]
+    L.cvx_draw_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.cvx_draw_segments_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.cvx_draw_segments_placed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+    L.cvx_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.cvx_set_latency_kernel.argtypes = [C.c_void_p, C.c_int]
+    L.cvx_set_world_repeat.argtypes = [C.c_void_p, C.c_int]
+    L.cvx_synchronize.argtypes = [C.c_void_p]
+    L.cvx_clear_raybuffer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
+    L.cvx_read_raybuffer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.cvx_blit_segments.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.cvx_blit_segments_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.cvx_raybuffer_device_ptr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.cvx_screen_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.cvx_last_draw_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_draw_time_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
+    L.cvx_enable_counters.argtypes = [C.c_void_p, C.c_int]
+    L.cvx_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
+    L.cvx_get_raybuffer_layout.argtypes = [C.c_void_p, C.c_int, C.POINTER(RaybufferLayout)]
+    L.cvx_bind_raybuffers.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    L.cvx_copy_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+    if hasattr(L, "cvx_selftest_math"):  # a diagnostics build (include/cpuvox_gpu_diag.h)
+        L.cvx_debug_section_cycles.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.cvx_debug_section_histogram.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
+        L.cvx_debug_occupancy.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int)]
+        L.cvx_debug_last_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.cvx_debug_settle.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
+        L.cvx_debug_cavities.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
+        L.cvx_selftest_math.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvx_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.cvx_selftest_lone.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_world_downsample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    L.cvx_world_build_lods.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    L.cvx_free.argtypes = [C.c_void_p]
+    L.cvx_free.restype = None
+    L.cvx_world_set_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int]
+    L.cvx_world_edit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.cvx_world_edit_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.cvx_world_brush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.cvx_world_pick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.cvx_world_pick_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_world_read_region.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int32)]
+    L.cvx_world_read_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.cvx_world_compact.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+    L.cvx_world_stamp_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_float)]
-        L.cvx_world_cavities.argtypes = [C.c_void_p, C.POINTER(CavityParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_light.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_int, C.POINTER(C.c_float)]
-        L.cvx_world_light_lamps.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.cvx_world_move.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.cvx_world_move_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.cvx_world_nav_build.argtypes = [C.c_void_p, C.POINTER(NavParams), C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_nav_field_goals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_nav_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.cvx_nav_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_nav_field_destroy.argtypes = [C.c_void_p]
-        L.cvx_world_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_surface_device.argtypes = L.cvx_world_surface.argtypes
-        L.cvx_surface_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.cvx_world_read_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_read_voxels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_world_write_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.cvx_world_write_voxels_device.argtypes = L.cvx_world_write_voxels.argtypes
-        L.cvx_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_distance_device.argtypes = L.cvx_world_distance.argtypes
-        L.cvx_world_read_heights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_read_heights_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_world_write_heights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              C.POINTER(C.c_float)]
-        L.cvx_world_write_heights_device.argtypes = L.cvx_world_write_heights.argtypes
-        L.cvx_world_place_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
-        L.cvx_world_place_models_device.argtypes = L.cvx_world_place_models.argtypes
-        L.cvx_world_read_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_read_model_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_model_instance_from_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.cvx_world_spread.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_spread_device.argtypes = L.cvx_world_spread.argtypes
-        L.cvx_world_surface_rects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_surface_rects_device.argtypes = L.cvx_world_surface_rects.argtypes
-        L.cvx_surface_rect_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.cvx_world_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_float)]
-        L.cvx_snapshot_info_get.argtypes = [C.c_void_p, C.POINTER(SnapshotInfo)]
-        L.cvx_world_snapshot_restore.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_snapshot_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
-        L.cvx_world_snapshot_diff_device.argtypes = L.cvx_world_snapshot_diff.argtypes
-        L.cvx_snapshot_destroy.argtypes = [C.c_void_p]
-        L.cvx_snapshot_destroy.restype = None
-        L.cvx_world_lift_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
-                                            C.POINTER(LiftSummary), C.POINTER(C.c_float)]
-        L.cvx_world_lift_pieces_device.argtypes = L.cvx_world_lift_pieces.argtypes
-        L.cvx_lifted_piece_mass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_nav_field_destroy.restype = None
-        L.cvx_free.restype = None
-        L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
-        L.cvx_shard_plan_destroy.restype = None
-        L.cvx_shard_plan_tile_count.argtypes = [C.c_void_p]
-        L.cvx_shard_plan_tile_count.restype = C.c_int64
-        L.cvx_shard_plan_sections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_shard_plan_tile_out.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_shard_plan_transfer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.cvx_comm_unique_id.argtypes = [C.c_void_p]
-        L.cvx_comm_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.cvx_comm_create_timeout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]
-        L.cvx_comm_destroy.argtypes = [C.c_void_p]
-        L.cvx_exchange.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_image_plan_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.cvx_image_plan_destroy.argtypes = [C.c_void_p]
-        L.cvx_image_plan_destroy.restype = None
-        L.cvx_image_plan_tile_count.argtypes = [C.c_void_p]
-        L.cvx_image_plan_tile_count.restype = C.c_int64
-        L.cvx_image_plan_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.cvx_image_plan_transfer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.cvx_image_plan_tile_out.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_image_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_image_exchange.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvx_image_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_world_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.cvx_world_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_settle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.POINTER(C.c_float)]
+    L.cvx_world_cavities.argtypes = [C.c_void_p, C.POINTER(CavityParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_light.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_int, C.POINTER(C.c_float)]
+    L.cvx_world_light_lamps.argtypes = [C.c_void_p, C.POINTER(LightParams), C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.cvx_world_move.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.cvx_world_move_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.cvx_world_nav_build.argtypes = [C.c_void_p, C.POINTER(NavParams), C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_nav_field_goals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_nav_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.cvx_nav_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_nav_field_destroy.argtypes = [C.c_void_p]
+    L.cvx_nav_field_destroy.restype = None
+    L.cvx_world_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_surface_device.argtypes = L.cvx_world_surface.argtypes
+    L.cvx_surface_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.cvx_world_read_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_read_voxels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_world_write_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.cvx_world_write_voxels_device.argtypes = L.cvx_world_write_voxels.argtypes
+    L.cvx_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_distance_device.argtypes = L.cvx_world_distance.argtypes
+    L.cvx_world_read_heights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_read_heights_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_world_write_heights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_float)]
+    L.cvx_world_write_heights_device.argtypes = L.cvx_world_write_heights.argtypes
+    L.cvx_world_place_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.cvx_world_place_models_device.argtypes = L.cvx_world_place_models.argtypes
+    L.cvx_world_read_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_read_model_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_model_instance_from_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.cvx_world_spread.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_spread_device.argtypes = L.cvx_world_spread.argtypes
+    L.cvx_world_surface_rects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_surface_rects_device.argtypes = L.cvx_world_surface_rects.argtypes
+    L.cvx_surface_rect_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.cvx_world_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_float)]
+    L.cvx_snapshot_info_get.argtypes = [C.c_void_p, C.POINTER(SnapshotInfo)]
+    L.cvx_world_snapshot_restore.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_snapshot_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvx_world_snapshot_diff_device.argtypes = L.cvx_world_snapshot_diff.argtypes
+    L.cvx_snapshot_destroy.argtypes = [C.c_void_p]
+    L.cvx_snapshot_destroy.restype = None
+    L.cvx_world_lift_pieces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.POINTER(LiftSummary), C.POINTER(C.c_float)]
+    L.cvx_world_lift_pieces_device.argtypes = L.cvx_world_lift_pieces.argtypes
+    L.cvx_lifted_piece_mass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
+    L.cvx_shard_plan_destroy.restype = None
+    L.cvx_shard_plan_tile_count.argtypes = [C.c_void_p]
+    L.cvx_shard_plan_tile_count.restype = C.c_int64
+    L.cvx_shard_plan_sections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_shard_plan_tile_out.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_shard_plan_transfer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.cvx_comm_unique_id.argtypes = [C.c_void_p]
+    L.cvx_comm_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.cvx_comm_create_timeout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]
+    L.cvx_comm_destroy.argtypes = [C.c_void_p]
+    L.cvx_exchange.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_image_plan_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.cvx_image_plan_destroy.argtypes = [C.c_void_p]
+    L.cvx_image_plan_destroy.restype = None
+    L.cvx_image_plan_tile_count.argtypes = [C.c_void_p]
+    L.cvx_image_plan_tile_count.restype = C.c_int64
+    L.cvx_image_plan_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.cvx_image_plan_transfer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.cvx_image_plan_tile_out.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_image_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_image_exchange.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvx_image_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 

@@ -6,7 +6,7 @@ tests/brush_rules.cpp, against independent numpy models.
   final_column: runs, colours, worldMin / worldMax and the over-limit rejections must match exactly.
 - The pick walk: random rays through small random worlds uploaded into a host-only context, against the float64 dense 3-D DDA of
   tests/pickmodel.py; exact on every ray the model calls unambiguous, and at least 99 % of the rays are.
-- The struct layouts of the header against the ctypes, numpy and C# mirrors; the new calls without a context / world."""
+- The new calls without a context / world (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -215,32 +215,6 @@ def test_pick_walk_matches_the_float64_model(rules, tmp_path, dims, sparse, seed
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layouts_match_the_mirrors():
-    assert (C.sizeof(gpu.BrushStroke), C.sizeof(gpu.PickRay), C.sizeof(gpu.PickHit)) == (40, 32, 24)
-    assert (gpu.STROKE_DTYPE.itemsize, gpu.PICK_RAY_DTYPE.itemsize, gpu.PICK_HIT_DTYPE.itemsize) == (40, 32, 24)
-    for ct, dt in ((gpu.BrushStroke, gpu.STROKE_DTYPE), (gpu.PickRay, gpu.PICK_RAY_DTYPE), (gpu.PickHit, gpu.PICK_HIT_DTYPE)):
-        assert [f[0] for f in ct._fields_] == list(dt.names)
-        assert [getattr(ct, f[0]).offset for f in ct._fields_] == [dt.fields[n][1] for n in dt.names]
-    assert [gpu.BrushStroke.a.offset, gpu.BrushStroke.b.offset, gpu.BrushStroke.argb.offset] == [8, 20, 32]
-    assert [gpu.PickHit.face.offset, gpu.PickHit.argb.offset, gpu.PickHit.t.offset] == [12, 16, 20]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    for name in ("cvx_brush_stroke", "cvx_pick_ray", "cvx_pick_hit"):
-        body = re.search(r"typedef struct " + name + r" \{[^\n]*\n(.*?)\} " + name + ";", header, flags=re.S).group(1)
-        fields = re.findall(r"^\s*(?:int32_t|uint32_t|float) ([a-zA-Z_]+)", body, flags=re.M)
-        ct = {"cvx_brush_stroke": gpu.BrushStroke, "cvx_pick_ray": gpu.PickRay, "cvx_pick_hit": gpu.PickHit}[name]
-        assert fields == [f[0] for f in ct._fields_], (name, fields)
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    sizes = {"int": 4, "uint": 4, "float": 4}
-    for name, want in (("BrushStroke", 40), ("PickRay", 32), ("PickHit", 24)):
-        body = re.search(r"public unsafe struct " + name + r"\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        total = 0
-        for m in re.finditer(r"public\s+(fixed\s+)?(int|uint|float)\s+([^;]+);", body):
-            for n in m.group(3).split(","):
-                k = re.search(r"\[(\d+)\]", n)
-                total += sizes[m.group(2)] * (int(k.group(1)) if k else 1)
-        assert total == want, (name, total)
-
 
 def test_new_calls_fail_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()

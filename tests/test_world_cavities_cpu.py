@@ -7,7 +7,7 @@
   colours, worldMin / worldMax in the builder's encoding) must equal the model's exactly.
 - World mode: the three _pick_world worlds and the two noise worlds uploaded into a host-only context; list and summary equal the model's and
   the sub-world blob of the FILL rectangle equals, byte for byte, the same rectangle of the model's world built on the host.
-- The struct layouts of the header against the ctypes, numpy and C# mirrors; the call without a context / world and every INVALID_ARGUMENT case."""
+- The call without a context / world and every INVALID_ARGUMENT case (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -232,30 +232,6 @@ def test_noise_worlds_with_random_boxes_masks_and_limits(rules, tmp_path, dims, 
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layouts_match_the_mirrors():
-    assert C.sizeof(gpu.CavityParams) == 48 and C.sizeof(gpu.CavitiesSummary) == gpu.CAVITIES_SUMMARY_DTYPE.itemsize == 48
-    assert [f[0] for f in gpu.CavitiesSummary._fields_] == list(gpu.CAVITIES_SUMMARY_DTYPE.names) == list(cavitymodel.SUMMARY_NAMES)
-    assert [getattr(gpu.CavityParams, n).offset for n in ("boxMin", "boxMax", "openFaces", "op", "argb", "pad_", "maxVoxels")] == [0, 12, 24, 28, 32, 36, 40]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    body = re.search(r"typedef struct cvx_cavity_params \{[^\n]*\n(.*?)\} cvx_cavity_params;", header, flags=re.S).group(1)
-    assert re.findall(r"^\s*u?int(?:32|64)_t ([a-zA-Z_]+)", body, flags=re.M) == [f[0] for f in gpu.CavityParams._fields_]
-    body = re.search(r"typedef struct cvx_cavities_summary \{[^\n]*\n(.*?)\} cvx_cavities_summary;", header, flags=re.S).group(1)
-    assert [n for part in re.findall(r"int64_t ([a-zA-Z, ]+);", body) for n in part.split(", ")] == [f[0] for f in gpu.CavitiesSummary._fields_]
-    for name, value in (("CVX_CAVITIES_REPORT", gpu.CAVITIES_REPORT), ("CVX_CAVITIES_FILL", gpu.CAVITIES_FILL)):
-        assert re.search(name + r" = (\d+)", header).group(1) == str(value)
-    assert int(re.search(r"#define CVX_CAVITY_OPEN_DEFAULT (0x[0-9A-Fa-f]+)", header).group(1), 16) == gpu.CAVITY_OPEN_DEFAULT == cavitymodel.OPEN_DEFAULT == 0x3B
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    sizes = {"int": 4, "uint": 4, "long": 8}
-    for name, want in (("CavityParams", 48), ("CavitiesSummary", 48)):
-        body = re.search(r"public (?:unsafe )?struct " + name + r"\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        total = 0
-        for m in re.finditer(r"public\s+(fixed\s+)?(int|uint|long)\s+([^;]+);", body):
-            for n in m.group(3).split(","):
-                k = re.search(r"\[(\d+)\]", n)
-                total += sizes[m.group(2)] * (int(k.group(1)) if k else 1)
-        assert total == want, (name, total)
-
 
 def test_cavities_fails_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()

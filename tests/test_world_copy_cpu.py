@@ -7,7 +7,7 @@ against the independent dense model of tests/copymodel.py.
 - World mode: small random worlds uploaded into a host-only context; the rule over every column of the call's rectangle gives the sub-world blob
   the write kernel makes, which must equal, byte for byte, the same rectangle of the model's world built on the host.  All 16 transforms, the four
   ops, moves onto themselves, later placements over earlier ones, destinations partly and wholly outside the world.
-- The struct layout of the header against the ctypes, numpy and C# mirrors; the call without a context / world; copy_placements_array."""
+- The call without a context / world; copy_placements_array (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -264,26 +264,6 @@ def test_copied_rectangle_equals_the_model_world(rules, tmp_path, dims, sparse, 
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layout_matches_the_mirrors():
-    assert C.sizeof(gpu.CopyPlacement) == gpu.COPY_PLACEMENT_DTYPE.itemsize == 48
-    assert [f[0] for f in gpu.CopyPlacement._fields_] == list(gpu.COPY_PLACEMENT_DTYPE.names)
-    assert [getattr(gpu.CopyPlacement, f[0]).offset for f in gpu.CopyPlacement._fields_] == [gpu.COPY_PLACEMENT_DTYPE.fields[n][1] for n in gpu.COPY_PLACEMENT_DTYPE.names]
-    assert [gpu.CopyPlacement.dst.offset, gpu.CopyPlacement.transform.offset, gpu.CopyPlacement.op.offset, gpu.CopyPlacement.move.offset] == [24, 36, 40, 44]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    body = re.search(r"typedef struct cvx_copy_placement \{[^\n]*\n(.*?)\} cvx_copy_placement;", header, flags=re.S).group(1)
-    assert re.findall(r"^\s*int32_t ([a-zA-Z_]+)", body, flags=re.M) == [f[0] for f in gpu.CopyPlacement._fields_]
-    assert re.search(r"CVX_COPY_REPLACE = (\d+)", header).group(1) == str(gpu.COPY_REPLACE)
-    assert re.search(r"#define CVX_COPY_MAX_PLACEMENTS (\d+)", header).group(1) == str(gpu.COPY_MAX_PLACEMENTS)
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    body = re.search(r"public unsafe struct CopyPlacement\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-    total = 0
-    for m in re.finditer(r"public\s+(fixed\s+)?int\s+([^;]+);", body):
-        for n in m.group(2).split(","):
-            k = re.search(r"\[(\d+)\]", n)
-            total += 4 * (int(k.group(1)) if k else 1)
-    assert total == 48
-
 
 def test_copy_fails_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()

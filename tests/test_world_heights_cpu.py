@@ -346,28 +346,3 @@ def test_python_wrappers_check_their_arrays():
         gpu.Context.read_heights_device(ctx, (0, 0), (1, 1, 1), 0)
     with pytest.raises(ValueError, match="three integers"):
         gpu.Context.write_heights_device(ctx, (0, 0, 0), (1, 1), 0, 0)
-
-
-def test_the_header_the_libraries_and_the_bindings_agree():
-    """include/cpuvox_gpu_heights.h against gpu.HEIGHTS_EXPORTS, the symbols of the product and the experiment library, and the DllImports of
-    host/csharp/CpuVoxGpuHeights.cs (parameter for parameter, with the parsers of tests/test_csharp_binding.py)."""
-    import test_csharp_binding as B
-
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cpuvox_gpu_heights.h")).read(), flags=re.S)
-    declared = {m.group(2): [p.strip() for p in m.group(3).split(",")]
-                for m in re.finditer(r"\b([a-z_0-9 ]+?[ \*]+)(cvx_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header)}
-    assert sorted(declared) == sorted(gpu.HEIGHTS_EXPORTS) and len(declared) == 4
-    assert not set(declared) & set(gpu.EXPORTS), "declared once: include/cpuvox_gpu.h does not repeat them"
-    for path in (gpu.lib_path(), os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_exp.so")):
-        library = C.CDLL(path)
-        assert not [n for n in declared if not hasattr(library, n)], path
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpuHeights.cs")).read()
-    imports = {m.group(2): (m.group(1), [p.strip() for p in m.group(3).split(",")])
-               for m in re.finditer(r"\[DllImport\(Lib\)\]\s*public static extern\s+([A-Za-z]+)\s+(cvx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", cs, flags=re.S)}
-    assert sorted(imports) == sorted(declared)
-    for name, params in declared.items():
-        ret, cs_params = imports[name]
-        assert ret == "int" and len(params) == len(cs_params), name
-        for i, (a, b) in enumerate(zip(params, cs_params)):
-            assert B._c_kind(a) == B._cs_kind(b), f"{name} parameter {i}: C `{a}` vs C# `{b}`"
-    assert re.search(r"CVX_HEIGHTS_WALLED = 1;", cs)

@@ -7,10 +7,9 @@
   column must equal the model's exactly.  The coverage conditions are asserted from the model BEFORE anything is compared.
 - Constructed cases whose terms are derived by hand and asserted as literals.
 - lampCount == 0 gives the bytes of the cvx_world_light rule (tests/light_rules.cpp on the same cases).
-- The struct layout of the header against the ctypes and C# mirrors; every INVALID_ARGUMENT case on a context without a world."""
+- Every INVALID_ARGUMENT case on a context without a world (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -261,30 +260,6 @@ def test_two_lamps_add_and_then_clamp(rules):
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layout_matches_the_mirrors():
-    assert C.sizeof(gpu.Lamp) == 32
-    names = [f[0] for f in gpu.Lamp._fields_]
-    assert [getattr(gpu.Lamp, n).offset for n in names] == [0, 12, 16, 20]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    body = re.search(r"typedef struct cvx_lamp \{[^\n]*\n(.*?)\} cvx_lamp;", header, flags=re.S).group(1)
-    assert re.findall(r"^\s*int32_t ([a-zA-Z_]+)(\[3\])?;", body, flags=re.M) == [("pos", "[3]"), ("radius", ""), ("level", ""), ("pad_", "[3]")]
-    assert re.search(r"#define CVX_LIGHT_MAX_LAMPS\s+(\d+)", header).group(1) == str(gpu.LIGHT_MAX_LAMPS) == "4096"
-    assert re.search(r"#define CVX_LAMP_MAX_RADIUS\s+(\d+)", header).group(1) == str(gpu.LAMP_MAX_RADIUS) == "64"
-    assert C.sizeof(gpu.LightParams) == 64
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    body = re.search(r"public unsafe struct Lamp\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-    fields = []
-    for m in re.finditer(r"public\s+(fixed\s+)?int\s+([^;]+);", body):
-        for n in m.group(2).split(","):
-            k = re.search(r"(\w+)\[(\d+)\]", n)
-            fields.append((k.group(1).lower(), int(k.group(2))) if k else (n.strip().lower(), 1))
-    assert fields == [("pos", 3), ("radius", 1), ("level", 1), ("pad", 3)] and sum(4 * n for _, n in fields) == 32
-    assert "CVX_LIGHT_MAX_LAMPS = 4096" in cs and "CVX_LAMP_MAX_RADIUS = 64" in cs
-    assert "cvx_world_light_lamps" in gpu.EXPORTS and "cvx_world_light_lamps" in open(os.path.join(ROOT, "README.md")).read()
-    arr = gpu.lamps_array([((1, -2, 3), 4, 5), dict(pos=(6, 7, 8), radius=9, level=10)])
-    assert np.frombuffer(bytes(arr), dtype=np.int32).tolist() == [1, -2, 3, 4, 5, 0, 0, 0, 6, 7, 8, 9, 10, 0, 0, 0]
-
 
 def test_lamps_fail_cleanly_without_a_context_or_world(rules):
     """Every INVALID_ARGUMENT case is decided on the host before the world is looked at: on a context without a device or world

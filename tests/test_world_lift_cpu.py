@@ -10,10 +10,8 @@ tolerance is cvx_lifted_piece_mass against exact rationals.
 - The same program under the address and undefined-behaviour sanitizers.
 - The argument checks that need no device.
 - The model on hand-made worlds.
-- The header against gpu.LIFT_EXPORTS, both libraries, the ctypes structures, the numpy dtype and host/csharp/CpuVoxGpuLift.cs; the documents."""
-import ctypes as C
+- The Python wrappers and the documents (the header's mirrors: tests/test_abi_mirrors.py)."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -299,50 +297,7 @@ def test_the_model_on_two_interlocked_pieces():
     assert len(one.pieces) == 1 and one.summary["storedPieces"] == 1 and one.summary["floatingPieces"] == 2 and one.summary["neededVoxels"] == 648
 
 
-# ---- bindings ----------------------------------------------------------------------------------------------------------------------------------------
-
-def test_the_header_the_libraries_and_the_bindings_agree():
-    """include/cpuvox_gpu_lift.h against gpu.LIFT_EXPORTS, the symbols of the product and the experiment library, the ctypes structures, the numpy
-    dtype and the DllImports and structs of host/csharp/CpuVoxGpuLift.cs (with the parsers of tests/test_csharp_binding.py)."""
-    import test_csharp_binding as B
-
-    text = open(os.path.join(ROOT, "include", "cpuvox_gpu_lift.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = {m.group(2): (m.group(1).strip(), [p.strip() for p in m.group(3).split(",")])
-                for m in re.finditer(r"\b([a-z_0-9 ]+?[ \*]+)(cvx_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header)}
-    assert sorted(declared) == sorted(gpu.LIFT_EXPORTS) and len(declared) == 3
-    others = (set(gpu.EXPORTS) | set(gpu.HEIGHTS_EXPORTS) | set(gpu.MODELS_EXPORTS) | set(gpu.SPREAD_EXPORTS) | set(gpu.SURFACE_RECTS_EXPORTS)
-              | set(gpu.SNAPSHOT_EXPORTS))
-    assert not set(declared) & others, "declared once"
-    assert len(gpu.EXPORTS) == 83, "include/cpuvox_gpu.h's list stays what its hosts were built against"
-    for path in (gpu.lib_path(), os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_exp.so")):
-        library = C.CDLL(path)
-        assert not [n for n in declared if not hasattr(library, n)], path
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpuLift.cs")).read()
-    imports = {m.group(2): (m.group(1), [p.strip() for p in m.group(3).split(",")])
-               for m in re.finditer(r"\[DllImport\(Lib\)\]\s*public static extern\s+([A-Za-z]+)\s+(cvx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", cs, flags=re.S)}
-    assert sorted(imports) == sorted(declared)
-    for name, (c_ret, params) in declared.items():
-        ret, cs_params = imports[name]
-        assert c_ret == ret == "int" and len(params) == len(cs_params), name
-        for i, (a, b) in enumerate(zip(params, cs_params)):
-            assert B._c_kind(a) == B._cs_kind(b), f"{name} parameter {i}: C `{a}` vs C# `{b}`"
-    for name, ctype, dtype, cs_name in (("cvx_lifted_piece", gpu.LiftedPiece, gpu.LIFTED_PIECE_DTYPE, "CvxLiftedPiece"),
-                                        ("cvx_lift_summary", gpu.LiftSummary, None, "CvxLiftSummary")):
-        stated = int(re.search(r"typedef struct " + name + r" \{\s*/\* (\d+) bytes", text).group(1))
-        assert C.sizeof(ctype) == stated and (dtype is None or dtype.itemsize == stated), name
-        assert re.search(r"public (?:unsafe )?struct " + cs_name + r" // " + str(stated) + r" bytes", cs), cs_name
-        body = re.search(r"struct " + cs_name + r"[^{]*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        assert B._size(body) == stated, cs_name
-        if dtype is not None:
-            assert [(n, dtype.fields[n][1]) for n in dtype.names] == [(n, getattr(ctype, n).offset) for n, _ in ctype._fields_], name
-    assert (C.sizeof(gpu.LiftedPiece), C.sizeof(gpu.LiftSummary)) == (128, 64)
-    assert (gpu.LiftedPiece.offset.offset, gpu.LiftedPiece.sum.offset, gpu.LiftedPiece.moment.offset) == (48, 56, 80)
-    assert (gpu.LiftSummary.storedPieces.offset, gpu.LiftSummary.storedVoxels.offset, gpu.LiftSummary.neededVoxels.offset) == (32, 40, 48)
-    assert liftmodel.LIFTED_PIECE_DTYPE == gpu.LIFTED_PIECE_DTYPE and gpu.LIFTED_PIECE_DTYPE["piece"] == gpu.PIECE_DTYPE
-    assert re.search(r"CVX_LIFT_COPY = 0, CVX_LIFT_REMOVE = 1\b", header) and "CVX_LIFT_COPY = 0;" in cs and "CVX_LIFT_REMOVE = 1;" in cs
-    assert (gpu.LIFT_COPY, gpu.LIFT_REMOVE) == (0, 1) == (liftmodel.COPY, liftmodel.REMOVE)
-
+# ---- wrappers and documents ----------------------------------------------------------------------------------------------------------------------------------------
 
 def test_python_wrappers():
     assert hasattr(gpu.Context, "world_lift_pieces") and hasattr(gpu.Context, "world_lift_pieces_device") and callable(gpu.lifted_model)

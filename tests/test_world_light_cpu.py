@@ -9,7 +9,7 @@
   rectangle of the model's world built on the host.
 - Constructed cases whose shades are derived by hand and asserted as literals.
 - TO_ALPHA twice equals once, TO_RGB with shade 255 is the identity.
-- The struct layout of the header against the ctypes and C# mirrors; the call without a context / world and every INVALID_ARGUMENT case."""
+- The call without a context / world and every INVALID_ARGUMENT case (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -324,29 +324,6 @@ def test_the_bake_in_the_rules(rules, tmp_path):
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layout_matches_the_mirrors():
-    assert C.sizeof(gpu.LightParams) == 64
-    names = [f[0] for f in gpu.LightParams._fields_]
-    assert [getattr(gpu.LightParams, n).offset for n in names] == [0, 12, 24, 36, 40, 44, 48, 52, 56, 60]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    body = re.search(r"typedef struct cvx_light_params \{[^\n]*\n(.*?)\} cvx_light_params;", header, flags=re.S).group(1)
-    assert re.findall(r"^\s*int32_t ([a-zA-Z_]+)", body, flags=re.M) == names
-    assert re.findall(r"^\s*int32_t [a-zA-Z_]+(\[3\])?;", body, flags=re.M) == ["[3]"] * 3 + [""] * 7
-    assert len(lightmodel.words(lightmodel.params((0, 0, 0), (1, 1, 1)))) * 4 == 64
-    for name, value in (("CVX_LIGHT_TO_RGB", RGB), ("CVX_LIGHT_TO_ALPHA", ALPHA)):
-        assert re.search(name + r" = (\d+)", header).group(1) == str(value)
-    assert (lightmodel.TO_RGB, lightmodel.TO_ALPHA) == (RGB, ALPHA)
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    body = re.search(r"public unsafe struct LightParams\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-    fields = []
-    for m in re.finditer(r"public\s+(fixed\s+)?int\s+([^;]+);", body):
-        for n in m.group(2).split(","):
-            k = re.search(r"(\w+)\[(\d+)\]", n)
-            fields.append((k.group(1).lower(), int(k.group(2))) if k else (n.strip().lower(), 1))
-    assert fields == [(n.rstrip("_").lower(), 3 if n in ("boxMin", "boxMax", "sunDir") else 1) for n in names]
-    assert "cvx_world_light" in gpu.EXPORTS and "all 64 exports" in open(os.path.join(ROOT, "README.md")).read()
-
 
 def test_light_fails_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()

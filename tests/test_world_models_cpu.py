@@ -8,7 +8,7 @@ dense volume.  Everything is integers: every comparison is byte for byte.
   volume.
 - The identity map against cvxb::DenseColumn, the 16 quarter-turn / mirror / flip transforms against tests/copymodel.py.
 - Column mode: the over-limit rejection on a synthetic 40000-voxel column.
-- The read, the matrix helper, the argument checks, the header / bindings agreement and the wrappers' array checks."""
+- The read, the matrix helper, the argument checks and the wrappers' array checks (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -469,38 +469,3 @@ def test_python_wrappers_check_their_arrays():
         gpu.Context.read_model_device(ctx, (2, 2, 2), np.eye(3), 0, 0)
     with pytest.raises(ValueError, match="3 x 4"):
         gpu.model_instance(np.eye(3), (2, 2, 2))
-
-
-def test_the_header_the_libraries_and_the_bindings_agree():
-    """include/cpuvox_gpu_models.h against gpu.MODELS_EXPORTS, the symbols of the product and the experiment library, the ctypes structures and
-    the DllImports and structs of host/csharp/CpuVoxGpuModels.cs (parameter for parameter, with the parsers of tests/test_csharp_binding.py)."""
-    import test_csharp_binding as B
-
-    text = open(os.path.join(ROOT, "include", "cpuvox_gpu_models.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = {m.group(2): [p.strip() for p in m.group(3).split(",")]
-                for m in re.finditer(r"\b([a-z_0-9 ]+?[ \*]+)(cvx_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header)}
-    assert sorted(declared) == sorted(gpu.MODELS_EXPORTS) and len(declared) == 5
-    assert not set(declared) & (set(gpu.EXPORTS) | set(gpu.HEIGHTS_EXPORTS)), "declared once"
-    for path in (gpu.lib_path(), os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_exp.so")):
-        library = C.CDLL(path)
-        assert not [n for n in declared if not hasattr(library, n)], path
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpuModels.cs")).read()
-    imports = {m.group(2): (m.group(1), [p.strip() for p in m.group(3).split(",")])
-               for m in re.finditer(r"\[DllImport\(Lib\)\]\s*public static extern\s+([A-Za-z]+)\s+(cvx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", cs, flags=re.S)}
-    assert sorted(imports) == sorted(declared)
-    for name, params in declared.items():
-        ret, cs_params = imports[name]
-        assert ret == "int" and len(params) == len(cs_params), name
-        for i, (a, b) in enumerate(zip(params, cs_params)):
-            assert B._c_kind(a) == B._cs_kind(b), f"{name} parameter {i}: C `{a}` vs C# `{b}`"
-    # the structures: the sizes the header states, in ctypes and in the C# declarations
-    for name, ctype, cs_name in (("cvx_model_map", gpu.ModelMap, "CvxModelMap"), ("cvx_model", gpu.Model, "CvxModel"),
-                                 ("cvx_model_instance", gpu.ModelInstance, "CvxModelInstance")):
-        stated = int(re.search(r"typedef struct " + name + r" \{\s*/\* (\d+) bytes", text).group(1))
-        assert C.sizeof(ctype) == stated, name
-        assert re.search(r"public unsafe struct " + cs_name + r" // " + str(stated) + r" bytes", cs), cs_name
-    assert (C.sizeof(gpu.ModelMap), C.sizeof(gpu.Model), C.sizeof(gpu.ModelInstance)) == (64, 32, 96)
-    assert gpu.ModelInstance.boxMin.offset == 64 and gpu.ModelInstance.model.offset == 88 and gpu.ModelMap.t.offset == 40
-    for name, value in (("CVX_MODELS_MAX_MODELS", gpu.MODELS_MAX_MODELS), ("CVX_MODELS_MAX_INSTANCES", gpu.MODELS_MAX_INSTANCES)):
-        assert re.search(r"#define " + name + r"\s+" + str(value) + r"\b", header) and re.search(name + r" = " + str(value) + ";", cs)

@@ -7,7 +7,7 @@ the independent dense model of tests/movemodel.py.  The rule is integer from end
   (a body that does not start in solid never ends in solid) is checked on every one of them with the model's overlap test.
 - World mode: the worlds of the pick test uploaded into a host-only context (both colour layouts, run-list columns), 3000 bodies each.
 - Hand-derived cases whose results are asserted as literals.
-- The struct layouts of the header against the ctypes, numpy and C# mirrors; every INVALID_ARGUMENT and NOT_READY case."""
+- Every INVALID_ARGUMENT and NOT_READY case (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -349,41 +349,6 @@ def test_wrapping_across_the_tile_edge(rules, tmp_path):
 
 
 # ---- layouts and entry points ----------------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layouts_match_the_mirrors():
-    assert C.sizeof(gpu.MoveBody) == 48 and C.sizeof(gpu.MoveResult) == 16
-    assert gpu.MOVE_BODY_DTYPE.itemsize == 48 and gpu.MOVE_RESULT_DTYPE.itemsize == 16
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    for c_name, ctype, dtype, cs_name, triples in (("cvx_move_body", gpu.MoveBody, gpu.MOVE_BODY_DTYPE, "MoveBody", ("pos", "size", "delta")),
-                                                   ("cvx_move_result", gpu.MoveResult, gpu.MOVE_RESULT_DTYPE, "MoveResult", ("pos",))):
-        names = [f[0] for f in ctype._fields_]
-        body = re.search(r"typedef struct " + c_name + r" \{[^\n]*\n(.*?)\} " + c_name + ";", header, flags=re.S).group(1)
-        assert re.findall(r"^\s*int32_t ([a-zA-Z_]+)", body, flags=re.M) == names
-        assert re.findall(r"^\s*int32_t [a-zA-Z_]+(\[3\])?;", body, flags=re.M) == ["[3]" if n in triples else "" for n in names]
-        assert list(dtype.names) == names and [dtype.fields[n][1] for n in names] == [getattr(ctype, n).offset for n in names]
-        body = re.search(r"public unsafe struct " + cs_name + r"\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        fields = []
-        for m in re.finditer(r"public\s+(fixed\s+)?int\s+([^;]+);", body):
-            for n in m.group(2).split(","):
-                k = re.search(r"(\w+)\[(\d+)\]", n)
-                fields.append((k.group(1).lower(), int(k.group(2))) if k else (n.strip().lower(), 1))
-        assert fields == [(n.rstrip("_").lower(), 3 if n in triples else 1) for n in names]
-    for name, value in (("CVX_MOVE_UNIT", gpu.MOVE_UNIT), ("CVX_MOVE_SOLID_BELOW =", gpu.MOVE_SOLID_BELOW), ("CVX_MOVE_SOLID_SIDES =", gpu.MOVE_SOLID_SIDES),
-                        ("CVX_MOVED_BLOCKED_MASK =", gpu.MOVED_BLOCKED_MASK)):
-        assert int(re.search(name + r" (\w+)", header).group(1), 0) == value
-    for name, value in (("CVX_MOVED_RESTING", gpu.MOVED_RESTING), ("CVX_MOVED_STARTS_SOLID", gpu.MOVED_STARTS_SOLID), ("CVX_MOVED_STEPPED", gpu.MOVED_STEPPED)):
-        assert 1 << int(re.search(name + r" = 1 << (\d+)", header).group(1)) == value
-    assert gpu.MOVED_INVALID == -(1 << 31) and np.int32(gpu.MOVED_INVALID) == np.int32(-2**31)
-    assert (movemodel.UNIT, movemodel.SOLID_BELOW, movemodel.SOLID_SIDES) == (gpu.MOVE_UNIT, gpu.MOVE_SOLID_BELOW, gpu.MOVE_SOLID_SIDES)
-    assert (movemodel.RESTING, movemodel.STARTS_SOLID, movemodel.STEPPED, movemodel.INVALID) == (gpu.MOVED_RESTING, gpu.MOVED_STARTS_SOLID, gpu.MOVED_STEPPED,
-                                                                                              gpu.MOVED_INVALID)
-    assert "cvx_world_move" in gpu.EXPORTS and "cvx_world_move_device" in gpu.EXPORTS
-    assert f"all {len(gpu.EXPORTS)} exports" in open(os.path.join(ROOT, "README.md")).read()
-    arr = gpu.bodies_array([{"pos": (1, 2, 3), "size": (4, 5, 6)}, movemodel.body((7, 8, 9), (1, 1, 1), (-1, -2, -3), 5, 3)])
-    assert arr.tobytes() == np.array([1, 2, 3, 4, 5, 6, 0, 0, 0, 0, 0, 0, 7, 8, 9, 1, 1, 1, -1, -2, -3, 5, 3, 0], dtype=np.int32).tobytes()
-    assert gpu.bodies_array(arr) is not None and gpu.bodies_array(arr).tobytes() == arr.tobytes()
-
 
 def test_move_fails_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()

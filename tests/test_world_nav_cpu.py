@@ -6,7 +6,7 @@ of tests/navmodel.py (blocked voxels by OR-ed shifts, clear ranges by cumulative
   odd bounds and random calls, over widths 1 .. 3, heights 1, 2, 5 and (stepUp, maxDrop) in (0, 0), (1, 3), (h, 4096), the cvx_nav_step of EVERY
   voxel position of the world and the deterministic summary fields equal the model's exactly.  Widths 8, 7 and 5 with heights 64, 63 and 1 (the
   largest the rule allows) on the constructed wall of limitworlds.nav_wide_world.
-- The struct layouts of the header against the ctypes, numpy and C# mirrors; every argument error that needs no device.
+- Every argument error that needs no device (the header's mirrors: tests/test_abi_mirrors.py).
 
 The noise worlds: noise_world's 70 % solid leaves little standing room for a body wider than a voxel, so width w draws the same generator at
 NOISE_DENSITY[dims, w] (nav_noise_world).  The densities were chosen with the model alone so that the preconditions of the GPU test hold
@@ -242,33 +242,6 @@ def test_the_walk_follows_next_on_the_models():
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layouts_match_the_mirrors():
-    assert C.sizeof(gpu.NavParams) == 48 and C.sizeof(gpu.NavStep) == gpu.NAV_STEP_DTYPE.itemsize == navmodel.STEP_DTYPE.itemsize == 32
-    assert C.sizeof(gpu.NavSummary) == gpu.NAV_SUMMARY_DTYPE.itemsize == 40
-    assert gpu.NAV_STEP_DTYPE == navmodel.STEP_DTYPE
-    assert [f[0] for f in gpu.NavSummary._fields_] == list(gpu.NAV_SUMMARY_DTYPE.names)
-    assert [getattr(gpu.NavParams, n).offset for n in ("boxMin", "boxMax", "width", "height", "stepUp", "maxDrop", "maxSteps", "pad_")] == [0, 12, 24, 28, 32, 36, 40, 44]
-    assert [getattr(gpu.NavSummary, n).offset for n in ("nodes", "reached", "goalsResolved", "largestDistance", "columnsWithSeveralNodes", "launches", "pad_")] \
-        == [0, 8, 16, 20, 24, 32, 36]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    for name, mirror in (("cvx_nav_params", gpu.NavParams), ("cvx_nav_step", gpu.NavStep), ("cvx_nav_summary", gpu.NavSummary)):
-        body = re.search(r"typedef struct " + name + r" \{[^\n]*\n(.*?)\} " + name + ";", header, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = [re.sub(r"\[\d+\]", "", n.strip()) for part in re.findall(r"int(?:32|64)_t ([a-zA-Z_0-9\[\], ]+);", body) for n in part.split(",")]
-        assert names == [f[0] for f in mirror._fields_], name
-    assert int(re.search(r"#define CVX_NAV_MAX_GOALS (\d+)", header).group(1)) == gpu.NAV_MAX_GOALS == 4096
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    sizes = {"int": 4, "uint": 4, "long": 8}
-    for name, want in (("NavParams", 48), ("NavStep", 32), ("NavSummary", 40)):
-        body = re.search(r"public (?:unsafe )?struct " + name + r"\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        total = 0
-        for m in re.finditer(r"public\s+(fixed\s+)?(int|uint|long)\s+([^;]+);", body):
-            for n in m.group(3).split(","):
-                k = re.search(r"\[(\d+)\]", n)
-                total += sizes[m.group(2)] * (int(k.group(1)) if k else 1)
-        assert total == want, (name, total)
-
 
 def test_nav_calls_fail_cleanly_without_a_context_or_world(rules):
     # a context without a device or world (tests/nav_rules.cpp): bad arguments first, then CVX_ERR_NOT_READY; no failing build leaves a field

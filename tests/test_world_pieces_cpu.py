@@ -7,7 +7,7 @@
   encoding) must equal the model's exactly.
 - World mode: small worlds uploaded into a host-only context; list and summary equal the model's and the sub-world blob of the REMOVE rectangle
   equals, byte for byte, the same rectangle of the model's world built on the host.
-- The struct layouts of the header against the ctypes, numpy and C# mirrors; the call without a context / world and every INVALID_ARGUMENT case."""
+- The call without a context / world and every INVALID_ARGUMENT case (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -189,34 +189,6 @@ def test_removed_rectangle_equals_the_model_world(rules, tmp_path, dims, sparse,
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layouts_match_the_mirrors():
-    assert C.sizeof(gpu.Piece) == gpu.PIECE_DTYPE.itemsize == piecesmodel.PIECE_DTYPE.itemsize == 48
-    assert C.sizeof(gpu.PiecesSummary) == gpu.PIECES_SUMMARY_DTYPE.itemsize == 32
-    assert gpu.PIECE_DTYPE == piecesmodel.PIECE_DTYPE
-    for ct, dt in ((gpu.Piece, gpu.PIECE_DTYPE), (gpu.PiecesSummary, gpu.PIECES_SUMMARY_DTYPE)):
-        assert [f[0] for f in ct._fields_] == list(dt.names)
-        assert [getattr(ct, f[0]).offset for f in ct._fields_] == [dt.fields[n][1] for n in dt.names]
-    assert [gpu.Piece.max.offset, gpu.Piece.seed.offset, gpu.Piece.pad_.offset, gpu.Piece.voxels.offset] == [12, 24, 36, 40]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    body = re.search(r"typedef struct cvx_piece \{[^\n]*\n(.*?)\} cvx_piece;", header, flags=re.S).group(1)
-    assert re.findall(r"^\s*int(?:32|64)_t ([a-zA-Z_]+)", body, flags=re.M) == [f[0] for f in gpu.Piece._fields_]
-    body = re.search(r"typedef struct cvx_pieces_summary \{[^\n]*\n(.*?)\} cvx_pieces_summary;", header, flags=re.S).group(1)
-    assert re.search(r"int64_t ([a-zA-Z, ]+);", body).group(1).split(", ") == [f[0] for f in gpu.PiecesSummary._fields_]
-    for name, value in (("CVX_PIECES_REPORT", gpu.PIECES_REPORT), ("CVX_PIECES_REMOVE", gpu.PIECES_REMOVE), ("CVX_ANCHOR_GROUND", GROUND),
-                        ("CVX_ANCHOR_OUTSIDE", OUTSIDE), ("CVX_ANCHOR_LARGEST", LARGEST)):
-        assert re.search(name + r" = (\d+)", header).group(1) == str(value)
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    sizes = {"int": 4, "long": 8}
-    for name, want in (("Piece", 48), ("PiecesSummary", 32)):
-        body = re.search(r"public (?:unsafe )?struct " + name + r"\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        total = 0
-        for m in re.finditer(r"public\s+(fixed\s+)?(int|long)\s+([^;]+);", body):
-            for n in m.group(3).split(","):
-                k = re.search(r"\[(\d+)\]", n)
-                total += sizes[m.group(2)] * (int(k.group(1)) if k else 1)
-        assert total == want, (name, total)
-
 
 def test_pieces_fails_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()

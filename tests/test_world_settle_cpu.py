@@ -6,7 +6,7 @@ tests/settlemodel.py, which knows only the contract's step rule.
   uploaded into a host-only context; the named boxes plus 40 random boxes and anchor masks each with maxDrop from {0, 1, 3}: the summary, the list,
   the drops and the decoded sub-world blob of the settle's rectangle equal the model's exactly, and the model changes nothing outside it.
 - Constructed shapes: a stack of twelve slabs, two interlocked pieces, a table stopped by a pole under one column.
-- The layout of cvx_settle_summary against the header and the ctypes, numpy and C# mirrors; every INVALID_ARGUMENT case without a world."""
+- Every INVALID_ARGUMENT case without a world (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -130,24 +130,6 @@ def test_stacks_cycles_and_ledges(rules, tmp_path):
             assert (got_solid == s).all() and (got_colour == c).all(), max_drop
     finally:
         ws.close()
-
-
-def test_struct_layout_matches_the_mirrors():
-    assert C.sizeof(gpu.SettleSummary) == gpu.SETTLE_SUMMARY_DTYPE.itemsize == 40
-    assert [f[0] for f in gpu.SettleSummary._fields_] == list(gpu.SETTLE_SUMMARY_DTYPE.names)
-    assert [getattr(gpu.SettleSummary, f[0]).offset for f in gpu.SettleSummary._fields_] == [gpu.SETTLE_SUMMARY_DTYPE.fields[n][1] for n in gpu.SETTLE_SUMMARY_DTYPE.names]
-    assert [gpu.SettleSummary.fallenPieces.offset, gpu.SettleSummary.largestDrop.offset, gpu.SettleSummary.pad_.offset] == [16, 32, 36]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    body = re.search(r"typedef struct cvx_settle_summary \{[^\n]*\n(.*?)\} cvx_settle_summary;", header, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body)
-    fields = [(m.group(1), n.strip()) for m in re.finditer(r"(int32_t|int64_t) ([a-zA-Z_, ]+);", body) for n in m.group(2).split(",")]
-    assert [n for _, n in fields] == [f[0] for f in gpu.SettleSummary._fields_]
-    assert [t for t, _ in fields] == ["int64_t"] * 4 + ["int32_t"] * 2
-    assert re.search(r"#define CVX_SETTLE_UNLIMITED (\d+)", header).group(1) == str(gpu.SETTLE_UNLIMITED)
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    body = re.search(r"public struct SettleSummary\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-    total = sum({"int": 4, "long": 8}[m.group(1)] * len(m.group(2).split(",")) for m in re.finditer(r"public\s+(int|long)\s+([^;]+);", body))
-    assert total == 40
 
 
 def test_settle_fails_cleanly_without_a_context_or_world(rules):

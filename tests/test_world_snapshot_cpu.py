@@ -7,10 +7,8 @@ tests/snapshot_rules.cpp, against the dense model of tests/snapshotmodel.py.  Ev
 - Whole worlds uploaded into a host-only context and compared with an edited world's blob: the list, its order and the summary.
 - The same program under the address and undefined-behaviour sanitizers.
 - The argument checks that need no device.
-- The header against gpu.SNAPSHOT_EXPORTS, both libraries, the ctypes structures, the numpy dtypes and host/csharp/CpuVoxGpuSnapshot.cs."""
-import ctypes as C
+- The Python wrappers and the documents (the header's mirrors: tests/test_abi_mirrors.py)."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -339,50 +337,7 @@ def test_python_wrappers():
     assert "destroyed before" in gpu.Snapshot.__doc__
 
 
-# ---- bindings -------------------------------------------------------------------------------------------------------------------------------------------
-
-def test_the_header_the_libraries_and_the_bindings_agree():
-    """include/cpuvox_gpu_snapshot.h against gpu.SNAPSHOT_EXPORTS, the symbols of the product and the experiment library, the ctypes structures,
-    the numpy dtypes and the DllImports and structs of host/csharp/CpuVoxGpuSnapshot.cs (with the parsers of tests/test_csharp_binding.py)."""
-    import test_csharp_binding as B
-
-    text = open(os.path.join(ROOT, "include", "cpuvox_gpu_snapshot.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = {m.group(2): (m.group(1).strip(), [p.strip() for p in m.group(3).split(",")])
-                for m in re.finditer(r"\b([a-z_0-9 ]+?[ \*]+)(cvx_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header)}
-    assert sorted(declared) == sorted(gpu.SNAPSHOT_EXPORTS) and len(declared) == 6
-    others = set(gpu.EXPORTS) | set(gpu.HEIGHTS_EXPORTS) | set(gpu.MODELS_EXPORTS) | set(gpu.SPREAD_EXPORTS) | set(gpu.SURFACE_RECTS_EXPORTS)
-    assert not set(declared) & others, "declared once"
-    assert len(gpu.EXPORTS) == 83, "include/cpuvox_gpu.h's list stays what its hosts were built against"
-    for path in (gpu.lib_path(), os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_exp.so")):
-        library = C.CDLL(path)
-        assert not [n for n in declared if not hasattr(library, n)], path
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpuSnapshot.cs")).read()
-    imports = {m.group(2): (m.group(1), [p.strip() for p in m.group(3).split(",")])
-               for m in re.finditer(r"\[DllImport\(Lib\)\]\s*public static extern\s+([A-Za-z]+)\s+(cvx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", cs, flags=re.S)}
-    assert sorted(imports) == sorted(declared)
-    for name, (c_ret, params) in declared.items():
-        ret, cs_params = imports[name]
-        assert ret == ("void" if c_ret == "void" else "int") and len(params) == len(cs_params), name
-        for i, (a, b) in enumerate(zip(params, cs_params)):
-            assert B._c_kind(a) == B._cs_kind(b), f"{name} parameter {i}: C `{a}` vs C# `{b}`"
-    for name, ctype, dtype, cs_name in (("cvx_snapshot_info", gpu.SnapshotInfo, None, "CvxSnapshotInfo"),
-                                        ("cvx_snapshot_change", gpu.SnapshotChange, gpu.SNAPSHOT_CHANGE_DTYPE, "CvxSnapshotChange"),
-                                        ("cvx_snapshot_diff_summary", gpu.SnapshotDiffSummary, None, "CvxSnapshotDiffSummary")):
-        stated = int(re.search(r"typedef struct " + name + r" \{\s*/\* (\d+) bytes", text).group(1))
-        assert C.sizeof(ctype) == stated and (dtype is None or dtype.itemsize == stated), name
-        assert re.search(r"public (?:unsafe )?struct " + cs_name + r" // " + str(stated) + r" bytes", cs), cs_name
-        body = re.search(r"struct " + cs_name + r"[^{]*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        assert B._size(body) == stated, cs_name
-        if dtype is not None:
-            assert [(n, dtype.fields[n][1]) for n in dtype.names] == [(n, getattr(ctype, n).offset) for n, _ in ctype._fields_], name
-    assert (C.sizeof(gpu.SnapshotInfo), C.sizeof(gpu.SnapshotChange), C.sizeof(gpu.SnapshotDiffSummary)) == (48, 16, 48)
-    assert gpu.SnapshotInfo.levelCount.offset == 16 and gpu.SnapshotInfo.deviceBytes.offset == 32 and gpu.SnapshotInfo.elements.offset == 40
-    assert gpu.SnapshotChange.yMin.offset == 8 and gpu.SnapshotDiffSummary.min.offset == 16 and gpu.SnapshotDiffSummary.max.offset == 28
-    assert snapshotmodel.CHANGE_DTYPE == gpu.SNAPSHOT_CHANGE_DTYPE
-    assert re.search(r"CVX_SNAPSHOT_IGNORE_COLOUR = 1\b", header) and re.search(r"CVX_SNAPSHOT_IGNORE_COLOUR = 1;", cs)
-    assert IGNORE == 1 == snapshotmodel.IGNORE_COLOUR
-
+# ---- wrappers and documents -------------------------------------------------------------------------------------------------------------------------------------------
 
 def test_the_documents_name_the_calls():
     readme = open(os.path.join(ROOT, "README.md")).read()

@@ -7,10 +7,8 @@ against the independent dense model of tests/spreadmodel.py.  Everything is inte
   direction alone; boxes that stick out of the world; field and totals equal the model's.
 - The 66 559-cell serpentine: distances above 32767 and the value 65534 (the working values are unsigned 16 bits), the last 1024 cells unreached.
 - The argument check: every rejection with its message, the order of the checks, the boundary values that pass.
-- The header against gpu.SPREAD_EXPORTS, both libraries, the ctypes structures, the numpy dtypes and host/csharp/CpuVoxGpuSpread.cs."""
-import ctypes as C
+- The Python wrappers and the documents (the header's mirrors: tests/test_abi_mirrors.py)."""
 import os
-import re
 import subprocess
 import time
 
@@ -246,53 +244,7 @@ def test_python_wrappers_check_their_arguments():
     assert gpu.seeds_array(s) is s or (gpu.seeds_array(s) == s).all()
 
 
-# ---- bindings -------------------------------------------------------------------------------------------------------------------------------------------
-
-def test_the_header_the_libraries_and_the_bindings_agree():
-    """include/cpuvox_gpu_spread.h against gpu.SPREAD_EXPORTS, the symbols of the product and the experiment library, the ctypes structures, the
-    numpy dtypes and the DllImports and structs of host/csharp/CpuVoxGpuSpread.cs (with the parsers of tests/test_csharp_binding.py)."""
-    import test_csharp_binding as B
-
-    text = open(os.path.join(ROOT, "include", "cpuvox_gpu_spread.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = {m.group(2): [p.strip() for p in m.group(3).split(",")]
-                for m in re.finditer(r"\b([a-z_0-9 ]+?[ \*]+)(cvx_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header)}
-    assert sorted(declared) == sorted(gpu.SPREAD_EXPORTS) and len(declared) == 2
-    assert not set(declared) & (set(gpu.EXPORTS) | set(gpu.HEIGHTS_EXPORTS) | set(gpu.MODELS_EXPORTS)), "declared once"
-    assert len(gpu.EXPORTS) == 83
-    for path in (gpu.lib_path(), os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_exp.so")):
-        library = C.CDLL(path)
-        assert not [n for n in declared if not hasattr(library, n)], path
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpuSpread.cs")).read()
-    imports = {m.group(2): (m.group(1), [p.strip() for p in m.group(3).split(",")])
-               for m in re.finditer(r"\[DllImport\(Lib\)\]\s*public static extern\s+([A-Za-z]+)\s+(cvx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", cs, flags=re.S)}
-    assert sorted(imports) == sorted(declared)
-    for name, params in declared.items():
-        ret, cs_params = imports[name]
-        assert ret == "int" and len(params) == len(cs_params), name
-        for i, (a, b) in enumerate(zip(params, cs_params)):
-            assert B._c_kind(a) == B._cs_kind(b), f"{name} parameter {i}: C `{a}` vs C# `{b}`"
-    for name, ctype, dtype, cs_name in (("cvx_spread_params", gpu.SpreadParams, None, "CvxSpreadParams"),
-                                        ("cvx_spread_seed", gpu.SpreadSeed, gpu.SPREAD_SEED_DTYPE, "CvxSpreadSeed"),
-                                        ("cvx_spread_summary", gpu.SpreadSummary, gpu.SPREAD_SUMMARY_DTYPE, "CvxSpreadSummary")):
-        stated = int(re.search(r"typedef struct " + name + r" \{\s*/\* (\d+) bytes", text).group(1))
-        assert C.sizeof(ctype) == stated and (dtype is None or dtype.itemsize == stated), name
-        assert re.search(r"public (?:unsafe )?struct " + cs_name + r" // " + str(stated) + r" bytes", cs), cs_name
-        if dtype is not None:
-            assert [(n, dtype.fields[n][1]) for n in dtype.names] == [(n, getattr(ctype, n).offset) for n, _ in ctype._fields_], name
-    assert (C.sizeof(gpu.SpreadParams), C.sizeof(gpu.SpreadSeed), C.sizeof(gpu.SpreadSummary)) == (40, 16, 40)
-    assert gpu.SpreadParams.medium.offset == 24 and gpu.SpreadSummary.tileVisits.offset == 32 and gpu.SpreadSeed.start.offset == 12
-    for name, value in (("CVX_SPREAD_MAX_SEEDS", gpu.SPREAD_MAX_SEEDS), ("CVX_SPREAD_MAX_STEPS", gpu.SPREAD_MAX_STEPS),
-                        ("CVX_SPREAD_UNREACHED", gpu.SPREAD_UNREACHED), ("CVX_SPREAD_BLOCKED", gpu.SPREAD_BLOCKED)):
-        assert re.search(r"#define " + name + r"\s+\(?" + str(value) + r"\)?\s", header) and re.search(name + r" = " + str(value) + ";", cs), name
-    assert re.search(r"CVX_SPREAD_AIR = 0, CVX_SPREAD_SOLID = 1", header) and (AIR, SOLID) == (0, 1) == (spreadmodel.AIR, spreadmodel.SOLID)
-    assert (UNREACHED, BLOCKED) == (spreadmodel.UNREACHED, spreadmodel.BLOCKED)
-    # the tile: the public header's macros are the constants of the rules and of the kernel, and gpu.SPREAD_TILE
-    tile = tuple(int(re.search(r"#define CVX_SPREAD_TILE_" + a + r"\s+(\d+)", header).group(1)) for a in "XYZ")
-    assert tile == gpu.SPREAD_TILE
-    rules_h = open(os.path.join(ROOT, "cpuvox_amd", "csrc", "cvx_spread.h")).read()
-    assert "kSpreadTileX = CVX_SPREAD_TILE_X, kSpreadTileY = CVX_SPREAD_TILE_Y, kSpreadTileZ = CVX_SPREAD_TILE_Z" in rules_h
-
+# ---- wrappers and documents -------------------------------------------------------------------------------------------------------------------------------------------
 
 def test_the_documents_name_the_call():
     readme = open(os.path.join(ROOT, "README.md")).read()

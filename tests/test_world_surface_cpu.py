@@ -9,7 +9,7 @@
 - Properties, of the model and of the rule: unitFaces is the sum of the lengths, the surface of a whole world with air outside is closed, and
   eight sub-boxes give the unit faces of one call.
 - cvx_surface_triangles: winding, areas, planes, indices and the colour round trip through the stamp rule's packing.
-- The struct layouts of the header against the ctypes, numpy and C# mirrors; the calls without a context / world and every INVALID_ARGUMENT case."""
+- The calls without a context / world and every INVALID_ARGUMENT case (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
 import re
@@ -284,33 +284,6 @@ def test_triangles_are_wound_outward_on_the_face_plane(rules):
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_struct_layouts_match_the_mirrors():
-    assert C.sizeof(gpu.SurfaceQuad) == gpu.SURFACE_QUAD_DTYPE.itemsize == surfacemodel.QUAD_DTYPE.itemsize == 24
-    assert C.sizeof(gpu.SurfaceSummary) == gpu.SURFACE_SUMMARY_DTYPE.itemsize == 64
-    assert [f[0] for f in gpu.SurfaceQuad._fields_] == list(gpu.SURFACE_QUAD_DTYPE.names) == list(surfacemodel.QUAD_DTYPE.names)
-    assert [f[0] for f in gpu.SurfaceSummary._fields_] == list(gpu.SURFACE_SUMMARY_DTYPE.names) == list(surfacemodel.SUMMARY_NAMES)
-    assert [getattr(gpu.SurfaceQuad, n).offset for n in ("voxel", "face", "length", "argb")] == [gpu.SURFACE_QUAD_DTYPE.fields[n][1] for n in ("voxel", "face", "length", "argb")] == [0, 12, 16, 20]
-    assert [getattr(gpu.SurfaceSummary, n).offset for n in ("quads", "unitFaces", "quadsPerFace")] == [0, 8, 16]
-    header = open(os.path.join(ROOT, "include", "cpuvox_gpu.h")).read()
-    body = re.search(r"typedef struct cvx_surface_quad \{[^\n]*\n(.*?)\} cvx_surface_quad;", header, flags=re.S).group(1)
-    assert re.findall(r"^\s*u?int(?:32|64)_t ([a-zA-Z_]+)", body, flags=re.M) == [f[0] for f in gpu.SurfaceQuad._fields_]
-    body = re.search(r"typedef struct cvx_surface_summary \{[^\n]*\n(.*?)\} cvx_surface_summary;", header, flags=re.S).group(1)
-    assert re.findall(r"^\s*int64_t ([a-zA-Z_]+)", body, flags=re.M) == [f[0] for f in gpu.SurfaceSummary._fields_]
-    assert int(re.search(r"#define CVX_SURFACE_OUTSIDE_DEFAULT (0x[0-9A-Fa-f]+)", header).group(1), 16) == gpu.SURFACE_OUTSIDE_DEFAULT == surfacemodel.OUTSIDE_DEFAULT == 0x04
-    assert int(re.search(r"CVX_SURFACE_IGNORE_COLOUR = (\d+)", header).group(1)) == gpu.SURFACE_IGNORE_COLOUR == surfacemodel.IGNORE_COLOUR == 1
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpu.cs")).read()
-    sizes = {"int": 4, "uint": 4, "long": 8}
-    for name, want in (("SurfaceQuad", 24), ("SurfaceSummary", 64)):
-        body = re.search(r"public (?:unsafe )?struct " + name + r"\s*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        total = 0
-        for m in re.finditer(r"public\s+(fixed\s+)?(int|uint|long)\s+([^;]+);", body):
-            for n in m.group(3).split(","):
-                k = re.search(r"\[(\d+)\]", n)
-                total += sizes[m.group(2)] * (int(k.group(1)) if k else 1)
-        assert total == want, (name, total)
-    assert re.search(r"CVX_SURFACE_OUTSIDE_DEFAULT = 0x04, CVX_SURFACE_IGNORE_COLOUR = 1;", cs)
-
 
 def test_surface_fails_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()

@@ -8,11 +8,9 @@ independent dense model of tests/surfacerectsmodel.py.
 - The slab (130 x 3 x 70 voxels of one colour, 18 600 strips, 6 rectangles), a solid block coloured as a checkerboard (nothing merges with
   colours, everything without), an L-shaped floor, a box cut in two.
 - cvx_surface_rect_triangles: equal to cvx_surface_triangles on single strips, wound outward on the face plane, areas that sum to unitFaces.
-- The header against gpu.SURFACE_RECTS_EXPORTS, both libraries, the ctypes structures, the numpy dtypes and host/csharp/CpuVoxGpuSurfaceRects.cs;
-  the calls without a context / world and every INVALID_ARGUMENT case."""
+- The calls without a context / world and every INVALID_ARGUMENT case (the header's mirrors: tests/test_abi_mirrors.py)."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -255,47 +253,6 @@ def test_triangles_point_outward_and_their_areas_sum_to_the_unit_faces():
 
 
 # ---- layouts and entry points ------------------------------------------------------------------------------------------------------------------
-
-def test_the_header_the_libraries_and_the_bindings_agree():
-    """include/cpuvox_gpu_surface_rects.h against gpu.SURFACE_RECTS_EXPORTS, the symbols of the product and the experiment library, the ctypes
-    structures, the numpy dtypes and the DllImports and structs of host/csharp/CpuVoxGpuSurfaceRects.cs (with the parsers of
-    tests/test_csharp_binding.py)."""
-    import test_csharp_binding as B
-
-    text = open(os.path.join(ROOT, "include", "cpuvox_gpu_surface_rects.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = {m.group(2): [p.strip() for p in m.group(3).split(",")]
-                for m in re.finditer(r"\b([a-z_0-9 ]+?[ \*]+)(cvx_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header)}
-    assert sorted(declared) == sorted(gpu.SURFACE_RECTS_EXPORTS) and len(declared) == 3
-    assert not set(declared) & (set(gpu.EXPORTS) | set(gpu.HEIGHTS_EXPORTS) | set(gpu.MODELS_EXPORTS) | set(gpu.SPREAD_EXPORTS)), "declared once"
-    for path in (gpu.lib_path(), os.path.join(ROOT, "cpuvox_amd", "libcpuvox_gpu_exp.so")):
-        library = C.CDLL(path)
-        assert not [n for n in declared if not hasattr(library, n)], path
-    cs = open(os.path.join(ROOT, "host", "csharp", "CpuVoxGpuSurfaceRects.cs")).read()
-    imports = {m.group(2): (m.group(1), [p.strip() for p in m.group(3).split(",")])
-               for m in re.finditer(r"\[DllImport\(Lib\)\]\s*public static extern\s+([A-Za-z]+)\s+(cvx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", cs, flags=re.S)}
-    assert sorted(imports) == sorted(declared)
-    for name, params in declared.items():
-        ret, cs_params = imports[name]
-        assert ret == "int" and len(params) == len(cs_params), name
-        for i, (a, b) in enumerate(zip(params, cs_params)):
-            assert B._c_kind(a) == B._cs_kind(b), f"{name} parameter {i}: C `{a}` vs C# `{b}`"
-    sizes = {"int": 4, "uint": 4, "long": 8}
-    for name, ctype, dtype, cs_name, want in (("cvx_surface_rect", gpu.SurfaceRect, gpu.SURFACE_RECT_DTYPE, "CvxSurfaceRect", 32),
-                                              ("cvx_surface_rects_summary", gpu.SurfaceRectsSummary, gpu.SURFACE_RECTS_SUMMARY_DTYPE, "CvxSurfaceRectsSummary", 72)):
-        stated = int(re.search(r"typedef struct " + name + r" \{\s*/\* (\d+) bytes", text).group(1))
-        assert C.sizeof(ctype) == dtype.itemsize == stated == want, name
-        assert [(n, dtype.fields[n][1]) for n in dtype.names] == [(n, getattr(ctype, n).offset) for n, _ in ctype._fields_], name
-        body = re.search(r"typedef struct " + name + r" \{[^\n]*\n(.*?)\} " + name + ";", text, flags=re.S).group(1)
-        assert re.findall(r"^\s*u?int(?:32|64)_t ([a-zA-Z_]+)", body, flags=re.M) == [n for n, _ in ctype._fields_], name
-        assert re.search(r"public (?:unsafe )?struct " + cs_name + r" // " + str(stated) + r" bytes", cs), cs_name
-        cs_body = re.search(r"public (?:unsafe )?struct " + cs_name + r"[^\{]*\{(.*?)\n\t\}", cs, flags=re.S).group(1)
-        fields = [(m.group(2), m.group(3), int(m.group(4) or 1)) for m in re.finditer(r"public\s+(fixed\s+)?(int|uint|long)\s+([a-zA-Z_]+)(?:\[(\d+)\])?;", cs_body)]
-        assert [n for _, n, _ in fields] == [n for n, _ in ctype._fields_] and sum(sizes[t] * k for t, _, k in fields) == want, cs_name
-    assert gpu.SURFACE_RECT_DTYPE == model.RECT_DTYPE and list(gpu.SURFACE_RECTS_SUMMARY_DTYPE.names) == list(model.SUMMARY_NAMES)
-    assert [gpu.SurfaceRect.size.offset, gpu.SurfaceRect.face.offset, gpu.SurfaceRect.argb.offset] == [12, 24, 28]
-    assert [gpu.SurfaceRectsSummary.strips.offset, gpu.SurfaceRectsSummary.rectsPerFace.offset] == [8, 24]
-
 
 def test_the_calls_fail_cleanly_without_a_context_or_world(rules):
     L = gpu.lib()
