@@ -60,6 +60,9 @@ SNAPSHOT_EXPORTS = ["cvx_world_snapshot", "cvx_snapshot_info_get", "cvx_world_sn
                     "cvx_snapshot_destroy"]
 # include/cpuvox_gpu_lift.h: the floating pieces as models with mass moments
 LIFT_EXPORTS = ["cvx_world_lift_pieces", "cvx_world_lift_pieces_device", "cvx_lifted_piece_mass"]
+# include/cpuvox_gpu_contacts.h: where placed models touch the world.  A family of its own (prefix cvxc_, as the host library's cvxh_), so not a row
+# of ABI_HEADERS: tests/test_abi_contacts.py checks this list against its header, the libraries, the C# file and the argtypes of _bind.
+CONTACTS_EXPORTS = ["cvxc_world_contacts", "cvxc_world_contacts_device", "cvxc_contact_response"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -134,6 +137,19 @@ class Model(C.Structure):
 
 class ModelInstance(C.Structure):
     _fields_ = [("toModel", ModelMap), ("boxMin", C.c_int32 * 3), ("boxMax", C.c_int32 * 3), ("model", C.c_int32), ("op", C.c_int32)]
+
+
+class ContactResult(C.Structure):  # cvxc_contact_result
+    _fields_ = [("voxels", C.c_int64), ("overlap", C.c_int64), ("points", C.c_int64), ("firstPoint", C.c_int64), ("sum", C.c_uint64 * 3),
+                ("normal", C.c_int64 * 3), ("origin", C.c_int32 * 3), ("min", C.c_int32 * 3), ("max", C.c_int32 * 3), ("pad_", C.c_int32)]
+
+
+class ContactPoint(C.Structure):  # cvxc_contact_point
+    _fields_ = [("voxel", C.c_int32 * 3), ("instance", C.c_int32), ("faces", C.c_int32), ("argb", C.c_uint32)]
+
+
+class ContactsSummary(C.Structure):  # cvxc_contacts_summary
+    _fields_ = [("touching", C.c_int64), ("overlap", C.c_int64), ("points", C.c_int64), ("voxels", C.c_int64)]
 
 
 class SpreadParams(C.Structure):  # cvx_spread_params
@@ -275,6 +291,7 @@ SPREAD_SEED_DTYPE, SPREAD_SUMMARY_DTYPE = np.dtype(SpreadSeed), np.dtype(SpreadS
 SNAPSHOT_CHANGE_DTYPE = np.dtype(SnapshotChange)
 SURFACE_QUAD_DTYPE, SURFACE_SUMMARY_DTYPE = np.dtype(SurfaceQuad), np.dtype(SurfaceSummary)
 SURFACE_RECT_DTYPE, SURFACE_RECTS_SUMMARY_DTYPE = np.dtype(SurfaceRect), np.dtype(SurfaceRectsSummary)
+CONTACT_RESULT_DTYPE, CONTACT_POINT_DTYPE, CONTACTS_SUMMARY_DTYPE = np.dtype(ContactResult), np.dtype(ContactPoint), np.dtype(ContactsSummary)
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
 
@@ -374,6 +391,17 @@ def lifted_piece_mass(piece):
     if rc != 0:
         raise ValueError("lifted_piece_mass: the piece has no voxels")
     return centre, inertia
+
+
+def contact_response(result):
+    """cvxc_contact_response of one CONTACT_RESULT_DTYPE element: (centre of the overlap (3,), unit normal (3,) -- the way to push the body, 0
+    when the faces cancel --, depth = overlap / |normal|) in float64; a body sunk k layers into flat ground gives depth k.  A pure host call.
+    ValueError for a result without overlap."""
+    one = np.ascontiguousarray(np.asarray(result, dtype=CONTACT_RESULT_DTYPE).reshape(1))
+    centre, normal, depth = np.zeros(3), np.zeros(3), C.c_double()
+    if lib().cvxc_contact_response(one.ctypes.data, centre.ctypes.data, normal.ctypes.data, C.byref(depth)) != 0:
+        raise ValueError("contact_response: the result has no overlap")
+    return centre, normal, depth.value
 
 
 def bodies_array(bodies) -> np.ndarray:
@@ -594,6 +622,10 @@ def _bind(path: str) -> C.CDLL:
                                         C.POINTER(LiftSummary), C.POINTER(C.c_float)]
     L.cvx_world_lift_pieces_device.argtypes = L.cvx_world_lift_pieces.argtypes
     L.cvx_lifted_piece_mass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvxc_world_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ContactsSummary),
+                                      C.POINTER(C.c_float)]
+    L.cvxc_world_contacts_device.argtypes = L.cvxc_world_contacts.argtypes
+    L.cvxc_contact_response.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
     L.cvx_shard_plan_destroy.restype = None
@@ -1039,27 +1071,45 @@ class Context:
             raise ValueError("instances are gpu.ModelInstance structures")
         return (ModelInstance * len(items))(*items)
 
+    @staticmethod
+    def _models(models, who):
+        """The cvx_model descriptors of a list of (argb, solid) host arrays, and the arrays they point to."""
+        keep, descriptors = [], (Model * max(len(models), 1))()
+        for k, entry in enumerate(models):
+            if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+                raise ValueError(f"{who}: a model is a pair (argb, solid)")
+            argb, solid = entry
+            if argb is not None and np.asarray(argb).dtype.kind not in "iu":
+                raise ValueError(f"{who}: argb is an integer array of shape (X, Z, Y)")
+            a = np.ascontiguousarray(argb, dtype=np.uint32) if argb is not None else None
+            m = np.ascontiguousarray(solid).astype(np.bool_, copy=False).view(np.uint8) if solid is not None else None
+            shape = a.shape if a is not None else (m.shape if m is not None else None)
+            if shape is None or len(shape) != 3 or (a is not None and m is not None and a.shape != m.shape):
+                raise ValueError(f"{who}: argb and solid are arrays of one shape (X, Z, Y)")
+            keep += [a, m]
+            descriptors[k].size[:] = [shape[0], shape[2], shape[1]]
+            descriptors[k].argb = a.ctypes.data if a is not None else None
+            descriptors[k].solid = m.ctypes.data if m is not None else None
+        return descriptors, keep
+
+    @staticmethod
+    def _device_models(models, who):
+        """The cvx_model descriptors of a list of ((sx, sy, sz), argb_ptr, solid_ptr)."""
+        descriptors = (Model * max(len(models), 1))()
+        for k, entry in enumerate(models):
+            if not isinstance(entry, (tuple, list)) or len(entry) != 3 or len(tuple(entry[0])) != 3:
+                raise ValueError(f"{who}: a model is ((sx, sy, sz), argb_ptr, solid_ptr)")
+            descriptors[k].size[:] = [int(v) for v in entry[0]]
+            descriptors[k].argb = entry[1] or None
+            descriptors[k].solid = entry[2] or None
+        return descriptors
+
     def place_models(self, models, instances, level_count: int = LOD_LEVELS - 1) -> float:
         """Places instances of voxel models into LOD 0, in order, and rebuilds LOD 1..level_count over their boxes.  `models`: a list of
         (argb, solid) -- uint32 colour words of shape (X, Z, Y) (None for a model only BRUSH_CARVE instances use) and an optional mask of the same
         shape (without it the voxels with a colour word other than 0 are set).  `instances`: gpu.ModelInstance structures (gpu.model_instance
         makes them from a matrix).  Returns the device milliseconds (0 when every box lies outside the world)."""
-        keep, descriptors = [], (Model * max(len(models), 1))()
-        for k, entry in enumerate(models):
-            if not isinstance(entry, (tuple, list)) or len(entry) != 2:
-                raise ValueError("place_models: a model is a pair (argb, solid)")
-            argb, solid = entry
-            if argb is not None and np.asarray(argb).dtype.kind not in "iu":
-                raise ValueError("place_models: argb is an integer array of shape (X, Z, Y)")
-            a = np.ascontiguousarray(argb, dtype=np.uint32) if argb is not None else None
-            m = np.ascontiguousarray(solid).astype(np.bool_, copy=False).view(np.uint8) if solid is not None else None
-            shape = a.shape if a is not None else (m.shape if m is not None else None)
-            if shape is None or len(shape) != 3 or (a is not None and m is not None and a.shape != m.shape):
-                raise ValueError("place_models: argb and solid are arrays of one shape (X, Z, Y)")
-            keep += [a, m]
-            descriptors[k].size[:] = [shape[0], shape[2], shape[1]]
-            descriptors[k].argb = a.ctypes.data if a is not None else None
-            descriptors[k].solid = m.ctypes.data if m is not None else None
+        descriptors, keep = self._models(models, "place_models")  # noqa: F841  (keep: the arrays the descriptors point to)
         inst = self._instances(instances)
         ms = C.c_float()
         self._check(lib().cvx_world_place_models(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), int(level_count), C.byref(ms)))
@@ -1069,18 +1119,56 @@ class Context:
         """place_models from device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr), the addresses of sx * sz * sy uint32 /
         uint8 laid out (X, Z, Y) (e.g. a torch tensor's data_ptr(); either may be 0, not both), read on the context's stream: the arrays must
         be complete when the call is made."""
-        descriptors = (Model * max(len(models), 1))()
-        for k, entry in enumerate(models):
-            if not isinstance(entry, (tuple, list)) or len(entry) != 3 or len(tuple(entry[0])) != 3:
-                raise ValueError("place_models_device: a model is ((sx, sy, sz), argb_ptr, solid_ptr)")
-            descriptors[k].size[:] = [int(v) for v in entry[0]]
-            descriptors[k].argb = entry[1] or None
-            descriptors[k].solid = entry[2] or None
+        descriptors = self._device_models(models, "place_models_device")
         inst = self._instances(instances)
         ms = C.c_float()
         self._check(lib().cvx_world_place_models_device(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), int(level_count),
                                                         C.byref(ms)))
         return ms.value
+
+    # -- where placed models touch the world (cvxc_world_contacts, include/cpuvox_gpu_contacts.h) --
+    def _contacts(self, entry, descriptors, model_count, instances, solid_outside, results_ptr, points_ptr, capacity):
+        inst = self._instances(instances)
+        summary, ms = ContactsSummary(), C.c_float()
+        self._check(entry(self._h, C.addressof(descriptors), model_count, C.addressof(inst), len(inst), int(solid_outside), results_ptr, points_ptr or None,
+                          int(capacity), C.byref(summary), C.byref(ms)))
+        return {name: int(getattr(summary, name)) for name in CONTACTS_SUMMARY_DTYPE.names}, ms.value
+
+    def world_contacts(self, models, instances, solid_outside: int = SURFACE_OUTSIDE_DEFAULT, capacity=None):
+        """Where every instance, placed as place_models would place it, touches the world: (one CONTACT_RESULT_DTYPE element per instance, the first
+        `capacity` contact points as a CONTACT_POINT_DTYPE array in (instance, x, z, descending y) order, the totals of cvxc_contacts_summary
+        as a dict, device milliseconds).  The overlap of an instance is exactly the voxels a BRUSH_FILL of it would write that are already
+        solid; `normal` sums the open faces of those voxels and points out of the world's solid.  `models` and `instances` as place_models'
+        (an instance's op is not read); `solid_outside` bits 0..5 = -X,+X,-Y,+Y,-Z,+Z: what lies across a face of the world.  capacity=0 asks
+        for the results alone; capacity=None asks for them first and then for every point (the milliseconds are the second call's)."""
+        descriptors, keep = self._models(models, "world_contacts")  # noqa: F841  (keep: the arrays the descriptors point to)
+        inst = self._instances(instances)
+        results = np.zeros(len(inst), dtype=CONTACT_RESULT_DTYPE)
+        call = lib().cvxc_world_contacts
+        if capacity is None:
+            totals, _ = self._contacts(call, descriptors, len(models), inst, solid_outside, results.ctypes.data if len(inst) else None, None, 0)
+            capacity = totals["points"]
+        points = np.zeros(max(int(capacity), 0), dtype=CONTACT_POINT_DTYPE)
+        totals, ms = self._contacts(call, descriptors, len(models), inst, solid_outside, results.ctypes.data if len(inst) else None,
+                                    points.ctypes.data if points.size else None, capacity)
+        return results, (points if points.size <= totals["points"] else points[:totals["points"]].copy()), totals, ms
+
+    def world_contacts_device(self, models, instances, results_tensor, points_tensor=None, solid_outside: int = SURFACE_OUTSIDE_DEFAULT):
+        """world_contacts on device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr) as place_models_device's (gpu.lifted_model of
+        device pools gives one), `results_tensor` a contiguous device tensor of at least 120 bytes per instance, `points_tensor` (or None: the
+        results alone) one whose bytes / 24 are the capacity; entries beyond the points found are left alone.  Returns (the totals as a dict,
+        device milliseconds) once the summary is on the host: the tensors are complete then."""
+        descriptors = self._device_models(models, "world_contacts_device")
+        inst = self._instances(instances)
+
+        def checked(tensor, item_bytes, at_least):
+            nbytes = tensor.numel() * tensor.element_size()
+            if not tensor.is_cuda or not tensor.is_contiguous() or nbytes < at_least * item_bytes:
+                raise ValueError(f"world_contacts_device: a contiguous device tensor of at least {at_least} x {item_bytes} bytes")
+            return tensor.data_ptr(), nbytes // item_bytes
+        results_ptr, _ = checked(results_tensor, C.sizeof(ContactResult), len(inst))
+        points_ptr, capacity = checked(points_tensor, C.sizeof(ContactPoint), 0) if points_tensor is not None else (None, 0)
+        return self._contacts(lib().cvxc_world_contacts_device, descriptors, len(models), inst, solid_outside, results_ptr, points_ptr if capacity else None, capacity)
 
     @staticmethod
     def _model_read(size, to_world):
