@@ -63,6 +63,9 @@ LIFT_EXPORTS = ["cvx_world_lift_pieces", "cvx_world_lift_pieces_device", "cvx_li
 # include/cpuvox_gpu_contacts.h: where placed models touch the world.  A family of its own (prefix cvxc_, as the host library's cvxh_), so not a row
 # of ABI_HEADERS: tests/test_abi_contacts.py checks this list against its header, the libraries, the C# file and the argtypes of _bind.
 CONTACTS_EXPORTS = ["cvxc_world_contacts", "cvxc_world_contacts_device", "cvxc_contact_response"]
+# include/cpuvox_gpu_pair_contacts.h: where placed models touch each other.  Another family of its own (prefix cvxp_), no row of ABI_HEADERS either:
+# tests/test_abi_pair_contacts.py checks it.
+PAIR_CONTACTS_EXPORTS = ["cvxp_model_contacts", "cvxp_model_contacts_device", "cvxp_box_pairs", "cvxp_pair_response"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -122,6 +125,7 @@ SPREAD_MAX_SEEDS, SPREAD_MAX_STEPS = 4096, 65534
 SPREAD_TILE = (8, 64, 8)                         # CVX_SPREAD_TILE_X / _Y / _Z: the (x, y, z) extents of the tile a workgroup relaxes
 SNAPSHOT_IGNORE_COLOUR = 1                       # cvx_world_snapshot_diff: flags
 LIFT_COPY, LIFT_REMOVE = 0, 1                    # cvx_world_lift_pieces: op
+PAIR_CONTACTS_MAX_PAIRS = 65536                  # CVXP_MAX_PAIRS: cvxp_model_contacts, pairCount
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -150,6 +154,20 @@ class ContactPoint(C.Structure):  # cvxc_contact_point
 
 class ContactsSummary(C.Structure):  # cvxc_contacts_summary
     _fields_ = [("touching", C.c_int64), ("overlap", C.c_int64), ("points", C.c_int64), ("voxels", C.c_int64)]
+
+
+class PairResult(C.Structure):  # cvxp_pair_result
+    _fields_ = [("overlap", C.c_int64), ("points", C.c_int64), ("firstPoint", C.c_int64), ("sum", C.c_uint64 * 3), ("pushA", C.c_int64 * 3),
+                ("pushB", C.c_int64 * 3), ("origin", C.c_int32 * 3), ("min", C.c_int32 * 3), ("max", C.c_int32 * 3), ("a", C.c_int32), ("b", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class PairPoint(C.Structure):  # cvxp_pair_point
+    _fields_ = [("voxel", C.c_int32 * 3), ("pair", C.c_int32), ("facesA", C.c_int32), ("facesB", C.c_int32), ("argbA", C.c_uint32), ("argbB", C.c_uint32)]
+
+
+class PairsSummary(C.Structure):  # cvxp_pairs_summary
+    _fields_ = [("touching", C.c_int64), ("overlap", C.c_int64), ("points", C.c_int64), ("jobs", C.c_int64)]
 
 
 class SpreadParams(C.Structure):  # cvx_spread_params
@@ -292,6 +310,7 @@ SNAPSHOT_CHANGE_DTYPE = np.dtype(SnapshotChange)
 SURFACE_QUAD_DTYPE, SURFACE_SUMMARY_DTYPE = np.dtype(SurfaceQuad), np.dtype(SurfaceSummary)
 SURFACE_RECT_DTYPE, SURFACE_RECTS_SUMMARY_DTYPE = np.dtype(SurfaceRect), np.dtype(SurfaceRectsSummary)
 CONTACT_RESULT_DTYPE, CONTACT_POINT_DTYPE, CONTACTS_SUMMARY_DTYPE = np.dtype(ContactResult), np.dtype(ContactPoint), np.dtype(ContactsSummary)
+PAIR_RESULT_DTYPE, PAIR_POINT_DTYPE, PAIRS_SUMMARY_DTYPE = np.dtype(PairResult), np.dtype(PairPoint), np.dtype(PairsSummary)
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
 
@@ -401,6 +420,39 @@ def contact_response(result):
     centre, normal, depth = np.zeros(3), np.zeros(3), C.c_double()
     if lib().cvxc_contact_response(one.ctypes.data, centre.ctypes.data, normal.ctypes.data, C.byref(depth)) != 0:
         raise ValueError("contact_response: the result has no overlap")
+    return centre, normal, depth.value
+
+
+def _instance_array(instances):
+    if isinstance(instances, C.Array) and instances._type_ is ModelInstance:
+        return instances
+    items = list(instances)
+    if not all(isinstance(i, ModelInstance) for i in items):
+        raise ValueError("instances are gpu.ModelInstance structures")
+    return (ModelInstance * len(items))(*items)
+
+
+def box_pairs(instances, margin: int = 0) -> np.ndarray:
+    """cvxp_box_pairs, the broad phase of model_contacts: every (a, b), a < b, whose boxes intersect once each is widened by `margin` voxels on
+    every side, as an (n, 2) int32 array in lexicographic order.  A pure host call."""
+    inst = _instance_array(instances)
+    found = C.c_int64()
+    if lib().cvxp_box_pairs(C.addressof(inst) if len(inst) else None, len(inst), int(margin), None, 0, C.byref(found)) != 0:
+        raise ValueError("box_pairs: margin is 0 .. 2^20")
+    pairs = np.zeros((found.value, 2), dtype=np.int32)
+    if found.value:
+        lib().cvxp_box_pairs(C.addressof(inst), len(inst), int(margin), pairs.ctypes.data, found.value, C.byref(found))
+    return pairs
+
+
+def pair_response(result, which: int):
+    """cvxp_pair_response of one PAIR_RESULT_DTYPE element: (centre of the overlap (3,), unit vector (3,) of pushA (which = 0: the way to move
+    body a out of b) or pushB (which = 1), depth = overlap / |push|) in float64.  A pure host call.  ValueError for a result without overlap or
+    another `which`."""
+    one = np.ascontiguousarray(np.asarray(result, dtype=PAIR_RESULT_DTYPE).reshape(1))
+    centre, normal, depth = np.zeros(3), np.zeros(3), C.c_double()
+    if lib().cvxp_pair_response(one.ctypes.data, int(which), centre.ctypes.data, normal.ctypes.data, C.byref(depth)) != 0:
+        raise ValueError("pair_response: the result has no overlap, or `which` is neither 0 nor 1")
     return centre, normal, depth.value
 
 
@@ -626,6 +678,11 @@ def _bind(path: str) -> C.CDLL:
                                       C.POINTER(C.c_float)]
     L.cvxc_world_contacts_device.argtypes = L.cvxc_world_contacts.argtypes
     L.cvxc_contact_response.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    L.cvxp_model_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.POINTER(PairsSummary), C.POINTER(C.c_float)]
+    L.cvxp_model_contacts_device.argtypes = L.cvxp_model_contacts.argtypes
+    L.cvxp_box_pairs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.cvxp_pair_response.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
     L.cvx_shard_plan_destroy.restype = None
@@ -1064,12 +1121,7 @@ class Context:
     # -- voxel models at any orientation and scale (cvx_world_place_models, cvx_world_read_model) --
     @staticmethod
     def _instances(instances):
-        if isinstance(instances, C.Array) and instances._type_ is ModelInstance:
-            return instances
-        items = list(instances)
-        if not all(isinstance(i, ModelInstance) for i in items):
-            raise ValueError("instances are gpu.ModelInstance structures")
-        return (ModelInstance * len(items))(*items)
+        return _instance_array(instances)
 
     @staticmethod
     def _models(models, who):
@@ -1169,6 +1221,58 @@ class Context:
         results_ptr, _ = checked(results_tensor, C.sizeof(ContactResult), len(inst))
         points_ptr, capacity = checked(points_tensor, C.sizeof(ContactPoint), 0) if points_tensor is not None else (None, 0)
         return self._contacts(lib().cvxc_world_contacts_device, descriptors, len(models), inst, solid_outside, results_ptr, points_ptr if capacity else None, capacity)
+
+    # -- where placed models touch each other (cvxp_model_contacts, include/cpuvox_gpu_pair_contacts.h) --
+    @staticmethod
+    def _pairs(pairs, inst, who):
+        p = box_pairs(inst) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"{who}: pairs is an (n, 2) integer array of indices into instances")
+        return p
+
+    def _pair_contacts(self, entry, descriptors, model_count, inst, pairs, results_ptr, points_ptr, capacity):
+        summary, ms = PairsSummary(), C.c_float()
+        self._check(entry(self._h, C.addressof(descriptors), model_count, C.addressof(inst), len(inst), pairs.ctypes.data if len(pairs) else None, len(pairs),
+                          results_ptr, points_ptr or None, int(capacity), C.byref(summary), C.byref(ms)))
+        return {name: int(getattr(summary, name)) for name in PAIRS_SUMMARY_DTYPE.names}, ms.value
+
+    def model_contacts(self, models, instances, pairs=None, capacity=None):
+        """Where placed instances touch EACH OTHER; no world is read and none need be uploaded: (one PAIR_RESULT_DTYPE element per pair, the first
+        `capacity` contact points as a PAIR_POINT_DTYPE array in (pair, x, z, descending y) order, the totals of cvxp_pairs_summary as a dict,
+        device milliseconds).  `models` and `instances` as world_contacts'; `pairs` an (n, 2) array of indices into instances, or None: the pairs
+        gpu.box_pairs finds.  A pair's overlap is the voxels in both bodies; pushA sums the open faces of body b over them (the way to move a),
+        pushB those of body a.  capacity=0 asks for the results alone; capacity=None asks for them first and then for every point (the
+        milliseconds are the second call's)."""
+        descriptors, keep = self._models(models, "model_contacts")  # noqa: F841  (keep: the arrays the descriptors point to)
+        inst = self._instances(instances)
+        p = self._pairs(pairs, inst, "model_contacts")
+        results = np.zeros(len(p), dtype=PAIR_RESULT_DTYPE)
+        call = lib().cvxp_model_contacts
+        results_ptr = results.ctypes.data if len(p) else None
+        if capacity is None:
+            totals, _ = self._pair_contacts(call, descriptors, len(models), inst, p, results_ptr, None, 0)
+            capacity = totals["points"]
+        points = np.zeros(max(int(capacity), 0), dtype=PAIR_POINT_DTYPE)
+        totals, ms = self._pair_contacts(call, descriptors, len(models), inst, p, results_ptr, points.ctypes.data if points.size else None, capacity)
+        return results, (points if points.size <= totals["points"] else points[:totals["points"]].copy()), totals, ms
+
+    def model_contacts_device(self, models, instances, pairs, results_tensor, points_tensor=None):
+        """model_contacts on device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr) as place_models_device's, `pairs` an (n, 2)
+        host array (None: gpu.box_pairs), `results_tensor` a contiguous device tensor of at least 144 bytes per pair, `points_tensor` (or None:
+        the results alone) one whose bytes / 32 are the capacity; entries beyond the points found are left alone.  Returns (the totals as a
+        dict, device milliseconds) once the summary is on the host: the tensors are complete then."""
+        descriptors = self._device_models(models, "model_contacts_device")
+        inst = self._instances(instances)
+        p = self._pairs(pairs, inst, "model_contacts_device")
+
+        def checked(tensor, item_bytes, at_least):
+            nbytes = tensor.numel() * tensor.element_size()
+            if not tensor.is_cuda or not tensor.is_contiguous() or nbytes < at_least * item_bytes:
+                raise ValueError(f"model_contacts_device: a contiguous device tensor of at least {at_least} x {item_bytes} bytes")
+            return tensor.data_ptr(), nbytes // item_bytes
+        results_ptr, _ = checked(results_tensor, C.sizeof(PairResult), len(p))
+        points_ptr, capacity = checked(points_tensor, C.sizeof(PairPoint), 0) if points_tensor is not None else (None, 0)
+        return self._pair_contacts(lib().cvxp_model_contacts_device, descriptors, len(models), inst, p, results_ptr, points_ptr if capacity else None, capacity)
 
     @staticmethod
     def _model_read(size, to_world):

@@ -12,7 +12,8 @@ extern "C" {
 #endif
 
 /* cvx_world_lift_pieces / _device: what a carve has cut loose, each piece as a dense array of its own voxels and the integer sums a host needs
- * for its mass, centre of mass and inertia tensor.  The loop it closes: carve, lift (REMOVE), integrate the rigid bodies on the host, per frame
+ * for its mass, centre of mass and inertia tensor.  The loop it closes: carve, lift (REMOVE), integrate the rigid bodies on the host (every step cvxc_world_contacts
+ * says where a body touches the world and cvxp_model_contacts where two bodies touch each other), per frame
  * cvx_world_snapshot + cvx_world_place_models_device of the lifted arrays + restore, and a last FILL when a body comes to rest.
  *
  * Which pieces.  The floating pieces F_1 .. F_m are exactly the list cvx_world_pieces(..., CVX_PIECES_REPORT, ...) gives for the same box and
