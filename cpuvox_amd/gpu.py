@@ -66,6 +66,9 @@ CONTACTS_EXPORTS = ["cvxc_world_contacts", "cvxc_world_contacts_device", "cvxc_c
 # include/cpuvox_gpu_pair_contacts.h: where placed models touch each other.  Another family of its own (prefix cvxp_), no row of ABI_HEADERS either:
 # tests/test_abi_pair_contacts.py checks it.
 PAIR_CONTACTS_EXPORTS = ["cvxp_model_contacts", "cvxp_model_contacts_device", "cvxp_box_pairs", "cvxp_pair_response"]
+# include/cpuvox_gpu_model_pick.h: first-hit rays against placed models.  A family of its own again (prefix cvxq_), no row of ABI_HEADERS:
+# tests/test_abi_model_pick.py checks it.
+MODEL_PICK_EXPORTS = ["cvxq_model_pick", "cvxq_model_pick_device"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -126,6 +129,7 @@ SPREAD_TILE = (8, 64, 8)                         # CVX_SPREAD_TILE_X / _Y / _Z: 
 SNAPSHOT_IGNORE_COLOUR = 1                       # cvx_world_snapshot_diff: flags
 LIFT_COPY, LIFT_REMOVE = 0, 1                    # cvx_world_lift_pieces: op
 PAIR_CONTACTS_MAX_PAIRS = 65536                  # CVXP_MAX_PAIRS: cvxp_model_contacts, pairCount
+MODEL_PICK_MAX_RAYS = 65536                      # CVXQ_PICK_MAX_RAYS: cvxq_model_pick, rayCount
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -168,6 +172,11 @@ class PairPoint(C.Structure):  # cvxp_pair_point
 
 class PairsSummary(C.Structure):  # cvxp_pairs_summary
     _fields_ = [("touching", C.c_int64), ("overlap", C.c_int64), ("points", C.c_int64), ("jobs", C.c_int64)]
+
+
+class ModelHit(C.Structure):  # cvxq_model_hit
+    _fields_ = [("voxel", C.c_int32 * 3), ("face", C.c_int32), ("argb", C.c_uint32), ("t", C.c_float), ("instance", C.c_int32), ("modelVoxel", C.c_int32 * 3),
+                ("pad_", C.c_int32 * 2)]
 
 
 class SpreadParams(C.Structure):  # cvx_spread_params
@@ -311,6 +320,7 @@ SURFACE_QUAD_DTYPE, SURFACE_SUMMARY_DTYPE = np.dtype(SurfaceQuad), np.dtype(Surf
 SURFACE_RECT_DTYPE, SURFACE_RECTS_SUMMARY_DTYPE = np.dtype(SurfaceRect), np.dtype(SurfaceRectsSummary)
 CONTACT_RESULT_DTYPE, CONTACT_POINT_DTYPE, CONTACTS_SUMMARY_DTYPE = np.dtype(ContactResult), np.dtype(ContactPoint), np.dtype(ContactsSummary)
 PAIR_RESULT_DTYPE, PAIR_POINT_DTYPE, PAIRS_SUMMARY_DTYPE = np.dtype(PairResult), np.dtype(PairPoint), np.dtype(PairsSummary)
+MODEL_HIT_DTYPE = np.dtype(ModelHit)
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
 
@@ -683,6 +693,8 @@ def _bind(path: str) -> C.CDLL:
     L.cvxp_model_contacts_device.argtypes = L.cvxp_model_contacts.argtypes
     L.cvxp_box_pairs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.cvxp_pair_response.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    L.cvxq_model_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
+    L.cvxq_model_pick_device.argtypes = L.cvxq_model_pick.argtypes
     L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
     L.cvx_shard_plan_destroy.restype = None
@@ -1273,6 +1285,47 @@ class Context:
         results_ptr, _ = checked(results_tensor, C.sizeof(PairResult), len(p))
         points_ptr, capacity = checked(points_tensor, C.sizeof(PairPoint), 0) if points_tensor is not None else (None, 0)
         return self._pair_contacts(lib().cvxp_model_contacts_device, descriptors, len(models), inst, p, results_ptr, points_ptr if capacity else None, capacity)
+
+    # -- first-hit rays against placed models (cvxq_model_pick, include/cpuvox_gpu_model_pick.h) --
+    def model_pick(self, models, instances, origins, directions, max_t):
+        """The first voxel of any placed instance along each ray; no world is read and none need be uploaded: (a MODEL_HIT_DTYPE array, one
+        element per ray: the world voxel, the face as pick's, the model's colour word, t, the instance and the model's voxel; a miss has
+        voxel -1, face -1, argb 0, t = max_t, instance -1 -- device milliseconds).  `models` and `instances` as world_contacts' (an instance's op
+        is not read); origins, directions, max_t as pick's.  For the first of world or bodies pass pick's t as max_t."""
+        descriptors, keep = self._models(models, "model_pick")  # noqa: F841  (keep: the arrays the descriptors point to)
+        inst = self._instances(instances)
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("model_pick: one direction per origin")
+        rays = np.zeros(n, dtype=PICK_RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["maxT"] = np.broadcast_to(np.asarray(max_t, dtype=np.float32), (n,))
+        hits = np.zeros(n, dtype=MODEL_HIT_DTYPE)
+        ms = C.c_float()
+        self._check(lib().cvxq_model_pick(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), rays.ctypes.data if n else None, n,
+                                          hits.ctypes.data if n else None, C.byref(ms)))
+        return hits, ms.value
+
+    def model_pick_device(self, models, instances, rays_tensor, hits_tensor, ray_count=None):
+        """model_pick on device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr) as place_models_device's, `rays_tensor` a
+        contiguous device tensor of 32 bytes per ray (cvx_pick_ray: the array cvx_world_pick_device reads), `hits_tensor` one of at least 48
+        bytes per ray; ray_count: the rays to pick (None: all of rays_tensor).  Returns the device milliseconds once the hits are complete."""
+        descriptors = self._device_models(models, "model_pick_device")
+        inst = self._instances(instances)
+
+        def checked(tensor, item_bytes, at_least):
+            nbytes = tensor.numel() * tensor.element_size()
+            if not tensor.is_cuda or not tensor.is_contiguous() or nbytes < at_least * item_bytes:
+                raise ValueError(f"model_pick_device: a contiguous device tensor of at least {at_least} x {item_bytes} bytes")
+            return tensor.data_ptr(), nbytes // item_bytes
+        rays_ptr, n = checked(rays_tensor, C.sizeof(PickRay), 0 if ray_count is None else int(ray_count))
+        n = n if ray_count is None else int(ray_count)
+        hits_ptr, _ = checked(hits_tensor, C.sizeof(ModelHit), n)
+        ms = C.c_float()
+        self._check(lib().cvxq_model_pick_device(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), rays_ptr, n, hits_ptr, C.byref(ms)))
+        return ms.value
 
     @staticmethod
     def _model_read(size, to_world):
