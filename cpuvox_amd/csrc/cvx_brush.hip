@@ -62,7 +62,7 @@ __device__ __forceinline__ int CullStrokes(const BrushArgs &A, uint16_t (*lists)
 			const int s = base + lane;
 			const bool keep = s < A.strokeCount && cvxb::StrokeMeetsStrip(A.strokes[s], x0, x1, z0, z1);
 			const unsigned long long kept = __ballot(keep);
-			if (keep) { list[count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(kept >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kept, 0u))] = (uint16_t)s; }
+			if (keep) { list[count + (int)cvxi::LanesBelow(kept)] = (uint16_t)s; }
 			count += __popcll(kept);
 		}
 	}
@@ -130,7 +130,7 @@ namespace {
 
 constexpr int kCapsuleMax = 8191, kEllipsoidMax = 1024; // the limits of include/cpuvox_gpu.h: the span rules (cvx_brush.h) are exact in int64 inside them
 
-unsigned Grid(size_t n, unsigned threads) { return (unsigned)((n + threads - 1) / threads); }
+using cvxi::Grid;
 
 int Prepare(cvx_context *ctx)
 {

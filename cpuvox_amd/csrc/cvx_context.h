@@ -243,9 +243,9 @@ private:
 	size_t failedBytes = 0;
 };
 
-// the world calls' kernels: a thread per column, node or pair, kThreads to a workgroup
+// the world calls' kernels: a thread per column, node or pair, kThreads to a workgroup (`per`: what a workgroup takes where that is not a thread's share)
 constexpr unsigned kThreads = 256;
-inline unsigned Grid(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+inline unsigned Grid(size_t n, unsigned per = kThreads) { return (unsigned)((n + per - 1) / per); }
 
 // The layout of one scratch allocation: layout(b) is the offset of the next b bytes, every offset a multiple of 16; `bytes` is what to allocate.
 struct ScratchLayout {
@@ -265,6 +265,34 @@ template <typename T, typename F> __device__ inline T WaveReduce(T v, F f)
 {
 	for (int d = 32; d > 0; d >>= 1) { v = f(v, __shfl_xor(v, d, 64)); }
 	return v;
+}
+
+__device__ __forceinline__ uint32_t LanesBelow(uint64_t mask) // the set bits of `mask` below this lane
+{
+	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The `Uniform` of the rules' wave-side job builders (cvxb::ModelsLaneVoxel, ContactsColumnJobOf, PairBodyJobOf, ModelPickBodyOf): the value is the
+// same in every lane, keep it in a scalar register
+struct WaveUniform {
+	__device__ __forceinline__ int32_t operator()(int32_t v) const { return __builtin_amdgcn_readfirstlane(v); }
+	__device__ __forceinline__ float operator()(float v) const { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+	__device__ __forceinline__ double operator()(double v) const
+	{
+		const unsigned long long w = (unsigned long long)__double_as_longlong(v);
+		return __longlong_as_double((long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(w >> 32)) << 32) |
+		                                        (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)w)));
+	}
+};
+
+// The waves of a launch of `wavesPerGroup` waves a workgroup take jobs 0 .. count - 1 in turn (a launch has at most so many workgroups, whatever
+// the jobs): f(job, lane), the job in scalar registers and as the loop's own 64-bit counter -- narrowed here, before the call, it cost the write
+// walks of the contacts scalar registers (profiles/model_calls_refactor.md); the callers narrow it where they use it.
+template <class F> __device__ __forceinline__ void ForEachWaveJob(uint32_t count, int wavesPerGroup, F f)
+{
+	const uint32_t waves = gridDim.x * (uint32_t)wavesPerGroup;
+	const int lane = (int)(threadIdx.x % CVX_WAVE);
+	for (uint64_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * wavesPerGroup + threadIdx.x / CVX_WAVE)); at < count; at += waves) { f(at, lane); }
 }
 #endif
 

@@ -64,11 +64,6 @@ struct WriteArgs {
 	uint32_t *elements;
 };
 
-__device__ __forceinline__ uint32_t LanesBelow(uint64_t mask) // the set bits of `mask` below this lane
-{
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 // The wave's walk of column `i` of the rectangle (the steps of cvx_dense.h).  kWrite: runs go to outRuns, colours to outColours
 // (cvxb::DenseColumn's out arrays).  Everything but y, the voxel and the lane's slots is the same in all lanes.
 template <bool kWrite>
@@ -98,8 +93,8 @@ __device__ __forceinline__ cvxb::BrushResult WalkColumn(const WriteArgs &A, int 
 		const uint64_t mask = __ballot(v.solid); // bit l: the voxel yTop - l
 		const uint64_t starts = cvxb::DenseStarts(w, mask, valid);
 		if (kWrite) {
-			const uint32_t solidBelow = LanesBelow(mask);
-			cvxb::DenseLaneRun(w, mask, starts, lane, LanesBelow(starts), solidBelow, outRuns);
+			const uint32_t solidBelow = cvxi::LanesBelow(mask);
+			cvxb::DenseLaneRun(w, mask, starts, lane, cvxi::LanesBelow(starts), solidBelow, outRuns);
 			if (v.solid) { outColours[w.colours + solidBelow] = v.argb; }
 		}
 		cvxb::DenseAdvance(w, mask, starts, valid, yTop, lane0Runs);
@@ -146,8 +141,7 @@ __global__ __launch_bounds__(kThreads) void dense_write_kernel(WriteArgs A)
 namespace {
 
 using cvxdense::kThreads;
-
-unsigned Grid(size_t n, unsigned per = kThreads) { return (unsigned)((n + per - 1) / per); }
+using cvxi::Grid;
 
 // The checks both directions share; *elements receives the box's voxel count.
 int CheckBox(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], cvxb::DenseBox *box, int64_t *elements)

@@ -15,7 +15,8 @@
 //   3. hits   a wave per ray reads the key and walks the winning pair again, the same walk, and the deciding lane writes the whole record
 //             (voxel, face, colour, model voxel); a ray without a key gets the miss.  A re-walk rather than a record per job: 8 bytes a ray
 //             instead of 48 a job, and the second walk of one pair per ray is cheap against the first walk of all of them.
-// No LDS, no scratch memory in the walk.  No world is read: the calls work on a context with nothing uploaded.
+// No LDS, no scratch memory in the walk.  No world is read: the calls work on a context with nothing uploaded.  Host models, rays and hits are
+// staged by cvxi::ModelStaging (cvx_model_call.h); the turn loop is cvxi::ForEachWaveJob.
 // CVXQ_LANE_PER_JOB (an experiment build, `make variant`): the walk as a lane per job running cvxb::ModelPickSequential, the measure
 // tools/model_pick_bench.py compares the wave's walk with.
 #include <hip/hip_runtime.h>
@@ -25,7 +26,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
+#include "cvx_model_call.h"
 #include "cvx_model_pick.h"
 
 using cvxi::Fail;
@@ -51,22 +52,6 @@ struct Args {
 	cvxq_model_hit *hits;
 };
 
-__device__ __forceinline__ uint32_t LanesBelow(uint64_t mask) // the set bits of `mask` below this lane
-{
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-struct WaveUniform { // the value is the same in every lane, keep it in a scalar register
-	__device__ __forceinline__ int32_t operator()(int32_t v) const { return __builtin_amdgcn_readfirstlane(v); }
-	__device__ __forceinline__ float operator()(float v) const { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-	__device__ __forceinline__ double operator()(double v) const
-	{
-		const unsigned long long w = (unsigned long long)__double_as_longlong(v);
-		return __longlong_as_double((long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(w >> 32)) << 32) |
-		                                        (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)w)));
-	}
-};
-
 // The clip of pair `pair`, by the thread that owns it.
 __device__ __forceinline__ bool PairCrosses(const Args &A, uint32_t pair)
 {
@@ -83,7 +68,7 @@ template <bool kWrite> __global__ __launch_bounds__(kThreads) void pick_clip_ker
 	const bool job = pair < A.pairs && PairCrosses(A, pair);
 	const uint64_t jobs = __ballot(job);
 	if (kWrite) {
-		if (job) { A.jobs[A.counts[pair / CVX_WAVE] + LanesBelow(jobs)] = pair; }
+		if (job) { A.jobs[A.counts[pair / CVX_WAVE] + cvxi::LanesBelow(jobs)] = pair; }
 		return;
 	}
 	if (threadIdx.x % CVX_WAVE == 0 && pair < A.pairs) { A.counts[pair / CVX_WAVE] = (uint32_t)__popcll(jobs); }
@@ -94,7 +79,7 @@ template <bool kWrite> __global__ __launch_bounds__(kThreads) void pick_clip_ker
 // readfirstlane into scalar registers.  False: the ray misses the box.
 __device__ __forceinline__ bool JobOf(const Args &A, uint32_t rayIndex, const cvxb::ModelPickBody &B, cvxb::ModelPickRay *uniformRay, cvxb::ModelPickState *uniformStart, int *M)
 {
-	const WaveUniform U;
+	const cvxi::WaveUniform U;
 	const cvx_pick_ray &ray = A.rays[rayIndex];
 	const float o[3] = { U(ray.origin[0]), U(ray.origin[1]), U(ray.origin[2]) }, d[3] = { U(ray.direction[0]), U(ray.direction[1]), U(ray.direction[2]) };
 	cvxb::ModelPickRay R;
@@ -117,7 +102,7 @@ __device__ __forceinline__ bool JobOf(const Args &A, uint32_t rayIndex, const cv
 // winner: it has one).
 template <bool kWrite> __device__ __forceinline__ void WalkJob(const Args &A, uint32_t rayIndex, int32_t instance, int lane, cvxq_model_hit *out)
 {
-	const cvxb::ModelPickBody B = cvxb::ModelPickBodyOf(WaveUniform{}, A.models, A.instances[instance]);
+	const cvxb::ModelPickBody B = cvxb::ModelPickBodyOf(cvxi::WaveUniform{}, A.models, A.instances[instance]);
 	cvxb::ModelPickRay R;
 	cvxb::ModelPickState start;
 	int M;
@@ -148,12 +133,10 @@ template <bool kWrite> __device__ __forceinline__ void WalkJob(const Args &A, ui
 #ifndef CVXQ_LANE_PER_JOB
 __global__ __launch_bounds__(kThreads) void pick_walk_kernel(Args A)
 {
-	const uint32_t waves = gridDim.x * (uint32_t)kWaves;
-	const int lane = (int)(threadIdx.x % CVX_WAVE);
-	for (uint64_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / CVX_WAVE)); at < A.jobCount; at += waves) {
+	cvxi::ForEachWaveJob(A.jobCount, kWaves, [&](uint64_t at, int lane) {
 		const uint32_t pair = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)A.jobs[at]);
 		WalkJob<false>(A, pair / (uint32_t)A.instanceCount, (int32_t)(pair % (uint32_t)A.instanceCount), lane, nullptr);
-	}
+	});
 }
 #else
 // the experiment: a lane per job, the pair rule a voxel at a time
@@ -188,9 +171,6 @@ __global__ __launch_bounds__(kThreads) void pick_hits_kernel(Args A)
 	WalkJob<true>(A, rayIndex, __builtin_amdgcn_readfirstlane((int32_t)(uint32_t)key), lane, A.hits + rayIndex);
 }
 
-static unsigned Grid(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-static size_t Align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
 // Both calls: `device` says where the models' arrays, `rays` and `hits` live.
 static int ModelPick(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount,
                      const cvx_pick_ray *rays, int rayCount, cvxq_model_hit *hits, bool device, float *outDeviceMs)
@@ -203,46 +183,16 @@ static int ModelPick(cvx_context *ctx, const char *call, const cvx_model *models
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
 
 	// (these outlive D: freeing the device blocks waits for a copy still under way)
-	std::vector<cvxq_model_hit> back;
-	std::vector<cvx_model> deviceModels(models, models + modelCount);
+	std::vector<cvxq_model_hit> back(device ? 0 : (size_t)rayCount);
+	cvxi::ModelStaging staging(models, modelCount, device);
 	unsigned long long jobCount = 0ull;
 	cvxi::DeviceCall D(ctx, call);
-	uint8_t *arrays = nullptr, *scratch = nullptr;
+	uint8_t *scratch = nullptr;
 	uint32_t *jobs = nullptr;
-	struct Upload {
-		size_t at, bytes;
-		const void *from;
-	};
-	std::vector<Upload> uploads;
-	hipError_t e = hipSuccess;
 	const size_t raysBytes = (size_t)rayCount * sizeof(cvx_pick_ray), hitsBytes = (size_t)rayCount * sizeof(cvxq_model_hit);
-	size_t oRays = 0, oHits = 0;
-	if (!device) { // host arrays: a device copy of them
-		size_t total = 0;
-		for (int k = 0; k < modelCount; k++) {
-			const size_t n = (size_t)models[k].size[0] * (size_t)models[k].size[1] * (size_t)models[k].size[2];
-			if (models[k].argb) {
-				uploads.push_back(Upload{ total, n * 4, models[k].argb });
-				total += Align16(n * 4);
-			}
-			if (models[k].solid) {
-				uploads.push_back(Upload{ total, n, models[k].solid });
-				total += Align16(n);
-			}
-		}
-		uploads.push_back(Upload{ oRays = total, raysBytes, rays });
-		total += Align16(raysBytes);
-		oHits = total;
-		total += Align16(hitsBytes);
-		e = D.Allocate(&arrays, total);
-		if (e != hipSuccess) { return D.Fail(e); }
-		size_t u = 0;
-		for (int k = 0; k < modelCount; k++) {
-			if (models[k].argb) { deviceModels[k].argb = reinterpret_cast<const uint32_t *>(arrays + uploads[u++].at); }
-			if (models[k].solid) { deviceModels[k].solid = arrays + uploads[u++].at; }
-		}
-		back.resize((size_t)rayCount);
-	}
+	const size_t oRays = device ? 0 : staging.Add(raysBytes, rays), oHits = device ? 0 : staging.Add(hitsBytes, nullptr); // host rays and hits: behind the arrays
+	hipError_t e = staging.Allocate(D);
+	if (e != hipSuccess) { return D.Fail(e); }
 	const size_t pairs = (size_t)rayCount * (size_t)instanceCount, waves = (pairs + CVX_WAVE - 1) / CVX_WAVE;
 	const size_t chunks = (waves + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	cvxi::ScratchLayout carve;
@@ -252,22 +202,20 @@ static int ModelPick(cvx_context *ctx, const char *call, const cvx_model *models
 	Args A{};
 	e = D.Allocate(&scratch, carve.bytes);
 	if (e == hipSuccess) { e = D.Begin(); }
-	for (const Upload &u : uploads) {
-		if (e == hipSuccess) { e = hipMemcpyAsync(arrays + u.at, u.from, u.bytes, hipMemcpyHostToDevice, ctx->stream); }
-	}
-	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oModels, deviceModels.data(), modelsBytes, hipMemcpyHostToDevice, ctx->stream); }
+	if (e == hipSuccess) { e = staging.Enqueue(ctx->stream); }
+	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oModels, staging.descriptors.data(), modelsBytes, hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oInstances, instances, instancesBytes, hipMemcpyHostToDevice, ctx->stream); }
 	if (e == hipSuccess) {
 		A.models = reinterpret_cast<const cvx_model *>(scratch + oModels);
 		A.instances = reinterpret_cast<const cvx_model_instance *>(scratch + oInstances);
-		A.rays = device ? rays : reinterpret_cast<const cvx_pick_ray *>(arrays + oRays);
+		A.rays = device ? rays : reinterpret_cast<const cvx_pick_ray *>(staging.block + oRays);
 		A.instanceCount = instanceCount;
 		A.rayCount = rayCount;
 		A.pairs = (uint32_t)pairs;
 		A.counts = reinterpret_cast<uint32_t *>(scratch + oCounts);
 		A.keys = reinterpret_cast<unsigned long long *>(scratch + oKeys);
-		A.hits = device ? hits : reinterpret_cast<cvxq_model_hit *>(arrays + oHits);
-		hipLaunchKernelGGL(pick_clip_kernel<false>, dim3(Grid(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, A);
+		A.hits = device ? hits : reinterpret_cast<cvxq_model_hit *>(staging.block + oHits);
+		hipLaunchKernelGGL(pick_clip_kernel<false>, dim3(cvxi::Grid(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, A);
 		cvxi::ExclusiveScan(ctx->stream, A.counts, (int)waves, reinterpret_cast<unsigned long long *>(scratch + oChunks), reinterpret_cast<unsigned long long *>(scratch + oTotal));
 		e = hipGetLastError();
 	}
@@ -279,15 +227,15 @@ static int ModelPick(cvx_context *ctx, const char *call, const cvx_model *models
 		A.jobs = jobs;
 		A.jobCount = (uint32_t)jobCount;
 		if (jobCount > 0ull) {
-			hipLaunchKernelGGL(pick_clip_kernel<true>, dim3(Grid(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, A);
+			hipLaunchKernelGGL(pick_clip_kernel<true>, dim3(cvxi::Grid(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, A);
 #ifndef CVXQ_LANE_PER_JOB
-			const unsigned walkGrid = std::min(Grid((size_t)jobCount, kWaves), kMaxWorkgroups);
+			const unsigned walkGrid = std::min(cvxi::Grid((size_t)jobCount, kWaves), kMaxWorkgroups);
 #else
-			const unsigned walkGrid = std::min(Grid((size_t)jobCount, kThreads), kMaxWorkgroups);
+			const unsigned walkGrid = std::min(cvxi::Grid((size_t)jobCount, kThreads), kMaxWorkgroups);
 #endif
 			hipLaunchKernelGGL(pick_walk_kernel, dim3(walkGrid), dim3(kThreads), 0, ctx->stream, A);
 		}
-		hipLaunchKernelGGL(pick_hits_kernel, dim3(Grid((size_t)rayCount, kWaves)), dim3(kThreads), 0, ctx->stream, A);
+		hipLaunchKernelGGL(pick_hits_kernel, dim3(cvxi::Grid((size_t)rayCount, kWaves)), dim3(kThreads), 0, ctx->stream, A);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess && !device) { e = hipMemcpyAsync(back.data(), A.hits, hitsBytes, hipMemcpyDeviceToHost, ctx->stream); }

@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "cvx_context.h"
+#include "cvx_model_call.h"
 #include "cvx_models.h"
 
 using cvxi::Fail;
@@ -66,15 +66,6 @@ struct PlaceArgs {
 	uint32_t *elements;
 };
 
-__device__ __forceinline__ uint32_t LanesBelow(uint64_t mask) // the set bits of `mask` below this lane
-{
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-struct WaveUniform { // cvxb::ModelsLaneVoxel's Uniform: the value is the same in every lane, keep it in a scalar register
-	__device__ __forceinline__ int32_t operator()(int32_t v) const { return __builtin_amdgcn_readfirstlane(v); }
-};
-
 // The instances whose box covers the wave's column, as ascending indices into A.instances, and the union [*lo, *hi) of their y ranges (empty: 0, 0).
 // CVX_MODELS_MAX_INSTANCES 16-bit indices per wave always fit: there is no overflow path.  A wave's list is written and read by that wave alone:
 // a wave-scope fence orders the lanes' stores before the other lanes' loads.  Returns the list's length.
@@ -88,7 +79,7 @@ __device__ __forceinline__ int CullInstances(const PlaceArgs &A, int cx, int cz,
 		const bool keep = s < A.instanceCount && cvxb::ModelCullCovers(b, cx, cz);
 		const unsigned long long kept = __ballot(keep);
 		if (keep) {
-			list[count + (int)LanesBelow(kept)] = (uint16_t)s;
+			list[count + (int)cvxi::LanesBelow(kept)] = (uint16_t)s;
 			myLo = min(myLo, b.y0);
 			myHi = max(myHi, b.y1);
 		}
@@ -128,12 +119,12 @@ __device__ __forceinline__ cvxb::BrushResult WalkColumn(const PlaceArgs &A, int 
 			continue;
 		}
 		const uint32_t valid = (uint32_t)(yTop + 1 < CVX_WAVE ? yTop + 1 : CVX_WAVE);
-		const cvxb::Voxel v = cvxb::ModelsLaneVoxel(WaveUniform{}, col, A.W.colourSlots, A.W.colorShift, A.models, A.instances, list, listCount, cx, cz, yTop, yTop - lane);
+		const cvxb::Voxel v = cvxb::ModelsLaneVoxel(cvxi::WaveUniform{}, col, A.W.colourSlots, A.W.colorShift, A.models, A.instances, list, listCount, cx, cz, yTop, yTop - lane);
 		const uint64_t mask = __ballot(v.solid); // bit l: the voxel yTop - l
 		const uint64_t starts = cvxb::DenseStarts(w, mask, valid);
 		if (kWrite) {
-			const uint32_t solidBelow = LanesBelow(mask);
-			cvxb::DenseLaneRun(w, mask, starts, lane, LanesBelow(starts), solidBelow, outRuns);
+			const uint32_t solidBelow = cvxi::LanesBelow(mask);
+			cvxb::DenseLaneRun(w, mask, starts, lane, cvxi::LanesBelow(starts), solidBelow, outRuns);
 			if (v.solid) { outColours[w.colours + solidBelow] = v.argb; }
 		}
 		cvxb::DenseAdvance(w, mask, starts, valid, yTop, lane0Runs);
@@ -183,17 +174,14 @@ __global__ __launch_bounds__(kThreads) void models_write_kernel(PlaceArgs A)
 
 namespace {
 
+using cvxi::Grid;
 using cvxmodels::kThreads;
-
-unsigned Grid(size_t n, unsigned per = kThreads) { return (unsigned)((n + per - 1) / per); }
 
 int Prepare(cvx_context *ctx)
 {
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
 	return cvxi::SyncWorld(ctx);
 }
-
-size_t Align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 int Read(cvx_context *ctx, const char *call, const int32_t size[3], const cvx_model_map *toWorld, uint32_t *argb, uint8_t *solid, bool device, void *hipStream,
          float *outDeviceMs)
@@ -275,35 +263,10 @@ int Place(cvx_context *ctx, const char *call, const cvx_model *models, int model
 	if (rc != CVX_OK) { return rc; }
 
 	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it
+	cvxi::ModelStaging staging(models, modelCount, device);
 	cvxi::DeviceCall upload(ctx, call);
-	uint8_t *arrays = nullptr;
-	std::vector<cvx_model> deviceModels(models, models + modelCount);
-	struct Upload {
-		size_t at, bytes;
-		const void *from;
-	};
-	std::vector<Upload> uploads;
-	if (!device) {
-		size_t total = 0;
-		for (int k = 0; k < modelCount; k++) {
-			const size_t n = (size_t)models[k].size[0] * (size_t)models[k].size[1] * (size_t)models[k].size[2];
-			if (models[k].argb) {
-				uploads.push_back(Upload{ total, n * 4, models[k].argb });
-				total += Align16(n * 4);
-			}
-			if (models[k].solid) {
-				uploads.push_back(Upload{ total, n, models[k].solid });
-				total += Align16(n);
-			}
-		}
-		const hipError_t e = upload.Allocate(&arrays, total);
-		if (e != hipSuccess) { return upload.Fail(e); }
-		size_t u = 0;
-		for (int k = 0; k < modelCount; k++) {
-			if (models[k].argb) { deviceModels[k].argb = reinterpret_cast<const uint32_t *>(arrays + uploads[u++].at); }
-			if (models[k].solid) { deviceModels[k].solid = arrays + uploads[u++].at; }
-		}
-	}
+	const hipError_t allocated = staging.Allocate(upload);
+	if (allocated != hipSuccess) { return upload.Fail(allocated); }
 	cvxmodels::PlaceArgs A{};
 	A.W = cvxi::WorldOf(ctx);
 	A.instanceCount = (int)live.size();
@@ -311,27 +274,25 @@ int Place(cvx_context *ctx, const char *call, const cvx_model *models, int model
 	A.z0 = R.z0;
 	A.sizeZ = R.sizeZ;
 	A.n = R.n;
-	const size_t countsBytes = Align16((size_t)R.n * 4), modelsBytes = (size_t)modelCount * sizeof(cvx_model), instancesBytes = live.size() * sizeof(cvx_model_instance),
-	             boxesBytes = boxes.size() * sizeof(cvxb::ModelCullBox);
+	const size_t modelsBytes = (size_t)modelCount * sizeof(cvx_model), instancesBytes = live.size() * sizeof(cvx_model_instance), boxesBytes = boxes.size() * sizeof(cvxb::ModelCullBox);
+	cvxi::ScratchLayout extra; // the run counts, the descriptors
+	const size_t oRunCounts = extra((size_t)R.n * 4), oModels = extra(modelsBytes), oInstances = extra(instancesBytes), oBoxes = extra(boxesBytes);
 	const dim3 grid(Grid((size_t)R.n, cvxmodels::kWaves)), block(kThreads);
 	cvxi::ColumnEditCall edit{ call, CVX_ERR_HIP, "a column under the models", "the columns under the models" };
-	edit.extraScratchBytes = countsBytes + modelsBytes + instancesBytes + boxesBytes; // the run counts, the descriptors
+	edit.extraScratchBytes = extra.bytes;
 	return cvxi::ColumnEdit(
 		ctx, R, levelCount, edit,
 		[&](const cvxi::ColumnEditJob &J) {
-			hipError_t e = hipSuccess;
-			for (const Upload &u : uploads) {
-				if (e == hipSuccess) { e = hipMemcpyAsync(arrays + u.at, u.from, u.bytes, hipMemcpyHostToDevice, ctx->stream); }
-			}
+			hipError_t e = staging.Enqueue(ctx->stream);
 			A.counts = J.counts;
-			A.runCounts = reinterpret_cast<uint32_t *>(J.extra);
-			A.models = reinterpret_cast<const cvx_model *>(J.extra + countsBytes);
-			A.instances = reinterpret_cast<const cvx_model_instance *>(J.extra + countsBytes + modelsBytes);
-			A.boxes = reinterpret_cast<const cvxb::ModelCullBox *>(J.extra + countsBytes + modelsBytes + instancesBytes);
+			A.runCounts = reinterpret_cast<uint32_t *>(J.extra + oRunCounts);
+			A.models = reinterpret_cast<const cvx_model *>(J.extra + oModels);
+			A.instances = reinterpret_cast<const cvx_model_instance *>(J.extra + oInstances);
+			A.boxes = reinterpret_cast<const cvxb::ModelCullBox *>(J.extra + oBoxes);
 			A.overLimit = J.overLimit;
-			if (e == hipSuccess) { e = hipMemcpyAsync(J.extra + countsBytes + modelsBytes + instancesBytes, boxes.data(), boxesBytes, hipMemcpyHostToDevice, ctx->stream); }
-			if (e == hipSuccess) { e = hipMemcpyAsync(J.extra + countsBytes, deviceModels.data(), modelsBytes, hipMemcpyHostToDevice, ctx->stream); }
-			if (e == hipSuccess) { e = hipMemcpyAsync(J.extra + countsBytes + modelsBytes, live.data(), instancesBytes, hipMemcpyHostToDevice, ctx->stream); }
+			if (e == hipSuccess) { e = hipMemcpyAsync(J.extra + oBoxes, boxes.data(), boxesBytes, hipMemcpyHostToDevice, ctx->stream); }
+			if (e == hipSuccess) { e = hipMemcpyAsync(J.extra + oModels, staging.descriptors.data(), modelsBytes, hipMemcpyHostToDevice, ctx->stream); }
+			if (e == hipSuccess) { e = hipMemcpyAsync(J.extra + oInstances, live.data(), instancesBytes, hipMemcpyHostToDevice, ctx->stream); }
 			if (e == hipSuccess) { hipLaunchKernelGGL(cvxmodels::models_count_kernel, grid, block, 0, ctx->stream, A); }
 			return e;
 		},

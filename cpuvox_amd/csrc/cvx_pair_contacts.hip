@@ -11,20 +11,18 @@
 //             column part per body, then the map's finish and one gather per lane.  Counts and face sums come from ballots on the scalar side;
 //             only the sum of y is kept per lane and reduced once.  The wave then issues ONE set of integer atomics on its pair's result, a
 //             lane each (64-bit adds, 32-bit min / max for the box).  With a list asked for, it also leaves the job's points.
-//   2. finish (one workgroup, a thread per 64 pairs: 65536 in all): firstPoint by a scan of the pairs' points, the box as [min, max) or zeros,
-//             the summary.  ONE copy brings the summary to the host.
-//   3. write  (only with pointCapacity > 0): cvxi::ExclusiveScan turns the jobs' points into offsets; the same walk writes each point at
-//             offset + the points of the steps above + the lanes below in the ballot (lane order is descending y).  A device list is
-//             enqueued behind the finish, before the one synchronisation; a host list is sized by the points found, after it.
-// No LDS in the walk, no float.  No world is read: the calls work on a context with nothing uploaded.
+//   2. finish (cvxi::FinishResults, a thread per 64 pairs: 65536 in all): firstPoint, the box as [min, max) or zeros, the summary.
+//   3. write  (only with pointCapacity > 0): the same walk writes each point at its job's offset + the points of the steps above + the lanes
+//             below in the ballot (lane order is descending y).
+// No LDS in the walk, no float.  No world is read: the calls work on a context with nothing uploaded.  The host's side is cvxi::RunPointsCall
+// (cvx_model_call.hip), a unit being a pair.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstddef>
-#include <cstring>
 #include <vector>
 
-#include "cvx_context.h"
+#include "cvx_model_call.h"
 #include "cvx_pair_contacts.h"
 
 using cvxi::Fail;
@@ -34,8 +32,7 @@ namespace cvxpairs {
 constexpr unsigned kThreads = 256;
 constexpr int kWaves = kThreads / CVX_WAVE;
 constexpr unsigned kMaxWorkgroups = 65536; // of the two walks: 2^18 waves
-constexpr int kFinishThreads = 1024, kFinishEach = CVXP_MAX_PAIRS / kFinishThreads;
-static_assert(kFinishThreads * kFinishEach == CVXP_MAX_PAIRS, "the finish kernel's one workgroup covers every pair");
+static_assert(sizeof(cvxp_pairs_summary) == 4 * sizeof(int64_t) && offsetof(cvxp_pairs_summary, points) == 2 * sizeof(int64_t), "the summary as cvxi::PointsCall takes it");
 
 // the 64-bit words of a result the count kernel adds to, a lane each
 static_assert(offsetof(cvxp_pair_result, overlap) == 0 && offsetof(cvxp_pair_result, points) == 8 && offsetof(cvxp_pair_result, sum) == 24 &&
@@ -56,15 +53,6 @@ struct Args {
 	cvxp_pairs_summary *summary;
 };
 
-__device__ __forceinline__ uint32_t LanesBelow(uint64_t mask) // the set bits of `mask` below this lane
-{
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-struct WaveUniform { // cvxb::PairBodyJobOf's Uniform: the value is the same in every lane, keep it in a scalar register
-	__device__ __forceinline__ int32_t operator()(int32_t v) const { return __builtin_amdgcn_readfirstlane(v); }
-};
-
 // The model's colour word of the image of voxel y of the job's column.
 __device__ __forceinline__ uint32_t ColourAt(const cvxb::ContactsColumnJob &J, int32_t y)
 {
@@ -77,7 +65,7 @@ __device__ __forceinline__ uint32_t ColourAt(const cvxb::ContactsColumnJob &J, i
 template <bool kWrite>
 __device__ __forceinline__ void WalkJob(const Args &A, uint32_t job, int lane, uint32_t first)
 {
-	const WaveUniform U;
+	const cvxi::WaveUniform U;
 	int32_t p = 0, within = A.pairCount; // the last p with prefix[p] <= job: 64 probes a round
 	while (within > 1) {
 		const int32_t probe = cvxb::PairSearchProbe(p, within, lane);
@@ -112,7 +100,7 @@ __device__ __forceinline__ void WalkJob(const Args &A, uint32_t job, int lane, u
 		}
 		const uint64_t points = __ballot((facesA | facesB) != 0);
 		if (kWrite) {
-			const uint32_t entry = at + LanesBelow(points);
+			const uint32_t entry = at + cvxi::LanesBelow(points);
 			if ((facesA | facesB) != 0 && entry < A.limit) { A.points[entry] = cvxp_pair_point{ { cx, y, cz }, p, facesA, facesB, ColourAt(Ja.J, y), ColourAt(Jb.J, y) }; }
 			at += (uint32_t)__popcll(points);
 			if (at >= A.limit) { return; }
@@ -159,14 +147,10 @@ __global__ __launch_bounds__(kThreads) void pairs_init_kernel(Args A)
 	cvxb::PairResultInit(A.instances[a], A.instances[b], a, b, A.results + p);
 }
 
-// Both walks: the launch's waves take the jobs in turn (a launch has at most kMaxWorkgroups workgroups, whatever the jobs).
+// Both walks: the launch's waves take the jobs in turn (cvxi::ForEachWaveJob: a launch has at most kMaxWorkgroups workgroups, whatever the jobs).
 __global__ __launch_bounds__(kThreads) void pairs_count_kernel(Args A)
 {
-	const uint32_t waves = gridDim.x * (uint32_t)kWaves;
-	const int lane = (int)(threadIdx.x % CVX_WAVE);
-	for (uint64_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / CVX_WAVE)); at < A.jobs; at += waves) {
-		WalkJob<false>(A, (uint32_t)at, lane, 0u);
-	}
+	cvxi::ForEachWaveJob(A.jobs, kWaves, [&](uint64_t at, int lane) { WalkJob<false>(A, (uint32_t)at, lane, 0u); });
 }
 
 // The list holds min(A.limit, the points found) entries: the finish kernel has left the points in the summary, and the offsets are good only
@@ -176,57 +160,26 @@ __global__ __launch_bounds__(kThreads) void pairs_write_kernel(Args A)
 	const uint64_t found = (uint64_t)A.summary->points;
 	if (found >= (1ull << 31)) { return; }
 	A.limit = found < A.limit ? (uint32_t)found : A.limit;
-	const uint32_t waves = gridDim.x * (uint32_t)kWaves;
-	const int lane = (int)(threadIdx.x % CVX_WAVE);
-	for (uint64_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kWaves + threadIdx.x / CVX_WAVE)); at < A.jobs; at += waves) {
+	cvxi::ForEachWaveJob(A.jobs, kWaves, [&](uint64_t at, int lane) {
 		const uint32_t job = (uint32_t)at, first = A.counts[job];
-		if (first >= A.limit || A.counts[job + 1u] == first) { continue; }
+		if (first >= A.limit || A.counts[job + 1u] == first) { return; }
 		WalkJob<true>(A, job, lane, first);
-	}
+	});
 }
 
-// One workgroup.  Thread t finishes pairs kFinishEach * t ..: firstPoint from an inclusive scan of the threads' points, the box, the summary.
-__global__ __launch_bounds__(kFinishThreads) void pairs_finish_kernel(Args A)
+// One workgroup (cvxi::FinishResults): firstPoint, the box, the summary.
+__global__ __launch_bounds__(cvxi::kFinishThreads) void pairs_finish_kernel(Args A)
 {
-	__shared__ unsigned long long scan[kFinishThreads];
-	__shared__ unsigned long long totals[2]; // touching, overlap
-	const int t = (int)threadIdx.x;
-	if (t < 2) { totals[t] = 0ull; }
-	unsigned long long mine = 0ull;
-	for (int j = 0; j < kFinishEach; j++) {
-		const int p = kFinishEach * t + j;
-		if (p < A.pairCount) { mine += (unsigned long long)A.results[p].points; }
-	}
-	scan[t] = mine;
-	__syncthreads();
-	for (int d = 1; d < kFinishThreads; d <<= 1) {
-		const unsigned long long before = t >= d ? scan[t - d] : 0ull;
-		__syncthreads();
-		scan[t] += before;
-		__syncthreads();
-	}
-	unsigned long long firstPoint = scan[t] - mine, touching = 0ull, overlap = 0ull;
-	for (int j = 0; j < kFinishEach; j++) {
-		const int p = kFinishEach * t + j;
-		if (p >= A.pairCount) { break; }
-		cvxp_pair_result *r = A.results + p;
-		r->firstPoint = (int64_t)firstPoint;
-		firstPoint += (unsigned long long)r->points;
-		cvxb::PairResultFinish(r);
-		touching += r->overlap > 0 ? 1ull : 0ull;
-		overlap += (unsigned long long)r->overlap;
-	}
-	if (touching != 0ull) {
-		atomicAdd(&totals[0], touching);
-		atomicAdd(&totals[1], overlap);
-	}
-	__syncthreads();
-	if (t == 0) { *A.summary = cvxp_pairs_summary{ (int64_t)totals[0], (int64_t)totals[1], (int64_t)scan[kFinishThreads - 1], (int64_t)A.jobs }; }
+	unsigned long long points;
+	const unsigned long long *totals = cvxi::FinishResults<CVXP_MAX_PAIRS, 2>(
+		A.results, A.pairCount, [](cvxp_pair_result *r) { cvxb::PairResultFinish(r); },
+		[](const cvxp_pair_result &r, unsigned long long *sums) { // touching, overlap
+			sums[0] += r.overlap > 0 ? 1ull : 0ull;
+			sums[1] += (unsigned long long)r.overlap;
+		},
+		&points);
+	if (threadIdx.x == 0) { *A.summary = cvxp_pairs_summary{ (int64_t)totals[0], (int64_t)totals[1], (int64_t)points, (int64_t)A.jobs }; }
 }
-
-static unsigned Grid(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-static unsigned WalkGrid(int64_t jobs) { return std::min(Grid((size_t)jobs, kWaves), kMaxWorkgroups); }
-static size_t Align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 // Both calls: `device` says where the models' arrays, `results` and `points` live.
 static int ModelContacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount,
@@ -243,110 +196,34 @@ static int ModelContacts(cvx_context *ctx, const char *call, const cvx_model *mo
 	if (jobs < 0) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: the pairs' common footprints sum to 2^31 - 1 or more (pair, column) jobs", call); }
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
 
-	// (these outlive D: freeing the device blocks waits for a copy still under way)
-	std::vector<cvxp_pair_result> backResults;
-	std::vector<cvxp_pair_point> backPoints;
-	std::vector<cvx_model> deviceModels(models, models + modelCount);
-	cvxp_pairs_summary host{};
-	cvxi::DeviceCall D(ctx, call);
-	uint8_t *arrays = nullptr, *scratch = nullptr, *list = nullptr;
-	struct Upload {
-		size_t at, bytes;
-		const void *from;
-	};
-	std::vector<Upload> uploads;
-	hipError_t e = hipSuccess;
-	if (!device) { // host arrays: a device copy of them
-		size_t total = 0;
-		for (int k = 0; k < modelCount; k++) {
-			const size_t n = (size_t)models[k].size[0] * (size_t)models[k].size[1] * (size_t)models[k].size[2];
-			if (models[k].argb) {
-				uploads.push_back(Upload{ total, n * 4, models[k].argb });
-				total += Align16(n * 4);
-			}
-			if (models[k].solid) {
-				uploads.push_back(Upload{ total, n, models[k].solid });
-				total += Align16(n);
-			}
-		}
-		e = D.Allocate(&arrays, total);
-		if (e != hipSuccess) { return D.Fail(e); }
-		size_t u = 0;
-		for (int k = 0; k < modelCount; k++) {
-			if (models[k].argb) { deviceModels[k].argb = reinterpret_cast<const uint32_t *>(arrays + uploads[u++].at); }
-			if (models[k].solid) { deviceModels[k].solid = arrays + uploads[u++].at; }
-		}
-		backResults.resize((size_t)pairCount);
-	}
-	const bool listing = pointCapacity > 0;
-	cvxi::ScratchLayout carve;
-	const size_t modelsBytes = (size_t)modelCount * sizeof(cvx_model), instancesBytes = (size_t)instanceCount * sizeof(cvx_model_instance),
-	             pairsBytes = (size_t)pairCount * 8, prefixBytes = prefix.size() * 4, resultsBytes = (size_t)pairCount * sizeof(cvxp_pair_result);
-	const size_t chunks = listing ? ((size_t)jobs + 1 + cvxi::ScanChunk() - 1) / cvxi::ScanChunk() : 0;
-	const size_t oSummary = carve(sizeof host), oTotal = carve(8), oModels = carve(modelsBytes), oInstances = carve(instancesBytes), oPairs = carve(pairsBytes),
-	             oPrefix = carve(prefixBytes), oResults = carve(device ? 0 : resultsBytes), oCounts = carve(listing ? ((size_t)jobs + 1) * 4 : 0), oChunks = carve(chunks * 8);
 	Args A{};
-	e = D.Allocate(&scratch, carve.bytes);
-	if (e == hipSuccess) { e = D.Begin(); }
-	for (const Upload &u : uploads) {
-		if (e == hipSuccess) { e = hipMemcpyAsync(arrays + u.at, u.from, u.bytes, hipMemcpyHostToDevice, ctx->stream); }
-	}
-	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oModels, deviceModels.data(), modelsBytes, hipMemcpyHostToDevice, ctx->stream); }
-	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oInstances, instances, instancesBytes, hipMemcpyHostToDevice, ctx->stream); }
-	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oPairs, pairs, pairsBytes, hipMemcpyHostToDevice, ctx->stream); }
-	if (e == hipSuccess) { e = hipMemcpyAsync(scratch + oPrefix, prefix.data(), prefixBytes, hipMemcpyHostToDevice, ctx->stream); }
-	if (e == hipSuccess && listing) { e = hipMemsetAsync(scratch + oCounts + (size_t)jobs * 4, 0, 4, ctx->stream); } // (the scan leaves the total behind the last job's offset)
-	if (e == hipSuccess) {
-		A.models = reinterpret_cast<const cvx_model *>(scratch + oModels);
-		A.instances = reinterpret_cast<const cvx_model_instance *>(scratch + oInstances);
-		A.pairs = reinterpret_cast<const int32_t *>(scratch + oPairs);
-		A.prefix = reinterpret_cast<const uint32_t *>(scratch + oPrefix);
-		A.pairCount = pairCount;
-		A.jobs = (uint32_t)jobs;
-		A.results = device ? results : reinterpret_cast<cvxp_pair_result *>(scratch + oResults);
-		A.counts = listing ? reinterpret_cast<uint32_t *>(scratch + oCounts) : nullptr;
-		A.summary = reinterpret_cast<cvxp_pairs_summary *>(scratch + oSummary);
-		hipLaunchKernelGGL(pairs_init_kernel, dim3(Grid((size_t)pairCount, kThreads)), dim3(kThreads), 0, ctx->stream, A);
-		if (jobs > 0) { hipLaunchKernelGGL(pairs_count_kernel, dim3(WalkGrid(jobs)), dim3(kThreads), 0, ctx->stream, A); } // (a call of pairs that all miss has none)
-		hipLaunchKernelGGL(pairs_finish_kernel, dim3(1), dim3(kFinishThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
-	// the list: the scan of the jobs' points and the second walk (its kernel cuts the list at the points found)
-	auto list_points = [&](cvxp_pair_point *into, uint32_t limit) {
-		if (jobs == 0) { return hipSuccess; }
-		A.points = into;
-		A.limit = limit;
-		cvxi::ExclusiveScan(ctx->stream, A.counts, (int)(jobs + 1), reinterpret_cast<unsigned long long *>(scratch + oChunks), reinterpret_cast<unsigned long long *>(scratch + oTotal));
-		hipLaunchKernelGGL(pairs_write_kernel, dim3(WalkGrid(jobs)), dim3(kThreads), 0, ctx->stream, A);
-		return hipGetLastError();
-	};
-	// A device list needs nothing from the host: everything is enqueued before the one synchronisation.  A host list is sized by the points found.
-	const bool staged = listing && !device;
-	if (e == hipSuccess && listing && device) { e = list_points(points, (uint32_t)std::min<int64_t>(pointCapacity, 0x7FFFFFFF)); }
-	if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.summary, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }
-	if (e == hipSuccess && !device) { e = hipMemcpyAsync(backResults.data(), A.results, resultsBytes, hipMemcpyDeviceToHost, ctx->stream); }
-	if (e == hipSuccess && !staged) { e = D.End(); }
-	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return D.Fail(e); }
-	if (listing && host.points >= ((int64_t)1 << 31)) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: the contacts hold %lld points", call, (long long)host.points); }
-	if (staged) {
-		const size_t wanted = (size_t)std::min<int64_t>(host.points, pointCapacity);
-		if (wanted) {
-			backPoints.resize(wanted);
-			e = D.Allocate(&list, wanted * sizeof(cvxp_pair_point));
-			if (e == hipSuccess) { e = list_points(reinterpret_cast<cvxp_pair_point *>(list), (uint32_t)wanted); }
-			if (e == hipSuccess) { e = hipMemcpyAsync(backPoints.data(), list, wanted * sizeof(cvxp_pair_point), hipMemcpyDeviceToHost, ctx->stream); }
-		}
-		if (e == hipSuccess) { e = D.End(); }
-		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-		if (e != hipSuccess) { return D.Fail(e); }
-	}
-	// (nothing is handed out to the host before the call can no longer fail)
-	if (!backResults.empty()) { std::memcpy(results, backResults.data(), resultsBytes); }
-	if (!backPoints.empty()) { std::memcpy(points, backPoints.data(), backPoints.size() * sizeof(cvxp_pair_point)); }
-	if (summary) { *summary = host; }
-	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
-	return CVX_OK;
+	A.pairCount = pairCount;
+	A.jobs = (uint32_t)jobs;
+	const dim3 walk(std::min(cvxi::Grid((size_t)jobs, kWaves), kMaxWorkgroups)), block(kThreads);
+	const cvxi::PointsCall C{ call, models, modelCount, instances, instanceCount, prefix.data(), pairCount, jobs, pairs, (size_t)pairCount * 8, sizeof(cvxp_pair_result),
+		                      sizeof(cvxp_pair_point), results, points, pointCapacity, device, reinterpret_cast<int64_t *>(summary) };
+	return cvxi::RunPointsCall(
+		ctx, C,
+		[&](const cvxi::PointsJob &J) {
+			A.models = J.models;
+			A.instances = J.instances;
+			A.pairs = static_cast<const int32_t *>(J.extra);
+			A.prefix = J.prefix;
+			A.results = static_cast<cvxp_pair_result *>(J.results);
+			A.counts = J.counts;
+			A.summary = reinterpret_cast<cvxp_pairs_summary *>(J.summary);
+			hipLaunchKernelGGL(pairs_init_kernel, dim3(cvxi::Grid((size_t)pairCount)), block, 0, ctx->stream, A);
+			if (jobs > 0) { hipLaunchKernelGGL(pairs_count_kernel, walk, block, 0, ctx->stream, A); } // (a call of pairs that all miss has none)
+			hipLaunchKernelGGL(pairs_finish_kernel, dim3(1), dim3(cvxi::kFinishThreads), 0, ctx->stream, A);
+			return hipSuccess;
+		},
+		[&](const cvxi::PointsJob &J) {
+			A.points = static_cast<cvxp_pair_point *>(J.points);
+			A.limit = J.limit;
+			hipLaunchKernelGGL(pairs_write_kernel, walk, block, 0, ctx->stream, A);
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 } // namespace cvxpairs

@@ -1217,6 +1217,14 @@ class Context:
                                     points.ctypes.data if points.size else None, capacity)
         return results, (points if points.size <= totals["points"] else points[:totals["points"]].copy()), totals, ms
 
+    @staticmethod
+    def _checked_tensor(who, tensor, item_bytes, at_least):
+        """(the device pointer, the items it holds) of a contiguous device tensor of at least `at_least` items of `item_bytes` bytes."""
+        nbytes = tensor.numel() * tensor.element_size()
+        if not tensor.is_cuda or not tensor.is_contiguous() or nbytes < at_least * item_bytes:
+            raise ValueError(f"{who}: a contiguous device tensor of at least {at_least} x {item_bytes} bytes")
+        return tensor.data_ptr(), nbytes // item_bytes
+
     def world_contacts_device(self, models, instances, results_tensor, points_tensor=None, solid_outside: int = SURFACE_OUTSIDE_DEFAULT):
         """world_contacts on device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr) as place_models_device's (gpu.lifted_model of
         device pools gives one), `results_tensor` a contiguous device tensor of at least 120 bytes per instance, `points_tensor` (or None: the
@@ -1224,14 +1232,8 @@ class Context:
         device milliseconds) once the summary is on the host: the tensors are complete then."""
         descriptors = self._device_models(models, "world_contacts_device")
         inst = self._instances(instances)
-
-        def checked(tensor, item_bytes, at_least):
-            nbytes = tensor.numel() * tensor.element_size()
-            if not tensor.is_cuda or not tensor.is_contiguous() or nbytes < at_least * item_bytes:
-                raise ValueError(f"world_contacts_device: a contiguous device tensor of at least {at_least} x {item_bytes} bytes")
-            return tensor.data_ptr(), nbytes // item_bytes
-        results_ptr, _ = checked(results_tensor, C.sizeof(ContactResult), len(inst))
-        points_ptr, capacity = checked(points_tensor, C.sizeof(ContactPoint), 0) if points_tensor is not None else (None, 0)
+        results_ptr, _ = self._checked_tensor("world_contacts_device", results_tensor, C.sizeof(ContactResult), len(inst))
+        points_ptr, capacity = self._checked_tensor("world_contacts_device", points_tensor, C.sizeof(ContactPoint), 0) if points_tensor is not None else (None, 0)
         return self._contacts(lib().cvxc_world_contacts_device, descriptors, len(models), inst, solid_outside, results_ptr, points_ptr if capacity else None, capacity)
 
     # -- where placed models touch each other (cvxp_model_contacts, include/cpuvox_gpu_pair_contacts.h) --
@@ -1276,14 +1278,8 @@ class Context:
         descriptors = self._device_models(models, "model_contacts_device")
         inst = self._instances(instances)
         p = self._pairs(pairs, inst, "model_contacts_device")
-
-        def checked(tensor, item_bytes, at_least):
-            nbytes = tensor.numel() * tensor.element_size()
-            if not tensor.is_cuda or not tensor.is_contiguous() or nbytes < at_least * item_bytes:
-                raise ValueError(f"model_contacts_device: a contiguous device tensor of at least {at_least} x {item_bytes} bytes")
-            return tensor.data_ptr(), nbytes // item_bytes
-        results_ptr, _ = checked(results_tensor, C.sizeof(PairResult), len(p))
-        points_ptr, capacity = checked(points_tensor, C.sizeof(PairPoint), 0) if points_tensor is not None else (None, 0)
+        results_ptr, _ = self._checked_tensor("model_contacts_device", results_tensor, C.sizeof(PairResult), len(p))
+        points_ptr, capacity = self._checked_tensor("model_contacts_device", points_tensor, C.sizeof(PairPoint), 0) if points_tensor is not None else (None, 0)
         return self._pair_contacts(lib().cvxp_model_contacts_device, descriptors, len(models), inst, p, results_ptr, points_ptr if capacity else None, capacity)
 
     # -- first-hit rays against placed models (cvxq_model_pick, include/cpuvox_gpu_model_pick.h) --
@@ -1314,15 +1310,9 @@ class Context:
         bytes per ray; ray_count: the rays to pick (None: all of rays_tensor).  Returns the device milliseconds once the hits are complete."""
         descriptors = self._device_models(models, "model_pick_device")
         inst = self._instances(instances)
-
-        def checked(tensor, item_bytes, at_least):
-            nbytes = tensor.numel() * tensor.element_size()
-            if not tensor.is_cuda or not tensor.is_contiguous() or nbytes < at_least * item_bytes:
-                raise ValueError(f"model_pick_device: a contiguous device tensor of at least {at_least} x {item_bytes} bytes")
-            return tensor.data_ptr(), nbytes // item_bytes
-        rays_ptr, n = checked(rays_tensor, C.sizeof(PickRay), 0 if ray_count is None else int(ray_count))
+        rays_ptr, n = self._checked_tensor("model_pick_device", rays_tensor, C.sizeof(PickRay), 0 if ray_count is None else int(ray_count))
         n = n if ray_count is None else int(ray_count)
-        hits_ptr, _ = checked(hits_tensor, C.sizeof(ModelHit), n)
+        hits_ptr, _ = self._checked_tensor("model_pick_device", hits_tensor, C.sizeof(ModelHit), n)
         ms = C.c_float()
         self._check(lib().cvxq_model_pick_device(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), rays_ptr, n, hits_ptr, C.byref(ms)))
         return ms.value

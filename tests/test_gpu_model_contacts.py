@@ -98,7 +98,22 @@ def test_bodies_clipped_by_their_own_boxes(ctx):
 @pytest.mark.parametrize("only", [False, True])
 def test_pairs_with_empty_intersections(ctx, only):
     scene = scene_empty(only)
-    assert_empty(scene, _check(ctx, scene, "empty"), only)
+    want = _check(ctx, scene, "empty")
+    assert_empty(scene, want, only)
+    if not only:
+        return
+    # a list asked for when there are no jobs: no walk and no scan is launched, and nothing is written
+    models, instances, pairs = scene
+    assert want[2]["jobs"] == 0 and want[2]["points"] == 0 and len(want[1]) == 0
+    results, points, totals, _ = ctx.model_contacts(models, instances, pairs, capacity=4)
+    assert len(points) == 0 and results.tobytes() == want[0].tobytes() and totals == want[2], "a host list of no jobs"
+    descriptors, keep = _device_models(models)  # noqa: F841  (keep: the tensors the descriptors point to)
+    device_results = torch.full((len(pairs) * RESULT_BYTES,), SENTINEL, dtype=torch.uint8, device="cuda")
+    device_points = torch.full((4 * POINT_BYTES,), SENTINEL, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    totals, ms = ctx.model_contacts_device(descriptors, instances, pairs, device_results, device_points)
+    assert ms >= 0.0 and totals == want[2] and device_results.cpu().numpy().tobytes() == want[0].tobytes(), "a device list of no jobs"
+    assert (device_points.cpu().numpy() == SENTINEL).all(), "no byte of the list is written"
 
 
 # ---- 6. more pairs than the finish kernel has threads --------------------------------------------------------------------------------------------
