@@ -287,7 +287,8 @@ def test_the_lattice(rules, tmp_path):
 
 # ---- random small calls -------------------------------------------------------------------------------------------------------------------------
 
-def test_both_forms_match_the_model_on_random_calls(rules, tmp_path):
+def random_calls():
+    """The 160 random calls (seed 20261) as [(models, instances, pairs, the name of every instance's map)]; the GPU tests run them too."""
     rng = np.random.default_rng(20261)
     names = sorted(MAPS)
     cases = []
@@ -316,6 +317,12 @@ def test_both_forms_match_the_model_on_random_calls(rules, tmp_path):
         pairs = np.int32([(a, b) for a in range(k) for b in range(k) if a != b])
         pairs = pairs[rng.permutation(len(pairs))[:int(rng.integers(1, len(pairs) + 1))]]
         cases.append((models, instances, pairs, used))
+    return cases
+
+
+def test_both_forms_match_the_model_on_random_calls(rules, tmp_path):
+    names = sorted(MAPS)
+    cases = random_calls()
     want = [model_of(*c[:3]) for c in cases]
     touching = {name: 0 for name in names}
     tall = clipped = empty = with_points = buried = 0
