@@ -1484,6 +1484,29 @@ int cvx_debug_section_histogram(cvx_context *ctx, uint64_t out[128], int reset)
 #endif
 }
 
+int cvxd_clip_census(cvx_context *ctx, uint64_t out[96], int reset)
+{
+	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
+	if (!out) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "out is NULL"); }
+#if defined(CVX_PROFILE_SECTIONS) && defined(CVX_PROFILE_COUNTS)
+	CVX_HIP(ctx, hipSetDevice(ctx->device));
+	CVX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	unsigned long long tmp[CVX_CLIP_CENSUS_WORDS];
+	static_assert(CVX_CLIP_CENSUS_WORDS == 96, "include/cpuvox_gpu_diag.h: out[96]");
+	CVX_HIP(ctx, hipMemcpyFromSymbol(tmp, HIP_SYMBOL(cvxk::g_clipCensus), sizeof tmp));
+	for (int i = 0; i < CVX_CLIP_CENSUS_WORDS; i++) { out[i] = tmp[i]; }
+	if (reset) {
+		std::memset(tmp, 0, sizeof tmp);
+		CVX_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(cvxk::g_clipCensus), tmp, sizeof tmp));
+	}
+	return CVX_OK;
+#else
+	(void)reset;
+	for (int i = 0; i < 96; i++) { out[i] = 0; }
+	return Fail(ctx, CVX_ERR_NOT_READY, "this is not the section-count build of the library (make gpu-count)");
+#endif
+}
+
 int cvx_selftest_math(cvx_context *ctx, int op, int n, const float *a, const float *b, float *out)
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }

@@ -506,6 +506,77 @@ struct ProfLane {};
 #define CVX_WAITPROBE(n) ((void)0)
 #endif
 
+// ---- counting build only: census of the frustum clip outside its all-straddle instance (cvxd_clip_census, tools/clip_census.py) ----
+// Per wave execution that fails the all-straddle ballot (the general instance as it was before the inverted-straddle one was split off), which cases of
+// GetWorldBoundsClippingCamSpace the clipping lanes are in.  A lane's class per end (Last, Next) from clip_world_bounds' own four compares:
+// 0 straddle, 1 foot below / top inside, 2 foot inside / top above, 3 both inside, 4 entirely outside, 5 inverted straddle (foot above the window, top
+// below it: the view of a world column in a segment whose pixel axis runs against the world's up), 6 the inverted rest.
+//   [cl * 7 + cn]   executions whose lanes all share the class pair (cl at Last, cn at Next)          [49] executions whose lanes do not share one pair
+//   [50]            all executions
+//   [51 + 3 k + j]  wave-uniform predicate k (both ends): j = 0 every lane satisfies it, 1 some but not all do, 2 the lanes that do in the executions of j = 1
+//                   k = 0: !a1 && !b2   1: ... && !a2 (no max clip)   2: ... && !b1 (no min clip)   3 - 5 the mirror image: !b1 && !a2, ... && !b2, ... && !a1
+//                   k = 6: a1 && !a2 && b2 (inverted straddle, the predicate of the instance that exists)
+//   [72] executions of the inverted-straddle instance   [73] of the general instance   [74] of the general instance with an inverted-straddling lane in it   [75] those lanes
+#if defined(CVX_PROFILE_SECTIONS) && defined(CVX_PROFILE_COUNTS)
+#define CVX_CLIP_CENSUS_WORDS 96
+__device__ unsigned long long g_clipCensus[CVX_CLIP_CENSUS_WORDS];
+__device__ __forceinline__ void clip_census(f3 minLast, f3 maxLast, f3 minNext, f3 maxNext, float fMin, float fMax)
+{
+	bool a1[2], a2[2], b1[2], b2[2];
+	int cls[2];
+	const f3 pMins[2] = { minLast, minNext }, pMaxs[2] = { maxLast, maxNext };
+	for (int e = 0; e < 2; e++) {
+		const f3 pMin = pMins[e], pMax = pMaxs[e];
+		a1[e] = pMin.x > pMin.z * fMax;
+		a2[e] = pMax.x > pMax.z * fMax;
+		b1[e] = pMin.x < pMin.z * fMin;
+		b2[e] = pMax.x < pMax.z * fMin;
+		const bool n1 = !a1[e], n2 = !a2[e];
+		int c = 6;
+		if (n1 && b1[e] && a2[e]) { c = 0; }
+		else if ((a1[e] && a2[e]) || (n1 && n2 && b1[e] && b2[e])) { c = 4; }
+		else if (a1[e] && b2[e]) { c = 5; }
+		else if (n1 && n2 && b1[e] && !b2[e]) { c = 1; }
+		else if (n1 && !b1[e] && a2[e] && !b2[e]) { c = 2; }
+		else if (n1 && n2 && !b1[e] && !b2[e]) { c = 3; }
+		cls[e] = c;
+	}
+	const bool pa = !a1[0] && !b2[0] && !a1[1] && !b2[1];
+	const bool pm = !b1[0] && !a2[0] && !b1[1] && !a2[1];
+	const bool pred[7] = { pa, pa && !a2[0] && !a2[1], pa && !b1[0] && !b1[1], pm, pm && !b2[0] && !b2[1], pm && !a1[0] && !a1[1],
+	                       a1[0] && !a2[0] && b2[0] && a1[1] && !a2[1] && b2[1] };
+	const unsigned long long act = __ballot(1);
+	const bool leader = (int)(threadIdx.x & 63) == __ffsll((long long)act) - 1;
+	const int pair = cls[0] * 7 + cls[1];
+	const int first = __builtin_amdgcn_readfirstlane(pair);
+	const bool onePair = __ballot(pair != first) == 0ull;
+	unsigned long long sat[7];
+	for (int k = 0; k < 7; k++) { sat[k] = __ballot(pred[k]); }
+	if (leader) {
+		atomicAdd(&g_clipCensus[onePair ? first : 49], 1ull);
+		atomicAdd(&g_clipCensus[50], 1ull);
+		for (int k = 0; k < 7; k++) {
+			if (sat[k] == act) { atomicAdd(&g_clipCensus[51 + 3 * k], 1ull); }
+			else if (sat[k] != 0ull) { atomicAdd(&g_clipCensus[51 + 3 * k + 1], 1ull); atomicAdd(&g_clipCensus[51 + 3 * k + 2], (unsigned long long)__popcll(sat[k])); }
+		}
+	}
+}
+// which instance the wave went to: arm 0 the inverted-straddle one, 1 the general one (`mine`: this lane satisfies the inverted-straddle predicate)
+__device__ __forceinline__ void clip_census_arm(int arm, bool mine)
+{
+	const unsigned long long act = __ballot(1), sat = __ballot(mine);
+	if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) {
+		atomicAdd(&g_clipCensus[72 + arm], 1ull);
+		if (arm == 1 && sat != 0ull) { atomicAdd(&g_clipCensus[74], 1ull); atomicAdd(&g_clipCensus[75], (unsigned long long)__popcll(sat)); }
+	}
+}
+#define CVX_CLIP_CENSUS(...) clip_census(__VA_ARGS__)
+#define CVX_CLIP_CENSUS_ARM(arm, mine) clip_census_arm(arm, mine)
+#else
+#define CVX_CLIP_CENSUS(...) ((void)0)
+#define CVX_CLIP_CENSUS_ARM(arm, mine) ((void)0)
+#endif
+
 #ifdef CVX_TILE_TIMES /* diagnostic build: clock ticks each launched wave lived, for the launch-order experiment (tools/lpt_oracle.py) */
 __device__ unsigned long long *g_tileTimes;
 #endif
@@ -641,11 +712,15 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 			// CameraData.cs:103,111.  frustumBounds = (integer pixel in [-1, 16385]) -/+ 0.501: magnitude in [0.499, 16386], always "safe"
 			const float invFrustumMin = quot_safe(1.0f, recip_safe(frustumBoundsMin)), invFrustumMax = quot_safe(1.0f, recip_safe(frustumBoundsMax));
 			// What follows the four lerps (:300-421), once per instance of the clip below.  ALL_STRADDLE: every lane of the wave that clips here straddles the
-			// window at both ends (nothing clipped away: the flags are constants); otherwise some lane does not, so the "window untouched" shortcut
-			// cannot hold for the wave and every lane takes the reference's path, which is right for any lane -- no residual tests, no branch.
+			// window at both ends, either the ordinary way (CLIP_STRADDLE: foot below the window, top above it) or inverted (CLIP_INVERTED: foot above, top
+			// below -- the same column in a segment whose pixel axis runs against the world's up); nothing is clipped away, the flags are constants.
+			// CLIP_GENERAL: some lane does neither, so the "window untouched" shortcut cannot hold for the wave and every lane takes the reference's path, which
+			// is right for any lane -- no residual tests, no branch.
 			// false = the ray is finished (counting build only).
-			const auto clipTail = [&](auto allStraddleTag, float clipLastMinLerp, float clipLastMaxLerp, float clipNextMinLerp, float clipNextMaxLerp, bool clippedLast_, bool clippedNext_) __attribute__((always_inline)) -> bool {
-				constexpr bool ALL_STRADDLE = decltype(allStraddleTag)::value;
+			enum { CLIP_GENERAL = 0, CLIP_STRADDLE = 1, CLIP_INVERTED = 2 };
+			const auto clipTail = [&](auto instanceTag, float clipLastMinLerp, float clipLastMaxLerp, float clipNextMinLerp, float clipNextMaxLerp, bool clippedLast_, bool clippedNext_) __attribute__((always_inline)) -> bool {
+				constexpr int INSTANCE = decltype(instanceTag)::value;
+				constexpr bool ALL_STRADDLE = INSTANCE != CLIP_GENERAL;
 				const bool clippedLast = !ALL_STRADDLE && clippedLast_, clippedNext = !ALL_STRADDLE && clippedNext_;
 				// (:297-299 leaves here when both ends are outside the window; that exit is taken together with the next one below --
 				// nothing in between has an effect that survives the end of the ray)
@@ -673,11 +748,15 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 				// floor(min) = k - 1 and ceil(max) = m + 1 whatever the exact quotients are: min < max (no swap, :339-346), the range contains
 				// [nextFreePixelMin, nextFreePixelMax] (no exit, nothing moves), and neither end was clipped away.  So nothing of :337-421 has any
 				// effect and the four divisions are not needed.  Any lane for which this cannot be shown takes the reference's path below.
+				// CLIP_INVERTED is the mirror image: the min points were clipped against frustumBoundsMax and the max points against frustumBoundsMin, so under
+				// the same residual test the "min" quotients lie within 0.402 of m + 0.501 and the "max" quotients within 0.402 of k - 0.501; k <= m, so
+				// max < min at both ends and :339-346 swaps them, after which floor(min) = k - 1 and ceil(max) = m + 1 as above.
+				const float minClipBound = INSTANCE == CLIP_INVERTED ? frustumBoundsMax : frustumBoundsMin, maxClipBound = INSTANCE == CLIP_INVERTED ? frustumBoundsMin : frustumBoundsMax;
 				const auto onBound = [](f3 p, float f) { return fabsf(p.x - f * p.z) < 0.4f * fabsf(p.z); };
 				// (`&`, not `&&`: six short tests evaluated straight-line instead of a chain of divergent branches)
 				// (a lane that does not straddle at both ends never qualifies: outside the all-straddle instance the wave holds one, its branch would always be taken)
-				const bool windowUntouched = !COUNT && ALL_STRADDLE && ((int)onBound(minClipA, frustumBoundsMin) & (int)onBound(minClipB, frustumBoundsMin) &
-				                                                        (int)onBound(maxClipA, frustumBoundsMax) & (int)onBound(maxClipB, frustumBoundsMax)) != 0;
+				const bool windowUntouched = !COUNT && ALL_STRADDLE && ((int)onBound(minClipA, minClipBound) & (int)onBound(minClipB, minClipBound) &
+				                                                        (int)onBound(maxClipA, maxClipBound) & (int)onBound(maxClipB, maxClipBound)) != 0;
 				if (!CVX_USUAL(windowUntouched)) {
 					float minNext = minClipB.x / minClipB.z;
 					float minLast = minClipA.x / minClipA.z;
@@ -712,22 +791,37 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 			{
 				const auto straddle = [&](f3 pMin, f3 pMax) { return ((int)!(pMin.x > pMin.z * frustumBoundsMax) & (int)(pMin.x < pMin.z * frustumBoundsMin) & (int)(pMax.x > pMax.z * frustumBoundsMax)) != 0; };
 				const bool both = ((int)straddle(camSpaceMinLast, camSpaceMaxLast) & (int)straddle(camSpaceMinNext, camSpaceMaxNext)) != 0;
+				// the inverted straddle: a1 && !a2 && b2 of clip_world_bounds (evaluated only by the waves that fail the ballot on `both`)
+				const auto inverted = [&](f3 pMin, f3 pMax) { return ((int)(pMin.x > pMin.z * frustumBoundsMax) & (int)!(pMax.x > pMax.z * frustumBoundsMax) & (int)(pMax.x < pMax.z * frustumBoundsMin)) != 0; };
+				const auto bothInverted = [&]() { return ((int)inverted(camSpaceMinLast, camSpaceMaxLast) & (int)inverted(camSpaceMinNext, camSpaceMaxNext)) != 0; };
 				// Round 5: when EVERY lane that clips here sees the column's foot below and its top above the window at both ends -- clip_world_bounds' straddle case, the
 				// ordinary view of a world column -- the four lerps are its clip_min against frustumBoundsMin and clip_max against frustumBoundsMax, nothing is
 				// clipped away, and the wave skips the selects and the flag algebra of the general form (same divisions on the same operands: -0.9 %)
 				bool goesOn;
 				if (__ballot(!both) == 0ull) {
 					CVX_COUNT(13);
-					goesOn = clipTail(std::true_type{}, clip_min(camSpaceMinLast, camSpaceMaxLast, invFrustumMin), clip_max(camSpaceMinLast, camSpaceMaxLast, invFrustumMax),
+					goesOn = clipTail(std::integral_constant<int, CLIP_STRADDLE>{}, clip_min(camSpaceMinLast, camSpaceMaxLast, invFrustumMin), clip_max(camSpaceMinLast, camSpaceMaxLast, invFrustumMax),
 					                  clip_min(camSpaceMinNext, camSpaceMaxNext, invFrustumMin), clip_max(camSpaceMinNext, camSpaceMaxNext, invFrustumMax), false, false);
 				} else {
-					CVX_COUNT(14);
-					if (both) { CVX_COUNT(15); } // (counting build: the straddling lanes of a wave that holds one that does not -- the lanes that the wave's instance sends down the reference's path)
-					float clipLastMinLerp, clipLastMaxLerp, clipNextMinLerp, clipNextMaxLerp;
-					bool straddlesLast, straddlesNext; // (the tail no longer asks: a wave comes here because some lane does not straddle)
-					const bool clippedLast = clip_world_bounds(camSpaceMinLast, camSpaceMaxLast, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipLastMinLerp, clipLastMaxLerp, straddlesLast);
-					const bool clippedNext = clip_world_bounds(camSpaceMinNext, camSpaceMaxNext, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipNextMinLerp, clipNextMaxLerp, straddlesNext);
-					goesOn = clipTail(std::false_type{}, clipLastMinLerp, clipLastMaxLerp, clipNextMinLerp, clipNextMaxLerp, clippedLast, clippedNext);
+					CVX_CLIP_CENSUS(camSpaceMinLast, camSpaceMaxLast, camSpaceMinNext, camSpaceMaxNext, frustumBoundsMin, frustumBoundsMax);
+					if (__ballot(!bothInverted()) == 0ull) {
+						// EVERY lane that clips here sees the column's foot above and its top below the window at both ends (a1 && !a2 && b2 in clip_world_bounds: 73 % of the
+						// executions that fail the ballot above on the benchmark's frames, profiles/clip_classes_census.txt).  clip_world_bounds then gives
+						// minLerp = clip_min against frustumBoundsMax, maxLerp = clip_max against frustumBoundsMin and "not outside", whatever b1 is: the same
+						// divisions on the same operands, without the selects and the flag algebra, and with the mirrored "window untouched" shortcut of the tail.
+						CVX_CLIP_CENSUS_ARM(0, true);
+						goesOn = clipTail(std::integral_constant<int, CLIP_INVERTED>{}, clip_min(camSpaceMinLast, camSpaceMaxLast, invFrustumMax), clip_max(camSpaceMinLast, camSpaceMaxLast, invFrustumMin),
+						                  clip_min(camSpaceMinNext, camSpaceMaxNext, invFrustumMax), clip_max(camSpaceMinNext, camSpaceMaxNext, invFrustumMin), false, false);
+					} else {
+						CVX_COUNT(14);
+						if (both) { CVX_COUNT(15); } // (counting build: the straddling lanes of a wave that holds one that does not -- the lanes that the wave's instance sends down the reference's path)
+						CVX_CLIP_CENSUS_ARM(1, bothInverted());
+						float clipLastMinLerp, clipLastMaxLerp, clipNextMinLerp, clipNextMaxLerp;
+						bool straddlesLast, straddlesNext; // (the tail no longer asks: a wave comes here because some lane does not straddle)
+						const bool clippedLast = clip_world_bounds(camSpaceMinLast, camSpaceMaxLast, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipLastMinLerp, clipLastMaxLerp, straddlesLast);
+						const bool clippedNext = clip_world_bounds(camSpaceMinNext, camSpaceMaxNext, frustumBoundsMin, frustumBoundsMax, invFrustumMin, invFrustumMax, clipNextMinLerp, clipNextMaxLerp, straddlesNext);
+						goesOn = clipTail(std::integral_constant<int, CLIP_GENERAL>{}, clipLastMinLerp, clipLastMaxLerp, clipNextMinLerp, clipNextMaxLerp, clippedLast, clippedNext);
+					}
 				}
 				if (COUNT && !goesOn) { return false; }
 			}

@@ -86,6 +86,12 @@ ABI_HEADERS = [
 # cvx_debug_last_launch: out[0], the kernel instance a draw went to
 INSTANCE_COUNTING, INSTANCE_BATCH, INSTANCE_LONE, INSTANCE_LONE_WIDE = 0, 1, 2, 3
 LAUNCH_FIELDS = ("instance", "tiles", "waves", "min_rays", "max_rays", "max_dup_shift", "split", "lds_words")
+# cvxd_clip_census (include/cpuvox_gpu_diag.h; the first of the diagnostics with the prefix cvxd_, which like the cvxc_ / cvxp_ / cvxq_ families are no rows of the
+# cvx_ export lists above): a lane's class at one end of the frustum clip, and the wave-uniform predicates counted
+CLIP_CLASSES = ("straddle", "foot below / top inside", "foot inside / top above", "both inside", "entirely outside", "inverted straddle", "inverted rest")
+CLIP_PREDICATES = (("nothing_clipped", "a1 and b2 false in every lane at both ends"), ("no_max_clip", "... and a2 false too"), ("no_min_clip", "... and b1 false too"),
+                   ("mirror_nothing_clipped", "b1 and a2 false in every lane at both ends"), ("mirror_no_max_clip", "... and b2 false too"),
+                   ("mirror_no_min_clip", "... and a1 false too"), ("inverted_straddle", "a1 and b2 true, a2 false in every lane at both ends"))
 
 
 class Counters(C.Structure):
@@ -616,6 +622,8 @@ def _bind(path: str) -> C.CDLL:
         L.cvx_selftest_math.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvx_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
         L.cvx_selftest_lone.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "cvxd_clip_census"):  # the counting / profiling / experiment builds; a name of its own family (cvxd_), so no row of DIAG_EXPORTS
+        L.cvxd_clip_census.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
     L.cvx_world_downsample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)]
     L.cvx_world_build_lods.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -1721,6 +1729,19 @@ class Context:
         out = (C.c_uint64 * 128)()
         self._check(self._diag("cvx_debug_section_histogram")(self._h, out, int(reset)))
         return [list(out[i * 8:(i + 1) * 8]) for i in range(16)]
+
+    def debug_clip_census(self, reset: bool = False) -> dict:
+        """Counting diagnostic build only: the census of the frustum clip's general instance (include/cpuvox_gpu_diag.h).  "pairs": {(class at Last,
+        class at Next): executions whose lanes all share it} (indices into CLIP_CLASSES), "mixed_pairs", "executions", "predicates": {name of
+        CLIP_PREDICATES: {"all", "some", "some_lanes"}}, "arms": executions of the "inverted_straddle" and the "general" instance, of the latter with an
+        inverted-straddling lane in it ("general_mixed") and those lanes ("general_mixed_lanes")."""
+        out = (C.c_uint64 * 96)()
+        self._check(self._diag("cvxd_clip_census")(self._h, out, int(reset)))
+        n = len(CLIP_CLASSES)
+        return {"pairs": {(cl, cn): int(out[cl * n + cn]) for cl in range(n) for cn in range(n)}, "mixed_pairs": int(out[n * n]), "executions": int(out[n * n + 1]),
+                "predicates": {name: {"all": int(out[51 + 3 * k]), "some": int(out[52 + 3 * k]), "some_lanes": int(out[53 + 3 * k])}
+                               for k, (name, _) in enumerate(CLIP_PREDICATES)},
+                "arms": {"inverted_straddle": int(out[72]), "general": int(out[73]), "general_mixed": int(out[74]), "general_mixed_lanes": int(out[75])}}
 
     def selftest_math(self, op: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -38,6 +38,17 @@ int cvx_debug_section_cycles(cvx_context *ctx, uint64_t out[32], int reset); /* 
 /* Counting diagnostic build only (make gpu-count): how many lanes were active each time a wave executed section i:
  * out[i * 8 + b] = executions with 8b+1 .. 8b+8 active lanes. */
 int cvx_debug_section_histogram(cvx_context *ctx, uint64_t out[128], int reset);
+/* Counting diagnostic build only: census of the batch kernel's frustum clip outside its all-straddle instance, per wave execution, accumulated over
+ * all launches.  A lane's class at one end (Last / Next intersection) from the four compares of GetWorldBoundsClippingCamSpace: 0 straddle,
+ * 1 foot below / top inside the window, 2 foot inside / top above, 3 both inside, 4 entirely outside, 5 inverted straddle (foot above, top below),
+ * 6 the inverted rest.  out[7 cl + cn] = executions whose clipping lanes all have class cl at Last and cn at Next, out[49] = executions whose lanes
+ * differ, out[50] = all executions.  out[51 + 3 k + j]: wave-uniform predicate k (a1 / a2 = foot / top above the window, b1 / b2 = below it, at both
+ * ends; k = 0: !a1 && !b2, 1: ... && !a2, 2: ... && !b1, 3: !b1 && !a2, 4: ... && !b2, 5: ... && !a1, 6: a1 && !a2 && b2, the inverted straddle);
+ * j = 0 executions in which every lane satisfies it, 1 in which some but not all do, 2 the lanes that do in the executions of j = 1.
+ * out[72] = executions of the inverted-straddle instance, out[73] = of the general instance, out[74] = of the general instance with at least one
+ * inverted-straddling lane in it, out[75] = those lanes.  (Prefix cvxd_: diagnostics added after the list of cvx_debug_ entry points was closed; bound by
+ * cpuvox_amd.gpu wherever a library exports it.) */
+int cvxd_clip_census(cvx_context *ctx, uint64_t out[96], int reset);
 
 /* Arithmetic self-test hook used by tests: evaluates op on n float pairs on
  * the device.  op: 0 a/b, 1 sqrt(a), 2 1/sqrt(a), 3 a*b+c style lerp a+b*(b-a),
