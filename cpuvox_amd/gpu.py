@@ -69,6 +69,9 @@ PAIR_CONTACTS_EXPORTS = ["cvxp_model_contacts", "cvxp_model_contacts_device", "c
 # include/cpuvox_gpu_model_pick.h: first-hit rays against placed models.  A family of its own again (prefix cvxq_), no row of ABI_HEADERS:
 # tests/test_abi_model_pick.py checks it.
 MODEL_PICK_EXPORTS = ["cvxq_model_pick", "cvxq_model_pick_device"]
+# include/cpuvox_gpu_model_draw.h: placed models drawn into the rendered frame.  One more family of its own (prefix cvxv_), no row of ABI_HEADERS:
+# tests/test_abi_model_draw.py checks it.
+MODEL_DRAW_EXPORTS = ["cvxv_view_from_camera", "cvxv_view_rays", "cvxv_models_draw", "cvxv_models_draw_device"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -136,6 +139,8 @@ SNAPSHOT_IGNORE_COLOUR = 1                       # cvx_world_snapshot_diff: flag
 LIFT_COPY, LIFT_REMOVE = 0, 1                    # cvx_world_lift_pieces: op
 PAIR_CONTACTS_MAX_PAIRS = 65536                  # CVXP_MAX_PAIRS: cvxp_model_contacts, pairCount
 MODEL_PICK_MAX_RAYS = 65536                      # CVXQ_PICK_MAX_RAYS: cvxq_model_pick, rayCount
+DRAW_WORLD, DRAW_DEPTH_TEST = 1, 2                # CVXV_DRAW_WORLD, CVXV_DRAW_DEPTH_TEST: cvxv_models_draw, flags
+DRAW_MAX_SIZE = 8192                             # CVXV_MAX_SIZE: cvxv_view, width and height
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -183,6 +188,15 @@ class PairsSummary(C.Structure):  # cvxp_pairs_summary
 class ModelHit(C.Structure):  # cvxq_model_hit
     _fields_ = [("voxel", C.c_int32 * 3), ("face", C.c_int32), ("argb", C.c_uint32), ("t", C.c_float), ("instance", C.c_int32), ("modelVoxel", C.c_int32 * 3),
                 ("pad_", C.c_int32 * 2)]
+
+
+class DrawView(C.Structure):  # cvxv_view
+    _fields_ = [("origin", C.c_float * 3), ("maxT", C.c_float), ("dir0", C.c_double * 3), ("dirX", C.c_double * 3), ("dirY", C.c_double * 3),
+                ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class DrawSummary(C.Structure):  # cvxv_draw_summary
+    _fields_ = [("pixelsDrawn", C.c_int64), ("pixelsOccluded", C.c_int64), ("jobs", C.c_int64), ("pad_", C.c_int64)]
 
 
 class SpreadParams(C.Structure):  # cvx_spread_params
@@ -327,6 +341,7 @@ SURFACE_RECT_DTYPE, SURFACE_RECTS_SUMMARY_DTYPE = np.dtype(SurfaceRect), np.dtyp
 CONTACT_RESULT_DTYPE, CONTACT_POINT_DTYPE, CONTACTS_SUMMARY_DTYPE = np.dtype(ContactResult), np.dtype(ContactPoint), np.dtype(ContactsSummary)
 PAIR_RESULT_DTYPE, PAIR_POINT_DTYPE, PAIRS_SUMMARY_DTYPE = np.dtype(PairResult), np.dtype(PairPoint), np.dtype(PairsSummary)
 MODEL_HIT_DTYPE = np.dtype(ModelHit)
+DRAW_VIEW_DTYPE, DRAW_SUMMARY_DTYPE = np.dtype(DrawView), np.dtype(DrawSummary)
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
 
@@ -532,6 +547,42 @@ def screen_rays(camera, width: int, height: int, px, py):
     return np.broadcast_to(pos, directions.shape).copy(), directions
 
 
+def view_from_camera(camera, width: int, height: int, max_t: float = float("inf")) -> "DrawView":
+    """cvxv_view_from_camera: the DrawView of a camera (host.CameraData, or anything with its WorldToScreenMatrix, PositionXZ and PositionY) at
+    width x height -- what screen_rays computes, in doubles: the eye, the un-normalised direction through the centre of pixel (0, 0) and its
+    change per pixel step in x and y.  A pure host call."""
+    if isinstance(camera, CameraData):
+        data = camera
+    else:
+        data = CameraData()
+        data.WorldToScreenMatrix[:] = [float(v) for v in camera.WorldToScreenMatrix[:]]
+        data.PositionXZ[:] = [float(v) for v in camera.PositionXZ[:]]
+        data.PositionY = float(camera.PositionY)
+    out = DrawView()
+    if lib().cvxv_view_from_camera(C.addressof(data), int(width), int(height), float(max_t), C.addressof(out)) != 0:
+        raise ValueError(f"view_from_camera: width and height are 1 .. {DRAW_MAX_SIZE} and the camera's matrix has an inverse")
+    return out
+
+
+def draw_view(origin, dir0, dir_x, dir_y, width: int, height: int, max_t: float = float("inf")) -> "DrawView":
+    """A DrawView from a host's own camera: pixel (x, y)'s ray leaves `origin` along dir0 + x * dir_x + y * dir_y (row 0 = the bottom row)."""
+    out = DrawView()
+    out.origin[:], out.dir0[:], out.dirX[:], out.dirY[:] = [float(v) for v in origin], [float(v) for v in dir0], [float(v) for v in dir_x], [float(v) for v in dir_y]
+    out.maxT, out.width, out.height = float(max_t), int(width), int(height)
+    return out
+
+
+def view_rays(view, x0: int = 0, y0: int = 0, w=None, h=None) -> np.ndarray:
+    """cvxv_view_rays: the rays models_draw gives the pixels [x0, x0 + w) x [y0, y0 + h) of the view (default: all of it) as a PICK_RAY_DTYPE array
+    of shape (h, w), byte for byte the rule's own; pick and model_pick take them.  A pure host call."""
+    w = view.width - int(x0) if w is None else int(w)
+    h = view.height - int(y0) if h is None else int(h)
+    rays = np.zeros((max(h, 0), max(w, 0)), dtype=PICK_RAY_DTYPE)
+    if lib().cvxv_view_rays(C.addressof(view), int(x0), int(y0), w, h, rays.ctypes.data if rays.size else None) != 0:
+        raise ValueError("view_rays: the window lies inside the view and is not empty")
+    return rays
+
+
 class RaybufferLayout(C.Structure):
     _fields_ = [("width", C.c_int32), ("rayCapacity", C.c_int32), ("tileRays", C.c_int32),
                 ("tileCapacity", C.c_int32), ("tileBytes", C.c_int64)]
@@ -703,6 +754,11 @@ def _bind(path: str) -> C.CDLL:
     L.cvxp_pair_response.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.cvxq_model_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]
     L.cvxq_model_pick_device.argtypes = L.cvxq_model_pick.argtypes
+    L.cvxv_view_from_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
+    L.cvxv_view_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.cvxv_models_draw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(DrawSummary), C.POINTER(C.c_float)]
+    L.cvxv_models_draw_device.argtypes = L.cvxv_models_draw.argtypes
     L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
     L.cvx_shard_plan_destroy.restype = None
@@ -1325,6 +1381,56 @@ class Context:
         self._check(lib().cvxq_model_pick_device(self._h, C.addressof(descriptors), len(models), C.addressof(inst), len(inst), rays_ptr, n, hits_ptr, C.byref(ms)))
         return ms.value
 
+    # -- placed models drawn into the rendered frame (cvxv_models_draw, include/cpuvox_gpu_model_draw.h) --
+    def _models_draw(self, entry, descriptors, model_count, instances, view, flags, image_ptr, depth_ptr, ids_ptr):
+        inst = self._instances(instances)
+        if not isinstance(view, DrawView):
+            raise ValueError("models_draw: view is a gpu.DrawView (gpu.view_from_camera or gpu.draw_view makes one)")
+        summary, ms = DrawSummary(), C.c_float()
+        self._check(entry(self._h, C.addressof(descriptors), model_count, C.addressof(inst), len(inst), C.addressof(view), int(flags), image_ptr or None,
+                          depth_ptr or None, ids_ptr or None, C.byref(summary), C.byref(ms)))
+        return {name: int(getattr(summary, name)) for name in DRAW_SUMMARY_DTYPE.names if name != "pad_"}, ms.value
+
+    def models_draw(self, models, instances, view, flags: int = 0, image=None, depth=None, ids=None):
+        """Draws the nearest placed instance of every pixel of `view` (a gpu.DrawView) into host arrays of shape (height, width), row 0 the bottom
+        row: image uint32 (the model's colour word), depth float32 (distance in voxels) and ids int32 (the instance's index).  An array
+        that is None is made here (image 0, depth +inf, ids -1); the arrays given are copied, and every pixel no body shows in keeps what it
+        held.  flags: DRAW_WORLD -- the uploaded world occludes --, DRAW_DEPTH_TEST -- a pixel's ray ends at the depth it holds.  `models` and
+        `instances` as world_contacts' (an instance's op is not read).  Returns (image, depth, ids, the counts of cvxv_draw_summary as a dict,
+        device milliseconds)."""
+        descriptors, keep = self._models(models, "models_draw")  # noqa: F841  (keep: the arrays the descriptors point to)
+        if not isinstance(view, DrawView):
+            raise ValueError("models_draw: view is a gpu.DrawView (gpu.view_from_camera or gpu.draw_view makes one)")
+        shape = (view.height, view.width)
+
+        def own(array, dtype, fill, name):
+            if array is None:
+                return np.full(shape, fill, dtype=dtype)
+            a = np.array(array, dtype=dtype, order="C")
+            if a.shape != shape:
+                raise ValueError(f"models_draw: {name} has the shape (height, width) = {shape}")
+            return a
+        image, depth, ids = own(image, np.uint32, 0, "image"), own(depth, np.float32, np.inf, "depth"), own(ids, np.int32, -1, "ids")
+        summary, ms = self._models_draw(lib().cvxv_models_draw, descriptors, len(models), instances, view, flags, image.ctypes.data, depth.ctypes.data, ids.ctypes.data)
+        return image, depth, ids, summary, ms
+
+    def models_draw_device(self, models, instances, view, flags, image_tensor, depth_tensor=None, ids_tensor=None):
+        """models_draw on device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr) as place_models_device's (gpu.lifted_model of
+        device pools gives one); image_tensor, depth_tensor and ids_tensor are contiguous device tensors of at least width * height 4-byte
+        elements, or None (not all three) -- or plain device addresses, as screen_device_ptr's, which are taken as they are.  Returns (the
+        counts of cvxv_draw_summary as a dict, device milliseconds) once the outputs are complete."""
+        descriptors = self._device_models(models, "models_draw_device")
+        if not isinstance(view, DrawView):
+            raise ValueError("models_draw_device: view is a gpu.DrawView (gpu.view_from_camera or gpu.draw_view makes one)")
+        pixels = view.width * view.height
+
+        def pointer(tensor):
+            if tensor is None or isinstance(tensor, int):
+                return tensor
+            return self._checked_tensor("models_draw_device", tensor, 4, pixels)[0]
+        return self._models_draw(lib().cvxv_models_draw_device, descriptors, len(models), instances, view, flags, pointer(image_tensor), pointer(depth_tensor),
+                                 pointer(ids_tensor))
+
     @staticmethod
     def _model_read(size, to_world):
         n = np.ascontiguousarray(size, dtype=np.int32)
@@ -1673,6 +1779,14 @@ class Context:
         p = C.c_void_p()
         self._check(lib().cvx_blit_segments_batch(self._h, first_buffer, frame_count, C.c_void_p(dst_device) if dst_device else None, C.byref(p)))
         return p.value
+
+    def screen_device_ptr(self):
+        """cvx_screen_device_ptr: (the device address of the image blit_segments(to_host=False) left on the device, its bytes);
+        models_draw_device takes the address as its image."""
+        p = C.c_void_p()
+        n = C.c_int64()
+        self._check(lib().cvx_screen_device_ptr(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def raybuffer_device_ptr(self, buffer_index: int, which: int):
         p = C.c_void_p()
