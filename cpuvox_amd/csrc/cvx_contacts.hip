@@ -168,10 +168,14 @@ __global__ __launch_bounds__(cvxi::kFinishThreads) void contacts_finish_kernel(A
 	if (threadIdx.x == 0) { *A.summary = cvxc_contacts_summary{ (int64_t)totals[0], (int64_t)totals[1], (int64_t)points, (int64_t)totals[2] }; }
 }
 
-// Both calls: `device` says where the models' arrays, `results` and `points` live.
-static int Contacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, int solidOutside,
-                    cvxc_contact_result *results, cvxc_contact_point *points, int64_t pointCapacity, bool device, cvxc_contacts_summary *summary, float *outDeviceMs)
+} // namespace cvxcontacts
+
+// Both calls (and cvx_sweep.hip's second phase: cvx_model_call.h): `device` says where the models' arrays, `results` and `points` live.
+int cvxi::WorldContacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount,
+                        int solidOutside, cvxc_contact_result *results, cvxc_contact_point *points, int64_t pointCapacity, bool device, bool modelsStaged,
+                        cvxc_contacts_summary *summary, float *outDeviceMs)
 {
+	using namespace cvxcontacts;
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	char message[160];
 	if (!cvxb::ContactsValidate(models, modelCount, instances, instanceCount, solidOutside, results, points, pointCapacity, message, sizeof message)) {
@@ -192,7 +196,7 @@ static int Contacts(cvx_context *ctx, const char *call, const cvx_model *models,
 	A.solidOutside = solidOutside;
 	const dim3 walk(std::min(cvxi::Grid((size_t)pairs, kWaves), kMaxWorkgroups)), block(kThreads);
 	const cvxi::PointsCall C{ call, models, modelCount, instances, instanceCount, prefix.data(), instanceCount, pairs, nullptr, 0, sizeof(cvxc_contact_result),
-		                      sizeof(cvxc_contact_point), results, points, pointCapacity, device, reinterpret_cast<int64_t *>(summary) };
+		                      sizeof(cvxc_contact_point), results, points, pointCapacity, device, reinterpret_cast<int64_t *>(summary), modelsStaged };
 	return cvxi::RunPointsCall(
 		ctx, C,
 		[&](const cvxi::PointsJob &J) {
@@ -216,23 +220,21 @@ static int Contacts(cvx_context *ctx, const char *call, const cvx_model *models,
 		outDeviceMs);
 }
 
-} // namespace cvxcontacts
-
 extern "C" {
 
 int cvxc_world_contacts(cvx_context *ctx, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, int solidOutside,
                         cvxc_contact_result *results, cvxc_contact_point *points, int64_t pointCapacity, cvxc_contacts_summary *summary, float *outDeviceMs)
 {
-	return cvxcontacts::Contacts(ctx, "cvxc_world_contacts", models, modelCount, instances, instanceCount, solidOutside, results, points, pointCapacity, false, summary,
-	                             outDeviceMs);
+	return cvxi::WorldContacts(ctx, "cvxc_world_contacts", models, modelCount, instances, instanceCount, solidOutside, results, points, pointCapacity, false, false, summary,
+	                           outDeviceMs);
 }
 
 int cvxc_world_contacts_device(cvx_context *ctx, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, int solidOutside,
                                cvxc_contact_result *resultsDevice, cvxc_contact_point *pointsDevice, int64_t pointCapacity, cvxc_contacts_summary *summary,
                                float *outDeviceMs)
 {
-	return cvxcontacts::Contacts(ctx, "cvxc_world_contacts_device", models, modelCount, instances, instanceCount, solidOutside, resultsDevice, pointsDevice, pointCapacity,
-	                             true, summary, outDeviceMs);
+	return cvxi::WorldContacts(ctx, "cvxc_world_contacts_device", models, modelCount, instances, instanceCount, solidOutside, resultsDevice, pointsDevice, pointCapacity,
+	                           true, false, summary, outDeviceMs);
 }
 
 int cvxc_contact_response(const cvxc_contact_result *r, double centre[3], double normal[3], double *depth)

@@ -5,6 +5,7 @@
 
 #include <vector>
 
+#include "cpuvox_gpu_contacts.h"
 #include "cpuvox_gpu_models.h"
 #include "cvx_context.h"
 
@@ -79,6 +80,7 @@ struct PointsCall {
 	int64_t pointCapacity;
 	bool device;
 	int64_t *summary;       // may be null
+	bool modelsStaged = false; // the models' arrays are on the device already whatever `device` says (cvxs_world_sweep's second phase)
 };
 // What RunPointsCall owns and hands to the caller's two launchers: device pointers all
 struct PointsJob {
@@ -95,6 +97,11 @@ struct PointsJob {
 // cvx_model_call.hip.  launchResults enqueues the family's init, count (unless there is no job) and finish kernels: the results complete and the
 // summary at J.summary; launchWrite enqueues its write kernel and is never called without jobs.  The rules it keeps are written down at its definition.
 int RunPointsCall(cvx_context *ctx, const PointsCall &call, Launcher<PointsJob> launchResults, Launcher<PointsJob> launchWrite, float *outDeviceMs);
+// cvx_contacts.hip: the body of cvxc_world_contacts[_device] under the name `call`; `device` says where results and points live, and the models'
+// arrays too unless modelsStaged says that they are on the device anyway (cvx_sweep.hip runs it on the moved instances).
+int WorldContacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, int solidOutside,
+                  cvxc_contact_result *results, cvxc_contact_point *points, int64_t pointCapacity, bool device, bool modelsStaged, cvxc_contacts_summary *summary,
+                  float *outDeviceMs);
 
 #ifdef __HIPCC__
 constexpr int kFinishThreads = 1024;

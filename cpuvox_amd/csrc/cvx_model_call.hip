@@ -26,7 +26,7 @@ int RunPointsCall(cvx_context *ctx, const PointsCall &call, Launcher<PointsJob> 
 {
 	const bool device = call.device, listing = call.pointCapacity > 0;
 	const size_t jobs = (size_t)call.jobs, resultsBytes = (size_t)call.units * call.resultBytes;
-	ModelStaging staging(call.models, call.modelCount, device);
+	ModelStaging staging(call.models, call.modelCount, device || call.modelsStaged);
 	std::vector<uint8_t> backResults(device ? 0 : resultsBytes), backPoints;
 	int64_t host[4] = {};
 	DeviceCall D(ctx, call.call);

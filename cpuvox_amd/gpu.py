@@ -72,6 +72,9 @@ MODEL_PICK_EXPORTS = ["cvxq_model_pick", "cvxq_model_pick_device"]
 # include/cpuvox_gpu_model_draw.h: placed models drawn into the rendered frame.  One more family of its own (prefix cvxv_), no row of ABI_HEADERS:
 # tests/test_abi_model_draw.py checks it.
 MODEL_DRAW_EXPORTS = ["cvxv_view_from_camera", "cvxv_view_rays", "cvxv_models_draw", "cvxv_models_draw_device"]
+# include/cpuvox_gpu_sweep.h: how far placed models can move before they touch the world.  A family of its own too (prefix cvxs_), no row of
+# ABI_HEADERS: tests/test_abi_sweep.py checks it.
+SWEEP_EXPORTS = ["cvxs_world_sweep", "cvxs_world_sweep_device", "cvxs_sweep_offset", "cvxs_instance_moved"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -141,6 +144,7 @@ PAIR_CONTACTS_MAX_PAIRS = 65536                  # CVXP_MAX_PAIRS: cvxp_model_co
 MODEL_PICK_MAX_RAYS = 65536                      # CVXQ_PICK_MAX_RAYS: cvxq_model_pick, rayCount
 DRAW_WORLD, DRAW_DEPTH_TEST = 1, 2                # CVXV_DRAW_WORLD, CVXV_DRAW_DEPTH_TEST: cvxv_models_draw, flags
 DRAW_MAX_SIZE = 8192                             # CVXV_MAX_SIZE: cvxv_view, width and height
+SWEEP_MAX_MOTION = 4096                          # CVXS_MAX_MOTION: cvxs_world_sweep, every component of a motion
 NAV_MAX_GOALS = 4096                             # cvx_world_nav_build / cvx_nav_field_goals: goalCount
 FACE_INSIDE, FACE_MISS = 6, -1                  # cvx_pick_hit.face besides 0..5 = -X, +X, -Y, +Y, -Z, +Z
 
@@ -188,6 +192,15 @@ class PairsSummary(C.Structure):  # cvxp_pairs_summary
 class ModelHit(C.Structure):  # cvxq_model_hit
     _fields_ = [("voxel", C.c_int32 * 3), ("face", C.c_int32), ("argb", C.c_uint32), ("t", C.c_float), ("instance", C.c_int32), ("modelVoxel", C.c_int32 * 3),
                 ("pad_", C.c_int32 * 2)]
+
+
+class SweepResult(C.Structure):  # cvxs_sweep_result
+    _fields_ = [("steps", C.c_int32), ("hit", C.c_int32), ("axis", C.c_int32), ("sign", C.c_int32), ("free", C.c_int32 * 3), ("at", C.c_int32 * 3),
+                ("pad_", C.c_int32 * 2)]
+
+
+class SweepsSummary(C.Structure):  # cvxs_sweeps_summary
+    _fields_ = [("hits", C.c_int64), ("startsSolid", C.c_int64), ("jobs", C.c_int64), ("points", C.c_int64)]
 
 
 class DrawView(C.Structure):  # cvxv_view
@@ -342,6 +355,7 @@ CONTACT_RESULT_DTYPE, CONTACT_POINT_DTYPE, CONTACTS_SUMMARY_DTYPE = np.dtype(Con
 PAIR_RESULT_DTYPE, PAIR_POINT_DTYPE, PAIRS_SUMMARY_DTYPE = np.dtype(PairResult), np.dtype(PairPoint), np.dtype(PairsSummary)
 MODEL_HIT_DTYPE = np.dtype(ModelHit)
 DRAW_VIEW_DTYPE, DRAW_SUMMARY_DTYPE = np.dtype(DrawView), np.dtype(DrawSummary)
+SWEEP_RESULT_DTYPE, SWEEPS_SUMMARY_DTYPE = np.dtype(SweepResult), np.dtype(SweepsSummary)
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
 
@@ -583,6 +597,31 @@ def view_rays(view, x0: int = 0, y0: int = 0, w=None, h=None) -> np.ndarray:
     return rays
 
 
+def sweep_offset(motion, j: int):
+    """cvxs_sweep_offset: (o_j as three ints, the axis of step j or -1 for j = 0) on the lattice path of `motion` (three integers of at most
+    SWEEP_MAX_MOTION in magnitude): the k-th step of axis a has the parameter (2 k - 1) / (2 |v_a|), steps go in ascending parameter, ties to the
+    lower axis.  A pure host call."""
+    v = np.ascontiguousarray(motion, dtype=np.int64)
+    if v.shape != (3,) or np.abs(v).max() > SWEEP_MAX_MOTION:
+        raise ValueError(f"sweep_offset: motion is three integers of at most {SWEEP_MAX_MOTION} in magnitude")
+    v, out, axis = v.astype(np.int32), np.zeros(3, dtype=np.int32), C.c_int(0)
+    if not -(1 << 31) <= int(j) < 1 << 31 or lib().cvxs_sweep_offset(v.ctypes.data, int(j), out.ctypes.data, C.byref(axis)) != 0:
+        raise ValueError(f"sweep_offset: j = {j} outside 0 .. {int(np.abs(v.astype(np.int64)).sum())}")
+    return [int(c) for c in out], axis.value
+
+
+def instance_moved(instance, offset) -> "ModelInstance":
+    """cvxs_instance_moved: the instance whose body is `instance`'s shifted by the integer `offset`, voxel for voxel (the box shifted, toModel.t
+    less toModel.m times the offset).  A pure host call."""
+    o = np.ascontiguousarray(offset, dtype=np.int64)
+    if not isinstance(instance, ModelInstance) or o.shape != (3,) or np.abs(o).max() >= 1 << 31:
+        raise ValueError("instance_moved: a gpu.ModelInstance and three int32 offsets")
+    o, out = o.astype(np.int32), ModelInstance()
+    if lib().cvxs_instance_moved(C.addressof(instance), o.ctypes.data, C.addressof(out)) != 0:
+        raise ValueError("instance_moved: the moved instance leaves the limits (a box coordinate beyond 2^30 or t beyond 2^46)")
+    return out
+
+
 class RaybufferLayout(C.Structure):
     _fields_ = [("width", C.c_int32), ("rayCapacity", C.c_int32), ("tileRays", C.c_int32),
                 ("tileCapacity", C.c_int32), ("tileBytes", C.c_int64)]
@@ -759,6 +798,11 @@ def _bind(path: str) -> C.CDLL:
     L.cvxv_models_draw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(DrawSummary), C.POINTER(C.c_float)]
     L.cvxv_models_draw_device.argtypes = L.cvxv_models_draw.argtypes
+    L.cvxs_world_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.POINTER(SweepsSummary), C.POINTER(C.c_float)]
+    L.cvxs_world_sweep_device.argtypes = L.cvxs_world_sweep.argtypes
+    L.cvxs_sweep_offset.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    L.cvxs_instance_moved.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
     L.cvx_shard_plan_destroy.restype = None
@@ -1430,6 +1474,50 @@ class Context:
             return self._checked_tensor("models_draw_device", tensor, 4, pixels)[0]
         return self._models_draw(lib().cvxv_models_draw_device, descriptors, len(models), instances, view, flags, pointer(image_tensor), pointer(depth_tensor),
                                  pointer(ids_tensor))
+
+    # -- how far placed models can move before they touch the world (cvxs_world_sweep, include/cpuvox_gpu_sweep.h) --
+    def _sweep(self, entry, who, descriptors, model_count, instances, motions, solid_outside, contacts_ptr, points_ptr, capacity):
+        inst = self._instances(instances)
+        v = np.asarray(motions)
+        if v.dtype.kind not in "iu" or v.shape != (len(inst), 3) or (v.size and np.abs(v.astype(np.int64)).max() >= 1 << 31):
+            raise ValueError(f"{who}: motions is an integer array of shape (instances, 3)")
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        sweeps = np.zeros(len(inst), dtype=SWEEP_RESULT_DTYPE)
+        summary, ms = SweepsSummary(), C.c_float()
+        self._check(entry(self._h, C.addressof(descriptors), model_count, C.addressof(inst), len(inst), v.ctypes.data if len(inst) else None, int(solid_outside),
+                          sweeps.ctypes.data if len(inst) else None, contacts_ptr or None, points_ptr or None, int(capacity), C.byref(summary), C.byref(ms)))
+        return sweeps, {name: int(getattr(summary, name)) for name in SWEEPS_SUMMARY_DTYPE.names}, ms.value
+
+    def world_sweep(self, models, instances, motions, solid_outside: int = SURFACE_OUTSIDE_DEFAULT, point_capacity=None):
+        """How far every instance can move along its integer motion (`motions`: shape (instances, 3), components of at most SWEEP_MAX_MOTION in
+        magnitude) before it touches the world: (one SWEEP_RESULT_DTYPE element per instance -- the first touching step `hit` of gpu.sweep_offset's
+        path or -1, its axis and sign, the last free offset and the touching one --, the CONTACT_RESULT_DTYPE results of world_contacts for the
+        instances moved to `at`, the first `point_capacity` contact points of those, the totals of cvxs_sweeps_summary as a dict, device
+        milliseconds).  `models`, `instances` and `solid_outside` as world_contacts'.  point_capacity=0 asks for no points; None asks for the
+        results first and then for every point (the milliseconds are the second call's)."""
+        descriptors, keep = self._models(models, "world_sweep")  # noqa: F841  (keep: the arrays the descriptors point to)
+        inst = self._instances(instances)
+        contacts = np.zeros(len(inst), dtype=CONTACT_RESULT_DTYPE)
+        call = lib().cvxs_world_sweep
+        if point_capacity is None:
+            _, totals, _ = self._sweep(call, "world_sweep", descriptors, len(models), inst, motions, solid_outside, contacts.ctypes.data if len(inst) else None, None, 0)
+            point_capacity = totals["points"]
+        points = np.zeros(max(int(point_capacity), 0), dtype=CONTACT_POINT_DTYPE)
+        sweeps, totals, ms = self._sweep(call, "world_sweep", descriptors, len(models), inst, motions, solid_outside, contacts.ctypes.data if len(inst) else None,
+                                         points.ctypes.data if points.size else None, point_capacity)
+        return sweeps, contacts, (points if points.size <= totals["points"] else points[:totals["points"]].copy()), totals, ms
+
+    def world_sweep_device(self, models, instances, motions, contacts_tensor=None, points_tensor=None, solid_outside: int = SURFACE_OUTSIDE_DEFAULT):
+        """world_sweep on device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr) as world_contacts_device's, `contacts_tensor` (or
+        None: the sweeps alone) a contiguous device tensor of at least 120 bytes per instance, `points_tensor` (or None) one whose bytes / 24 are
+        the capacity; entries beyond the points found are left alone.  Returns (the sweeps, a host array, the totals as a dict, device
+        milliseconds) once the tensors are complete."""
+        descriptors = self._device_models(models, "world_sweep_device")
+        inst = self._instances(instances)
+        contacts_ptr = self._checked_tensor("world_sweep_device", contacts_tensor, C.sizeof(ContactResult), len(inst))[0] if contacts_tensor is not None else None
+        points_ptr, capacity = self._checked_tensor("world_sweep_device", points_tensor, C.sizeof(ContactPoint), 0) if points_tensor is not None else (None, 0)
+        return self._sweep(lib().cvxs_world_sweep_device, "world_sweep_device", descriptors, len(models), inst, motions, solid_outside, contacts_ptr,
+                           points_ptr if capacity else None, capacity)
 
     @staticmethod
     def _model_read(size, to_world):
