@@ -134,9 +134,8 @@ using cvxi::Grid;
 
 int Prepare(cvx_context *ctx)
 {
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxi::SyncWorld(ctx);
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
+	return cvxi::PrepareWorld(ctx);
 }
 
 // The columns [x0, x1) x [z0, z1) a stroke can touch, clipped to the world; false: none (the stroke does nothing)
@@ -216,7 +215,7 @@ int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strok
 			}
 		}
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dimX = ctx->hostWorld.dimX, dimY = ctx->hostWorld.dimY, dimZ = ctx->hostWorld.dimZ;
 	// the strokes that touch the world, and the rectangle: the union of their footprints rounded out to 2^levelCount, clipped to the world
 	std::vector<cvx_brush_stroke> live;

@@ -159,9 +159,8 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (!params) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "params is NULL"); }
 	const cvx_cavity_params P = *params;
-	for (int a = 0; a < 3; a++) {
-		if (P.boxMin[a] >= P.boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box [%d, %d) on axis %d is empty", P.boxMin[a], P.boxMax[a], a); }
-	}
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::BoxCheck(P.boxMin, P.boxMax, 0, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", bad); }
 	if (P.openFaces & ~0x3F) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "unknown openFaces bits 0x%x", (unsigned)P.openFaces); }
 	if (P.op != CVX_CAVITIES_REPORT && P.op != CVX_CAVITIES_FILL) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad op %d", P.op); }
 	if (P.maxVoxels < 0) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "maxVoxels %lld is negative", (long long)P.maxVoxels); }
@@ -169,7 +168,7 @@ int cvx_world_cavities(cvx_context *ctx, const cvx_cavity_params *params, int le
 	if (cavityCapacity < 0 || (cavityCapacity > 0 && !cavities)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "cavityCapacity %d with %s list", cavityCapacity, cavities ? "a" : "no");
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 
 	const cvxcomp::Call engine{ call, "air intervals", cvxcomp::KernelsOf<CavityRule>(), P.openFaces, cavityCapacity, sizeof(Totals) };
 	CavityArgs C{};

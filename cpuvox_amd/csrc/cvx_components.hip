@@ -60,9 +60,7 @@ int Analyse(cvx_context *ctx, const Call &call, const int32_t boxMin[3], const i
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box lies outside the world");
 	}
 	if (A.B.Columns() >= ((int64_t)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "a box of %lld columns", (long long)A.B.Columns()); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	const int rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	const int n = (int)A.B.Columns();
 	const RuleKernels &K = call.kernels;

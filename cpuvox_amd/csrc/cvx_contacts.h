@@ -328,16 +328,7 @@ inline bool ContactsValidate(const cvx_model *models, int modelCount, const cvx_
 			snprintf(message, bytes, "instance %d: model %d outside 0 .. %d", k, I.model, modelCount - 1);
 			return false;
 		}
-		for (int a = 0; a < 3; a++) {
-			if (I.boxMin[a] < -(1 << 30) || I.boxMin[a] > (1 << 30) || I.boxMax[a] < -(1 << 30) || I.boxMax[a] > (1 << 30)) {
-				snprintf(message, bytes, "instance %d: the box [%d, %d) on axis %d has a coordinate beyond 2^30", k, I.boxMin[a], I.boxMax[a], a);
-				return false;
-			}
-			if (I.boxMin[a] >= I.boxMax[a]) {
-				snprintf(message, bytes, "instance %d: the box [%d, %d) on axis %d is empty", k, I.boxMin[a], I.boxMax[a], a);
-				return false;
-			}
-		}
+		if (!InstanceBoxValidate(I, k, message, bytes)) { return false; }
 		snprintf(what, sizeof what, "instance %d: toModel", k);
 		if (!ModelMapValidate(I.toModel, what, message, bytes)) { return false; }
 	}

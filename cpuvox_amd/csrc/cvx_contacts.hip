@@ -181,13 +181,11 @@ int cvxi::WorldContacts(cvx_context *ctx, const char *call, const cvx_model *mod
 	if (!cvxb::ContactsValidate(models, modelCount, instances, instanceCount, solidOutside, results, points, pointCapacity, message, sizeof message)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, message);
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	std::vector<uint32_t> prefix((size_t)instanceCount + 1);
 	const int64_t pairs = cvxb::ContactsPairs(instances, instanceCount, prefix.data());
 	if (pairs < 0) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: the boxes' footprints sum to 2^31 - 1 or more (instance, column) pairs", call); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	const int rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	Args A{};
 	A.W = cvxi::WorldOf(ctx);

@@ -205,6 +205,9 @@ public:
 		}
 		return e;
 	}
+	// `bytes` of host memory for a copy back.  What a copy names must outlive the device blocks (freeing those waits for a copy still under way):
+	// a member, destroyed behind the destructor's body
+	void *Host(size_t bytes) { return host.resize(bytes), host.data(); }
 	// Hands the block to the caller: the destructor no longer frees it
 	template <class T> T *Keep(T *block)
 	{
@@ -241,6 +244,7 @@ private:
 	hipEvent_t ev[2] = { nullptr, nullptr };
 	bool adopted = false;
 	size_t failedBytes = 0;
+	std::vector<uint8_t> host;
 };
 
 // the world calls' kernels: a thread per column, node or pair, kThreads to a workgroup (`per`: what a workgroup takes where that is not a thread's share)
@@ -312,6 +316,11 @@ int ValidateRepeat(cvx_context *ctx);
 
 // cvx_gpu.hip: lays the uploaded levels out in the arena if any is pending (what the next draw would do first)
 int SyncWorld(cvx_context *ctx);
+// cvx_gpu.hip: the world gate of a call that reads the arena.  RequireWorld is the last of its argument checks: CVX_ERR_NOT_READY until LOD 0 has been
+// uploaded.  PrepareWorld makes the context's device current and lays the arena out (SyncWorld).  Two functions: the capacity checks that need the
+// world's dimensions run between them, and a refusal must leave the device alone.
+int RequireWorld(cvx_context *ctx);
+int PrepareWorld(cvx_context *ctx);
 // cvx_gpu.hip: LOD 0 of the arena as the kernels of the world calls read it (cvx_copy.h); valid from SyncWorld to the next call that lays the arena out again
 cvxb::CopyWorld WorldOf(const cvx_context *ctx);
 // cvx_world.hip: exclusive prefix sum of n counts in place on `stream`, *total (device) = their sum; chunkSums: (n + CVX_SCAN_CHUNK - 1) / CVX_SCAN_CHUNK words of 8 bytes
@@ -411,6 +420,35 @@ int64_t LaunchUntilUnchanged(cvx_context *ctx, unsigned int *changed, int64_t bo
 // outMs (may be null) is written only when call.done is null, see there.
 int ColumnEdit(cvx_context *ctx, const EditRectangle &R, int levelCount, const ColumnEditCall &call, ColumnEditLauncher launchCount, ColumnEditLauncher launchWrite,
                float *outMs);
+
+// ---- the query drivers (cvx_query_call.hip): what the calls that read the world into a caller's arrays or capped list share ----
+// Up to three arrays of a read, each optional: to[k], bytes[k] long, is the caller's (null: not wanted).  The launcher gets where its kernel writes
+// array k (null where to[k] is) and the stream to launch on.
+struct ReadArraysJob {
+	void *array[3];
+	hipStream_t stream;
+};
+// `device`: the arrays are device memory; the launch goes straight through on hipStream (null: ctx->stream), nothing is timed or waited for and
+// *outDeviceMs is left alone.  Else: one scratch block for the arrays, the launch on ctx->stream, the timing window closed behind it, a copy per
+// array, one synchronisation, then *outDeviceMs.
+int ReadArrays(cvx_context *ctx, const char *call, void *const to[3], const size_t bytes[3], bool device, void *hipStream, Launcher<ReadArraysJob> launch,
+               float *outDeviceMs);
+// The capped list of a call: the world holds `found` items, the caller's `list` (device memory with `device`) takes `capacity` of them
+struct ListCall {
+	size_t itemBytes;
+	unsigned long long found;
+	int64_t capacity;
+	void *list;
+	bool device;
+};
+struct ListJob {
+	void *into;     // device: items 0 .. limit - 1 go here
+	uint32_t limit; // min(found, capacity), above 0
+};
+// The tail of such a call, behind its count inside D's window: launchWrite (not called for an empty list) writes into the caller's device list or a
+// staged block that one copy brings to D.Host; D.End(); one synchronisation.  Nothing is handed out before the call can no longer fail: the caller's
+// host list is written last here, its summary and time by the caller behind a CVX_OK.
+int FinishList(cvx_context *ctx, DeviceCall &D, const ListCall &list, Launcher<ListJob> launchWrite);
 
 // cvx_brush.hip: releases the picking scratch (cvx_destroy)
 void FreeBrushState(cvx_context *ctx);

@@ -98,7 +98,7 @@ int cvx_world_copy(cvx_context *ctx, const cvx_copy_placement *placements, int p
 			}
 		}
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
 	for (int i = 0; i < placementCount; i++) {
 		const cvx_copy_placement &p = placements[i];
@@ -134,9 +134,7 @@ int cvx_world_copy(cvx_context *ctx, const cvx_copy_placement *placements, int p
 	cvxi::EditRectangle R;
 	int rc = cvxi::RoundEditRectangle(ctx, x0, x1, z0, z1, levelCount, "a copy over", &R);
 	if (rc != CVX_OK) { return rc; }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	const size_t placementBytes = live.size() * sizeof(cvx_copy_placement);
 	cvxcopy::CopyArgs A{};

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "cpuvox_gpu.h"
+#include "cvx_box.h"
 #include "cvx_copy.h"
 
 namespace cvxb {
@@ -23,6 +24,20 @@ struct DenseBox {
 	int32_t min[3];
 	int32_t size[3]; // > 0, size[0] * size[1] * size[2] < 2^31
 };
+
+// The box of a call that hands out a value per voxel: given, within +-2^30, no empty axis, fewer than 2^31 voxels (BoxCheck's return and message).
+// *elements receives its voxels.
+inline int DenseBoxCheck(const int32_t boxMin[3], const int32_t boxMax[3], DenseBox *box, int64_t *elements, char *message, size_t size)
+{
+	const int rc = BoxCheck(boxMin, boxMax, kBoxWithin | kBoxVoxels, message, size);
+	*elements = 1;
+	for (int a = 0; a < 3 && rc == 0; a++) {
+		box->min[a] = boxMin[a];
+		box->size[a] = boxMax[a] - boxMin[a];
+		*elements *= box->size[a];
+	}
+	return rc;
+}
 
 struct Voxel {
 	bool solid;

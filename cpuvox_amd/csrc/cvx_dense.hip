@@ -143,73 +143,30 @@ namespace {
 using cvxdense::kThreads;
 using cvxi::Grid;
 
-// The checks both directions share; *elements receives the box's voxel count.
-int CheckBox(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], cvxb::DenseBox *box, int64_t *elements)
-{
-	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a NULL box", call); }
-	int64_t n = 1;
-	for (int a = 0; a < 3; a++) {
-		if (boxMin[a] < -(1 << 30) || boxMin[a] > (1 << 30) || boxMax[a] < -(1 << 30) || boxMax[a] > (1 << 30)) {
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d has a coordinate beyond 2^30", call, boxMin[a], boxMax[a], a);
-		}
-		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d is empty", call, boxMin[a], boxMax[a], a); }
-		box->min[a] = boxMin[a];
-		box->size[a] = (int32_t)((int64_t)boxMax[a] - boxMin[a]); // (at most 2^31 - 1: the product check below rejects it anyway)
-	}
-	for (int a = 0; a < 3; a++) {
-		n *= (int64_t)boxMax[a] - boxMin[a]; // (each factor at most 2^31, the running product below 2^31 before it: no overflow)
-		if (n >= ((int64_t)1 << 31)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a box of 2^31 or more voxels", call); }
-	}
-	*elements = n;
-	return CVX_OK;
-}
-
-int Prepare(cvx_context *ctx)
-{
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxi::SyncWorld(ctx);
-}
-
 int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], uint32_t *argb, uint8_t *solid, bool device, void *hipStream,
          float *outDeviceMs)
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	cvxdense::ReadArgs A{};
 	int64_t n = 0;
-	int rc = CheckBox(ctx, call, boxMin, boxMax, &A.box, &n);
-	if (rc != CVX_OK) { return rc; }
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::DenseBoxCheck(boxMin, boxMax, &A.box, &n, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, bad); }
 	if (!argb && !solid) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: argb and solid are both NULL", call); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	rc = Prepare(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 	A.W = cvxi::WorldOf(ctx);
 	A.n = (uint32_t)n;
-	if (device) {
-		A.argb = argb;
-		A.solid = solid;
-		hipStream_t stream = hipStream ? static_cast<hipStream_t>(hipStream) : ctx->stream;
-		hipLaunchKernelGGL(cvxdense::dense_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, stream, A);
-		CVX_HIP(ctx, hipGetLastError());
-		return CVX_OK;
-	}
-	cvxi::DeviceCall D(ctx, call);
-	uint8_t *scratch = nullptr;
-	const size_t argbBytes = argb ? (size_t)n * 4 : 0, solidBytes = solid ? (size_t)n : 0;
-	hipError_t e = D.Allocate(&scratch, argbBytes + solidBytes);
-	if (e == hipSuccess) { e = D.Begin(); }
-	if (e == hipSuccess) {
-		A.argb = argb ? reinterpret_cast<uint32_t *>(scratch) : nullptr;
-		A.solid = solid ? scratch + argbBytes : nullptr;
-		hipLaunchKernelGGL(cvxdense::dense_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) { e = D.End(); }
-	if (e == hipSuccess && argb) { e = hipMemcpyAsync(argb, A.argb, argbBytes, hipMemcpyDeviceToHost, ctx->stream); }
-	if (e == hipSuccess && solid) { e = hipMemcpyAsync(solid, A.solid, solidBytes, hipMemcpyDeviceToHost, ctx->stream); }
-	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return D.Fail(e); }
-	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
-	return CVX_OK;
+	void *const to[3] = { argb, solid, nullptr };
+	const size_t bytes[3] = { (size_t)n * 4, (size_t)n, 0 };
+	return cvxi::ReadArrays(
+		ctx, call, to, bytes, device, hipStream,
+		[&](const cvxi::ReadArraysJob &J) {
+			A.argb = static_cast<uint32_t *>(J.array[0]);
+			A.solid = static_cast<uint8_t *>(J.array[1]);
+			hipLaunchKernelGGL(cvxdense::dense_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, J.stream, A);
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 // Both writes: `device` says where argb / solid live.
@@ -219,12 +176,12 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	cvxdense::WriteArgs A{};
 	int64_t elements = 0;
-	int rc = CheckBox(ctx, call, boxMin, boxMax, &A.box, &elements);
-	if (rc != CVX_OK) { return rc; }
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::DenseBoxCheck(boxMin, boxMax, &A.box, &elements, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, bad); }
 	if (op < CVX_BRUSH_FILL || op > CVX_COPY_REPLACE) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: bad op %d", call, op); }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
 	if (!argb && !(op == CVX_BRUSH_CARVE && solid)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: argb is NULL (only a CARVE with a solid mask may leave it out)", call); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
 	// the rectangle: the box clipped to the world, its footprint rounded out to 2^levelCount, clipped again
 	int64_t lo[3], hi[3];
@@ -237,8 +194,8 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	if (!touches) { return CVX_OK; }
 	cvxi::EditRectangle R;
-	rc = cvxi::RoundEditRectangle(ctx, lo[0], hi[0], lo[2], hi[2], levelCount, "a write over", &R);
-	if (rc == CVX_OK) { rc = Prepare(ctx); }
+	int rc = cvxi::RoundEditRectangle(ctx, lo[0], hi[0], lo[2], hi[2], levelCount, "a write over", &R);
+	if (rc == CVX_OK) { rc = cvxi::PrepareWorld(ctx); }
 	if (rc != CVX_OK) { return rc; }
 
 	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it

@@ -58,29 +58,7 @@ __global__ __launch_bounds__(kThreads) void distance_x_kernel(Args A, bool signe
 namespace {
 
 using cvxdistance::kThreads;
-
-// cvx_world_read_voxels' checks of the box.
-int CheckBox(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], cvxb::DenseBox *box, int64_t *elements)
-{
-	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a NULL box", call); }
-	int64_t n = 1;
-	for (int a = 0; a < 3; a++) {
-		if (boxMin[a] < -(1 << 30) || boxMin[a] > (1 << 30) || boxMax[a] < -(1 << 30) || boxMax[a] > (1 << 30)) {
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d has a coordinate beyond 2^30", call, boxMin[a], boxMax[a], a);
-		}
-		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d is empty", call, boxMin[a], boxMax[a], a); }
-		box->min[a] = boxMin[a];
-		box->size[a] = (int32_t)((int64_t)boxMax[a] - boxMin[a]);
-	}
-	for (int a = 0; a < 3; a++) {
-		n *= (int64_t)boxMax[a] - boxMin[a]; // (each factor at most 2^31, the running product below 2^31 before it: no overflow)
-		if (n >= ((int64_t)1 << 31)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a box of 2^31 or more voxels", call); }
-	}
-	*elements = n;
-	return CVX_OK;
-}
-
-unsigned Grid(uint64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+using cvxi::Grid;
 
 int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], int maxDistance, int mode, int solidOutside, int32_t *out,
              bool device, float *outDeviceMs)
@@ -88,13 +66,13 @@ int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const 
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	cvxdistance::Args A{};
 	int64_t n = 0;
-	int rc = CheckBox(ctx, call, boxMin, boxMax, &A.G.box, &n);
-	if (rc != CVX_OK) { return rc; }
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::DenseBoxCheck(boxMin, boxMax, &A.G.box, &n, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, bad); }
 	if (!out) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: out is NULL", call); }
 	if (maxDistance < 1 || maxDistance > 255) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: maxDistance %d outside 1 .. 255", call, maxDistance); }
 	if (mode < CVX_DISTANCE_TO_SOLID || mode > CVX_DISTANCE_SIGNED) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: bad mode %d", call, mode); }
 	if (solidOutside & ~0x3F) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: solidOutside 0x%x has bits above 0x3F", call, solidOutside); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	A.G.R = maxDistance;
 	A.G.solidOutside = solidOutside;
 	// the scratch: 2 bytes per element of the two intermediate arrays (at most 511^2 * 2^31 elements: no overflow); the grids stay below 2^31 blocks
@@ -104,9 +82,7 @@ int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const 
 	if (elementsY >= (uint64_t)1 << 38) {
 		return Fail(ctx, CVX_ERR_CAPACITY, "%s: %llu bytes of device memory for the scratch", call, (unsigned long long)(bytesY + bytesZ + bytesOut));
 	}
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	cvxi::DeviceCall D(ctx, call);
 	uint8_t *scratch = nullptr;
@@ -121,7 +97,7 @@ int Distance(cvx_context *ctx, const char *call, const int32_t boxMin[3], const 
 			const bool toAir = mode == CVX_DISTANCE_TO_AIR || pass == 1;
 			hipLaunchKernelGGL(cvxdistance::distance_y_kernel, dim3(Grid(elementsY)), dim3(kThreads), 0, ctx->stream, A, toAir);
 			hipLaunchKernelGGL(cvxdistance::distance_z_kernel, dim3(Grid(elementsZ)), dim3(kThreads), 0, ctx->stream, A);
-			hipLaunchKernelGGL(cvxdistance::distance_x_kernel, dim3(Grid((uint64_t)n)), dim3(kThreads), 0, ctx->stream, A, pass == 1);
+			hipLaunchKernelGGL(cvxdistance::distance_x_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A, pass == 1);
 		}
 		e = hipGetLastError();
 	}

@@ -263,9 +263,8 @@ int CheckRect(cvx_context *ctx, int lod, int x0, int z0, int sizeX, int sizeZ)
 // The world must be complete and laid out in the arena before an edit can work on it
 int Prepare(cvx_context *ctx)
 {
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxi::SyncWorld(ctx);
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
+	return cvxi::PrepareWorld(ctx);
 }
 
 // Lays the arena out again with the tails `runsCap` / `elementsCap` for the levels that have (or get) one, by device-to-device copies (SyncWorld's
@@ -621,7 +620,7 @@ int cvx_world_set_columns(cvx_context *ctx, int lod, int x0, int z0, int sizeX, 
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (lod < 0 || lod >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "bad lod %d", lod); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	int rc = CheckRect(ctx, lod, x0, z0, sizeX, sizeZ);
 	if (rc != CVX_OK) { return rc; }
 	int64_t elementsOfColumns = 0;
@@ -653,7 +652,7 @@ int cvx_world_edit(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, const
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int align = (1 << levelCount) - 1;
 	if ((x0 & align) || (z0 & align) || (sizeX & align) || (sizeZ & align)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "rectangle (%d, %d) + %d x %d is not aligned to %d columns (2^levelCount)", x0, z0, sizeX, sizeZ, align + 1);

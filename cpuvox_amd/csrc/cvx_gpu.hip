@@ -336,9 +336,7 @@ int NextEventPair(cvx_context *ctx, hipEvent_t &start, hipEvent_t &stop)
 
 int SyncWorld(cvx_context *ctx)
 {
-	if (!ctx->levelSet[0]) {
-		return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded");
-	}
+	if (const int rc = cvxi::RequireWorld(ctx)) { return rc; }
 	if (ctx->worldDirty) {
 		// Missing higher LODs alias the last uploaded one only if never reached; require all 6 like the reference's World[6].
 		for (int i = 0; i < CVX_LOD_LEVELS; i++) {
@@ -507,6 +505,14 @@ int Launch(cvx_context *ctx, int frameCount, int flags)
 } // namespace
 
 int cvxi::SyncWorld(cvx_context *ctx) { return ::SyncWorld(ctx); }
+
+int cvxi::RequireWorld(cvx_context *ctx) { return ctx->levelSet[0] ? CVX_OK : Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+
+int cvxi::PrepareWorld(cvx_context *ctx)
+{
+	CVX_HIP(ctx, hipSetDevice(ctx->device));
+	return ::SyncWorld(ctx);
+}
 
 cvxb::CopyWorld cvxi::WorldOf(const cvx_context *ctx)
 {

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 
+#include "cvx_box.h"
 #include "cvx_context.h"
 #include "cvx_heights.h"
 
@@ -90,30 +91,17 @@ __global__ __launch_bounds__(kThreads) void heights_write_kernel(WriteArgs A)
 namespace {
 
 using cvxheights::kThreads;
-
-unsigned Grid(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+using cvxi::Grid;
 
 // The checks both directions share; *columns receives the footprint's column count.
 int CheckBox(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], cvxb::HeightsBox *box, int64_t *columns)
 {
-	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a NULL box", call); }
-	for (int a = 0; a < 3; a++) {
-		if (boxMin[a] < -(1 << 30) || boxMin[a] > (1 << 30) || boxMax[a] < -(1 << 30) || boxMax[a] > (1 << 30)) {
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d has a coordinate beyond 2^30", call, boxMin[a], boxMax[a], a);
-		}
-		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the box [%d, %d) on axis %d is empty", call, boxMin[a], boxMax[a], a); }
-	}
-	const int64_t sizeX = (int64_t)boxMax[0] - boxMin[0], sizeZ = (int64_t)boxMax[2] - boxMin[2]; // (each at most 2^31: the product fits)
-	if (sizeX * sizeZ >= ((int64_t)1 << 31)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a footprint of 2^31 or more columns", call); }
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::BoxCheck(boxMin, boxMax, cvxb::kBoxWithin | cvxb::kBoxFootprint, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, bad); }
+	const int64_t sizeX = (int64_t)boxMax[0] - boxMin[0], sizeZ = (int64_t)boxMax[2] - boxMin[2];
 	*box = cvxb::HeightsBox{ boxMin[0], boxMin[2], (int32_t)sizeX, (int32_t)sizeZ, boxMin[1], boxMax[1] };
 	*columns = sizeX * sizeZ;
 	return CVX_OK;
-}
-
-int Prepare(cvx_context *ctx)
-{
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxi::SyncWorld(ctx);
 }
 
 int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int32_t boxMax[3], int32_t *heights, uint32_t *argb, int32_t *bottoms, bool device,
@@ -125,46 +113,22 @@ int Read(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int3
 	int rc = CheckBox(ctx, call, boxMin, boxMax, &A.box, &n);
 	if (rc != CVX_OK) { return rc; }
 	if (!heights && !argb && !bottoms) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: heights, argb and bottoms are all NULL", call); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	rc = Prepare(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 	A.W = cvxi::WorldOf(ctx);
 	A.n = (uint32_t)n;
-	if (device) {
-		A.heights = heights;
-		A.argb = argb;
-		A.bottoms = bottoms;
-		hipStream_t stream = hipStream ? static_cast<hipStream_t>(hipStream) : ctx->stream;
-		hipLaunchKernelGGL(cvxheights::heights_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, stream, A);
-		CVX_HIP(ctx, hipGetLastError());
-		return CVX_OK;
-	}
-	cvxi::DeviceCall D(ctx, call);
-	uint32_t *scratch = nullptr;
-	void *const host[3] = { heights, argb, bottoms };
-	uint32_t *dev[3] = { nullptr, nullptr, nullptr };
-	const size_t arrayBytes = (size_t)n * 4;
-	size_t arrays = 0;
-	for (void *p : host) { arrays += p ? 1 : 0; }
-	hipError_t e = D.Allocate(&scratch, arrays * arrayBytes);
-	if (e == hipSuccess) { e = D.Begin(); }
-	if (e == hipSuccess) {
-		size_t k = 0;
-		for (int a = 0; a < 3; a++) { if (host[a]) { dev[a] = scratch + (k++) * (size_t)n; } }
-		A.heights = reinterpret_cast<int32_t *>(dev[0]);
-		A.argb = dev[1];
-		A.bottoms = reinterpret_cast<int32_t *>(dev[2]);
-		hipLaunchKernelGGL(cvxheights::heights_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) { e = D.End(); }
-	for (int a = 0; a < 3; a++) {
-		if (e == hipSuccess && host[a]) { e = hipMemcpyAsync(host[a], dev[a], arrayBytes, hipMemcpyDeviceToHost, ctx->stream); }
-	}
-	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return D.Fail(e); }
-	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
-	return CVX_OK;
+	void *const to[3] = { heights, argb, bottoms };
+	const size_t bytes[3] = { (size_t)n * 4, (size_t)n * 4, (size_t)n * 4 };
+	return cvxi::ReadArrays(
+		ctx, call, to, bytes, device, hipStream,
+		[&](const cvxi::ReadArraysJob &J) {
+			A.heights = static_cast<int32_t *>(J.array[0]);
+			A.argb = static_cast<uint32_t *>(J.array[1]);
+			A.bottoms = static_cast<int32_t *>(J.array[2]);
+			hipLaunchKernelGGL(cvxheights::heights_read_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, J.stream, A);
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 // Both writes: `device` says where the three arrays live.
@@ -182,7 +146,7 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	if (!argb && op != CVX_BRUSH_CARVE) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: argb is NULL (only a CARVE may leave it out)", call); }
 	if (thickness < 0 || thickness > 32767) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: thickness %d outside 0 .. 32767", call, thickness); }
 	if (flags & ~CVX_HEIGHTS_WALLED) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", call, (unsigned)(flags & ~CVX_HEIGHTS_WALLED)); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
 	// the rectangle: the box clipped to the world, its footprint rounded out to 2^levelCount, clipped again
 	int64_t lo[3], hi[3];
@@ -196,7 +160,7 @@ int Write(cvx_context *ctx, const char *call, const int32_t boxMin[3], const int
 	if (!touches) { return CVX_OK; }
 	cvxi::EditRectangle R;
 	rc = cvxi::RoundEditRectangle(ctx, lo[0], hi[0], lo[2], hi[2], levelCount, "a height map over", &R);
-	if (rc == CVX_OK) { rc = Prepare(ctx); }
+	if (rc == CVX_OK) { rc = cvxi::PrepareWorld(ctx); }
 	if (rc != CVX_OK) { return rc; }
 
 	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it

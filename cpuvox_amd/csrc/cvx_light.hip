@@ -301,11 +301,7 @@ __global__ __launch_bounds__(kThreads) void light_brick_kernel(LightArgs A)
 
 } // namespace cvxlight
 
-namespace {
-
-unsigned Grid(size_t n, unsigned threads = 256) { return (unsigned)((n + threads - 1) / threads); }
-
-} // namespace
+using cvxi::Grid;
 
 // cvx_world_light (lamps NULL, lampCount 0) and cvx_world_light_lamps
 static int Light(cvx_context *ctx, const cvx_light_params *params, const cvx_lamp *lamps, int lampCount, int levelCount, float *outDeviceMs)
@@ -315,7 +311,7 @@ static int Light(cvx_context *ctx, const cvx_light_params *params, const cvx_lam
 	if (const char *what = cvxb::LightParamsError(*params)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "cvx_light_params: bad %s", what); }
 	if (const char *what = cvxb::LampParamsError(lamps, lampCount)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "cvx_lamp: bad %s (lampCount %d)", what, lampCount); }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dimX = ctx->hostWorld.dimX, dimY = ctx->hostWorld.dimY, dimZ = ctx->hostWorld.dimZ;
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	cvxb::PiecesBox B;
@@ -323,9 +319,7 @@ static int Light(cvx_context *ctx, const cvx_light_params *params, const cvx_lam
 	cvxi::EditRectangle R;
 	int rc = cvxi::RoundEditRectangle(ctx, B.x0, B.x1, B.z0, B.z1, levelCount, "lighting", &R);
 	if (rc != CVX_OK) { return rc; }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	const size_t lampBytes = (size_t)lampCount * sizeof(cvx_lamp);
 	cvxlight::LightArgs A{};

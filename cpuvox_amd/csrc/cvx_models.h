@@ -245,6 +245,13 @@ inline bool ModelSizeValidate(const int32_t size[3], const char *what, char *mes
 	return true;
 }
 
+// The box of instance k (the placed-model calls and the contacts): within +-2^30, no empty axis; BoxCheck's reason behind "instance <k>: "
+inline bool InstanceBoxValidate(const cvx_model_instance &I, int k, char *message, size_t bytes)
+{
+	const int at = snprintf(message, bytes, "instance %d: ", k);
+	return BoxCheck(I.boxMin, I.boxMax, kBoxWithin, message + at, bytes - (size_t)at) == 0;
+}
+
 // The argument checks of cvx_world_place_models[_device], in the order include/cpuvox_gpu_models.h lists them; false: the message says what.
 inline bool ModelsValidate(const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, int levelCount, char *message, size_t bytes)
 {
@@ -283,16 +290,7 @@ inline bool ModelsValidate(const cvx_model *models, int modelCount, const cvx_mo
 			snprintf(message, bytes, "instance %d: model %d has no argb (only a CARVE may use it)", k, I.model);
 			return false;
 		}
-		for (int a = 0; a < 3; a++) {
-			if (I.boxMin[a] < -(1 << 30) || I.boxMin[a] > (1 << 30) || I.boxMax[a] < -(1 << 30) || I.boxMax[a] > (1 << 30)) {
-				snprintf(message, bytes, "instance %d: the box [%d, %d) on axis %d has a coordinate beyond 2^30", k, I.boxMin[a], I.boxMax[a], a);
-				return false;
-			}
-			if (I.boxMin[a] >= I.boxMax[a]) {
-				snprintf(message, bytes, "instance %d: the box [%d, %d) on axis %d is empty", k, I.boxMin[a], I.boxMax[a], a);
-				return false;
-			}
-		}
+		if (!InstanceBoxValidate(I, k, message, bytes)) { return false; }
 		snprintf(what, sizeof what, "instance %d: toModel", k);
 		if (!ModelMapValidate(I.toModel, what, message, bytes)) { return false; }
 	}

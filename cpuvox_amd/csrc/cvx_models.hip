@@ -177,12 +177,6 @@ namespace {
 using cvxi::Grid;
 using cvxmodels::kThreads;
 
-int Prepare(cvx_context *ctx)
-{
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxi::SyncWorld(ctx);
-}
-
 int Read(cvx_context *ctx, const char *call, const int32_t size[3], const cvx_model_map *toWorld, uint32_t *argb, uint8_t *solid, bool device, void *hipStream,
          float *outDeviceMs)
 {
@@ -193,41 +187,25 @@ int Read(cvx_context *ctx, const char *call, const int32_t size[3], const cvx_mo
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, message);
 	}
 	if (!argb && !solid) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: argb and solid are both NULL", call); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	int rc = Prepare(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 	cvxmodels::ReadArgs A{};
 	const size_t n = (size_t)size[0] * (size_t)size[1] * (size_t)size[2];
 	A.W = cvxi::WorldOf(ctx);
 	A.toWorld = *toWorld;
 	for (int a = 0; a < 3; a++) { A.size[a] = size[a]; }
 	A.n = (uint32_t)n;
-	if (device) {
-		A.argb = argb;
-		A.solid = solid;
-		hipStream_t stream = hipStream ? static_cast<hipStream_t>(hipStream) : ctx->stream;
-		hipLaunchKernelGGL(cvxmodels::model_read_kernel, dim3(Grid(n)), dim3(kThreads), 0, stream, A);
-		CVX_HIP(ctx, hipGetLastError());
-		return CVX_OK;
-	}
-	cvxi::DeviceCall D(ctx, call);
-	uint8_t *scratch = nullptr;
-	const size_t argbBytes = argb ? n * 4 : 0, solidBytes = solid ? n : 0;
-	hipError_t e = D.Allocate(&scratch, argbBytes + solidBytes);
-	if (e == hipSuccess) { e = D.Begin(); }
-	if (e == hipSuccess) {
-		A.argb = argb ? reinterpret_cast<uint32_t *>(scratch) : nullptr;
-		A.solid = solid ? scratch + argbBytes : nullptr;
-		hipLaunchKernelGGL(cvxmodels::model_read_kernel, dim3(Grid(n)), dim3(kThreads), 0, ctx->stream, A);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) { e = D.End(); }
-	if (e == hipSuccess && argb) { e = hipMemcpyAsync(argb, A.argb, argbBytes, hipMemcpyDeviceToHost, ctx->stream); }
-	if (e == hipSuccess && solid) { e = hipMemcpyAsync(solid, A.solid, solidBytes, hipMemcpyDeviceToHost, ctx->stream); }
-	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return D.Fail(e); }
-	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
-	return CVX_OK;
+	void *const to[3] = { argb, solid, nullptr };
+	const size_t bytes[3] = { n * 4, n, 0 };
+	return cvxi::ReadArrays(
+		ctx, call, to, bytes, device, hipStream,
+		[&](const cvxi::ReadArraysJob &J) {
+			A.argb = static_cast<uint32_t *>(J.array[0]);
+			A.solid = static_cast<uint8_t *>(J.array[1]);
+			hipLaunchKernelGGL(cvxmodels::model_read_kernel, dim3(Grid(n)), dim3(kThreads), 0, J.stream, A);
+			return hipSuccess;
+		},
+		outDeviceMs);
 }
 
 // Both places: `device` says where the models' arrays live.
@@ -239,7 +217,7 @@ int Place(cvx_context *ctx, const char *call, const cvx_model *models, int model
 	if (!cvxb::ModelsValidate(models, modelCount, instances, instanceCount, levelCount, message, sizeof message)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, message);
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int64_t dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
 	// the instances that touch the world, and the rectangle: the union of their clipped boxes' footprints rounded out to 2^levelCount, clipped again
 	std::vector<cvx_model_instance> live;
@@ -259,7 +237,7 @@ int Place(cvx_context *ctx, const char *call, const cvx_model *models, int model
 	if (live.empty()) { return CVX_OK; }
 	cvxi::EditRectangle R;
 	int rc = cvxi::RoundEditRectangle(ctx, x0, x1, z0, z1, levelCount, "models over", &R);
-	if (rc == CVX_OK) { rc = Prepare(ctx); }
+	if (rc == CVX_OK) { rc = cvxi::PrepareWorld(ctx); }
 	if (rc != CVX_OK) { return rc; }
 
 	// host arrays: a device copy of them, uploaded behind the pipeline's start so that outDeviceMs covers it

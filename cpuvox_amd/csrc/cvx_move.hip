@@ -81,9 +81,8 @@ int cvx_world_move_device(cvx_context *ctx, int bodyCount, const cvx_move_body *
 	if (lanesPerBody != 0 && lanesPerBody != 1 && lanesPerBody != 4 && lanesPerBody != 16 && lanesPerBody != 64) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "lanesPerBody %d is not 0, 1, 4, 16 or 64", lanesPerBody);
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	int rc = cvxi::SyncWorld(ctx);
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
+	int rc = cvxi::PrepareWorld(ctx);
 	if (rc == CVX_OK && ctx->worldRepeat) { rc = cvxi::ValidateRepeat(ctx); }
 	if (rc != CVX_OK) { return rc; }
 	hipStream_t stream = hipStream ? static_cast<hipStream_t>(hipStream) : ctx->stream;
@@ -109,7 +108,7 @@ int cvx_world_move(cvx_context *ctx, int bodyCount, const cvx_move_body *bodies,
 		}
 		region = std::max(region, cvxb::MoveLegRegion(bodies[i]));
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	CVX_HIP(ctx, hipSetDevice(ctx->device));
 	const size_t bodiesBytes = ((size_t)bodyCount * sizeof(cvx_move_body) + 255) & ~(size_t)255, resultsBytes = (size_t)bodyCount * sizeof(cvx_move_result);
 	if (ctx->pickScratchBytes < bodiesBytes + resultsBytes) { // the pick's scratch: grown on demand, kept

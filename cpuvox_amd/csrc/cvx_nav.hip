@@ -424,9 +424,8 @@ int cvx_world_nav_build(cvx_context *ctx, const cvx_nav_params *params, const in
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (!params || !outField) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "params or outField is NULL"); }
 	const cvx_nav_params P = *params;
-	for (int a = 0; a < 3; a++) {
-		if (P.boxMin[a] >= P.boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box [%d, %d) on axis %d is empty", P.boxMin[a], P.boxMax[a], a); }
-	}
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::BoxCheck(P.boxMin, P.boxMax, 0, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", bad); }
 	const cvxb::NavRule R{ P.width, P.height, P.stepUp, P.maxDrop };
 	if (!cvxb::NavRuleValid(R)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "width %d outside 1 .. %d, height %d outside 1 .. %d, stepUp %d outside 0 .. height or maxDrop %d outside 0 .. %d", P.width,
@@ -434,7 +433,7 @@ int cvx_world_nav_build(cvx_context *ctx, const cvx_nav_params *params, const in
 	}
 	int rc = CheckGoals(ctx, goals, goalCount, P.maxSteps);
 	if (rc != CVX_OK) { return rc; }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
 	cvxb::PiecesBox B;
 	if (!cvxb::PiecesClipBox(P.boxMin, P.boxMax, dim[0], dim[1], dim[2], &B)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box lies outside the world"); }
@@ -442,9 +441,7 @@ int cvx_world_nav_build(cvx_context *ctx, const cvx_nav_params *params, const in
 	A.T.G = cvxb::NavGridOf(B, R.w);
 	A.T.R = R;
 	if (A.T.G.Columns() >= ((int64_t)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "a field of %lld cell columns", (long long)A.T.G.Columns()); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 	cvx_nav_field *F = new (std::nothrow) cvx_nav_field();
 	if (!F) { return Fail(ctx, CVX_ERR_CAPACITY, "out of host memory"); }
 	F->ctx = ctx;

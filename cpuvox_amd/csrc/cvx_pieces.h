@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "cpuvox_gpu.h"
+#include "cvx_box.h" // BoxCheck: what a box must keep before it is clipped
 #include "cvx_copy.h"
 
 namespace cvxb {

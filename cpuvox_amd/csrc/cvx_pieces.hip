@@ -136,14 +136,13 @@ int Analyse(cvx_context *ctx, const char *call, const int32_t boxMin[3], const i
             const cvx_piece *pieces, int pieceCapacity, Analysis *R)
 {
 	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box is NULL"); }
-	for (int a = 0; a < 3; a++) {
-		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box [%d, %d) on axis %d is empty", boxMin[a], boxMax[a], a); }
-	}
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::BoxCheck(boxMin, boxMax, 0, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", bad); }
 	if (anchors & ~(CVX_ANCHOR_GROUND | CVX_ANCHOR_OUTSIDE | CVX_ANCHOR_LARGEST)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "unknown anchors bits 0x%x", (unsigned)anchors); }
 	if (extraError) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", extraError); }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
 	if (pieceCapacity < 0 || (pieceCapacity > 0 && !pieces)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "pieceCapacity %d with %s list", pieceCapacity, pieces ? "a" : "no"); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const cvxcomp::Call engine{ call, "solid runs", cvxcomp::KernelsOf<PiecesRule>(), anchors, pieceCapacity, sizeof(Totals) };
 	R->host = Totals{};
 	return cvxcomp::Analyse(

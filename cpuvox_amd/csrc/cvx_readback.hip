@@ -290,8 +290,7 @@ int CheckRead(cvx_context *ctx, int lod, void **outStorage, int64_t *outByteLeng
 int Prepare(cvx_context *ctx, int lod)
 {
 	if (!ctx->levelSet[lod]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD %d has not been uploaded", lod); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxi::SyncWorld(ctx);
+	return cvxi::PrepareWorld(ctx);
 }
 
 // Per level of a compaction: the scratch of the counts and the totals the host sizes the new arena with
@@ -345,9 +344,8 @@ int cvx_world_compact(cvx_context *ctx, int64_t *outReclaimedBytes, float *outDe
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (outReclaimedBytes) { *outReclaimedBytes = 0; }
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	int rc = cvxi::SyncWorld(ctx);
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
+	int rc = cvxi::PrepareWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 	bool any = false;
 	for (const cvx_context::EditLevel &E : ctx->edit) { any = any || E.ready; }

@@ -21,7 +21,6 @@
 #include <climits>
 #include <cstring>
 #include <new>
-#include <vector>
 
 #include "cpuvox_gpu_snapshot.h"
 #include "cvx_context.h"
@@ -142,15 +141,14 @@ static int CheckPair(cvx_context *ctx, const cvx_snapshot *snap, const char *cal
 
 static int CheckWorld(cvx_context *ctx, const cvx_snapshot *snap, const char *call)
 {
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const DevWorld &W = ctx->hostWorld;
 	const cvx_snapshot_info &I = snap->info;
 	if (W.dimX != I.dimX || W.dimY != I.dimY || W.dimZ != I.dimZ) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: the world is %d x %d x %d, the snapshot was taken from one of %d x %d x %d", call, W.dimX, W.dimY, W.dimZ, I.dimX,
 		            I.dimY, I.dimZ);
 	}
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	return cvxi::SyncWorld(ctx);
+	return cvxi::PrepareWorld(ctx);
 }
 
 // Both calls: `device` says where `changes` lives.
@@ -169,9 +167,8 @@ static int Diff(cvx_context *ctx, const char *call, const cvx_snapshot *snap, in
 
 	const cvx_snapshot_info &I = snap->info;
 	const int n = I.sizeX * I.sizeZ;
-	std::vector<cvx_snapshot_change> back; // (outlives D: freeing the device blocks waits for a copy still under way)
 	cvxi::DeviceCall D(ctx, call);
-	uint8_t *scratch = nullptr, *list = nullptr;
+	uint8_t *scratch = nullptr;
 	cvxi::ScratchLayout carve;
 	const size_t chunks = ((size_t)n + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	const size_t groups = Grid((size_t)n);
@@ -203,27 +200,14 @@ static int Diff(cvx_context *ctx, const char *call, const cvx_snapshot *snap, in
 		if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
 	}
 	if (e != hipSuccess) { return D.Fail(e); }
-	const size_t wanted = (size_t)std::min<unsigned long long>(host.sum.changedColumns, (unsigned long long)changeCapacity);
-	if (wanted) {
-		if (device) {
-			A.changes = changes;
-		} else {
-			back.resize(wanted);
-			e = D.Allocate(&list, wanted * sizeof(cvx_snapshot_change));
-			A.changes = reinterpret_cast<cvx_snapshot_change *>(list);
-		}
-		if (e == hipSuccess) {
-			A.limit = (uint32_t)wanted;
-			hipLaunchKernelGGL(snapshot_diff_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
-			e = hipGetLastError();
-		}
-		if (e == hipSuccess && !device) { e = hipMemcpyAsync(back.data(), list, wanted * sizeof(cvx_snapshot_change), hipMemcpyDeviceToHost, ctx->stream); }
-	}
-	if (e == hipSuccess) { e = D.End(); }
-	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return D.Fail(e); }
-	// (nothing is handed out before the call can no longer fail)
-	if (!back.empty()) { std::memcpy(changes, back.data(), back.size() * sizeof(cvx_snapshot_change)); }
+	const cvxi::ListCall list{ sizeof(cvx_snapshot_change), host.sum.changedColumns, changeCapacity, changes, device };
+	rc = cvxi::FinishList(ctx, D, list, [&](const cvxi::ListJob &J) {
+		A.changes = static_cast<cvx_snapshot_change *>(J.into);
+		A.limit = J.limit;
+		hipLaunchKernelGGL(snapshot_diff_write_kernel, dim3(Grid((size_t)n)), dim3(kThreads), 0, ctx->stream, A);
+		return hipSuccess;
+	});
+	if (rc != CVX_OK) { return rc; }
 	if (summary) {
 		std::memset(summary, 0, sizeof *summary);
 		summary->changedColumns = (int64_t)host.sum.changedColumns;
@@ -249,7 +233,7 @@ int cvx_world_snapshot(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, i
 	*out = nullptr;
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const DevWorld &W = ctx->hostWorld;
 	const int64_t x1 = std::min<int64_t>((int64_t)x0 + sizeX, W.dimX), z1 = std::min<int64_t>((int64_t)z0 + sizeZ, W.dimZ);
 	if (sizeX < 1 || sizeZ < 1 || std::max(x0, 0) >= x1 || std::max(z0, 0) >= z1) {
@@ -258,9 +242,7 @@ int cvx_world_snapshot(cvx_context *ctx, int x0, int z0, int sizeX, int sizeZ, i
 	cvxi::EditRectangle R{};
 	int rc = cvxi::RoundEditRectangle(ctx, std::max(x0, 0), x1, std::max(z0, 0), z1, levelCount, "a snapshot of", &R);
 	if (rc != CVX_OK) { return rc; }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	cvx_snapshot *snap = new (std::nothrow) cvx_snapshot();
 	if (!snap) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: no host memory", call); }

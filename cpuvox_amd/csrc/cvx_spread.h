@@ -44,24 +44,7 @@ inline int SpreadCheck(const cvx_spread_params *params, const cvx_spread_seed *s
 		return CVX_ERR_INVALID_ARGUMENT;
 	}
 	const cvx_spread_params &P = *params;
-	int64_t n = 1;
-	for (int a = 0; a < 3; a++) {
-		if (P.boxMin[a] < -(1 << 30) || P.boxMin[a] > (1 << 30) || P.boxMax[a] < -(1 << 30) || P.boxMax[a] > (1 << 30)) {
-			snprintf(message, size, "the box [%d, %d) on axis %d has a coordinate beyond 2^30", P.boxMin[a], P.boxMax[a], a);
-			return CVX_ERR_INVALID_ARGUMENT;
-		}
-		if (P.boxMin[a] >= P.boxMax[a]) {
-			snprintf(message, size, "the box [%d, %d) on axis %d is empty", P.boxMin[a], P.boxMax[a], a);
-			return CVX_ERR_INVALID_ARGUMENT;
-		}
-	}
-	for (int a = 0; a < 3; a++) {
-		n *= (int64_t)P.boxMax[a] - P.boxMin[a]; // (each factor at most 2^31, the running product below 2^31 before it: no overflow)
-		if (n >= ((int64_t)1 << 31)) {
-			snprintf(message, size, "a box of 2^31 or more voxels");
-			return CVX_ERR_INVALID_ARGUMENT;
-		}
-	}
+	if (BoxCheck(P.boxMin, P.boxMax, kBoxWithin | kBoxVoxels, message, size)) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (P.medium != CVX_SPREAD_AIR && P.medium != CVX_SPREAD_SOLID) {
 		snprintf(message, size, "bad medium %d", P.medium);
 		return CVX_ERR_INVALID_ARGUMENT;

@@ -295,10 +295,10 @@ __global__ __launch_bounds__(kThreads) void spread_finish_kernel(Args A, uint32_
 
 namespace {
 
+using cvxi::Grid;
 using cvxspread::kThreads;
 
 size_t Align(uint64_t bytes) { return (size_t)((bytes + 255) & ~(uint64_t)255); }
-unsigned Blocks(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, const cvx_spread_seed *seeds, int seedCount, int32_t *out, bool device,
            cvx_spread_summary *summary, float *outDeviceMs)
@@ -306,7 +306,7 @@ int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, 
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	char message[160];
 	if (cvxb::SpreadCheck(params, seeds, seedCount, out, message, sizeof message) != 0) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, message); }
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	cvxspread::Args A{};
 	A.G = cvxb::SpreadGridOf(*params);
 	const uint64_t n = A.G.Elements(), words = A.G.Words();
@@ -315,8 +315,7 @@ int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, 
 	const size_t seedsAt = Align(sizeof(cvxspread::Totals)), flagsAt = seedsAt + Align((uint64_t)seedCount * sizeof(cvx_spread_seed));
 	const size_t bitsAt = flagsAt + 2 * Align((uint64_t)tiles), distAt = bitsAt + Align(words * 8), outAt = distAt + Align(n * 2);
 	const size_t bytes = outAt + (device ? 0 : (size_t)n * 4);
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	int rc = cvxi::SyncWorld(ctx);
+	int rc = cvxi::PrepareWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
 	cvxi::DeviceCall D(ctx, call);
@@ -334,8 +333,8 @@ int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, 
 		A.dist = reinterpret_cast<uint16_t *>(scratch + distAt);
 		A.out = device ? out : reinterpret_cast<int32_t *>(scratch + outAt);
 		uint8_t *flags[2] = { scratch + flagsAt, scratch + flagsAt + Align((uint64_t)tiles) };
-		hipLaunchKernelGGL(cvxspread::spread_init_kernel, dim3(Blocks(words, cvxspread::kWaves * cvxspread::kInitWords)), dim3(kThreads), 0, ctx->stream, A, words);
-		hipLaunchKernelGGL(cvxspread::spread_seeds_kernel, dim3(Blocks((uint64_t)seedCount, kThreads)), dim3(kThreads), 0, ctx->stream, A,
+		hipLaunchKernelGGL(cvxspread::spread_init_kernel, dim3(Grid(words, cvxspread::kWaves * cvxspread::kInitWords)), dim3(kThreads), 0, ctx->stream, A, words);
+		hipLaunchKernelGGL(cvxspread::spread_seeds_kernel, dim3(Grid((uint64_t)seedCount, kThreads)), dim3(kThreads), 0, ctx->stream, A,
 		                   reinterpret_cast<const cvx_spread_seed *>(scratch + seedsAt), seedCount, flags[0]);
 		e = hipGetLastError();
 		const int64_t bound = (int64_t)A.G.maxSteps + 2;
@@ -351,7 +350,7 @@ int Spread(cvx_context *ctx, const char *call, const cvx_spread_params *params, 
 		}
 	}
 	if (e == hipSuccess) {
-		hipLaunchKernelGGL(cvxspread::spread_finish_kernel, dim3(Blocks(n, kThreads * cvxspread::kFinishElements)), dim3(kThreads), 0, ctx->stream, A, (uint32_t)n);
+		hipLaunchKernelGGL(cvxspread::spread_finish_kernel, dim3(Grid(n, kThreads * cvxspread::kFinishElements)), dim3(kThreads), 0, ctx->stream, A, (uint32_t)n);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) { e = hipMemcpyAsync(&host, A.totals, sizeof host, hipMemcpyDeviceToHost, ctx->stream); }

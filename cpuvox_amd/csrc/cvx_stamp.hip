@@ -377,13 +377,12 @@ int cvx_world_stamp_mesh(cvx_context *ctx, const cvx_mesh_vertex *vertices, int 
 		textures[(size_t)m] = cvxs::Texture{ t.width, t.height, texelBytes };
 		texelBytes += (int64_t)t.width * t.height * 4;
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	if (outDeviceMs) { *outDeviceMs = 0.f; }
 	const int triangles = (int)(indexCount / 3);
 	if (triangles == 0) { return CVX_OK; }
 	const int dimX = ctx->hostWorld.dimX, dimY = ctx->hostWorld.dimY, dimZ = ctx->hostWorld.dimZ;
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	int rc = cvxi::SyncWorld(ctx);
+	int rc = cvxi::PrepareWorld(ctx);
 	if (rc != CVX_OK) { return rc; }
 
 	static const char *const call = "cvx_world_stamp_mesh";

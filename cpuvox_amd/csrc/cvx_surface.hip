@@ -11,10 +11,8 @@
 // the arena.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <vector>
 
 #include "cvx_context.h"
 #include "cvx_surface.h"
@@ -109,27 +107,23 @@ static int Surface(cvx_context *ctx, const char *call, const int32_t boxMin[3], 
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	if (!boxMin || !boxMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: a NULL box", call); }
-	for (int a = 0; a < 3; a++) {
-		if (boxMin[a] >= boxMax[a]) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box [%d, %d) on axis %d is empty", boxMin[a], boxMax[a], a); }
-	}
+	char bad[cvxb::kBoxMessage];
+	if (cvxb::BoxCheck(boxMin, boxMax, 0, bad, sizeof bad)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", bad); }
 	if (solidOutside & ~0x3F) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "unknown solidOutside bits 0x%x", (unsigned)solidOutside); }
 	if (flags & ~CVX_SURFACE_IGNORE_COLOUR) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "unknown flags bits 0x%x", (unsigned)flags); }
 	if (quadCapacity < 0 || (quadCapacity > 0 && !quads)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "quadCapacity %lld with %s list", (long long)quadCapacity, quads ? "a" : "no");
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dim[3] = { ctx->hostWorld.dimX, ctx->hostWorld.dimY, ctx->hostWorld.dimZ };
 	SurfaceArgs A{};
 	if (!cvxb::PiecesClipBox(boxMin, boxMax, dim[0], dim[1], dim[2], &A.B)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "the box lies outside the world"); }
 	if (A.B.Columns() * kFaces >= ((int64_t)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "a box of %lld columns", (long long)A.B.Columns()); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	const int rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	const int pairs = (int)(A.B.Columns() * kFaces);
-	std::vector<cvx_surface_quad> back; // (outlives D: freeing the device blocks waits for a copy still under way)
 	cvxi::DeviceCall D(ctx, call);
-	uint8_t *scratch = nullptr, *list = nullptr;
+	uint8_t *scratch = nullptr;
 	cvxi::ScratchLayout carve;
 	const size_t chunks = ((size_t)pairs + 1 + cvxi::ScanChunk() - 1) / cvxi::ScanChunk();
 	const size_t oTotals = carve(sizeof(Totals)), oOffsets = carve(((size_t)pairs + 1) * 4), oChunks = carve(chunks * 8);
@@ -152,27 +146,14 @@ static int Surface(cvx_context *ctx, const char *call, const int32_t boxMin[3], 
 	}
 	if (e != hipSuccess) { return D.Fail(e); }
 	if (host.quads >= ((unsigned long long)1 << 31) - 1) { return Fail(ctx, CVX_ERR_CAPACITY, "the box holds %llu quads", host.quads); }
-	const size_t wanted = (size_t)std::min<unsigned long long>(host.quads, (unsigned long long)quadCapacity);
-	if (wanted) {
-		if (device) {
-			A.quads = quads;
-		} else {
-			back.resize(wanted);
-			e = D.Allocate(&list, wanted * sizeof(cvx_surface_quad));
-			A.quads = reinterpret_cast<cvx_surface_quad *>(list);
-		}
-		if (e == hipSuccess) {
-			A.limit = (uint32_t)wanted;
-			hipLaunchKernelGGL(surface_write_kernel, dim3(Grid((size_t)pairs)), dim3(kThreads), 0, ctx->stream, A);
-			e = hipGetLastError();
-		}
-		if (e == hipSuccess && !device) { e = hipMemcpyAsync(back.data(), list, wanted * sizeof(cvx_surface_quad), hipMemcpyDeviceToHost, ctx->stream); }
-	}
-	if (e == hipSuccess) { e = D.End(); }
-	if (e == hipSuccess) { e = hipStreamSynchronize(ctx->stream); }
-	if (e != hipSuccess) { return D.Fail(e); }
-	// (nothing is handed out before the call can no longer fail)
-	if (!back.empty()) { std::memcpy(quads, back.data(), back.size() * sizeof(cvx_surface_quad)); }
+	const cvxi::ListCall list{ sizeof(cvx_surface_quad), host.quads, quadCapacity, quads, device };
+	const int rc = cvxi::FinishList(ctx, D, list, [&](const cvxi::ListJob &J) {
+		A.quads = static_cast<cvx_surface_quad *>(J.into);
+		A.limit = J.limit;
+		hipLaunchKernelGGL(surface_write_kernel, dim3(Grid((size_t)pairs)), dim3(kThreads), 0, ctx->stream, A);
+		return hipSuccess;
+	});
+	if (rc != CVX_OK) { return rc; }
 	if (summary) { std::memcpy(summary, &host, sizeof *summary); }
 	if (outDeviceMs) { *outDeviceMs = D.Ms(); }
 	return CVX_OK;

@@ -90,7 +90,7 @@ static int Sweep(cvx_context *ctx, const char *call, const cvx_model *models, in
 	if (!cvxb::SweepValidate(models, modelCount, instances, instanceCount, motions, solidOutside, sweeps, contacts, points, pointCapacity, message, sizeof message)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, message);
 	}
-	if (!ctx->levelSet[0]) { return Fail(ctx, CVX_ERR_NOT_READY, "world LOD 0 has not been uploaded"); }
+	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	std::vector<uint32_t> prefix((size_t)instanceCount + 1), first((size_t)instanceCount);
 	std::vector<cvxb::SweepInstanceJob> info((size_t)instanceCount);
 	int64_t stationCount = 0;
@@ -98,9 +98,7 @@ static int Sweep(cvx_context *ctx, const char *call, const cvx_model *models, in
 	if (jobs < 0) { return Fail(ctx, CVX_ERR_CAPACITY, "%s: the boxes' footprints times their motions' stations sum to 2^31 - 1 or more jobs", call); }
 	std::vector<cvxb::SweepStation> stations((size_t)stationCount);
 	for (int k = 0; k < instanceCount; k++) { cvxb::SweepStations(motions + 3 * (size_t)k, stations.data() + info[k].stationBase); }
-	CVX_HIP(ctx, hipSetDevice(ctx->device));
-	const int rc = cvxi::SyncWorld(ctx);
-	if (rc != CVX_OK) { return rc; }
+	if (const int refused = cvxi::PrepareWorld(ctx)) { return refused; }
 
 	// phase 1 (the vectors above outlive D: freeing the device blocks waits for a copy still under way)
 	std::vector<cvxs_sweep_result> out((size_t)instanceCount);

@@ -535,3 +535,35 @@ def test_snapshots_close_with_their_context(dense_world):
     assert not a._h and ctx._snapshots == [b]
     ctx.close()
     assert not b._h and ctx._snapshots == []
+
+
+def test_the_diff_list_around_the_count_in_both_forms():
+    """The 8 x 8 columns in the middle of a 16 x 16 x 16 noise world after a carve through some of them, capacities 0 (no list), 1, found - 1,
+    found and found + 1: the host and the device form give the same bytes, leave a list filled with a sentinel alone from min(found, capacity)
+    on, and the summary is the same at every capacity."""
+    dims, rect = (16, 16, 16), (4, 4, 8, 8)
+    x, y, z = np.nonzero(np.random.default_rng(7).random(dims) < 0.5)
+    ws = host.WorldSet.from_voxels(dims, x.astype(np.int32), y.astype(np.int32), z.astype(np.int32), np.full(len(x), 0xFF204060, dtype=np.uint32), threads=2)
+    ctx = _context(ws)
+    try:
+        before = voxels(ctx, dims)
+        snapshot = ctx.world_snapshot(*rect, 0)
+        ctx.brush([_box(CARVE, (5, 3, 5), (10, 12, 9))], 0)
+        want, want_summary = snapshotmodel.diff(cut(before, rect), cut(voxels(ctx, dims), rect), rect[:2], 0)
+        found = len(want)
+        assert 2 < found < rect[2] * rect[3]
+        for capacity in (0, 1, found - 1, found, found + 1):
+            listed = min(capacity, found)
+            on_host = np.full((found + 2, 4), -7, dtype=np.int32)
+            on_device = torch.full((found + 2, 4), -7, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            summary = snapshot._diff(gpu.lib().cvx_world_snapshot_diff, 0, on_host.ctypes.data if capacity else None, capacity)
+            device_summary = snapshot.diff_device(on_device.data_ptr() if capacity else None, capacity, 0)
+            torch.cuda.synchronize()
+            back = on_device.cpu().numpy()
+            assert summary == want_summary and device_summary == want_summary, capacity
+            assert on_host[:listed].tobytes() == want[:listed].tobytes() and back[:listed].tobytes() == want[:listed].tobytes(), capacity
+            assert (on_host[listed:] == -7).all() and (back[listed:] == -7).all(), f"capacity {capacity}: written behind entry {listed}"
+    finally:
+        ctx.close()
+        ws.close()

@@ -314,3 +314,32 @@ def test_rejected_calls_and_the_world_after_the_calls(built):
     _rects(ctx, solid, colour, (0, 0, 0), DIMS, 0x3F, IGNORE, label="whole world")
     _rects_device(ctx, solid, colour, *AROUND, 0x04, 0, 3, label="device")
     assert [ctx.read_level(k) for k in range(6)] == before and ctx.edit_stats() == stats, "a call changed the arena"
+
+
+def test_the_list_around_the_count_in_both_forms():
+    """An 8 x 8 x 8 box of a 16 x 16 x 16 noise world, capacities 0 (no list), 1, found - 1, found and found + 1: the host and the device form
+    give the same bytes, leave a list filled with a sentinel alone from min(found, capacity) on, and the summary is the same at every capacity."""
+    dims, box = (16, 16, 16), ((4, 4, 4), (12, 12, 12))
+    solid = np.random.default_rng(7).random(dims) < 0.5
+    colour = _few_colours(solid, 8)
+    ws = _built_world(dims, solid, colour)
+    ctx = _context(ws)
+    try:
+        want, want_summary = model.rects(solid, colour, *box, 0x04, 0)
+        found = len(want)
+        assert found > 2
+        for capacity in (0, 1, found - 1, found, found + 1):
+            listed = min(capacity, found)
+            on_host = np.full((found + 2, 8), SENTINEL, dtype=np.uint32)
+            on_device = torch.full((found + 2, 8), SENTINEL, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            summary, _ = ctx._surface_rects(gpu.lib().cvx_world_surface_rects, *box, 0x04, 0, on_host.ctypes.data if capacity else None, capacity)
+            device_summary, _ = ctx.world_surface_rects_device(*box, on_device.data_ptr() if capacity else 0, capacity, 0x04, 0)
+            torch.cuda.synchronize()
+            back = on_device.cpu().numpy().view(np.uint32)
+            assert summary == want_summary and device_summary == want_summary, capacity
+            assert on_host[:listed].tobytes() == want[:listed].tobytes() and back[:listed].tobytes() == want[:listed].tobytes(), capacity
+            assert (on_host[listed:] == SENTINEL).all() and (back[listed:] == SENTINEL).all(), f"capacity {capacity}: written behind entry {listed}"
+    finally:
+        ctx.close()
+        ws.close()
