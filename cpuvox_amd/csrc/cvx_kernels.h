@@ -364,10 +364,31 @@ __device__ __forceinline__ int tex_row_exact(int y, float boundsX, float boundsY
 //   pixel is certain) whenever Ex > |wux'| / 2; |u'| >= 2^21 gives D > 1/2 too, so a certain u' is far inside the int range (where the x86 rule of
 //   f2i_floor is the plain floor); a NaN or an infinity anywhere makes the comparison false.  Outside the normal range: |d| > 2^100 makes every pixel of the
 //   run uncertain, 2^-110 |wux'| in D does the same for |wux'| > 2^126 (denormal reciprocals), and Sx >= 2^-140 covers what underflowing products lose.
-//   cvx_selftest_math op 16 compares the two forms on the device (tests: 2^24 samples incl. float soup, no certain row may differ).
+//   cvx_selftest_math op 16 compares the two forms on the device (tests: 2^24 samples incl. float soup, no certain row may differ); op 17 does it for the
+//   widened form below, from the side block's own inputs, and checks the fall-back's row too (tests/test_gpu_texture_row_inputs.py).
+//
+// Approximate end quotients (the batch kernel's side block, tex_ends_approx below; WIDE).  The reference divides (1, uA) by bottom.z and (1, 0) by top.z,
+// correctly rounded; the side block passes r = recip_safe(z).r for 1 / z and fl(uA * r) for uA / z instead, and keeps the zero.  What they are off by:
+//   r0 = rcp(z) within one ulp of fl(1 / z), so r0 = (1 + t) / z with |t| <= 3 e;  e0 = fma(-z, r0, 1) = -t (1 + e);  r = fma(e0, r0, r0) = fl((1 - t^2 (1 + e)) / z):
+//   the rounding of a number within 2^-44 of 1 / z, so r is fl(1 / z) or one of its two neighbours,                      |r - fl(1 / z)| <= 2 e |r|
+//   fl(uA * r) against fl(uA / z): one rounding each and r's (1 + 2^-44) e,                                    |fl(uA r) - fl(uA / z)| <= 3.01 e |fl(uA r)|
+// (tests/test_texture_row_inputs_model.py checks both for a hardware reciprocal off by an ulp either way.)  With these inputs (tilde) against the exact ones:
+//   wux - wux' = (uvA.x - ~uvA.x) + (l - l') a1 + l' (a1 - ~a1) + roundings,  |a1 - ~a1| <= 2 e (|~uvA.x| + |~uvB.x|) + e (|a1| + |~a1|)
+//   =>  |wux - wux'| <= 9 e (|~uvA.x| + |l'| |~a1|) + 2 e |~uvA.x| + 2 e |l'| (|~uvA.x| + |~uvB.x|);  for wuy the same with 3.01 e
+// The new terms do not shrink with a1 when the two ends lie at (nearly) the same depth, which is why they are terms of their own and not a larger 40.  With
+// the same factor 2.2 over 2 Ex as above (3.01 x 2.2 = 6.7 <= 8): Sx = 48 e |uvA.x| + |l'| (40 e |a1| + 8 e (|uvA.x| + |uvB.x|)), and
+// Sy = 48 e (|uvA.y| + |l'| |a2|): an approximate uvA.y comes with uvB.y = the zero the side block leaves there, so |a2| = |uvA.y| + |uvB.y| and this is
+// 40 e (...) + 8 e (...) as for x; a lane whose uvB.y is no zero (an end clipped at the near plane) holds the reference's quotients and needs the 40 alone.
+// Sy is therefore computed per pixel from a2 and uvA.y themselves (the factor 48 e goes into the fma that adds Sx): as many instructions per pixel as the
+// narrow form, two values fewer to carry across the pixel loop.  Symmetric in the two ends, so the swap of :496-499 needs no case of its own; exact
+// inputs (lanes that redid their quotients with plain divisions) pass a bound that is only wider.  A span d that rounds to zero needs no term: rcp(0) is an
+// infinity by definition, l' is infinite or NaN, and wuy' * rcp(wux') ends in a NaN whichever way a1 points -- no pixel of such a run is certain (as before).
 struct TexRun { // per run: what the cheap row needs of (boundsX, boundsY, uvA, uvB)
 	float rd, a1, a2, a1s, a2s, bxs, bys;
 };
+#define CVX_TEX_K (40.0f * 0x1p-24f)
+#define CVX_TEX_K_INPUT (8.0f * 0x1p-24f)
+template <bool WIDE = false>
 __device__ __forceinline__ TexRun tex_run(float boundsX, float boundsY, float uvAx, float uvBx, float uvAy, float uvBy)
 {
 	TexRun T;
@@ -375,13 +396,20 @@ __device__ __forceinline__ TexRun tex_run(float boundsX, float boundsY, float uv
 	T.rd = fabsf(d) <= 0x1p100f ? __builtin_amdgcn_rcpf(d) : __builtin_nanf(""); // (a reciprocal below 2^-126 is not "within one ulp": no pixel of such a run is certain)
 	T.a1 = uvBx - uvAx;
 	T.a2 = uvBy - uvAy;
-	const float k = 40.0f * 0x1p-24f;
+	const float k = CVX_TEX_K;
+	if (WIDE) { // (a2s, bys: not used by tex_row_cheap<true>)
+		T.a1s = __builtin_fmaf(CVX_TEX_K_INPUT, fabsf(uvAx) + fabsf(uvBx), k * fabsf(T.a1));
+		T.bxs = __builtin_fmaf(k + CVX_TEX_K_INPUT, fabsf(uvAx), 0x1p-140f);
+		T.a2s = T.bys = 0.0f;
+		return T;
+	}
 	T.a1s = k * fabsf(T.a1);
 	T.a2s = k * fabsf(T.a2);
 	T.bxs = __builtin_fmaf(k, fabsf(uvAx), 0x1p-140f); // (the floor covers what an underflowing product can lose: 2^-149 per operation)
 	T.bys = k * fabsf(uvAy);
 	return T;
 }
+template <bool WIDE = false>
 __device__ __forceinline__ int tex_row_cheap(int y, float boundsX, float uvAx, float uvAy, const TexRun &T, bool &certain)
 {
 	const float n = (float)y - boundsX;
@@ -389,13 +417,46 @@ __device__ __forceinline__ int tex_row_cheap(int y, float boundsX, float uvAx, f
 	const float wx = __builtin_fmaf(lq, T.a1, uvAx), wy = __builtin_fmaf(lq, T.a2, uvAy);
 	const float r = __builtin_amdgcn_rcpf(wx);
 	const float uq = wy * r;
-	const float sx = __builtin_fmaf(fabsf(lq), T.a1s, T.bxs), sy = __builtin_fmaf(fabsf(lq), T.a2s, T.bys);
+	const float sx = __builtin_fmaf(fabsf(lq), T.a1s, T.bxs);
+	const float sxy = WIDE ? __builtin_fmaf(CVX_TEX_K + CVX_TEX_K_INPUT, __builtin_fmaf(fabsf(lq), fabsf(T.a2), fabsf(uvAy)), sx) : __builtin_fmaf(fabsf(lq), T.a2s, T.bys) + sx; // Sy + Sx
 	// (the |wux'| term: beyond 2^126 its reciprocal is denormal, not "within one ulp" -- the bound then exceeds every distance)
-	const float bound = __builtin_fmaf(__builtin_fmaf(fabsf(uq), sx, sy + sx), fabsf(r), __builtin_fmaf(fabsf(wx), 0x1p-110f, 0x1p-21f * fabsf(uq)));
+	const float bound = __builtin_fmaf(__builtin_fmaf(fabsf(uq), sx, sxy), fabsf(r), __builtin_fmaf(fabsf(wx), 0x1p-110f, 0x1p-21f * fabsf(uq)));
 	certain = fabsf(uq - rintf(uq)) > bound;
 	int row;
 	asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(row) : "v"(uq));
 	return row;
+}
+// The two ends of an ordinary run's side for tex_run<true>: (1, uA) / bottom.z and (1, 0) / top.z from the refined reciprocals the block has anyway -- one product
+// where the correctly rounded quotients cost thirteen instructions.
+__device__ __forceinline__ void tex_ends_approx(Recip rb, Recip rt, float uA, float topZ, float &uvAx, float &uvAy, float &uvBx, float &uvBy)
+{
+	uvAx = rb.r;
+	uvAy = uA * rb.r;
+	uvBx = rt.r;
+	uvBy = __int_as_float(__float_as_int(topZ) & (int)0x80000000); // +0 / z: a zero with the sign of z
+}
+// The pixels that are not certain take the reference's row from the reference's quotients.  No lane keeps those.  A lane that was not `ordinary` redid its ends
+// with the clip and the plain divisions and HOLDS them (ax, ay, and uvB through a1 = fl(uvB.x - uvA.x), a2 likewise: the reference's own differences, :526-527);
+// it passes a NaN for its depths.  An ordinary lane passes the depths of its two front points (the caller computes them again: f3_lerp's own expression on the
+// Last-intersection points and the run's portions, hence the same floats) and gets its quotients here, by the side block's former instructions, written over
+// the approximate ones: exact inputs pass the widened bound too, so the lane keeps them for the rest of the run (and computes the same again should another of
+// its pixels come here).  The swap of :496-499 is read off the held end: uA >= 1 and a depth in the range make uvA.y a non-zero number, and uvB.y is the zero.
+__device__ __forceinline__ int tex_row_fallback(int y, float boundsX, float boundsY, float &ax, float &ay, float &a1, float &a2, float bottomZ, float topZ, float uA)
+{
+	if (bottomZ == bottomZ) {
+		const bool swapped = ay == 0.0f;
+		const Recip rb = recip_safe(bottomZ), rt = recip_safe(topZ);
+		const float bx_ = quot_safe(1.0f, rb), by_ = quot_safe(uA, rb), tx_ = quot_safe(1.0f, rt);
+		const float ty_ = __int_as_float(__float_as_int(topZ) & (int)0x80000000); // +0 / z: a zero with the sign of z
+		ax = swapped ? tx_ : bx_;
+		ay = swapped ? ty_ : by_;
+		a1 = swapped ? bx_ - tx_ : tx_ - bx_;
+		a2 = swapped ? by_ - ty_ : ty_ - by_;
+	}
+	const float l = ((float)y - boundsX) / (boundsY - boundsX); // tex_row_exact with the two differences as operands (m_lerp(a, b, l) = a + l * (b - a))
+	const float wux = ax + l * a1;
+	const float wuy = ay + l * a2;
+	return f2i_floor(wuy / wux);
 }
 
 // ---- seen-pixel bitmask in LDS ---------------------------------------------
@@ -1018,20 +1079,28 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 				// uB = 0, and all of x, z of both ends within [2^-30, 2^30]): one refined reciprocal per end (see quot_safe).  Every lane
 				// computes that; ONE rare branch then redoes the lanes that are not ordinary -- an end behind the near plane (:141-157) or an
 				// operand outside the range -- with the clip and the plain divisions (an if / else costs two branches, a test per case one each).
+				// The rendering build takes the three texture quotients as they come out of the reciprocals (tex_ends_approx): their only consumer is the
+				// certified cheap row, whose bound covers what they are off by (tex_run<true>), and the few pixels that are not certain divide for themselves.
+				// The two screen quotients stay exact: they decide rbMin / rbMax, and the certificate takes the bounds as the same floats in both forms.
 				float uvAx, uvAy, uvBx, uvBy;
 				{
 					const Recip rb = recip_safe(camSpaceFrontBottom.z), rt = recip_safe(camSpaceFrontTop.z);
-					uvAx = quot_safe(1.0f, rb);
-					uvAy = quot_safe(uA, rb);
+					if (COUNT) {
+						uvAx = quot_safe(1.0f, rb);
+						uvAy = quot_safe(uA, rb);
+						uvBx = quot_safe(1.0f, rt);
+						uvBy = __int_as_float(__float_as_int(camSpaceFrontTop.z) & (int)0x80000000); // +0 / z: a zero with the sign of z
+					} else {
+						tex_ends_approx(rb, rt, uA, camSpaceFrontTop.z, uvAx, uvAy, uvBx, uvBy);
+					}
 					frontBottomQuotient = quot_safe(camSpaceFrontBottom.x, rb);
-					uvBx = quot_safe(1.0f, rt);
-					uvBy = __int_as_float(__float_as_int(camSpaceFrontTop.z) & (int)0x80000000); // +0 / z: a zero with the sign of z
 					frontTopQuotient = quot_safe(camSpaceFrontTop.x, rt);
 				}
 				secBQuotient = faceTop ? frontTopQuotient : frontBottomQuotient;
 				const bool ordinary = ((int)!(camSpaceFrontBottom.y <= 0.0f) & (int)!(camSpaceFrontTop.y <= 0.0f) & (int)!(secA.y <= 0.0f) & (int)div_safe(camSpaceFrontBottom.z) & (int)div_safe(camSpaceFrontTop.z) &
 				                       (int)div_safe(camSpaceFrontBottom.x) & (int)div_safe(camSpaceFrontTop.x)) != 0;
 				if (CVX_RARE(!ordinary)) {
+					if (!COUNT) { elementBoundsMin = __builtin_nanf(""); } // (dead from here on but for tex_row_fallback: this lane holds the reference's quotients)
 					if (camSpaceFrontBottom.y <= 0.0f) {
 						if (camSpaceFrontTop.y <= 0.0f) {
 							visible = false;
@@ -1092,12 +1161,20 @@ uint2 countInfo = uint2{ 0u, 0u }; // counting build: {RunCount | elementIndex o
 								frustumDirMaxWorld = CVX_FLOAT_EPSILON;
 								// perspective-correct colour of pixel y of the run's side, :524-531
 								// the texture row of pixel y: the cheap form where it is certain, the reference's two divisions where not (tex_row_cheap above)
-								const TexRun texRun = COUNT ? TexRun{} : tex_run(boundsX, boundsY, uvAx, uvBx, uvAy, uvBy);
+								TexRun texRun = COUNT ? TexRun{} : tex_run<true>(boundsX, boundsY, uvAx, uvBx, uvAy, uvBy);
 								auto textureRow = [&](int y) -> int {
 									if (COUNT) { return tex_row_exact(y, boundsX, boundsY, uvAx, uvBx, uvAy, uvBy); }
 									bool certain;
-									int row = tex_row_cheap(y, boundsX, uvAx, uvAy, texRun, certain);
-									if (CVX_RARE(!certain)) { row = tex_row_exact(y, boundsX, boundsY, uvAx, uvBx, uvAy, uvBy); }
+									int row = tex_row_cheap<true>(y, boundsX, uvAx, uvAy, texRun, certain);
+									if (CVX_RARE(!certain)) {
+										// (tex_row_fallback above.  The empty asm keeps the compiler from finding the side block's own values in these and carrying them
+										// across the pixel loop instead of computing them here.)
+										float pb = elementBoundsMin, pt = elementBoundsMax;
+										asm volatile("" : "+v"(pb), "+v"(pt));
+										pb *= invWorldMaxY; pt *= invWorldMaxY;
+										const float bottomZ = camSpaceMinLast.z + (camSpaceMaxLast.z - camSpaceMinLast.z) * pb, topZ = camSpaceMinLast.z + (camSpaceMaxLast.z - camSpaceMinLast.z) * pt;
+										row = tex_row_fallback(y, boundsX, boundsY, uvAx, uvAy, texRun.a1, texRun.a2, bottomZ, topZ, (float)elementLength);
+									}
 									return row;
 								};
 								auto colourOffset = [&](int y) -> uint32_t {
@@ -1803,6 +1880,30 @@ __global__ void selftest_math_kernel(int op, int n, const float *__restrict__ a,
 			out[i + 1] = __int_as_float(cheap);
 			out[i + 2] = __int_as_float(certain ? 1 : 0);
 			out[i + 3] = 0.0f;
+		}
+		return;
+	}
+	if (op == 17) { // texture row from the side block's inputs: {y, boundsX, boundsY, bottom.z} / {top.z, uA, swap, -} -> {reference row, shipped row, certain, fall-back row}
+		if ((i & 3) == 0 && i + 3 < n) {
+			const int py = (int)a[i];
+			const float boundsX = a[i + 1], boundsY = a[i + 2], bottomZ = a[i + 3], topZ = b[i], uA = b[i + 1];
+			const bool sw = b[i + 2] != 0.0f;
+			// the reference: IEEE quotients (:490-493), the swap (:496-499), two divisions per pixel
+			const float ax = 1.0f / bottomZ, ay = uA / bottomZ, bx = 1.0f / topZ, by = 0.0f / topZ;
+			const float eAx = sw ? bx : ax, eBx = sw ? ax : bx, eAy = sw ? by : ay, eBy = sw ? ay : by;
+			out[i] = __int_as_float(tex_row_exact(py, boundsX, boundsY, eAx, eBx, eAy, eBy));
+			// the batch kernel: approximate ends where both depths are in the short form's range (of the kernel's `ordinary`, the part that concerns these quotients),
+			// plain divisions elsewhere; the widened certificate; the fall-back that recomputes its quotients
+			const bool ordinary = div_safe(bottomZ) && div_safe(topZ) && uA >= 1.0f && uA <= 65535.0f; // (uA: a run's length)
+			float qAx = ax, qAy = ay, qBx = bx, qBy = by;
+			if (ordinary) { tex_ends_approx(recip_safe(bottomZ), recip_safe(topZ), uA, topZ, qAx, qAy, qBx, qBy); }
+			float sAx = sw ? qBx : qAx, sAy = sw ? qBy : qAy;
+			const float sBx = sw ? qAx : qBx, sBy = sw ? qAy : qBy;
+			bool certain;
+			TexRun T = tex_run<true>(boundsX, boundsY, sAx, sBx, sAy, sBy);
+			out[i + 1] = __int_as_float(tex_row_cheap<true>(py, boundsX, sAx, sAy, T, certain));
+			out[i + 2] = __int_as_float(certain ? 1 : 0);
+			out[i + 3] = __int_as_float(tex_row_fallback(py, boundsX, boundsY, sAx, sAy, T.a1, T.a2, ordinary ? bottomZ : __builtin_nanf(""), topZ, uA));
 		}
 		return;
 	}

@@ -9,7 +9,8 @@ unmodified build) is exactly how often block b was executed by a wave.  Executio
 = the dynamic instruction budget per block; the column sums reproduce SQ_INSTS_VALU / SQ_INSTS_SALU of the plain kernel,
 which is the self-check printed at the end.
 
-  python tools/bbprof.py build <workdir> [-j N]      compile the base + all variants (CPU only; hipcc needed)
+  python tools/bbprof.py build <workdir> [-j N] [--lines a-b,c-d]   compile the base + all variants (CPU only; hipcc needed); --lines: variants only for the
+                                                     blocks that hold instructions of these source lines of cvx_kernels.h (a partial profile: the self-check sums do not apply)
   python tools/bbprof.py drive <workdir> [frames]    (run under rocprofv3 --pmc ...) one dispatch per variant
   python tools/bbprof.py report <workdir> <pmc csv dir>   table: block, source lines, static counts, executions, dynamic counts
   tools/bbprof.sh <tag>                              all three on the GPU box, results under gpurun_out/<tag>/
@@ -86,7 +87,7 @@ def parse_blocks(lines):
     return blocks
 
 
-def cmd_build(work, jobs):
+def cmd_build(work, jobs, line_ranges=None):
     os.makedirs(work, exist_ok=True)
     base = os.path.join(work, "base")
     os.makedirs(base, exist_ok=True)
@@ -131,9 +132,10 @@ def cmd_build(work, jobs):
         return name
 
     os.makedirs(os.path.join(work, "libs"), exist_ok=True)
+    wanted = [b for b, blk in enumerate(blocks) if line_ranges is None or any(lo <= l <= hi for l in blk["src"] for lo, hi in line_ranges)]
     with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as ex:
-        done = list(ex.map(build_variant, range(-1, len(blocks))))
-    print(f"{len(done)} libraries ({len(blocks)} blocks) under {work}/libs")
+        done = list(ex.map(build_variant, [-1] + wanted))
+    print(f"{len(done)} libraries ({len(wanted)} of {len(blocks)} blocks) under {work}/libs")
 
 
 def cmd_drive(work, frames):
@@ -220,7 +222,8 @@ if __name__ == "__main__":
     cmd = sys.argv[1]
     if cmd == "build":
         jobs = int(sys.argv[sys.argv.index("-j") + 1]) if "-j" in sys.argv else 8
-        cmd_build(sys.argv[2], jobs)
+        ranges = [tuple(int(v) for v in r.split("-")) for r in sys.argv[sys.argv.index("--lines") + 1].split(",")] if "--lines" in sys.argv else None
+        cmd_build(sys.argv[2], jobs, ranges)
     elif cmd == "drive":
         cmd_drive(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 32)
     elif cmd == "report":
