@@ -7,6 +7,7 @@
 
 #include "cpuvox_gpu_contacts.h"
 #include "cpuvox_gpu_models.h"
+#include "cpuvox_gpu_pair_contacts.h"
 #include "cvx_context.h"
 
 namespace cvxi {
@@ -102,6 +103,12 @@ int RunPointsCall(cvx_context *ctx, const PointsCall &call, Launcher<PointsJob> 
 int WorldContacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, int solidOutside,
                   cvxc_contact_result *results, cvxc_contact_point *points, int64_t pointCapacity, bool device, bool modelsStaged, cvxc_contacts_summary *summary,
                   float *outDeviceMs);
+// cvx_pair_contacts.hip: the body of cvxp_model_contacts[_device] under the name `call`.  offsets (may be null: those calls as they are): three
+// int32 a pair, body a of pair p is I_a + offsets[p] for that pair alone, and the results still carry the pair as given (cvx_pair_sweep.hip runs
+// it on the touching poses; the offsets keep every moved instance inside the limits).  device and modelsStaged as WorldContacts'.
+int PairContacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, const int32_t *pairs,
+                 int pairCount, const int32_t *offsets, cvxp_pair_result *results, cvxp_pair_point *points, int64_t pointCapacity, bool device, bool modelsStaged,
+                 cvxp_pairs_summary *summary, float *outDeviceMs);
 
 #ifdef __HIPCC__
 constexpr int kFinishThreads = 1024;

@@ -24,6 +24,7 @@
 
 #include "cvx_model_call.h"
 #include "cvx_pair_contacts.h"
+#include "cvx_sweep.h"
 
 using cvxi::Fail;
 
@@ -51,6 +52,7 @@ struct Args {
 	cvxp_pair_point *points;             // write: the list, entries below `limit`
 	uint32_t limit;
 	cvxp_pairs_summary *summary;
+	const int32_t *names;                // null, or pairCount: the `a` every result is to carry (cvxi::PairContacts with offsets)
 };
 
 // The model's colour word of the image of voxel y of the job's column.
@@ -181,15 +183,46 @@ __global__ __launch_bounds__(cvxi::kFinishThreads) void pairs_finish_kernel(Args
 	if (threadIdx.x == 0) { *A.summary = cvxp_pairs_summary{ (int64_t)totals[0], (int64_t)totals[1], (int64_t)points, (int64_t)A.jobs }; }
 }
 
-// Both calls: `device` says where the models' arrays, `results` and `points` live.
-static int ModelContacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount,
-                         const int32_t *pairs, int pairCount, cvxp_pair_result *results, cvxp_pair_point *points, int64_t pointCapacity, bool device,
-                         cvxp_pairs_summary *summary, float *outDeviceMs)
+// With offsets: every result's `a` back to the pair's own, as given (the walk ran on the moved copy behind the caller's instances).
+__global__ __launch_bounds__(kThreads) void pairs_name_kernel(Args A)
 {
+	const int p = (int)(blockIdx.x * kThreads + threadIdx.x);
+	if (p < A.pairCount) { A.results[p].a = A.names[p]; }
+}
+
+} // namespace cvxpairs
+
+// Both calls (and cvx_pair_sweep.hip's second phase: cvx_model_call.h): `device` says where the models' arrays, `results` and `points` live.
+// With `offsets`, body a of pair p is I_a + offsets[p] for that pair alone: the moved instances (cvxb::SweepInstanceMoved, the caller has checked
+// that they stay inside the limits) go behind the caller's own, one a pair, the walk's pairs name them, and pairs_name_kernel writes the pair as
+// given into the results.  Without, nothing of that is built or launched.
+int cvxi::PairContacts(cvx_context *ctx, const char *call, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount,
+                       const int32_t *pairs, int pairCount, const int32_t *offsets, cvxp_pair_result *results, cvxp_pair_point *points, int64_t pointCapacity, bool device,
+                       bool modelsStaged, cvxp_pairs_summary *summary, float *outDeviceMs)
+{
+	using namespace cvxpairs;
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
 	char message[160];
 	if (!cvxb::PairsValidate(models, modelCount, instances, instanceCount, pairs, pairCount, results, points, pointCapacity, message, sizeof message)) {
 		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: %s", call, message);
+	}
+	std::vector<cvx_model_instance> placed;
+	std::vector<int32_t> named; // the walk's pairs, then the names
+	if (offsets) {
+		placed.assign(instances, instances + instanceCount);
+		placed.resize((size_t)instanceCount + (size_t)pairCount);
+		named.resize(3 * (size_t)pairCount);
+		for (int p = 0; p < pairCount; p++) {
+			if (!cvxb::SweepInstanceMoved(instances[pairs[2 * p]], offsets + 3 * (size_t)p, &placed[(size_t)instanceCount + p])) {
+				return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s: pair %d: the moved instance leaves the limits", call, p);
+			}
+			named[2 * (size_t)p] = instanceCount + p;
+			named[2 * (size_t)p + 1] = pairs[2 * p + 1];
+			named[2 * (size_t)pairCount + p] = pairs[2 * p];
+		}
+		instances = placed.data();
+		instanceCount += pairCount;
+		pairs = named.data();
 	}
 	std::vector<uint32_t> prefix((size_t)pairCount + 1);
 	const int64_t jobs = cvxb::PairJobs(instances, pairs, pairCount, prefix.data());
@@ -200,8 +233,8 @@ static int ModelContacts(cvx_context *ctx, const char *call, const cvx_model *mo
 	A.pairCount = pairCount;
 	A.jobs = (uint32_t)jobs;
 	const dim3 walk(std::min(cvxi::Grid((size_t)jobs, kWaves), kMaxWorkgroups)), block(kThreads);
-	const cvxi::PointsCall C{ call, models, modelCount, instances, instanceCount, prefix.data(), pairCount, jobs, pairs, (size_t)pairCount * 8, sizeof(cvxp_pair_result),
-		                      sizeof(cvxp_pair_point), results, points, pointCapacity, device, reinterpret_cast<int64_t *>(summary) };
+	const cvxi::PointsCall C{ call, models, modelCount, instances, instanceCount, prefix.data(), pairCount, jobs, pairs, (size_t)pairCount * (offsets ? 12 : 8),
+		                      sizeof(cvxp_pair_result), sizeof(cvxp_pair_point), results, points, pointCapacity, device, reinterpret_cast<int64_t *>(summary), modelsStaged };
 	return cvxi::RunPointsCall(
 		ctx, C,
 		[&](const cvxi::PointsJob &J) {
@@ -215,6 +248,10 @@ static int ModelContacts(cvx_context *ctx, const char *call, const cvx_model *mo
 			hipLaunchKernelGGL(pairs_init_kernel, dim3(cvxi::Grid((size_t)pairCount)), block, 0, ctx->stream, A);
 			if (jobs > 0) { hipLaunchKernelGGL(pairs_count_kernel, walk, block, 0, ctx->stream, A); } // (a call of pairs that all miss has none)
 			hipLaunchKernelGGL(pairs_finish_kernel, dim3(1), dim3(cvxi::kFinishThreads), 0, ctx->stream, A);
+			if (offsets) {
+				A.names = A.pairs + 2 * (size_t)pairCount;
+				hipLaunchKernelGGL(pairs_name_kernel, dim3(cvxi::Grid((size_t)pairCount)), block, 0, ctx->stream, A);
+			}
 			return hipSuccess;
 		},
 		[&](const cvxi::PointsJob &J) {
@@ -226,23 +263,21 @@ static int ModelContacts(cvx_context *ctx, const char *call, const cvx_model *mo
 		outDeviceMs);
 }
 
-} // namespace cvxpairs
-
 extern "C" {
 
 int cvxp_model_contacts(cvx_context *ctx, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, const int32_t *pairs,
                         int pairCount, cvxp_pair_result *results, cvxp_pair_point *points, int64_t pointCapacity, cvxp_pairs_summary *summary, float *outDeviceMs)
 {
-	return cvxpairs::ModelContacts(ctx, "cvxp_model_contacts", models, modelCount, instances, instanceCount, pairs, pairCount, results, points, pointCapacity, false, summary,
-	                               outDeviceMs);
+	return cvxi::PairContacts(ctx, "cvxp_model_contacts", models, modelCount, instances, instanceCount, pairs, pairCount, nullptr, results, points, pointCapacity, false, false,
+	                          summary, outDeviceMs);
 }
 
 int cvxp_model_contacts_device(cvx_context *ctx, const cvx_model *models, int modelCount, const cvx_model_instance *instances, int instanceCount, const int32_t *pairs,
                                int pairCount, cvxp_pair_result *resultsDevice, cvxp_pair_point *pointsDevice, int64_t pointCapacity, cvxp_pairs_summary *summary,
                                float *outDeviceMs)
 {
-	return cvxpairs::ModelContacts(ctx, "cvxp_model_contacts_device", models, modelCount, instances, instanceCount, pairs, pairCount, resultsDevice, pointsDevice,
-	                               pointCapacity, true, summary, outDeviceMs);
+	return cvxi::PairContacts(ctx, "cvxp_model_contacts_device", models, modelCount, instances, instanceCount, pairs, pairCount, nullptr, resultsDevice, pointsDevice,
+	                          pointCapacity, true, false, summary, outDeviceMs);
 }
 
 int cvxp_box_pairs(const cvx_model_instance *instances, int instanceCount, int margin, int32_t *pairs, int64_t pairCapacity, int64_t *found)

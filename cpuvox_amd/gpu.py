@@ -75,6 +75,9 @@ MODEL_DRAW_EXPORTS = ["cvxv_view_from_camera", "cvxv_view_rays", "cvxv_models_dr
 # include/cpuvox_gpu_sweep.h: how far placed models can move before they touch the world.  A family of its own too (prefix cvxs_), no row of
 # ABI_HEADERS: tests/test_abi_sweep.py checks it.
 SWEEP_EXPORTS = ["cvxs_world_sweep", "cvxs_world_sweep_device", "cvxs_sweep_offset", "cvxs_instance_moved"]
+# include/cpuvox_gpu_pair_sweep.h: how far placed models can move before they touch each other.  A family of its own as well (prefix cvxm_), no
+# row of ABI_HEADERS: tests/test_abi_pair_sweep.py checks it.
+PAIR_SWEEP_EXPORTS = ["cvxm_pair_sweep", "cvxm_pair_sweep_device"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -201,6 +204,14 @@ class SweepResult(C.Structure):  # cvxs_sweep_result
 
 class SweepsSummary(C.Structure):  # cvxs_sweeps_summary
     _fields_ = [("hits", C.c_int64), ("startsSolid", C.c_int64), ("jobs", C.c_int64), ("points", C.c_int64)]
+
+
+class PairSweepResult(C.Structure):  # cvxm_pair_sweep_result
+    _fields_ = [("sweep", SweepResult), ("a", C.c_int32), ("b", C.c_int32)]
+
+
+class PairSweepsSummary(C.Structure):  # cvxm_pair_sweeps_summary
+    _fields_ = [("hits", C.c_int64), ("startsSolid", C.c_int64), ("jobs", C.c_int64), ("pad_", C.c_int64)]
 
 
 class DrawView(C.Structure):  # cvxv_view
@@ -356,6 +367,7 @@ PAIR_RESULT_DTYPE, PAIR_POINT_DTYPE, PAIRS_SUMMARY_DTYPE = np.dtype(PairResult),
 MODEL_HIT_DTYPE = np.dtype(ModelHit)
 DRAW_VIEW_DTYPE, DRAW_SUMMARY_DTYPE = np.dtype(DrawView), np.dtype(DrawSummary)
 SWEEP_RESULT_DTYPE, SWEEPS_SUMMARY_DTYPE = np.dtype(SweepResult), np.dtype(SweepsSummary)
+PAIR_SWEEP_RESULT_DTYPE, PAIR_SWEEPS_SUMMARY_DTYPE = np.dtype(PairSweepResult), np.dtype(PairSweepsSummary)
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
 
@@ -803,6 +815,9 @@ def _bind(path: str) -> C.CDLL:
     L.cvxs_world_sweep_device.argtypes = L.cvxs_world_sweep.argtypes
     L.cvxs_sweep_offset.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
     L.cvxs_instance_moved.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvxm_pair_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.POINTER(PairSweepsSummary), C.POINTER(C.c_float)]
+    L.cvxm_pair_sweep_device.argtypes = L.cvxm_pair_sweep.argtypes
     L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
     L.cvx_shard_plan_destroy.restype = None
@@ -1518,6 +1533,45 @@ class Context:
         points_ptr, capacity = self._checked_tensor("world_sweep_device", points_tensor, C.sizeof(ContactPoint), 0) if points_tensor is not None else (None, 0)
         return self._sweep(lib().cvxs_world_sweep_device, "world_sweep_device", descriptors, len(models), inst, motions, solid_outside, contacts_ptr,
                            points_ptr if capacity else None, capacity)
+
+    # -- how far placed models can move before they touch each other (cvxm_pair_sweep, include/cpuvox_gpu_pair_sweep.h) --
+    def _pair_sweep(self, entry, who, descriptors, model_count, inst, pairs, motions, contacts_ptr):
+        p = self._pairs(pairs, inst, who)
+        v = np.asarray(motions)
+        if v.dtype.kind not in "iu" or v.shape != (len(p), 3) or (v.size and np.abs(v.astype(np.int64)).max() >= 1 << 31):
+            raise ValueError(f"{who}: motions is an integer array of shape (pairs, 3)")
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        sweeps = np.zeros(len(p), dtype=PAIR_SWEEP_RESULT_DTYPE)
+        summary, ms = PairSweepsSummary(), C.c_float()
+        self._check(entry(self._h, C.addressof(descriptors), model_count, C.addressof(inst), len(inst), p.ctypes.data if len(p) else None, v.ctypes.data if len(p) else None,
+                          len(p), sweeps.ctypes.data if len(p) else None, contacts_ptr or None, C.byref(summary), C.byref(ms)))
+        return sweeps, {name: int(getattr(summary, name)) for name in PAIR_SWEEPS_SUMMARY_DTYPE.names if name != "pad_"}, ms.value
+
+    def model_sweep(self, models, instances, pairs, motions, want_contacts=True):
+        """How far body a of every pair (a, b) can move along its integer motion RELATIVE TO b (`motions`: shape (pairs, 3), components of at most
+        SWEEP_MAX_MOTION in magnitude; for two moving bodies pass v_a - v_b) before the two bodies share a voxel; no world is read and none
+        need be uploaded: (one PAIR_SWEEP_RESULT_DTYPE element per pair -- `sweep` as world_sweep's: the first touching step `hit` of
+        gpu.sweep_offset's path or -1, its axis and sign, the last free offset and the touching one; then the pair --, the PAIR_RESULT_DTYPE
+        results of model_contacts with body a of every pair moved to its `at` (None without want_contacts), the totals of
+        cvxm_pair_sweeps_summary as a dict, device milliseconds).  `models`, `instances` and `pairs` as model_contacts' (pairs None:
+        gpu.box_pairs)."""
+        descriptors, keep = self._models(models, "model_sweep")  # noqa: F841  (keep: the arrays the descriptors point to)
+        inst = self._instances(instances)
+        p = self._pairs(pairs, inst, "model_sweep")
+        contacts = np.zeros(len(p), dtype=PAIR_RESULT_DTYPE) if want_contacts else None
+        sweeps, totals, ms = self._pair_sweep(lib().cvxm_pair_sweep, "model_sweep", descriptors, len(models), inst, p, motions,
+                                              contacts.ctypes.data if want_contacts and len(p) else None)
+        return sweeps, contacts, totals, ms
+
+    def model_sweep_device(self, models, instances, pairs, motions, contacts_tensor=None):
+        """model_sweep on device memory: `models` is a list of ((sx, sy, sz), argb_ptr, solid_ptr) as model_contacts_device's, `contacts_tensor`
+        (or None: the sweeps alone) a contiguous device tensor of at least 144 bytes per pair.  Returns (the sweeps, a host array, the totals
+        as a dict, device milliseconds) once the tensor is complete."""
+        descriptors = self._device_models(models, "model_sweep_device")
+        inst = self._instances(instances)
+        p = self._pairs(pairs, inst, "model_sweep_device")
+        contacts_ptr = self._checked_tensor("model_sweep_device", contacts_tensor, C.sizeof(PairResult), len(p))[0] if contacts_tensor is not None else None
+        return self._pair_sweep(lib().cvxm_pair_sweep_device, "model_sweep_device", descriptors, len(models), inst, p, motions, contacts_ptr)
 
     @staticmethod
     def _model_read(size, to_world):
