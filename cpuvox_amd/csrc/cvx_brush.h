@@ -5,6 +5,8 @@
 //   ArenaColumn  what a LOD-0 record of the arena says about its column: the solid runs top-down (records with 1 .. 3 runs, run-list blocks),
 //                each with its colour index; colours at colorsBase + index << colorShift (blocks of 4 x 8 columns or column after column).
 //   StrokeSpan   the y interval a stroke (box, sphere, capsule, ellipsoid) covers in a column: exact integers decide every voxel.
+//                StrokeSpanUnclipped is the interval itself (cvx_model_brush.h: bodies have no frame), StrokeSpan its clip to the world's height.
+//   StrokeCountValidate, StrokeShapesValidate  the stroke checks of cvx_world_brush and cvxd_models_brush, one copy.
 //   BrushColumn  a column after a list of strokes, emitted as the builder emits it (WordBuilder.cs:181-268): maximal runs from the top, the
 //                top air run first, ColorsIndex = solid voxels above, worldMin / worldMax as the RLEColumn constructor computes them.
 //   PickRay      the first solid voxel along a ray (a 2-D DDA over the columns, one record per step, the solid runs walked in the ray's y order).
@@ -12,6 +14,7 @@
 #pragma once
 
 #include <stdint.h>
+#include <stdio.h>
 
 #include "cpuvox_gpu.h"
 #include "cvx_edit.h" // CVX_HD
@@ -81,6 +84,66 @@ CVX_HD inline void StrokeFootprint(const cvx_brush_stroke &s, int64_t lo[3], int
 	}
 }
 
+// The limits of include/cpuvox_gpu.h: the span rules are exact in int64 inside them.
+constexpr int kCapsuleMax = 8191, kEllipsoidMax = 1024;
+
+// The stroke checks of cvx_world_brush and cvxd_models_brush, in the order include/cpuvox_gpu.h lists them: the list (StrokeCountValidate), then
+// every stroke's op and shape (StrokeShapesValidate; cvx_world_brush checks its levelCount between the two); false: the message says what.
+// (Plain host functions: not CVX_HD.)
+inline bool StrokeCountValidate(const cvx_brush_stroke *strokes, int strokeCount, char *message, size_t bytes)
+{
+	if (!strokes || strokeCount <= 0 || strokeCount > CVX_BRUSH_MAX_STROKES) {
+		snprintf(message, bytes, "strokeCount %d outside 1 .. %d", strokeCount, CVX_BRUSH_MAX_STROKES);
+		return false;
+	}
+	return true;
+}
+
+inline bool StrokeShapesValidate(const cvx_brush_stroke *strokes, int strokeCount, char *message, size_t bytes)
+{
+	for (int s = 0; s < strokeCount; s++) {
+		const cvx_brush_stroke &k = strokes[s];
+		if (k.op < CVX_BRUSH_FILL || k.op > CVX_BRUSH_PAINT) {
+			snprintf(message, bytes, "stroke %d: bad op %d", s, k.op);
+			return false;
+		}
+		if (k.shape != CVX_SHAPE_BOX && k.shape != CVX_SHAPE_SPHERE && k.shape != CVX_SHAPE_CAPSULE && k.shape != CVX_SHAPE_ELLIPSOID) {
+			snprintf(message, bytes, "stroke %d: bad shape %d", s, k.shape);
+			return false;
+		}
+		if (k.shape == CVX_SHAPE_SPHERE && (k.b[0] < 0 || k.b[0] > (1 << 30))) {
+			snprintf(message, bytes, "stroke %d: sphere radius %d outside 0 .. 2^30", s, k.b[0]);
+			return false;
+		}
+		if (k.shape == CVX_SHAPE_CAPSULE) {
+			if (k.pad_ < 0 || k.pad_ > kCapsuleMax) {
+				snprintf(message, bytes, "stroke %d: capsule radius %d outside 0 .. %d", s, k.pad_, kCapsuleMax);
+				return false;
+			}
+			for (int a = 0; a < 3; a++) {
+				const int64_t d = (int64_t)k.b[a] - k.a[a];
+				if (d < -kCapsuleMax || d > kCapsuleMax) {
+					snprintf(message, bytes, "stroke %d: capsule ends %lld apart on axis %d, more than %d", s, (long long)d, a, kCapsuleMax);
+					return false;
+				}
+				if (k.a[a] < -(1 << 30) || k.a[a] > (1 << 30)) {
+					snprintf(message, bytes, "stroke %d: capsule end a[%d] = %d outside -2^30 .. 2^30", s, a, k.a[a]);
+					return false;
+				}
+			}
+		}
+		if (k.shape == CVX_SHAPE_ELLIPSOID) {
+			for (int a = 0; a < 3; a++) {
+				if (k.b[a] < 1 || k.b[a] > kEllipsoidMax) {
+					snprintf(message, bytes, "stroke %d: ellipsoid radius b[%d] = %d outside 1 .. %d", s, a, k.b[a], kEllipsoidMax);
+					return false;
+				}
+			}
+		}
+	}
+	return true;
+}
+
 // floor(n / q) for q > 0, in 32 bits (the capsule's slab bounds: |n| < 2^30)
 CVX_HD inline int64_t FloorDiv32(int32_t n, int32_t q)
 {
@@ -118,9 +181,11 @@ CVX_HD inline void CapsuleMiddle(int64_t a2, int64_t b1, int64_t c0, int64_t p0,
 	*outHi = t2;
 }
 
-// The y interval [lo, hi) a stroke covers in column (cx, cz), clipped to [0, dimY); lo >= hi: none.  The rules are those of include/cpuvox_gpu.h; a
-// capsule's and an ellipsoid's products are formed only for columns inside the footprint, which keeps them in int64 for strokes far from the world.
-CVX_HD inline void StrokeSpan(const cvx_brush_stroke &s, int64_t cx, int64_t cz, int64_t dimY, int64_t *lo, int64_t *hi)
+// The y interval [lo, hi) a stroke covers in column (cx, cz), clipped to nothing; lo >= hi: none.  The rules are those of include/cpuvox_gpu.h; a
+// capsule's and an ellipsoid's products are formed only for columns inside the footprint, which keeps them in int64 for strokes far from the
+// column.  (A sphere's are formed for every column, as they always were: a caller whose columns can lie 2^31 from the stroke tests
+// StrokeFootprint first, as cvx_model_brush.h does.)
+CVX_HD inline void StrokeSpanUnclipped(const cvx_brush_stroke &s, int64_t cx, int64_t cz, int64_t *lo, int64_t *hi)
 {
 	int64_t l = 0, h = 0;
 	if (s.shape == CVX_SHAPE_BOX) {
@@ -184,6 +249,15 @@ CVX_HD inline void StrokeSpan(const cvx_brush_stroke &s, int64_t cx, int64_t cz,
 			}
 		}
 	}
+	*lo = l;
+	*hi = h;
+}
+
+// StrokeSpanUnclipped clipped to [0, dimY): what a stroke covers of a column of the world.
+CVX_HD inline void StrokeSpan(const cvx_brush_stroke &s, int64_t cx, int64_t cz, int64_t dimY, int64_t *lo, int64_t *hi)
+{
+	int64_t l, h;
+	StrokeSpanUnclipped(s, cx, cz, &l, &h);
 	*lo = l < 0 ? 0 : l;
 	*hi = h > dimY ? dimY : h;
 }

@@ -128,8 +128,6 @@ __global__ __launch_bounds__(CVX_WAVE) void pick_kernel(cvxb::PickWorld W, int r
 
 namespace {
 
-constexpr int kCapsuleMax = 8191, kEllipsoidMax = 1024; // the limits of include/cpuvox_gpu.h: the span rules (cvx_brush.h) are exact in int64 inside them
-
 using cvxi::Grid;
 
 int Prepare(cvx_context *ctx)
@@ -188,33 +186,10 @@ extern "C" {
 int cvx_world_brush(cvx_context *ctx, const cvx_brush_stroke *strokes, int strokeCount, int levelCount, float *outDeviceMs)
 {
 	if (!ctx) { return CVX_ERR_INVALID_ARGUMENT; }
-	if (!strokes || strokeCount <= 0 || strokeCount > CVX_BRUSH_MAX_STROKES) {
-		return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "strokeCount %d outside 1 .. %d", strokeCount, CVX_BRUSH_MAX_STROKES);
-	}
+	char message[160];
+	if (!cvxb::StrokeCountValidate(strokes, strokeCount, message, sizeof message)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", message); }
 	if (levelCount < 0 || levelCount >= CVX_LOD_LEVELS) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "levelCount %d outside 0 .. %d", levelCount, CVX_LOD_LEVELS - 1); }
-	for (int s = 0; s < strokeCount; s++) {
-		const cvx_brush_stroke &k = strokes[s];
-		if (k.op < CVX_BRUSH_FILL || k.op > CVX_BRUSH_PAINT) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: bad op %d", s, k.op); }
-		if (k.shape != CVX_SHAPE_BOX && k.shape != CVX_SHAPE_SPHERE && k.shape != CVX_SHAPE_CAPSULE && k.shape != CVX_SHAPE_ELLIPSOID) {
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: bad shape %d", s, k.shape);
-		}
-		if (k.shape == CVX_SHAPE_SPHERE && (k.b[0] < 0 || k.b[0] > (1 << 30))) {
-			return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: sphere radius %d outside 0 .. 2^30", s, k.b[0]);
-		}
-		if (k.shape == CVX_SHAPE_CAPSULE) {
-			if (k.pad_ < 0 || k.pad_ > kCapsuleMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: capsule radius %d outside 0 .. %d", s, k.pad_, kCapsuleMax); }
-			for (int a = 0; a < 3; a++) {
-				const int64_t d = (int64_t)k.b[a] - k.a[a];
-				if (d < -kCapsuleMax || d > kCapsuleMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: capsule ends %lld apart on axis %d, more than %d", s, (long long)d, a, kCapsuleMax); }
-				if (k.a[a] < -(1 << 30) || k.a[a] > (1 << 30)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: capsule end a[%d] = %d outside -2^30 .. 2^30", s, a, k.a[a]); }
-			}
-		}
-		if (k.shape == CVX_SHAPE_ELLIPSOID) {
-			for (int a = 0; a < 3; a++) {
-				if (k.b[a] < 1 || k.b[a] > kEllipsoidMax) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "stroke %d: ellipsoid radius b[%d] = %d outside 1 .. %d", s, a, k.b[a], kEllipsoidMax); }
-			}
-		}
-	}
+	if (!cvxb::StrokeShapesValidate(strokes, strokeCount, message, sizeof message)) { return Fail(ctx, CVX_ERR_INVALID_ARGUMENT, "%s", message); }
 	if (const int refused = cvxi::RequireWorld(ctx)) { return refused; }
 	const int dimX = ctx->hostWorld.dimX, dimY = ctx->hostWorld.dimY, dimZ = ctx->hostWorld.dimZ;
 	// the strokes that touch the world, and the rectangle: the union of their footprints rounded out to 2^levelCount, clipped to the world

@@ -78,6 +78,9 @@ SWEEP_EXPORTS = ["cvxs_world_sweep", "cvxs_world_sweep_device", "cvxs_sweep_offs
 # include/cpuvox_gpu_pair_sweep.h: how far placed models can move before they touch each other.  A family of its own as well (prefix cvxm_), no
 # row of ABI_HEADERS: tests/test_abi_pair_sweep.py checks it.
 PAIR_SWEEP_EXPORTS = ["cvxm_pair_sweep", "cvxm_pair_sweep_device"]
+# include/cpuvox_gpu_model_brush.h: world-space brush strokes that carve and paint placed models.  A family of its own too (prefix cvxd_, which
+# the diagnostic cvxd_clip_census of include/cpuvox_gpu_diag.h shares), no row of ABI_HEADERS: tests/test_abi_model_brush.py checks it.
+MODEL_BRUSH_EXPORTS = ["cvxd_models_brush", "cvxd_models_brush_device", "cvxd_model_mass"]
 # include/cpuvox_gpu_diag.h: only the experiment / profiling builds export these (cpuvox_amd.gpu.use_library(".../libcpuvox_gpu_exp.so"))
 DIAG_EXPORTS = ["cvx_selftest_math", "cvx_selftest_scan", "cvx_selftest_lone", "cvx_debug_occupancy", "cvx_debug_section_cycles", "cvx_debug_section_histogram",
                 "cvx_debug_last_launch", "cvx_debug_settle", "cvx_debug_cavities"]
@@ -212,6 +215,19 @@ class PairSweepResult(C.Structure):  # cvxm_pair_sweep_result
 
 class PairSweepsSummary(C.Structure):  # cvxm_pair_sweeps_summary
     _fields_ = [("hits", C.c_int64), ("startsSolid", C.c_int64), ("jobs", C.c_int64), ("pad_", C.c_int64)]
+
+
+class ModelBrushResult(C.Structure):  # cvxd_model_result
+    _fields_ = [("voxels", C.c_int64), ("carved", C.c_int64), ("painted", C.c_int64), ("sum", C.c_uint64 * 3), ("moment", C.c_uint64 * 6), ("min", C.c_int32 * 3),
+                ("max", C.c_int32 * 3), ("pad_", C.c_int32 * 2)]
+
+
+class ModelBrushInstanceResult(C.Structure):  # cvxd_instance_result
+    _fields_ = [("carved", C.c_int64), ("painted", C.c_int64)]
+
+
+class ModelBrushSummary(C.Structure):  # cvxd_brush_summary
+    _fields_ = [("carved", C.c_int64), ("painted", C.c_int64), ("models", C.c_int64), ("jobs", C.c_int64)]
 
 
 class DrawView(C.Structure):  # cvxv_view
@@ -368,6 +384,8 @@ MODEL_HIT_DTYPE = np.dtype(ModelHit)
 DRAW_VIEW_DTYPE, DRAW_SUMMARY_DTYPE = np.dtype(DrawView), np.dtype(DrawSummary)
 SWEEP_RESULT_DTYPE, SWEEPS_SUMMARY_DTYPE = np.dtype(SweepResult), np.dtype(SweepsSummary)
 PAIR_SWEEP_RESULT_DTYPE, PAIR_SWEEPS_SUMMARY_DTYPE = np.dtype(PairSweepResult), np.dtype(PairSweepsSummary)
+MODEL_BRUSH_RESULT_DTYPE, MODEL_BRUSH_INSTANCE_RESULT_DTYPE = np.dtype(ModelBrushResult), np.dtype(ModelBrushInstanceResult)
+MODEL_BRUSH_SUMMARY_DTYPE = np.dtype(ModelBrushSummary)
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("rgba", "u1", 4), ("uv", "<f4", 2), ("material", "<i4")])  # cvx_mesh_vertex (no structure here)
 STAMP_MAX_MATERIALS = 128
 
@@ -466,6 +484,17 @@ def lifted_piece_mass(piece):
     rc = lib().cvx_lifted_piece_mass(one.ctypes.data, centre.ctypes.data, inertia.ctypes.data)
     if rc != 0:
         raise ValueError("lifted_piece_mass: the piece has no voxels")
+    return centre, inertia
+
+
+def model_mass(result):
+    """cvxd_model_mass of one MODEL_BRUSH_RESULT_DTYPE element (models_brush's): (centre of mass (3,), inertia (Ixx, Iyy, Izz, Ixy, Iyz, Izx)
+    about it) as float64 arrays in MODEL coordinates, for unit cubes of unit mass: lifted_piece_mass' formula with min = 0.  A pure host call.
+    ValueError for a model with no voxel left."""
+    one = np.ascontiguousarray(np.asarray(result, dtype=MODEL_BRUSH_RESULT_DTYPE).reshape(1))
+    centre, inertia = np.zeros(3), np.zeros(6)
+    if lib().cvxd_model_mass(one.ctypes.data, centre.ctypes.data, inertia.ctypes.data) != 0:
+        raise ValueError("model_mass: the model has no voxels")
     return centre, inertia
 
 
@@ -818,6 +847,10 @@ def _bind(path: str) -> C.CDLL:
     L.cvxm_pair_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.POINTER(PairSweepsSummary), C.POINTER(C.c_float)]
     L.cvxm_pair_sweep_device.argtypes = L.cvxm_pair_sweep.argtypes
+    L.cvxd_models_brush.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ModelBrushSummary),
+                                    C.POINTER(C.c_float)]
+    L.cvxd_models_brush_device.argtypes = L.cvxd_models_brush.argtypes
+    L.cvxd_model_mass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.cvx_shard_plan_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.cvx_shard_plan_destroy.argtypes = [C.c_void_p]
     L.cvx_shard_plan_destroy.restype = None
@@ -1572,6 +1605,57 @@ class Context:
         p = self._pairs(pairs, inst, "model_sweep_device")
         contacts_ptr = self._checked_tensor("model_sweep_device", contacts_tensor, C.sizeof(PairResult), len(p))[0] if contacts_tensor is not None else None
         return self._pair_sweep(lib().cvxm_pair_sweep_device, "model_sweep_device", descriptors, len(models), inst, p, motions, contacts_ptr)
+
+    # -- brush strokes that carve and paint placed models (cvxd_models_brush, include/cpuvox_gpu_model_brush.h) --
+    def _models_brush(self, entry, descriptors, model_count, instances, strokes):
+        inst = self._instances(instances)
+        k = strokes_array(strokes)
+        results = np.zeros(model_count, dtype=MODEL_BRUSH_RESULT_DTYPE)
+        hit = np.zeros(len(inst), dtype=MODEL_BRUSH_INSTANCE_RESULT_DTYPE)
+        summary, ms = ModelBrushSummary(), C.c_float()
+        self._check(entry(self._h, C.addressof(descriptors), model_count, C.addressof(inst), len(inst), k.ctypes.data if len(k) else None, len(k),
+                          results.ctypes.data if model_count else None, hit.ctypes.data if len(inst) else None, C.byref(summary), C.byref(ms)))
+        return results, hit, {name: int(getattr(summary, name)) for name in MODEL_BRUSH_SUMMARY_DTYPE.names}, ms.value
+
+    def models_brush(self, models, instances, strokes):
+        """World-space brush strokes (strokes_array's; BRUSH_CARVE and BRUSH_PAINT only) applied to the MODELS through the instances that place
+        them; no world is read and none need be uploaded.  A CARVE unsets the model voxels of the body voxels inside its shape, a PAINT recolours
+        them, in stroke order; every instance of a model contributes, so a shared model changes for all of them.  `models` and `instances` as
+        world_contacts'; the caller's arrays are left alone: (the models after the call, a list of (argb, solid) copies of shape (X, Z, Y), one
+        MODEL_BRUSH_RESULT_DTYPE element per model -- voxels left, carved, painted, the mass sums gpu.model_mass takes, the tight box --, one
+        MODEL_BRUSH_INSTANCE_RESULT_DTYPE element per instance -- the body voxels inside a CARVE, and of the others those inside a PAINT --, the
+        totals of cvxd_brush_summary as a dict, device milliseconds)."""
+        copies = []
+        for entry in models:
+            if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+                raise ValueError("models_brush: a model is a pair (argb, solid)")
+            argb, solid = entry
+            if argb is not None and np.asarray(argb).dtype.kind not in "iu":
+                raise ValueError("models_brush: argb is an integer array of shape (X, Z, Y)")
+            copies.append((np.array(argb, dtype=np.uint32, order="C") if argb is not None else None,
+                           np.array(np.asarray(solid) != 0, dtype=np.bool_, order="C") if solid is not None else None))
+        descriptors, keep = self._models(copies, "models_brush")  # noqa: F841  (keep: views of the copies, which the call writes in place)
+        results, hit, totals, ms = self._models_brush(lib().cvxd_models_brush, descriptors, len(models), instances, strokes)
+        return copies, results, hit, totals, ms
+
+    def models_brush_device(self, device_models, instances, strokes):
+        """models_brush in place on device memory: `device_models` is a list of (argb, solid) torch tensors on the context's device -- uint32 /
+        int32 colour words and a uint8 / bool mask of one shape (X, Z, Y), contiguous, either may be None, not both --, written in place; two
+        models may not share memory.  Returns (the model results, the instance results, the totals as a dict, device milliseconds) once the
+        tensors are complete."""
+        entries = []
+        for entry in device_models:
+            if not isinstance(entry, (tuple, list)) or len(entry) != 2 or (entry[0] is None and entry[1] is None):
+                raise ValueError("models_brush_device: a model is a pair (argb, solid) of device tensors, not both None")
+            argb, solid = entry
+            shape = tuple((argb if argb is not None else solid).shape)
+            for tensor, item_bytes in ((argb, 4), (solid, 1)):
+                if tensor is not None and (not tensor.is_cuda or not tensor.is_contiguous() or tensor.element_size() != item_bytes or tuple(tensor.shape) != shape
+                                           or len(shape) != 3):
+                    raise ValueError("models_brush_device: argb (4-byte items) and solid (1-byte items) are contiguous device tensors of one shape (X, Z, Y)")
+            entries.append(((shape[0], shape[2], shape[1]), argb.data_ptr() if argb is not None else 0, solid.data_ptr() if solid is not None else 0))
+        descriptors = self._device_models(entries, "models_brush_device")
+        return self._models_brush(lib().cvxd_models_brush_device, descriptors, len(entries), instances, strokes)
 
     @staticmethod
     def _model_read(size, to_world):
