@@ -5,7 +5,8 @@
 //     Each case, as int32 words: tests/models_rules.cpp's call (the models, the instances), strokeCount, then ten words a stroke.  The call goes
 //     through cvxb::ModelBrushSequential -- a stroke at a time and a voxel at a time, a later stroke seeing what the earlier ones did -- AND
 //     through the kernels' form (WaveForm below: the cull's words, the (instance, column) jobs in order, each found by the 64-probe search,
-//     cvxb::ModelBrushColumn with the 64 lanes run in turn into the key array, then the (model, chunk) jobs of cvxb::ModelBrushApplyLane), each
+//     cvxb::ModelBrushColumn with the 64 lanes run in turn into the key array, then the (model, chunk) jobs of cvxb::ModelBrushApplyLane in
+//     order, each found by the same search in the prefix of the models' chunks), each
 //     on its own copy of the arrays; arrays and results must agree byte for byte (exit code 3 otherwise).  Out per case: per model its argb words
 //     and its solid bytes where it has them, the model results (128 bytes each), the instance results (16 each), the summary (32).
 //   model_brush_rules spans <in> <out>
@@ -134,21 +135,35 @@ static bool WaveForm(BrushCall &C, BrushAnswer *out)
 		out->instances[k].carved += carved;
 		out->instances[k].painted += painted;
 	}
-	// apply: a wave per (model, chunk) job
+	// apply: a wave per (model, chunk) job, the model found in the prefix of the models' chunks as the kernel finds it
 	out->models.resize((size_t)modelCount);
+	std::vector<uint32_t> chunkPrefix((size_t)modelCount + 1, 0u);
 	for (int g = 0; g < modelCount; g++) {
-		cvxd_model_result *r = &out->models[g];
-		cvxb::ModelBrushResultInit(r);
-		const int64_t volume = cvxb::ModelBrushVolume(C.models[g]);
-		for (uint32_t chunk = 0; chunk < cvxb::ModelBrushChunks(volume); chunk++) {
-			for (int lane = 0; lane < 64; lane++) {
-				cvxb::ModelBrushSums S;
-				cvxb::ModelBrushApplyLane(C.models[g], keys.data() + C.volumePrefix[g], C.strokes.data(), (uint32_t)volume, chunk, lane, &S);
-				cvxb::ModelBrushResultAdd(S, r);
-			}
-		}
-		cvxb::ModelBrushFinish(r);
+		cvxb::ModelBrushResultInit(&out->models[g]);
+		chunkPrefix[g + 1] = chunkPrefix[g] + cvxb::ModelBrushChunks(cvxb::ModelBrushVolume(C.models[g]));
 	}
+	for (uint32_t at = 0; at < chunkPrefix[modelCount]; at++) {
+		int32_t g = 0, within = modelCount;
+		while (within > 1) {
+			uint64_t le = 0ull;
+			for (int lane = 0; lane < 64; lane++) {
+				const int32_t probe = cvxb::PairSearchProbe(g, within, lane);
+				if (probe >= 0 && chunkPrefix[probe] <= at) { le |= 1ull << lane; }
+			}
+			cvxb::PairSearchNarrow(&g, &within, le);
+		}
+		if (chunkPrefix[g] > at || chunkPrefix[g + 1] <= at) {
+			std::fprintf(stderr, "chunk %u: the search lands on model %d, whose chunks are %u .. %u\n", at, g, chunkPrefix[g], chunkPrefix[g + 1]);
+			return false;
+		}
+		const uint32_t chunk = at - chunkPrefix[g];
+		for (int lane = 0; lane < 64; lane++) {
+			cvxb::ModelBrushSums S;
+			cvxb::ModelBrushApplyLane(C.models[g], keys.data() + C.volumePrefix[g], C.strokes.data(), (uint32_t)cvxb::ModelBrushVolume(C.models[g]), chunk, lane, &S);
+			cvxb::ModelBrushResultAdd(S, &out->models[g]);
+		}
+	}
+	for (int g = 0; g < modelCount; g++) { cvxb::ModelBrushFinish(&out->models[g]); }
 	out->summary = cvxb::ModelBrushSummary(out->models.data(), modelCount, jobs);
 	return true;
 }
